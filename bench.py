@@ -1,9 +1,15 @@
 #!/usr/bin/env python
-"""bench.py -- BA LM-iterations/s + residuals/s and RANSAC hypotheses/s on N x MI355X, with the kernel rooflines
+"""bench.py -- BA LM-iterations/s + residuals/s on N x MI355X; with --full also RANSAC hypotheses/s, the kernel rooflines
 and the CPU baseline (host cores of the same box) in the same JSON line.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up the headline workload, warms up, times exactly K steps and prints the JSON line (metric, value, unit,
+higher_is_better, dtype, ms_per_step, config).  --full adds everything else on the same line: the instrumented pass for the
+rooflines and the phase split, the PCIe-inclusive rate, the other option sets (inner iterations, intrinsics), the one-shot
+call, C2, the CPU baseline, RANSAC and the relative-position IRLS.  --dump-outputs DIR writes what the last timed step
+computed (the parameters a caller of the solve receives, and its costs) as DIR/<name>.npy, before any of the --full work.
 
 A "step" is ONE Levenberg-Marquardt iteration of the BA hot path (Jacobian evaluation + Schur elimination +
 reduced-camera solve + back-substitution + trial-cost evaluation) on a synthetic reconstruction resident in HBM.
@@ -30,6 +36,34 @@ ITERS_PER_SOLVE = 8      # LM iterations per solve from the perturbed start (tol
 HBM_PEAK_GBPS = 8000.0   # MI355X_MICROARCH.md: 8 TB/s spec
 FP64_VECTOR_PEAK_TFLOPS = 78.6   # MI355X FP64 vector = FP64 matrix peak (half of the guide's 157.3 TF FP32 vector rate)
 PROFILE_TAG = "r6"       # committed rocprofv3 PMC passes of this command: profiles/<tag>_pmc_{fetch,write}_size.csv
+
+
+def usable_cores():
+    """CPUs this process may run on: the affinity mask, capped by a cgroup CPU quota and by OMP_NUM_THREADS when either is
+    set (a shared host may give a job far fewer cores than os.cpu_count() reports)."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        with open("/sys/fs/cgroup/cpu.max") as f:
+            quota, period = f.read().split()[:2]
+        if quota != "max":
+            n = min(n, max(1, int(quota) // int(period)))
+    except (OSError, ValueError):
+        pass
+    try:
+        n = min(n, int(os.environ["OMP_NUM_THREADS"]))
+    except (KeyError, ValueError):
+        pass
+    return max(1, n)
+
+
+def dump_outputs(d, prob, summary):
+    """What the last timed step computed, as a caller of the solve receives it: the parameters after the solve (downloaded
+    from the handle) and its initial / final cost, FP64, one DIR/<name>.npy each (C4: ~16 MB in all)."""
+    os.makedirs(d, exist_ok=True)
+    arrays = {"cam_ext": prob.cam_ext, "points": prob.points, "intrinsics": prob.intrinsics,
+              "cost": np.array([summary.initial_cost, summary.final_cost])}
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def bench_options(ba, max_iters):
@@ -152,6 +186,7 @@ class BaRunner:
         self.opts = bench_options(ba, ITERS_PER_SOLVE)
         self.h = ba.BaHandle(prob, self.opts)
         self.pristine = pristine
+        self.last_summary = None
 
     def prepare(self):
         self.h.reset(self.pristine)
@@ -171,6 +206,7 @@ class BaRunner:
             s, _ = self.h.run(trace_capacity=1)
             if s.num_iterations != m:
                 raise RuntimeError(f"solve stopped after {s.num_iterations} of {m} iterations (term {s.termination_type})")
+            self.last_summary = s
             done += m
             acc["lin_kernel"] += s.time_kernel_linearize; acc["launches"] += s.num_linearize_launches
             acc["lin"] += s.time_linearize; acc["solve"] += s.time_solve_reduced; acc["backsub"] += s.time_backsub
@@ -351,6 +387,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=8)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: rooflines, phase split, PCIe-inclusive rate, the other option sets, the one-shot call, "
+                         "C2, the CPU baseline, RANSAC and the relative-position IRLS (the --no-* switches below prune this)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (FP64; rank 0 only: with N > 1 its "
+                         "points are rank 0's shard)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-ransac", action="store_true")
     ap.add_argument("--no-c2", action="store_true")
@@ -358,6 +400,8 @@ def main():
                     help="with --gpus N under torch.distributed.run: all N ranks share cuda:0 and the collective goes through the host "
                          "(gloo); everything else is the multi-GPU code path -- a rehearsal of the SCALE run on a one-GPU box, not a measurement")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -426,16 +470,20 @@ def main():
     R.run(args.steps)
     barrier()
     elapsed = time.perf_counter() - t0
-    # Kernel-group durations for the rooflines: the timed region above has no events inside; the same workload is run
-    # once more with HIP events around the kernel groups on the library's stream (THEIA_HIP_PHASE_TIMING=1).
-    acc = R.phase_timed(max(ITERS_PER_SOLVE, min(args.steps, 40)))
-    barrier()
-    # for the record: the same solves with the parameters re-uploaded from host memory per solve
-    tp0 = time.perf_counter()
-    npcie = max(ITERS_PER_SOLVE, min(args.steps, 40))
-    R.run(npcie, from_host=True)
-    barrier()
-    pcie_it_per_s = npcie / (time.perf_counter() - tp0)
+    if args.dump_outputs and rank == 0:
+        # before anything else runs on the handle: its parameters are still those of the last timed solve
+        dump_outputs(args.dump_outputs, R.h.download(pristine.copy()), R.last_summary)
+    if args.full:
+        # Kernel-group durations for the rooflines: the timed region above has no events inside; the same workload is run
+        # once more with HIP events around the kernel groups on the library's stream (THEIA_HIP_PHASE_TIMING=1).
+        acc = R.phase_timed(max(ITERS_PER_SOLVE, min(args.steps, 40)))
+        barrier()
+        # for the record: the same solves with the parameters re-uploaded from host memory per solve
+        tp0 = time.perf_counter()
+        npcie = max(ITERS_PER_SOLVE, min(args.steps, 40))
+        R.run(npcie, from_host=True)
+        barrier()
+        pcie_it_per_s = npcie / (time.perf_counter() - tp0)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -444,18 +492,10 @@ def main():
     out = None
     if rank == 0:
         it_per_s = args.steps / elapsed
-        abytes = algorithmic_bytes_linearize(full) if world == 1 else None
-        nl = max(1, acc["launches"])
-        avg_lin = acc["lin_kernel"] / nl
-        achieved = abytes / avg_lin / 1e9 if (abytes and avg_lin > 0) else 0.0
-        Ltrk = np.bincount(prob.obs_pt)      # this rank's tracks (all of them at N = 1)
-        afma = float(108.0 * np.sum(Ltrk * (Ltrk + 1) // 2) + 300.0 * prob.obs_uv.shape[0])
-        k3_s = acc["solve"] / nl
         out = {
             "metric": "BA residuals/sec (LM-iterations/sec x observations); RANSAC hypotheses/sec alongside",
             "value": nobs_total * it_per_s, "unit": "residuals/s",
             "lm_iterations_per_sec": it_per_s,
-            "lm_iterations_per_sec_pcie_inclusive": pcie_it_per_s,
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": 1e3 * elapsed / args.steps,
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
@@ -474,6 +514,17 @@ def main():
                        # library's own communicator; the one-GPU rehearsal has no RCCL communicator: gloo's group size)
                        "n_ranks_seen_by_rccl": (comm.count() if comm is not None else (None if world > 1 else 1)),
                        "n_ranks_in_process_group": (dist.get_world_size() if world > 1 else 1)},
+        }
+    if rank == 0 and args.full:
+        abytes = algorithmic_bytes_linearize(full) if world == 1 else None
+        nl = max(1, acc["launches"])
+        avg_lin = acc["lin_kernel"] / nl
+        achieved = abytes / avg_lin / 1e9 if (abytes and avg_lin > 0) else 0.0
+        Ltrk = np.bincount(prob.obs_pt)      # this rank's tracks (all of them at N = 1)
+        afma = float(108.0 * np.sum(Ltrk * (Ltrk + 1) // 2) + 300.0 * prob.obs_uv.shape[0])
+        k3_s = acc["solve"] / nl
+        out.update({
+            "lm_iterations_per_sec_pcie_inclusive": pcie_it_per_s,
             "roofline": {"kernel": "linearize + Schur assembly launch group (k_lin_schur + k_schur_sum; k_cam_prep only on the first launch of a solve)",
                          "bound": "hbm",
                          "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
@@ -498,13 +549,13 @@ def main():
                             "mfma_utilisation": mfma_util(info["k3_levels"], k3_s)},
             "phase_ms_per_iteration": {"linearize_schur": 1e3 * acc["lin"] / nl, "reduced_solve": 1e3 * acc["solve"] / nl,
                                        "backsub_trial_cost": 1e3 * acc["backsub"] / nl},
-        }
+        })
     R.h.close()
     if comm is not None:
         comm.close()
 
-    host_cores = os.cpu_count() or 1
-    if rank == 0 and world == 1:
+    host_cores = usable_cores()
+    if rank == 0 and world == 1 and args.full:
         # the reference's DEFAULT options run Ceres' inner iterations after every accepted step (bundle_adjustment.h:144):
         # the same problem with use_inner_iterations = true, for the record (not the headline: the inner sweeps are per-block
         # LM solves outside north_star's hot path)
@@ -568,7 +619,7 @@ def main():
                                    "note": "intrinsics_to_optimize = FOCAL_LENGTH | RADIAL_DISTORTION AND use_inner_iterations = true: what "
                                            "BundleAdjustReconstruction runs with inside the reference's pipelines; not the headline configuration"}
         del hb
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         # what one theia_hip_ba_solve call costs end to end (BundleAdjustReconstruction through the boundary: host-side
         # structure analysis + uploads + 25 LM iterations + download), for the record next to the steady-state rate
         o1 = ba.default_options(); o1.max_num_iterations = 25; o1.use_inner_iterations = 0
@@ -593,7 +644,7 @@ def main():
                                 "default_tolerances_total_ms": 1e3 * (t21 - t20), "default_tolerances_iterations": int(s2.num_iterations),
                                 "handle_creation_ms": 1e3 * tc[-1],
                                 "note": "handle creation (host-side plan of 3.0 M observations) ~16 ms of it: see DESIGN.md 3.4"}
-    if rank == 0 and world == 1 and not args.no_c2:
+    if rank == 0 and world == 1 and args.full and not args.no_c2:
         # secondary block: BASELINE.json configs[1] (the round-1 headline), same measurement
         c2 = synth.ba_config("C2")
         R2 = BaRunner(ba, c2, c2.copy())
@@ -614,7 +665,7 @@ def main():
                                                 "backsub_trial_cost": 1e3 * a2["backsub"] / max(1, a2["launches"])}}
         R2.h.close()
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         what = f"the same {nviews}-view / {ntracks}-track problem"
         # all-cores leg: the thread count that runs fastest on this host (the oracle's OpenMP loops stop scaling where
         # the dense reduced matrix and the Jacobian arrays saturate the memory system), each tried on 3 LM iterations
@@ -633,10 +684,10 @@ def main():
                                                 "stops scaling -- at most ncv / (2 x track span) chunks run concurrently, and the Jet buffers saturate the "
                                                 "memory system); the envelope Cholesky of the reduced system is one thread")
 
-    if world == 1 and not args.no_ransac:
+    if world == 1 and args.full and not args.no_ransac:
         out["ransac"] = ransac_block(not args.no_cpu_baseline, host_cores)
         out["relative_position_irls"] = relative_position_block(not args.no_cpu_baseline)
-    elif not args.no_ransac:
+    elif args.full and not args.no_ransac:
         # configs[4] on N GPUs: the 10 000 pairs are dealt round robin over the ranks, no collective on the data path
         rb = ransac_block(False, host_cores, rank=rank, world=world)
         names = ("five_point_relative_pose", "sqpnp_absolute_pose", "dls_absolute_pose")

@@ -5,7 +5,7 @@ set -u
 R="${GRAFT_REPO_ROOT:-/root/repo}"
 cd "$R/pytheiasfm_amd/csrc"
 cp ../libtheia_hip.so /tmp/libtheia_hip.orig.so
-run() { python "$R/bench.py" --steps 24 --warmup 8 --no-cpu-baseline --no-ransac --no-c2 2>/dev/null | python -c "import sys,json; b=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(b['ms_per_step'], b['roofline']['avg_launch_ms'])"; }
+run() { python "$R/bench.py" --full --steps 24 --warmup 8 --no-cpu-baseline --no-ransac --no-c2 2>/dev/null | python -c "import sys,json; b=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(b['ms_per_step'], b['roofline']['avg_launch_ms'])"; }
 echo "== with barriers"; python "$R/scripts/gpu_time_lin_kernel.py" | tail -1
 sed -e '266s/__syncthreads();/__builtin_amdgcn_wave_barrier();/' -e '328s/__syncthreads();/__builtin_amdgcn_wave_barrier();/' ba_fused.hip > /tmp/ba_fused_nb.hip
 cp /tmp/ba_fused_nb.hip ./ba_fused_nb_tmp.hip

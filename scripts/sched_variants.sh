@@ -6,7 +6,7 @@ R="${GRAFT_REPO_ROOT:-/root/repo}"
 cd "$R/pytheiasfm_amd/csrc"
 cp ../libtheia_hip.so /tmp/libtheia_hip.orig.so
 FL="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=fast -freciprocal-math -fno-math-errno -fapprox-func -munsafe-fp-atomics -I../../include -I."
-run() { python "$R/bench.py" --steps 24 --warmup 8 --no-cpu-baseline --no-ransac --no-c2 2>/dev/null | python -c "import sys,json; b=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(b['ms_per_step'], b['phase_ms_per_iteration'], b['roofline']['avg_launch_ms'])"; }
+run() { python "$R/bench.py" --full --steps 24 --warmup 8 --no-cpu-baseline --no-ransac --no-c2 2>/dev/null | python -c "import sys,json; b=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(b['ms_per_step'], b['phase_ms_per_iteration'], b['roofline']['avg_launch_ms'])"; }
 echo "== default"; run
 for strat in max-ilp max-memory-clause; do
   for f in ba_fused ba_kernels; do /opt/rocm/bin/hipcc $FL -mllvm -amdgpu-sched-strategy=$strat -c $f.hip -o /tmp/${f}_$strat.o & done; wait

@@ -357,7 +357,9 @@ def test_host_thread_team_survives_a_fork():
     (generation, worker count, active count) must not be inherited either.  The validation pass of create() runs its
     observation scan on the team (THEIA_HIP_HOST_CHUNK_MIN lowers the size at which it does) before any device call, so it
     is reachable without a GPU: the parent runs it, forks, and the child runs it again -- with an out-of-range index in the
-    LAST part, which only a complete parallel region finds."""
+    LAST part, which only a complete parallel region finds.  The subprocess sees no device (HIP_VISIBLE_DEVICES=-1), so on a
+    GPU host too every create() stops at the device step after the scan, and no fork child of a process that holds a HIP
+    context ever calls the runtime."""
     import subprocess, sys, textwrap
     code = textwrap.dedent("""
         import os, sys
@@ -372,6 +374,8 @@ def test_host_thread_team_survives_a_fork():
             except capi.TheiaHipError as e:
                 return str(e)
         first = create(p)                       # parent: the team's workers start here
+        if first == "ok":
+            sys.exit(5)                         # a device is visible after all: do not fork a process that holds a HIP context
         bad = p.copy(); bad.obs_cam = bad.obs_cam.copy(); bad.obs_cam[-1] = 10 ** 6
         pid = os.fork()
         if pid == 0:
@@ -382,7 +386,8 @@ def test_host_thread_team_survives_a_fork():
         again = create(bad)
         sys.exit(0 if (os.WIFEXITED(status) and os.WEXITSTATUS(status) == 0 and "out of range" in again) else 4)
         """ % ROOT)
-    r = subprocess.run([sys.executable, "-c", code], timeout=120, capture_output=True, text=True)
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1")
+    r = subprocess.run([sys.executable, "-c", code], timeout=120, capture_output=True, text=True, env=env)
     assert r.returncode == 0, (r.returncode, r.stdout[-400:], r.stderr[-400:])
 
 

@@ -1,7 +1,7 @@
 """CPU: the UPnP oracle (oracle/upnp_oracle.h) pinned against (a) the reference's own golden action matrix
 (build_upnp_action_matrix_using_symmetry_test.cc:49-84 -> tests/golden/upnp_action_matrix.json), (b) the known-answer scenes
 and tolerances of the reference's upnp_test.cc, (c) numpy (the action matrix' eigenvectors solve the polynomial system it was
-built from; the template layout is checked against the reference's text when /root/reference is present); plus the estimator's
+built from; the template layout is checked against digests of the reference's text, tests/golden/upnp_template_digest.json); plus the estimator's
 accumulating cost parameters and the RANSAC front end on a synthetic camera rig."""
 import json
 import os
@@ -25,16 +25,61 @@ def test_action_matrix_equals_the_reference_golden():
     assert np.abs(act - want).max() < 2e-5                                         # (the golden is printed to 6 digits)
 
 
-def test_template_layout_reproduces_the_reference_assignments():
-    if not os.path.exists("/root/reference/src/theia/sfm/pose/build_upnp_action_matrix_using_symmetry.cc"):
-        pytest.skip("the reference is not on this machine; the layout header was checked when it was generated")
+def _load(name, path):
     import importlib.util
-    spec = importlib.util.spec_from_file_location("gen_upnp_layout", os.path.join(os.path.dirname(__file__), "..", "scripts", "gen_upnp_layout.py"))
+    spec = importlib.util.spec_from_file_location(name, path)
     mod = importlib.util.module_from_spec(spec); spec.loader.exec_module(mod)
-    txt = mod.emit(*mod.derive())        # derive() asserts: the supports, the input-matrix rule, the 2109 assignments reproduced
+    return mod
+
+
+def test_template_layout_reproduces_the_reference_assignments():
+    """The committed layout header rebuilds the reference's template assignment for assignment, and the input-matrix rule of
+    scripts/gen_upnp_layout.py rebuilds the reference's input matrix term for term: both compared with digests of the
+    reference's text (tests/golden/upnp_template_digest.json, written by tests/golden/make_upnp_template_golden.py)."""
+    import re
     root = os.path.join(os.path.dirname(__file__), "..")
-    assert open(os.path.join(root, "oracle", "upnp_layout.h")).read() == txt
+    gen = _load("gen_upnp_layout", os.path.join(root, "scripts", "gen_upnp_layout.py"))
+    gold_mod = _load("make_upnp_template_golden", os.path.join(GOLD, "make_upnp_template_golden.py"))
+    gold = json.load(open(os.path.join(GOLD, "upnp_template_digest.json")))
+    txt = open(os.path.join(root, "oracle", "upnp_layout.h")).read()
     assert open(os.path.join(root, "pytheiasfm_amd", "csrc", "upnp_layout.h")).read() == txt
+
+    def table(name):
+        body = re.search(r"%s\[\d+\](?:\[4\])? = \{(.*?)\};" % name, txt, re.S).group(1)
+        return [tuple(int(v) for v in m) for m in re.findall(r"\{(-?\d+), (-?\d+), (-?\d+), (-?\d+)\}", body)] if "{" in body \
+            else [int(v) for v in body.split(",")]
+    row_eq, row_mul, col_mono = table("kRowEq"), table("kRowMul"), table("kColMono")
+    nent = int(re.search(r"kEntries = (\d+);", txt).group(1))
+    assert len(row_eq) == 141 and len(row_mul) == 141 and len(col_mono) == 149
+    assert len(set(col_mono)) == 149 and all(min(e) >= 0 for e in col_mono)
+    assert gen.emit(row_eq, row_mul, col_mono, nent) == txt            # the header is the generator's output for this layout
+    # the template: every row places exactly the support of its equation, at the columns of multiplier x input monomial
+    mono = gen.input_monomials()
+    back = {e: c for c, e in enumerate(col_mono)}
+    rebuilt = set()
+    for r in range(141):
+        sup = [10, 12, 15, 19, 23] if row_eq[r] == 7 else sorted({row_eq[r], 7, 8, 9} | set(range(11, 24)))
+        for j in sup:
+            rebuilt.add((r, back[tuple(x + y for x, y in zip(row_mul[r], mono[j]))], row_eq[r], j))
+    assert len(rebuilt) == nent == gold["template"]["count"]
+    assert gold_mod.digest(rebuilt) == (gold["template"]["count"], gold["template"]["sha256"])
+    # the input matrix: the cost-derivative rows by the rule (terms ordered by q descending), the linear columns
+    # 2 b^T d s / d q_i, and the constant rows q_i (|q|^2 - 1)
+    inp, fixed = [], []
+    for i in range(4):
+        for j in range(24):
+            if j < 20:
+                inp.append((i, j, tuple(gen.derivative_terms(i, mono[j])), ()))
+            else:
+                lin = tuple((2 * sp[i], p) for p, sp in enumerate(gen.S_MONO)
+                            if sp[i] and tuple(x - (1 if t == i else 0) for t, x in enumerate(sp)) == mono[j])
+                inp.append((i, j, (), lin))
+        for k in range(4):
+            e = [0, 0, 0, 0]; e[k] += 2; e[i] += 1
+            fixed.append((4 + i, mono.index(tuple(e)), 1))
+        fixed.append((4 + i, 20 + i, -1))
+    assert gold_mod.digest(inp) == (gold["input"]["count"], gold["input"]["sha256"])
+    assert gold_mod.digest(fixed) == (gold["fixed"]["count"], gold["fixed"]["sha256"])
 
 
 def test_template_is_a_set_of_multiples_of_the_input_equations():
