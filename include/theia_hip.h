@@ -688,6 +688,46 @@ int theia_hip_ransac_estimate_batch(const theia_ransac_batch* batch,
                                     const theia_ransac_params* params,
                                     theia_ransac_result* result);
 
+/* ---- generator state carried across Estimate() calls
+ * The reference keeps ONE thread_local std::mt19937 (util/random.cc:46-66); every RandomNumberGenerator object is a view onto
+ * it, and a pipeline hands one generator to every estimate it makes, so call k starts where call k - 1 stopped.  A
+ * theia_rng_state stands for that generator of one reference thread, owned by the caller.  mt + pos are exactly what
+ * libstdc++'s operator<<(std::mt19937) prints (the 624 words of _M_x, then _M_p), and numpy's RandomState.get_state() key and
+ * pos: a host moves the state to and from a real std::mt19937 through a stringstream. */
+typedef struct theia_rng_state {
+  uint32_t mt[624];             /* std::mt19937 words, in libstdc++'s order (_M_x) */
+  int32_t pos;                  /* libstdc++ _M_p, 0..624; 624 right after seeding */
+  int32_t p4pfr_static_seeded;  /* the P4Pfr solver's function-static RandomNumberGenerator(42) has already run */
+  int64_t dls_calls;            /* DlsPnp / gDLS calls so far on this stream (4 glibc rand() draws each) */
+} theia_rng_state;
+
+/* Host only (no GPU).  seed = RandomNumberGenerator(seed) / Seed(seed): resets mt and pos only.  rand_int = n draws of
+ * RandInt(lo, hi) (uniform_int_distribution<int>, libstdc++'s Lemire reduction), rand_double = n draws of RandDouble(lo, hi)
+ * (generate_canonical<double, 53>: two words per draw), discard = `words` raw 32-bit outputs.  An argument error (NULL state,
+ * pos outside [0, 624], n < 0, lo > hi) leaves the state untouched. */
+int theia_hip_rng_seed(theia_rng_state* state, uint32_t seed);
+int theia_hip_rng_rand_int(theia_rng_state* state, int32_t lo, int32_t hi, int32_t n, int32_t* out);
+int theia_hip_rng_rand_double(theia_rng_state* state, double lo, double hi, int32_t n, double* out);
+int theia_hip_rng_discard(theia_rng_state* state, uint64_t words);
+
+typedef struct theia_ransac_streams {
+  int32_t num_streams;
+  const int32_t* stream_of_problem; /* [num_problems]; NULL = every problem on stream 0 */
+  theia_rng_state* states;          /* [num_streams], read at entry, advanced in place */
+} theia_ransac_streams;
+
+/* theia_hip_ransac_estimate_batch with the generators carried: the problems of one stream are successive Estimate() calls
+ * of one reference thread, in increasing problem index; streams are independent threads.  After the call every state is
+ * what the reference generator holds after that stream's last Estimate(): RANSAC / LMED take m RandInt per iteration (a
+ * fresh index permutation per call), PROSAC its draws (its sample counter restarting per call), EXHAUSTIVE none; P4Pfr three
+ * RandDouble after every sample, re-seeded with 42 after its first sample when p4pfr_static_seeded == 0 (which it then sets;
+ * this replaces estimator_params[4], of which only the four limits are read); DLS / gDLS call k of a problem uses the
+ * Macaulay terms of call dls_calls + k, and dls_calls grows by num_iterations.  LO refinement draws nothing.  params.seed
+ * is not read and batch->seeds must be NULL.  An undersized problem gets success = 0 and leaves its stream untouched.  On
+ * an argument error (a stream id out of range, pos outside [0, 624], a NULL state) nothing is written. */
+int theia_hip_ransac_estimate_streams(const theia_ransac_batch* batch, const theia_ransac_params* params,
+                                      const theia_ransac_streams* streams, theia_ransac_result* result);
+
 /* Directly bound minimal solvers (src/pytheia/sfm/sfm.cc:573-592,
  * pose_wrapper.cc:166-173).  Batched: `num` independent minimal problems.
  *  five point: in = [num][5][4] (x1 y1 x2 y2), out E = [num][10][9],

@@ -142,6 +142,16 @@ class RansacResult(C.Structure):
                 ("time_fit_seconds", C.c_double), ("time_score_seconds", C.c_double)]
 
 
+class RngState(C.Structure):
+    """theia_rng_state: one reference thread's std::mt19937 (libstdc++ _M_x, _M_p) + the P4Pfr / DLS counters."""
+    _fields_ = [("mt", C.c_uint32 * 624), ("pos", C.c_int32), ("p4pfr_static_seeded", C.c_int32), ("dls_calls", C.c_int64)]
+
+
+class RansacStreams(C.Structure):
+    """theia_ransac_streams."""
+    _fields_ = [("num_streams", C.c_int32), ("stream_of_problem", c_int32_p), ("states", C.POINTER(RngState))]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p)
 
 # every symbol include/theia_hip.h declares (checked by tests/test_capi_symbols.py)
@@ -154,6 +164,7 @@ EXPORTED_SYMBOLS = [
     "theia_hip_optimize_relative_position_batch", "theia_hip_rccl_comm_destroy", "theia_hip_rccl_comm_count", "theia_hip_ba_set_rccl", "theia_hip_dense_spd_solve", "theia_ransac_params_default",
     "theia_hip_ransac_estimate_batch", "theia_hip_five_point_relative_pose",
     "theia_hip_pose_from_three_points", "theia_hip_sqpnp", "theia_hip_dls_pnp", "theia_hip_dls_macaulay_terms", "theia_hip_four_point_pose_and_focal_length", "theia_hip_four_point_focal_length_radial_distortion", "theia_hip_four_point_focal_length_radial_distortion_ex", "theia_hip_release_scratch", "theia_hip_guided_knn", "theia_hip_randint_stream", "theia_hip_selftest_wave_primitives",
+    "theia_hip_rng_seed", "theia_hip_rng_rand_int", "theia_hip_rng_rand_double", "theia_hip_rng_discard", "theia_hip_ransac_estimate_streams",
 ]
 
 _lib = None

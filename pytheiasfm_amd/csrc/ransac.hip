@@ -1277,22 +1277,36 @@ void dls_terms(std::vector<double>& u, dls::GlibcRand& gen, size_t ncalls) {
 // ------------------------------------------------------------------ host side
 // std::mt19937 + libstdc++ uniform_int_distribution<int> (Lemire), i.e. the
 // stream RandomNumberGenerator::RandInt draws (util/random.cc:46-84).
+// mt + idx are libstdc++'s _M_x + _M_p (theia_rng_state); `twists` counts regenerations, so drawn() is the number of words taken
+// since the last seed (the streams driver's round accounting)
 struct Mt19937 {
   uint32_t mt[624];
   int idx;
+  uint64_t twists = 0;
   void seed(uint32_t s) {
     mt[0] = s;
     for (int i = 1; i < 624; ++i) mt[i] = 1812433253u * (mt[i - 1] ^ (mt[i - 1] >> 30)) + (uint32_t)i;
     idx = 624;
+    twists = 0;
+  }
+  void twist() {
+    for (int i = 0; i < 624; ++i) {
+      const uint32_t y = (mt[i] & 0x80000000u) | (mt[(i + 1) % 624] & 0x7fffffffu);
+      mt[i] = mt[(i + 397) % 624] ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
+    }
+    idx = 0;
+    twists++;
+  }
+  uint64_t drawn() const { return twists * 624 + (uint64_t)idx; }
+  void discard(uint64_t words) {   // = std::mt19937::discard: the tempering of the skipped words is never needed
+    while (words > 0) {
+      if (idx >= 624) twist();
+      const uint64_t k = std::min<uint64_t>(words, (uint64_t)(624 - idx));
+      idx += (int)k; words -= k;
+    }
   }
   uint32_t next() {
-    if (idx >= 624) {
-      for (int i = 0; i < 624; ++i) {
-        const uint32_t y = (mt[i] & 0x80000000u) | (mt[(i + 1) % 624] & 0x7fffffffu);
-        mt[i] = mt[(i + 397) % 624] ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
-      }
-      idx = 0;
-    }
+    if (idx >= 624) twist();
     uint32_t y = mt[idx++];
     y ^= y >> 11; y ^= (y << 7) & 0x9d2c5680u; y ^= (y << 15) & 0xefc60000u; y ^= y >> 18;
     return y;
@@ -1446,6 +1460,26 @@ struct ProblemState {
   bool round_done, best_refined;
   double pending_ratio;
   int num_lo;
+  bool p4pfr_first;   // the P4Pfr solver's static generator re-seeds this problem's stream with 42 after its first sample
+  int last_k;         // iterations of the last finished round
+};
+// streams mode only (StreamInit; kept apart so that the seeded path does not initialise it): the generator at the start of
+// the current round (or at the P4Pfr re-seed inside it), the words iteration b of the round had taken since then (cum[b])
+struct StreamRound {
+  Mt19937 anchor;
+  uint64_t anchor_drawn = 0;
+  std::vector<uint64_t> cum;
+};
+
+// theia_hip_ransac_estimate_streams: the problems of one driver call are the head problems of their streams, one per stream
+// (every problem starts where its stream stands).  gen[stream[p]] is the generator problem p starts from; the driver
+// overwrites it with the generator after exactly num_iterations samples.  Per stream the P4Pfr first-call flag and (DLS /
+// gDLS) the rand() stream positioned at the problem's first call.
+struct StreamInit {
+  Mt19937* gen;
+  const int* stream;
+  const uint8_t* p4pfr_first;
+  const dls::GlibcRand* dls_start;   // NULL unless the estimator is DLS / gDLS
 };
 
 #define HIP_TRYR(expr)                                                                               \
@@ -1460,6 +1494,9 @@ struct ProblemState {
 }  // namespace thip
 
 using namespace thip;
+
+static int ransac_run(const theia_ransac_batch* batch, const theia_ransac_params* params, theia_ransac_result* result,
+                      const StreamInit* si);
 
 extern "C" {
 
@@ -1477,6 +1514,14 @@ void theia_ransac_params_default(theia_ransac_params* p) {
 
 int theia_hip_ransac_estimate_batch(const theia_ransac_batch* batch, const theia_ransac_params* params,
                                     theia_ransac_result* result) {
+  return ransac_run(batch, params, result, nullptr);
+}
+
+}  // extern "C"
+
+// the host driver of both entry points: si == NULL is the seeded batch (problem i: RandomNumberGenerator(seed + i))
+static int ransac_run(const theia_ransac_batch* batch, const theia_ransac_params* params, theia_ransac_result* result,
+                      const StreamInit* si) {
   if (!batch || !params || !result) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "null argument");
   const theia_ransac_params& P = *params;
   // SampleConsensusEstimator ctor CHECKs (sample_consensus_estimator.h:217-223)
@@ -1535,7 +1580,7 @@ int theia_hip_ransac_estimate_batch(const theia_ransac_batch* batch, const theia
     if (!batch->estimator_params)
       return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "the radial-distortion absolute-pose estimator needs estimator_params = {max focal length, min focal length, max distortion, min distortion, first call (0 / 1)}");
     for (int k = 0; k < 4; ++k) p4pfr_limits[k] = batch->estimator_params[k];
-    p4pfr_first_call = batch->estimator_params[4] != 0.0;
+    p4pfr_first_call = !si && batch->estimator_params[4] != 0.0;   // (streams: per problem, StreamInit::p4pfr_first)
     // the reference CHECKs these (four_point_focal_length_radial_distortion.cc:82-90)
     if (!(p4pfr_limits[1] >= 0.0 && p4pfr_limits[0] >= 0.0 && p4pfr_limits[0] >= p4pfr_limits[1] && p4pfr_limits[2] <= 0.0 && p4pfr_limits[3] <= 0.0 &&
           p4pfr_limits[2] <= p4pfr_limits[3]))
@@ -1643,10 +1688,16 @@ int theia_hip_ransac_estimate_batch(const theia_ransac_batch* batch, const theia
   }
   std::vector<int> best_samples_all((size_t)nprob * kMaxSample, 0), best_slot_all(nprob, -1);
   std::vector<ProblemState> S(nprob);
+  std::vector<StreamRound> SR(si ? nprob : 0);
+  std::vector<dls::GlibcRand> SD(si && si->dls_start ? nprob : 0);   // streams: every problem's own rand() stream (DLS / gDLS)
   host_parallel_for(nprob, [&](int p) {   // (the generator's 624-word seeding and the index permutation of every problem: ~1 us each)
     ProblemState& s = S[p];
     s.n = (int)(batch->offsets[p + 1] - batch->offsets[p]);
-    s.rng.seed(batch->seeds ? batch->seeds[p] : P.seed + (uint32_t)p);
+    if (si) s.rng = si->gen[si->stream[p]];
+    else s.rng.seed(batch->seeds ? batch->seeds[p] : P.seed + (uint32_t)p);
+    s.p4pfr_first = si ? si->p4pfr_first[si->stream[p]] != 0 : p4pfr_first_call;
+    s.last_k = 0;
+    if (si && si->dls_start) SD[p] = si->dls_start[si->stream[p]];
     s.idx.resize(s.n);
     for (int i = 0; i < s.n; ++i) s.idx[i] = i;
     s.best_cost = std::numeric_limits<double>::max();
@@ -1759,31 +1810,37 @@ int theia_hip_ransac_estimate_batch(const theia_ransac_batch* batch, const theia
     host_parallel_for(cn, [&](int q) {
       ProblemState& s = S[c0 + q];
       int* out = smp.data() + (size_t)q * B * m;
+      StreamRound* sr = si ? &SR[c0 + q] : nullptr;
+      if (sr && s.round_iters > 0) { sr->anchor = s.rng; sr->anchor_drawn = s.rng.drawn(); sr->cum.resize(s.round_iters); }
       // P4Pfr takes three RandDouble(-0.5, 0.5) from the SAME generator after every sample (every RandomNumberGenerator object
       // shares one std::mt19937, util/random.cc:46-66); the solver's static RandomNumberGenerator(42) re-seeds that generator the
       // first time it runs in a process (four_point_focal_length_radial_distortion.cc:134-138)
       auto p4pfr_draws = [&](int b) {
         if (!p4pfr_est) return;
-        if (p4pfr_first_call && s.it + b == 0) s.rng.seed(42);
+        if (s.p4pfr_first && s.it + b == 0) {
+          s.rng.seed(42);
+          if (sr) { sr->anchor = s.rng; sr->anchor_drawn = s.rng.drawn(); }   // (a problem ends after >= 1 iteration: past this point)
+        }
         double v[3];
         for (int k = 0; k < 3; ++k) v[k] = s.rng.rand_double(-0.5, 0.5);
         p4pfr_rotation_from_draws(v, rotb.data() + ((size_t)q * B + b) * 9);
       };
       for (int b = 0; b < s.round_iters; ++b) {
-        if (P.ransac_type == THEIA_RANSAC_PROSAC) { prosac_sample(s.rng, s.n, m, s.kth++, out + (size_t)b * m); p4pfr_draws(b); continue; }
-        if (P.ransac_type == THEIA_RANSAC_EXHAUSTIVE) {   // all pairs (i, j > i), wrapping around
+        if (P.ransac_type == THEIA_RANSAC_PROSAC) { prosac_sample(s.rng, s.n, m, s.kth++, out + (size_t)b * m); p4pfr_draws(b); }
+        else if (P.ransac_type == THEIA_RANSAC_EXHAUSTIVE) {   // all pairs (i, j > i), wrapping around
           out[(size_t)b * 2] = s.ex_i; out[(size_t)b * 2 + 1] = s.ex_j;
           if (++s.ex_j >= s.n) {
             if (++s.ex_i >= s.n - 1) s.ex_i = 0;
             s.ex_j = s.ex_i + 1;
           }
-          continue;
+        } else {
+          for (int i = 0; i < m; ++i) {
+            std::swap(s.idx[i], s.idx[s.rng.rand_int(i, s.n - 1)]);
+            out[(size_t)b * m + i] = s.idx[i];
+          }
+          p4pfr_draws(b);
         }
-        for (int i = 0; i < m; ++i) {
-          std::swap(s.idx[i], s.idx[s.rng.rand_int(i, s.n - 1)]);
-          out[(size_t)b * m + i] = s.idx[i];
-        }
-        p4pfr_draws(b);
+        if (sr) sr->cum[b] = s.rng.drawn() - sr->anchor_drawn;
       }
       for (size_t e = (size_t)s.round_iters * m; e < (size_t)B * m; ++e) out[e] = 0;   // iterations beyond this problem's round
     });
@@ -1833,10 +1890,19 @@ int theia_hip_ransac_estimate_batch(const theia_ransac_batch* batch, const theia
       HIP_TRYR(hipEventRecord(ev0, st));
       if (dls_est) {
         h_iter_base.assign(cn, 0);
-        int calls = 0;
-        for (int q = 0; q < cn; ++q) { h_iter_base[q] = S[c0 + q].it; calls = std::max(calls, S[c0 + q].it + S[c0 + q].round_iters); }
-        const size_t had = h_dls_u.size();
-        dls_terms(h_dls_u, dls_gen, (size_t)calls);
+        size_t had = h_dls_u.size();
+        if (si) {   // streams: every problem's calls continue its own rand() stream -- this round's terms, problem after problem
+          h_dls_u.clear(); had = (size_t)-1;
+          for (int q = 0; q < cn; ++q) {
+            ProblemState& s = S[c0 + q];
+            h_iter_base[q] = (int)(h_dls_u.size() / 4);
+            for (int k = 0; k < 4 * s.round_iters; ++k) h_dls_u.push_back(dls::macaulay_term_from_rand(SD[c0 + q].next()));
+          }
+        } else {
+          int calls = 0;
+          for (int q = 0; q < cn; ++q) { h_iter_base[q] = S[c0 + q].it; calls = std::max(calls, S[c0 + q].it + S[c0 + q].round_iters); }
+          dls_terms(h_dls_u, dls_gen, (size_t)calls);
+        }
         if ((rc = d_dls_action.ensure(nh * 729)) || (rc = d_dls_tfac.ensure(nh * 36)) || (rc = d_dls_ok.ensure(nh)) ||
             (rc = d_iter_base.ensure(cn)))
           return rc;
@@ -2046,6 +2112,7 @@ int theia_hip_ransac_estimate_batch(const theia_ransac_batch* batch, const theia
           if (!paused) {
             s.round_done = true;
             s.it = s.base_it + s.rb;
+            s.last_k = s.rb;
             if (s.it >= s.max_iterations) s.done = true;
           }
           n_hyp += my_hyp; n_scored += my_scored;
@@ -2162,11 +2229,186 @@ int theia_hip_ransac_estimate_batch(const theia_ransac_batch* batch, const theia
   }
   result->time_fit_score_seconds = fit_score_ms * 1e-3;
   result->time_fit_seconds = fit_ms * 1e-3; result->time_score_seconds = score_ms * 1e-3;
+  if (si) {   // the generator after exactly num_iterations samples: the last round's start, advanced by the words its finished iterations took
+    host_parallel_for(nprob, [&](int p) {   // (a discard may regenerate the 624 words: ~3 us a problem)
+      const ProblemState& s = S[p];
+      if (s.it == 0) return;   // undersized, or no iteration at all: nothing drawn
+      Mt19937& g = si->gen[si->stream[p]];
+      g = SR[p].anchor;
+      g.discard(s.last_k > 0 ? SR[p].cum[s.last_k - 1] : 0);
+    });
+  }
   if (host_timing) {
     auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     std::fprintf(stderr, "[theia_hip ransac] call: set-up %.1f ms, rounds %.1f ms, best models + inlier masks + results %.1f ms\n", ms(t_entry, t_loop),
                  ms(t_loop, t_final), ms(t_final, std::chrono::steady_clock::now()));
   }
+  return 0;
+}
+
+static bool rng_state_ok(const theia_rng_state* st) { return st && st->pos >= 0 && st->pos <= 624; }
+static void rng_load(Mt19937& g, const theia_rng_state& st) {
+  std::memcpy(g.mt, st.mt, sizeof(g.mt)); g.idx = st.pos; g.twists = 0;
+}
+static void rng_store(theia_rng_state& st, const Mt19937& g) { std::memcpy(st.mt, g.mt, sizeof(g.mt)); st.pos = g.idx; }
+
+extern "C" {
+
+// Every problem of one stream is an Estimate() call that starts where the previous one of its stream stopped, so the k-th
+// problems of all streams ("wave" k) are independent of each other and run as one call of the batch driver; wave k + 1
+// starts from the states wave k handed back.  A wave's problems are contiguous in the batch when the streams are
+// interleaved (or one problem each); otherwise their data are gathered.
+int theia_hip_ransac_estimate_streams(const theia_ransac_batch* batch, const theia_ransac_params* params,
+                                      const theia_ransac_streams* streams, theia_ransac_result* result) {
+  if (!batch || !params || !streams || !result) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  if (batch->seeds) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "the streams entry point draws from the caller's generators: batch->seeds must be NULL");
+  const int nprob = batch->num_problems, ns = streams->num_streams;
+  if (nprob < 0 || (nprob > 0 && (!batch->offsets || !batch->data))) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "bad batch");
+  if (ns < 1 || !streams->states) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "streams: num_streams >= 1 and a states array are needed");
+  for (int k = 0; k < ns; ++k) {
+    if (!rng_state_ok(&streams->states[k])) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "stream %d: pos outside [0, 624]", k);
+    if (streams->states[k].dls_calls < 0) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "stream %d: dls_calls < 0", k);
+  }
+  if (nprob > 0 && (!result->success || !result->models || !result->num_inliers || !result->inlier_mask ||
+                    !result->num_iterations || !result->confidence))
+    return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "null result array");
+  std::vector<int> sid(nprob, 0), rank(nprob, 0), count(ns, 0);
+  for (int p = 0; p < nprob; ++p) {
+    const int k = streams->stream_of_problem ? streams->stream_of_problem[p] : 0;
+    if (k < 0 || k >= ns) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "problem %d: stream id %d outside [0, %d)", p, k, ns);
+    if (batch->offsets[p + 1] - batch->offsets[p] <= 0) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "Cannot perform estimation with 0 data measurements!");
+    sid[p] = k; rank[p] = count[k]++;
+  }
+  const int est = batch->estimator;
+  const bool dls_est = est == THEIA_EST_ABSOLUTE_POSE_DLS || est == THEIA_EST_SIMILARITY_2D3D;
+  const bool p4pfr_est = est == THEIA_EST_RADIAL_DIST_UNCALIBRATED_ABSOLUTE_POSE;
+  double p4pfr_params[5] = {0.0, 0.0, 0.0, 0.0, 0.0};   // the four limits; the first-call flag comes from the streams
+  if (p4pfr_est && batch->estimator_params) std::memcpy(p4pfr_params, batch->estimator_params, sizeof(double) * 4);
+  theia_ransac_batch sub = *batch;
+  if (p4pfr_est && batch->estimator_params) sub.estimator_params = p4pfr_params;
+  if (nprob == 0) { sub.num_problems = 0; return ransac_run(&sub, params, result, nullptr); }   // (the parameter checks)
+  const int ds = (est >= 0 && est <= THEIA_EST_RADIAL_DIST_UNCALIBRATED_ABSOLUTE_POSE) ? datum_size(est) : 1;
+
+  // the streams, worked on in copies: the caller's states change only when every wave succeeded
+  std::vector<Mt19937> gen(ns);
+  std::vector<uint8_t> first(ns);   // the P4Pfr solver's static generator has not run on this stream yet
+  std::vector<int64_t> dls_calls(ns);
+  std::vector<dls::GlibcRand> dls_gen(dls_est ? ns : 0);
+  for (int k = 0; k < ns; ++k) {
+    rng_load(gen[k], streams->states[k]);
+    first[k] = streams->states[k].p4pfr_static_seeded == 0;
+    dls_calls[k] = streams->states[k].dls_calls;
+    if (dls_est)
+      for (int64_t i = 0; i < 4 * dls_calls[k]; ++i) (void)dls_gen[k].next();
+  }
+  const int nwaves = *std::max_element(count.begin(), count.end());
+  std::vector<std::vector<int>> waves(nwaves);
+  for (int p = 0; p < nprob; ++p) waves[rank[p]].push_back(p);
+
+  result->hypotheses_evaluated = 0; result->models_scored = 0; result->time_fit_score_seconds = 0.0;
+  result->time_fit_seconds = 0.0; result->time_score_seconds = 0.0;
+  constexpr int kS = THEIA_RANSAC_MODEL_STRIDE;
+  std::vector<int64_t> off;
+  std::vector<double> gathered;
+  std::vector<int> wsid;
+  std::vector<int32_t> r_succ, r_ninl, r_nit, r_nlo;
+  std::vector<double> r_models, r_conf;
+  std::vector<uint8_t> r_mask;
+  for (const std::vector<int>& W : waves) {
+    const int nw = (int)W.size(), p0 = W[0];
+    bool contiguous = true;
+    for (int i = 1; i < nw; ++i) contiguous &= W[i] == p0 + i;
+    off.assign(nw + 1, 0);
+    for (int i = 0; i < nw; ++i) off[i + 1] = off[i] + (batch->offsets[W[i] + 1] - batch->offsets[W[i]]);
+    const double* data = batch->data + (size_t)batch->offsets[p0] * ds;
+    theia_ransac_result r{};
+    if (contiguous) {   // the wave's slice of the batch: data and results in place
+      r.success = result->success + p0; r.models = result->models + (size_t)p0 * kS; r.num_inliers = result->num_inliers + p0;
+      r.inlier_mask = result->inlier_mask + batch->offsets[p0]; r.num_iterations = result->num_iterations + p0;
+      r.confidence = result->confidence + p0; r.num_lo_iterations = result->num_lo_iterations ? result->num_lo_iterations + p0 : nullptr;
+    } else {
+      gathered.resize((size_t)off[nw] * ds);
+      for (int i = 0; i < nw; ++i)
+        std::memcpy(gathered.data() + (size_t)off[i] * ds, batch->data + (size_t)batch->offsets[W[i]] * ds, sizeof(double) * (size_t)(off[i + 1] - off[i]) * ds);
+      data = gathered.data();
+      r_succ.assign(nw, 0); r_ninl.assign(nw, 0); r_nit.assign(nw, 0); r_nlo.assign(nw, 0);
+      r_models.assign((size_t)nw * kS, 0.0); r_conf.assign(nw, 0.0); r_mask.assign((size_t)off[nw], 0);
+      r.success = r_succ.data(); r.models = r_models.data(); r.num_inliers = r_ninl.data(); r.inlier_mask = r_mask.data();
+      r.num_iterations = r_nit.data(); r.confidence = r_conf.data(); r.num_lo_iterations = r_nlo.data();
+    }
+    wsid.resize(nw);
+    for (int i = 0; i < nw; ++i) wsid[i] = sid[W[i]];
+    sub.num_problems = nw; sub.offsets = off.data(); sub.data = data; sub.seeds = nullptr;
+    const StreamInit si{gen.data(), wsid.data(), first.data(), dls_est ? dls_gen.data() : nullptr};
+    const int rc = ransac_run(&sub, params, &r, &si);   // (advances gen[] of the wave's streams)
+    if (rc) return rc;
+    if (!contiguous) {
+      for (int i = 0; i < nw; ++i) {
+        const int p = W[i];
+        result->success[p] = r_succ[i]; result->num_inliers[p] = r_ninl[i]; result->num_iterations[p] = r_nit[i];
+        result->confidence[p] = r_conf[i];
+        if (result->num_lo_iterations) result->num_lo_iterations[p] = r_nlo[i];
+        std::memcpy(result->models + (size_t)p * kS, r_models.data() + (size_t)i * kS, sizeof(double) * kS);
+        std::memcpy(result->inlier_mask + batch->offsets[p], r_mask.data() + off[i], (size_t)(off[i + 1] - off[i]));
+      }
+    }
+    for (int i = 0; i < nw; ++i) {
+      const int k = wsid[i], nit = r.num_iterations[i];
+      if (nit > 0) {   // (an undersized problem leaves its stream as it was)
+        if (p4pfr_est) first[k] = 0;
+        if (dls_est) {
+          dls_calls[k] += nit;
+          for (int64_t j = 0; j < 4 * (int64_t)nit; ++j) (void)dls_gen[k].next();
+        }
+      }
+    }
+    result->hypotheses_evaluated += r.hypotheses_evaluated; result->models_scored += r.models_scored;
+    result->time_fit_score_seconds += r.time_fit_score_seconds;
+    result->time_fit_seconds += r.time_fit_seconds; result->time_score_seconds += r.time_score_seconds;
+  }
+  for (int k = 0; k < ns; ++k) {
+    theia_rng_state& st = streams->states[k];
+    rng_store(st, gen[k]);
+    if (p4pfr_est) st.p4pfr_static_seeded = !first[k];
+    st.dls_calls = dls_calls[k];
+  }
+  return 0;
+}
+
+int theia_hip_rng_seed(theia_rng_state* state, uint32_t seed) {
+  if (!state) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "null state");
+  Mt19937 g;
+  g.seed(seed);
+  rng_store(*state, g);
+  return 0;
+}
+
+int theia_hip_rng_rand_int(theia_rng_state* state, int32_t lo, int32_t hi, int32_t n, int32_t* out) {
+  if (!rng_state_ok(state)) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "null state or pos outside [0, 624]");
+  if (n < 0 || (n > 0 && !out) || lo > hi) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "bad argument");
+  Mt19937 g;
+  rng_load(g, *state);
+  for (int32_t i = 0; i < n; ++i) out[i] = g.rand_int(lo, hi);
+  rng_store(*state, g);
+  return 0;
+}
+
+int theia_hip_rng_rand_double(theia_rng_state* state, double lo, double hi, int32_t n, double* out) {
+  if (!rng_state_ok(state)) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "null state or pos outside [0, 624]");
+  if (n < 0 || (n > 0 && !out) || !(lo <= hi)) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "bad argument");
+  Mt19937 g;
+  rng_load(g, *state);
+  for (int32_t i = 0; i < n; ++i) out[i] = g.rand_double(lo, hi);
+  rng_store(*state, g);
+  return 0;
+}
+
+int theia_hip_rng_discard(theia_rng_state* state, uint64_t words) {
+  if (!rng_state_ok(state)) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "null state or pos outside [0, 624]");
+  Mt19937 g;
+  rng_load(g, *state);
+  g.discard(words);
+  rng_store(*state, g);
   return 0;
 }
 

@@ -9,6 +9,7 @@ Same names / argument order as the pybind wrappers
 import copy
 import ctypes as C
 import enum
+import threading
 import time
 
 import numpy as np
@@ -41,10 +42,70 @@ EST_RIGID_TRANSFORMATION_2D3D = 15
 EST_RADIAL_DIST_UNCALIBRATED_ABSOLUTE_POSE = 16
 
 
+_MT_DEFAULT_SEED = 5489   # std::mt19937::default_seed: a thread's generator before anything seeds it
+
+
+class RandomNumberGenerator:
+    """util/random.h:47-80 as bound in solvers.cc:68-75.  The reference keeps ONE thread_local std::mt19937
+    (util/random.cc:46-66) and every RandomNumberGenerator object is a view onto it; here every object in one Python thread
+    shares one thread-local theia_rng_state (include/theia_hip.h), which the Estimate* wrappers advance when
+    RansacParameters.rng is set.  RandomNumberGenerator() seeds from the clock, as the reference does."""
+
+    _tls = threading.local()
+
+    def __init__(self, seed=None):
+        if seed is None:
+            seed = time.time_ns()   # system_clock::now().time_since_epoch().count() (nanoseconds), truncated to unsigned
+        self.Seed(seed)
+
+    @classmethod
+    def thread_state(cls):
+        """The calling thread's theia_rng_state (capi.RngState), created as std::mt19937 default-constructs."""
+        st = getattr(cls._tls, "state", None)
+        if st is None:
+            st = capi.RngState()
+            capi.check(_sig().theia_hip_rng_seed(C.byref(st), _MT_DEFAULT_SEED))
+            cls._tls.state = st
+        return st
+
+    def Seed(self, seed):
+        capi.check(_sig().theia_hip_rng_seed(C.byref(self.thread_state()), int(seed) & 0xFFFFFFFF))
+
+    def RandInt(self, lower, upper):
+        out = C.c_int32(0)
+        capi.check(_sig().theia_hip_rng_rand_int(C.byref(self.thread_state()), int(lower), int(upper), 1, C.byref(out)))
+        return out.value
+
+    def RandDouble(self, lower, upper):
+        out = C.c_double(0.0)
+        capi.check(_sig().theia_hip_rng_rand_double(C.byref(self.thread_state()), float(lower), float(upper), 1, C.byref(out)))
+        return out.value
+
+    def Discard(self, words):
+        capi.check(_sig().theia_hip_rng_discard(C.byref(self.thread_state()), int(words)))
+
+    def get_state(self):
+        """The generator as numpy's MT19937 tuple (RandomState.get_state()): ('MT19937', key, pos, 0, 0.0)."""
+        st = self.thread_state()
+        return ("MT19937", np.array(st.mt[:], dtype=np.uint32), int(st.pos), 0, 0.0)
+
+    def set_state(self, state):
+        """From numpy's MT19937 tuple (or a RandomState); the P4Pfr / DLS counters of the thread are kept."""
+        if isinstance(state, np.random.RandomState):
+            state = state.get_state(legacy=True)
+        name, key, pos = state[0], np.asarray(state[1], dtype=np.uint32), int(state[2])
+        if name != "MT19937" or key.shape != (624,) or not 0 <= pos <= 624:
+            raise capi.TheiaHipError(capi.THEIA_HIP_ERR_INVALID_ARGUMENT, "not an MT19937 state with 624 words and pos in [0, 624]")
+        st = self.thread_state()
+        st.mt[:] = [int(v) for v in key]
+        st.pos = pos
+
+
 class RansacParameters:
     """solvers/sample_consensus_estimator.h:58-126, same fields and defaults.
-    `rng` is not bound to Python in the reference either (solvers.cc:89-102);
-    `seed` is this backend's handle on RandomNumberGenerator(seed)."""
+    `seed` is this backend's handle on RandomNumberGenerator(seed): every Estimate* call starts a fresh generator from it.
+    `rng` (default None) is the reference's shared generator instead: when it holds a RandomNumberGenerator, every
+    Estimate* call draws from the calling thread's generator and leaves it where the reference's would stand."""
 
     def __init__(self):
         self.error_thresh = -1.0
@@ -57,6 +118,7 @@ class RansacParameters:
         self.use_lo = False
         self.lo_start_iterations = 50
         self.seed = 0
+        self.rng = None
         self.ransac_type = RansacType.RANSAC  # set by the Estimate* wrappers from their ransac_type argument
 
     def to_c(self):
@@ -117,14 +179,34 @@ def _sig():
                                                                           capi.c_double_p, capi.c_int32_p, capi.c_int32_p]
         L.theia_hip_dls_macaulay_terms.restype = None
         L.theia_ransac_params_default.argtypes = [C.POINTER(capi.RansacParams)]
+        L.theia_hip_ransac_estimate_streams.argtypes = [C.POINTER(capi.RansacBatch), C.POINTER(capi.RansacParams),
+                                                        C.POINTER(capi.RansacStreams), C.POINTER(capi.RansacResult)]
+        L.theia_hip_rng_seed.argtypes = [C.POINTER(capi.RngState), C.c_uint32]
+        L.theia_hip_rng_rand_int.argtypes = [C.POINTER(capi.RngState), C.c_int32, C.c_int32, C.c_int32, capi.c_int32_p]
+        L.theia_hip_rng_rand_double.argtypes = [C.POINTER(capi.RngState), C.c_double, C.c_double, C.c_int32, capi.c_double_p]
+        L.theia_hip_rng_discard.argtypes = [C.POINTER(capi.RngState), C.c_uint64]
         L._ransac_ready = True
     return L
 
 
-def estimate_batch(estimator, data, offsets, params, estimator_params=None, seeds=None):
-    """theia_hip_ransac_estimate_batch.  data [total][datum], offsets [P+1]; seeds: optional per-problem
-    RandomNumberGenerator seeds (default params.seed + problem index).  Returns dict of per-problem arrays."""
+def rng_states(n, seeds=None):
+    """n theia_rng_state (a ctypes array), each RandomNumberGenerator(seeds[i]) (default: std::mt19937's default seed)."""
     L = _sig()
+    st = (capi.RngState * int(n))()
+    for i in range(int(n)):
+        capi.check(L.theia_hip_rng_seed(C.byref(st[i]), (_MT_DEFAULT_SEED if seeds is None else int(seeds[i])) & 0xFFFFFFFF))
+    return st
+
+
+def estimate_batch(estimator, data, offsets, params, estimator_params=None, seeds=None, streams=None):
+    """theia_hip_ransac_estimate_batch.  data [total][datum], offsets [P+1]; seeds: optional per-problem
+    RandomNumberGenerator seeds (default params.seed + problem index).  Returns dict of per-problem arrays.
+    streams = (states, stream_of_problem): theia_hip_ransac_estimate_streams instead -- states is a ctypes array of
+    capi.RngState (rng_states) or one capi.RngState, advanced in place; stream_of_problem [P] (None: all on stream 0); the
+    problems of one stream are successive Estimate() calls of one reference thread."""
+    L = _sig()
+    if streams is not None and seeds is not None:
+        raise capi.TheiaHipError(capi.THEIA_HIP_ERR_INVALID_ARGUMENT, "seeds and streams exclude each other")
     data = np.ascontiguousarray(data, dtype=np.float64)
     offsets = np.ascontiguousarray(offsets, dtype=np.int64)
     P = len(offsets) - 1
@@ -134,7 +216,7 @@ def estimate_batch(estimator, data, offsets, params, estimator_params=None, seed
     b.offsets = capi.ptr(offsets, C.c_int64); b.data = capi.ptr(data, C.c_double)
     ep = None if estimator_params is None else np.ascontiguousarray(estimator_params, dtype=np.float64)
     # (the C side reads a fixed number of entries: two focal-length limits, or the radial-distortion metadata + first-call flag)
-    need = {EST_UNCALIBRATED_RELATIVE_POSE: 2, EST_RADIAL_DIST_UNCALIBRATED_ABSOLUTE_POSE: 5}.get(int(estimator), 0)
+    need = {EST_UNCALIBRATED_RELATIVE_POSE: 2, EST_RADIAL_DIST_UNCALIBRATED_ABSOLUTE_POSE: 5 if streams is None else 4}.get(int(estimator), 0)
     if ep is not None and ep.size < need:
         raise capi.TheiaHipError(capi.THEIA_HIP_ERR_INVALID_ARGUMENT, f"estimator {int(estimator)} reads {need} estimator_params, got {ep.size}")
     b.estimator_params = None if ep is None else capi.ptr(ep, C.c_double)
@@ -151,7 +233,19 @@ def estimate_batch(estimator, data, offsets, params, estimator_params=None, seed
     r.num_inliers = capi.ptr(ninl, C.c_int32); r.inlier_mask = capi.ptr(mask, C.c_uint8)
     r.num_iterations = capi.ptr(nit, C.c_int32); r.confidence = capi.ptr(conf, C.c_double)
     pc = params.to_c() if isinstance(params, RansacParameters) else params
-    capi.check(L.theia_hip_ransac_estimate_batch(C.byref(b), C.byref(pc), C.byref(r)))
+    if streams is None:
+        capi.check(L.theia_hip_ransac_estimate_batch(C.byref(b), C.byref(pc), C.byref(r)))
+    else:
+        states, sop = streams
+        if isinstance(states, capi.RngState):
+            states = (capi.RngState * 1).from_address(C.addressof(states))   # a view: advanced in place
+        sop_a = None if sop is None else np.ascontiguousarray(sop, dtype=np.int32)
+        if sop_a is not None and sop_a.shape != (P,):
+            raise capi.TheiaHipError(capi.THEIA_HIP_ERR_INVALID_ARGUMENT, "stream_of_problem must hold one entry per problem")
+        sv = capi.RansacStreams()
+        sv.num_streams = len(states); sv.stream_of_problem = capi.ptr(sop_a, C.c_int32)
+        sv.states = C.cast(states, C.POINTER(capi.RngState))
+        capi.check(L.theia_hip_ransac_estimate_streams(C.byref(b), C.byref(pc), C.byref(sv), C.byref(r)))
     return {"success": success[:P], "models": models[:P], "num_inliers": ninl[:P], "inlier_mask": mask[:total],
             "num_iterations": nit[:P], "confidence": conf[:P], "num_lo_iterations": nlo[:P], "hypotheses_evaluated": r.hypotheses_evaluated,
             "models_scored": r.models_scored, "time_fit_score_seconds": r.time_fit_score_seconds,
@@ -168,7 +262,9 @@ def _single(estimator, ransac_params, ransac_type, data, estimator_params=None):
     if data.shape[0] < _SAMPLE_SIZE[estimator]:
         # a single Estimate() call: the reference's sampler CHECKs (random_sampler.cc:53-58); in a batch the C-ABI fails that pair only
         raise capi.TheiaHipError(capi.THEIA_HIP_ERR_INVALID_ARGUMENT, "fewer data than the minimal sample size")
-    res = estimate_batch(estimator, data, np.array([0, data.shape[0]], dtype=np.int64), pc, estimator_params)
+    # rng set: the call continues the calling thread's generator (theia_hip_ransac_estimate_streams on its state)
+    streams = None if getattr(ransac_params, "rng", None) is None else (RandomNumberGenerator.thread_state(), None)
+    res = estimate_batch(estimator, data, np.array([0, data.shape[0]], dtype=np.int64), pc, estimator_params, streams=streams)
     s = RansacSummary()
     s.inliers = np.nonzero(res["inlier_mask"])[0].tolist()
     s.num_input_data_points = data.shape[0]
@@ -590,7 +686,8 @@ def EstimateRadialDistUncalibratedAbsolutePose(ransac_params, ransac_type, norma
     correspondences: (N, 5) u v X Y Z, the observed (distorted) pixels with the principal point removed.  RANSAC over P4Pfr
     samples on the device.  The solver's "random rotation" draws come out of the sampler's stream, as in the reference
     (include/theia_hip.h); first_call_in_process: the stream is re-seeded with 42 after the first sample, which is what the
-    solver's static generator does the first time it runs in a process."""
+    solver's static generator does the first time it runs in a process.  With ransac_params.rng set the flag is the calling
+    thread's instead (its p4pfr_static_seeded) and first_call_in_process is not read."""
     ep = np.concatenate([meta_data.limits(), [1.0 if first_call_in_process else 0.0]])
     ok, m, s = _single(EST_RADIAL_DIST_UNCALIBRATED_ABSOLUTE_POSE, ransac_params, ransac_type, normalized_correspondences, ep)
     return ok, RadialDistUncalibratedAbsolutePose(m), s

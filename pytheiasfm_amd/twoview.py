@@ -45,7 +45,8 @@ class EstimateTwoViewInfoOptions:  # estimate_twoview_info.h:51-81
         self.lo_start_iterations = 10
         self.min_focal_length = 1.0
         self.max_focal_length = 1.7976931348623157e308
-        self.seed = 0   # RandomNumberGenerator seed (options.rng in the reference)
+        self.seed = 0   # RandomNumberGenerator seed of every estimate (the batch functions: of every pair)
+        self.rng = None   # options.rng: a ransac.RandomNumberGenerator makes the single-pair calls continue the thread's generator
 
 
 class TwoViewInfo:  # twoview_info.h:54-86
@@ -148,12 +149,16 @@ def _ransac_params(options, error_thresh, use_mle=None):
     return pc
 
 
-def EstimateTwoViewInfoBatch(options, priors1, priors2, correspondences_list, pair_seeds=None):
+def EstimateTwoViewInfoBatch(options, priors1, priors2, correspondences_list, pair_seeds=None, _rng_stream=False):
     """EstimateTwoViewInfo for a list of image pairs.  Returns a list of
     (success, TwoViewInfo, inlier_indices).  Every pair draws from its own RandomNumberGenerator(options.seed)
     (or pair_seeds[i]): a pair's result does not depend on which other pairs share the batch, and
-    EstimateTwoViewInfo(pair) == EstimateTwoViewInfoBatch([.., pair, ..])[i]."""
+    EstimateTwoViewInfo(pair) == EstimateTwoViewInfoBatch([.., pair, ..])[i] when options.rng is not set.
+    (_rng_stream: the single-pair form with options.rng set -- the pair draws from the calling thread's generator.)"""
     n = len(correspondences_list)
+    if _rng_stream and n != 1:
+        raise capi.TheiaHipError(capi.THEIA_HIP_ERR_INVALID_ARGUMENT, "the thread's generator serves single-pair calls")
+    streams = (_ransac.RandomNumberGenerator.thread_state(), None) if _rng_stream else None
     if pair_seeds is None:
         pair_seeds = [options.seed] * n
     results = [None] * n
@@ -174,7 +179,7 @@ def EstimateTwoViewInfoBatch(options, priors1, priors2, correspondences_list, pa
         est = _ransac.EST_RELATIVE_POSE if calibrated else _ransac.EST_UNCALIBRATED_RELATIVE_POSE
         eparams = None if calibrated else np.array([options.min_focal_length, options.max_focal_length])
         res = _ransac.estimate_batch(est, np.concatenate(data, axis=0), offsets, _ransac_params(options, thresh, use_mle=options.use_mle if calibrated else False), eparams,
-                                     seeds=[pair_seeds[i] for i in idx])
+                                     seeds=None if streams else [pair_seeds[i] for i in idx], streams=streams)
         for k, i in enumerate(idx):
             ok = bool(res["success"][k])
             info = TwoViewInfo()
@@ -198,8 +203,10 @@ def EstimateTwoViewInfoBatch(options, priors1, priors2, correspondences_list, pa
 
 
 def EstimateTwoViewInfo(options, intrinsics1, intrinsics2, correspondences):
-    """estimate_twoview_info.cc:262-305 -> (success, TwoViewInfo, inlier_indices)."""
-    return EstimateTwoViewInfoBatch(options, [intrinsics1], [intrinsics2], [correspondences])[0]
+    """estimate_twoview_info.cc:262-305 -> (success, TwoViewInfo, inlier_indices).  With options.rng set the estimate
+    continues the calling thread's generator (ransac_options.rng = options.rng, :147,209)."""
+    return EstimateTwoViewInfoBatch(options, [intrinsics1], [intrinsics2], [correspondences],
+                                    _rng_stream=getattr(options, "rng", None) is not None)[0]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -508,7 +515,7 @@ def GuidedEpipolarMatches(camera1, camera2, features1, features2, matches, guide
     return out
 
 
-def VerifyMatchesBatch(options, priors1, priors2, correspondences_list, indexed=None):
+def VerifyMatchesBatch(options, priors1, priors2, correspondences_list, indexed=None, _rng_stream=False):
     """TwoViewMatchGeometricVerification::VerifyMatches (two_view_match_geometric_verification.cc:114-183) for a list of
     image pairs given as pixel correspondences [(x1, y1, x2, y2)] (the reference indexes keypoint lists).  Returns a
     list of (success, TwoViewInfo, verified_indices).  The homography count (:331-368) and EstimateTwoViewInfo run as
@@ -517,7 +524,9 @@ def VerifyMatchesBatch(options, priors1, priors2, correspondences_list, indexed=
     images: it runs in the indexed form (VerifyMatchesIndexedBatch: indexed = (features1, features2, matches) per pair; the
     third element of a result is then the list of verified (feature1, feature2) pairs) and is refused here without them.
     Stated deviation: the reference draws the homography and the relative-pose samples from ONE generator in sequence; here both
-    batches start from `seed`."""
+    batches start from `seed` -- except in the single-pair VerifyMatches with estimate_twoview_info_options.rng set
+    (_rng_stream), where the homography estimate and then the relative-pose estimate continue the calling thread's generator,
+    as homography_params.rng = etvi_options.rng does (:331-336)."""
     from . import ba as _ba
     if options.guided_matching and indexed is None:
         raise capi.TheiaHipError(capi.THEIA_HIP_ERR_UNSUPPORTED, "guided matching needs keypoints and descriptors: use VerifyMatchesIndexed(Batch)")
@@ -534,8 +543,12 @@ def VerifyMatchesBatch(options, priors1, priors2, correspondences_list, indexed=
     hp.use_lo = 0                                   # a fresh RansacParameters: use_lo keeps its default
     offsets = np.zeros(len(live) + 1, dtype=np.int64)
     offsets[1:] = np.cumsum([len(corr[i]) for i in live])
-    hres = _ransac.estimate_batch(_ransac.EST_HOMOGRAPHY, np.concatenate([corr[i] for i in live]), offsets, hp, seeds=[eo.seed] * len(live))
-    tv = EstimateTwoViewInfoBatch(eo, [priors1[i] for i in live], [priors2[i] for i in live], [corr[i] for i in live])
+    streams = (_ransac.RandomNumberGenerator.thread_state(), None) if _rng_stream else None
+    if _rng_stream and n != 1:
+        raise capi.TheiaHipError(capi.THEIA_HIP_ERR_INVALID_ARGUMENT, "the thread's generator serves single-pair calls")
+    hres = _ransac.estimate_batch(_ransac.EST_HOMOGRAPHY, np.concatenate([corr[i] for i in live]), offsets, hp,
+                                  seeds=None if streams else [eo.seed] * len(live), streams=streams)
+    tv = EstimateTwoViewInfoBatch(eo, [priors1[i] for i in live], [priors2[i] for i in live], [corr[i] for i in live], _rng_stream=_rng_stream)
     cand = []   # pairs that go through the two-view BA: [i, info, idx, c, cams]
     for k, i in enumerate(live):
         ok, info, inliers = tv[k]
@@ -603,7 +616,8 @@ def VerifyMatchesBatch(options, priors1, priors2, correspondences_list, indexed=
 
 
 def VerifyMatches(options, intrinsics1, intrinsics2, correspondences):
-    return VerifyMatchesBatch(options, [intrinsics1], [intrinsics2], [correspondences])[0]
+    return VerifyMatchesBatch(options, [intrinsics1], [intrinsics2], [correspondences],
+                              _rng_stream=getattr(options.estimate_twoview_info_options, "rng", None) is not None)[0]
 
 
 def VerifyMatchesIndexedBatch(options, priors1, priors2, features1_list, features2_list, matches_list):

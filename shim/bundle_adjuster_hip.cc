@@ -3,6 +3,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstring>
+#include <sstream>
 
 namespace theia_hip_shim {
 
@@ -203,6 +204,48 @@ bool BundleAdjustViews(const BundleAdjustmentOptions& options, std::vector<ViewP
   return true;
 }
 
+RandomNumberGenerator::RandomNumberGenerator() {
+  Seed((unsigned)std::chrono::system_clock::now().time_since_epoch().count());
+}
+
+void RandomNumberGenerator::Seed(unsigned seed) { theia_hip_rng_seed(&state_, seed); }
+
+int RandomNumberGenerator::RandInt(int lower, int upper) {
+  int32_t v = 0;
+  theia_hip_rng_rand_int(&state_, lower, upper, 1, &v);
+  return v;
+}
+
+double RandomNumberGenerator::RandDouble(double lower, double upper) {
+  double v = 0.0;
+  theia_hip_rng_rand_double(&state_, lower, upper, 1, &v);
+  return v;
+}
+
+// libstdc++ writes the 624 words of the state, then the position: the layout of theia_rng_state's mt and pos
+void RandomNumberGenerator::Import(const std::mt19937& generator) {
+  std::stringstream ss;
+  ss << generator;
+  for (int i = 0; i < 624; ++i) ss >> state_.mt[i];
+  ss >> state_.pos;
+}
+
+void RandomNumberGenerator::Export(std::mt19937* generator) const {
+  std::stringstream ss;
+  for (int i = 0; i < 624; ++i) ss << state_.mt[i] << ' ';
+  ss << state_.pos;
+  ss >> *generator;
+}
+
+// the seeded batch, or (params.rng set) the streams call with every problem on the one stream of that generator
+static int run_ransac(const theia_ransac_batch& batch, const theia_ransac_params& prm, const RansacParameters& params,
+                      theia_ransac_result* res) {
+  if (!params.rng) return theia_hip_ransac_estimate_batch(&batch, &prm, res);
+  theia_ransac_streams streams;
+  streams.num_streams = 1; streams.stream_of_problem = nullptr; streams.states = params.rng->state();
+  return theia_hip_ransac_estimate_streams(&batch, &prm, &streams, res);
+}
+
 bool EstimateBatch(int estimator, int ransac_type, const RansacParameters& params, const std::vector<std::vector<double>>& data_in,
                    const double* estimator_params, EstimatorBatchResult* result, std::string* error) {
   const int np = (int)data_in.size(), ds = datum_doubles(estimator);
@@ -231,7 +274,7 @@ bool EstimateBatch(int estimator, int ransac_type, const RansacParameters& param
   std::memset(&res, 0, sizeof(res));
   res.success = ok.data(); res.models = models.data(); res.num_inliers = ninl.data(); res.inlier_mask = mask.data();
   res.num_iterations = nit.data(); res.confidence = conf.data();
-  if (theia_hip_ransac_estimate_batch(&batch, &prm, &res) != THEIA_HIP_OK) { if (error) *error = theia_hip_last_error(); return false; }
+  if (run_ransac(batch, prm, params, &res) != THEIA_HIP_OK) { if (error) *error = theia_hip_last_error(); return false; }
   result->success.assign(np, false); result->models.assign(np, std::vector<double>()); result->summaries.assign(np, RansacSummary());
   for (int p = 0; p < np; ++p) {
     result->success[p] = ok[p] != 0;
@@ -282,7 +325,7 @@ bool EstimateRelativePoseBatch(const RansacParameters& params, const std::vector
   std::memset(&res, 0, sizeof(res));
   res.success = ok.data(); res.models = models.data(); res.num_inliers = ninl.data(); res.inlier_mask = mask.data();
   res.num_iterations = nit.data(); res.confidence = conf.data();
-  if (theia_hip_ransac_estimate_batch(&batch, &prm, &res) != THEIA_HIP_OK) { if (error) *error = theia_hip_last_error(); return false; }
+  if (run_ransac(batch, prm, params, &res) != THEIA_HIP_OK) { if (error) *error = theia_hip_last_error(); return false; }
   success->assign(np, false); poses->resize(np); summaries->assign(np, RansacSummary());
   for (int p = 0; p < np; ++p) {
     (*success)[p] = ok[p] != 0;

@@ -12,6 +12,8 @@
 #define THEIA_HIP_SHIM_BUNDLE_ADJUSTER_HIP_H_
 
 #include <cstdint>
+#include <memory>
+#include <random>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -99,12 +101,32 @@ bool BundleAdjustViews(const BundleAdjustmentOptions& options, std::vector<ViewP
 
 // SampleConsensusEstimator front ends (sfm/estimators/estimate_relative_pose.h:49-70, estimate_calibrated_absolute_pose.h):
 // one call per image pair list, all pairs as one device batch.
+// util/random.h:47-80 over a caller-owned theia_rng_state: one object stands for the thread_local std::mt19937 of one
+// reference thread (util/random.cc:46-66) -- hand the same object to every estimate that thread would make.  Import / Export
+// move the state to and from a real std::mt19937 (through its operator<< / operator>> text form).
+class RandomNumberGenerator {
+ public:
+  RandomNumberGenerator();                          // seeded from the clock, as the reference's default constructor
+  explicit RandomNumberGenerator(unsigned seed) { Seed(seed); }
+  void Seed(unsigned seed);
+  int RandInt(int lower, int upper);
+  double RandDouble(double lower, double upper);
+  void Import(const std::mt19937& generator);
+  void Export(std::mt19937* generator) const;
+  theia_rng_state* state() { return &state_; }
+  const theia_rng_state* state() const { return &state_; }
+
+ private:
+  theia_rng_state state_{};
+};
+
 struct RansacParameters {   // solvers/sample_consensus_estimator.h:58-126
   double error_thresh = -1.0, failure_probability = 0.01, min_inlier_ratio = 0.0;
   int min_iterations = 100, max_iterations = 2147483647;
   bool use_mle = false, use_lo = false;
   int lo_start_iterations = 50;
-  uint32_t seed = 0;
+  uint32_t seed = 0;                                // rng == nullptr: problem p draws from RandomNumberGenerator(seed + p)
+  std::shared_ptr<RandomNumberGenerator> rng;       // set: the problems are successive Estimate() calls on this generator
 };
 struct RansacSummary { std::vector<int> inliers; int num_iterations = 0; double confidence = 0.0; };
 struct RelativePose { double essential_matrix[9], rotation[9], position[3]; };
