@@ -463,6 +463,33 @@ int theia_hip_ba_reduced_system(theia_ba_handle h, double radius, int32_t* n,
  * pivot is not positive (what makes an LM step "invalid"). */
 int theia_hip_dense_spd_solve(int32_t n, const double* A, const double* b, double* x);
 
+/* The same kernels factored once and solved many times (the ADMM solves of theia_hip_robust_rotation_averaging):
+ * factor the n x n SPD matrix A (row-major, lower triangle read) once, then solve A X = B for the k right-hand sides
+ * B [k][n] into X [k][n] against the stored factor.  THEIA_HIP_ERR_INTERNAL when a pivot is not positive. */
+int theia_hip_dense_spd_solve_multi(int32_t n, const double* A, int32_t k, const double* B, double* X);
+
+/* RobustRotationEstimator::EstimateRotations (global_pose_estimation/robust_rotation_estimator.cc:66-110; pybind
+ * sfm.cc:1749-1780, the ROBUST_L1L2 global rotation estimator of the global pipeline): L1 ADMM regression on the view
+ * graph (math/l1_solver.h), then IRLS with the weight sigma / (|e|^2 + sigma^2)^2 per edge, through one N x N Laplacian
+ * factorisation per solve (csrc/rotation_averaging.hip).  orientations [num_views][3] angle-axis, in/out; fixed
+ * [num_views] non-zero = held constant, or NULL (no view flagged: view 0 is fixed -- the reference fixes the first key
+ * of its unordered_map); edges [num_edges][2] = (i, j) with relative_rotations [num_edges][3] = r_ij, R_j ~ R_ij R_i.
+ * THEIA_HIP_ERR_INVALID_ARGUMENT (the reference's CHECK failures; orientations untouched): no edge, an edge naming a
+ * view out of range, a connected component of the view graph without a fixed view.  THEIA_HIP_ERR_INTERNAL: a
+ * factorisation failed (the reference's `return false`); orientations hold the state reached so far.
+ * THEIA_HIP_ERR_OUT_OF_MEMORY: the dense (N + 3)^2 array of doubles (N = free views) does not fit on the device. */
+typedef struct theia_rotation_options {
+  int32_t max_num_l1_iterations, max_num_irls_iterations;
+  double l1_step_convergence_threshold, irls_step_convergence_threshold, irls_loss_parameter_sigma;
+} theia_rotation_options;
+typedef struct theia_rotation_summary {
+  int32_t l1_iterations, admm_iterations, irls_iterations, reserved;
+  double final_squared_residual, setup_ms, l1_ms, irls_ms;
+} theia_rotation_summary;
+int theia_hip_robust_rotation_averaging(int32_t num_views, double* orientations, const uint8_t* fixed, int32_t num_edges,
+                                        const int32_t* edges, const double* relative_rotations,
+                                        const theia_rotation_options* options, theia_rotation_summary* summary);
+
 /* Multi-GPU (one process per GPU): tracks are sharded by the caller; each
  * rank's handle holds its shard plus ALL cameras.  The reduced camera system
  * (and the scalar reductions) are summed across ranks through this callback,

@@ -152,6 +152,20 @@ class RansacStreams(C.Structure):
     _fields_ = [("num_streams", C.c_int32), ("stream_of_problem", c_int32_p), ("states", C.POINTER(RngState))]
 
 
+class RotationOptions(C.Structure):
+    """theia_rotation_options."""
+    _fields_ = [("max_num_l1_iterations", C.c_int32), ("max_num_irls_iterations", C.c_int32),
+                ("l1_step_convergence_threshold", C.c_double), ("irls_step_convergence_threshold", C.c_double),
+                ("irls_loss_parameter_sigma", C.c_double)]
+
+
+class RotationSummary(C.Structure):
+    """theia_rotation_summary."""
+    _fields_ = [("l1_iterations", C.c_int32), ("admm_iterations", C.c_int32), ("irls_iterations", C.c_int32),
+                ("reserved", C.c_int32), ("final_squared_residual", C.c_double), ("setup_ms", C.c_double),
+                ("l1_ms", C.c_double), ("irls_ms", C.c_double)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p)
 
 # every symbol include/theia_hip.h declares (checked by tests/test_capi_symbols.py)
@@ -161,7 +175,7 @@ EXPORTED_SYMBOLS = [
     "theia_hip_ba_reset_parameters", "theia_hip_estimate_tracks", "theia_hip_ba_set_shard", "theia_hip_ba_snapshot_parameters", "theia_hip_ba_restore_parameters", "theia_hip_ba_set_options", "theia_hip_ba_run", "theia_hip_ba_download",
     "theia_hip_ba_destroy", "theia_hip_ba_covariance", "theia_hip_ba_evaluate", "theia_hip_ba_evaluate_ex", "theia_hip_ba_reduced_system",
     "theia_hip_ba_set_allreduce", "theia_hip_ba_set_inner_global", "theia_hip_ba_plan_info", "theia_hip_rccl_unique_id", "theia_hip_rccl_comm_create",
-    "theia_hip_optimize_relative_position_batch", "theia_hip_rccl_comm_destroy", "theia_hip_rccl_comm_count", "theia_hip_ba_set_rccl", "theia_hip_dense_spd_solve", "theia_ransac_params_default",
+    "theia_hip_optimize_relative_position_batch", "theia_hip_rccl_comm_destroy", "theia_hip_rccl_comm_count", "theia_hip_ba_set_rccl", "theia_hip_dense_spd_solve", "theia_hip_dense_spd_solve_multi", "theia_hip_robust_rotation_averaging", "theia_ransac_params_default",
     "theia_hip_ransac_estimate_batch", "theia_hip_five_point_relative_pose",
     "theia_hip_pose_from_three_points", "theia_hip_sqpnp", "theia_hip_dls_pnp", "theia_hip_dls_macaulay_terms", "theia_hip_four_point_pose_and_focal_length", "theia_hip_four_point_focal_length_radial_distortion", "theia_hip_four_point_focal_length_radial_distortion_ex", "theia_hip_release_scratch", "theia_hip_guided_knn", "theia_hip_randint_stream", "theia_hip_selftest_wave_primitives",
     "theia_hip_rng_seed", "theia_hip_rng_rand_int", "theia_hip_rng_rand_double", "theia_hip_rng_discard", "theia_hip_ransac_estimate_streams",
@@ -206,6 +220,9 @@ def lib():
     L.theia_hip_ba_set_allreduce.argtypes = [C.c_void_p, ALLREDUCE_FN, C.c_void_p]
     L.theia_ba_options_default.argtypes = [C.POINTER(BaOptions)]
     L.theia_hip_dense_spd_solve.argtypes = [C.c_int32, c_double_p, c_double_p, c_double_p]
+    L.theia_hip_dense_spd_solve_multi.argtypes = [C.c_int32, c_double_p, C.c_int32, c_double_p, c_double_p]
+    L.theia_hip_robust_rotation_averaging.argtypes = [C.c_int32, c_double_p, c_uint8_p, C.c_int32, c_int32_p, c_double_p,
+                                                      C.POINTER(RotationOptions), C.POINTER(RotationSummary)]
     _lib = L
     return L
 

@@ -19,6 +19,7 @@
 //   backward substitution in 64-wide steps with the same block inverses.
 #include "ba_kernels.h"
 #include "cholesky_device.h"
+#include "wave_reduce.h"
 
 #include <algorithm>
 
@@ -135,9 +136,9 @@ __global__ __launch_bounds__(256) void k_syrk(double* __restrict__ A, int lda, i
 // Backward substitution x = L^-T y in 64-wide block steps with the block
 // inverses saved by k_potrf: x_k = Linv_k^T y_k, then y_j -= L[k-rows][j]^T x_k
 // spread over one workgroup per 256 columns.
-__global__ __launch_bounds__(256) void k_back_step(const double* __restrict__ A, int lda, int n, int kb,
-                                                   const double* __restrict__ Linv, double* __restrict__ y,
-                                                   double* __restrict__ x) {
+__device__ __forceinline__ void back_step(const double* __restrict__ A, int lda, int n, int kb,
+                                          const double* __restrict__ Linv, double* __restrict__ y,
+                                          double* __restrict__ x) {
   __shared__ double yk[NB], xk[NB], part[4][NB];
   const int k0 = kb * NB;
   const int nb = min(NB, n - k0);
@@ -177,6 +178,64 @@ __global__ __launch_bounds__(256) void k_back_step(const double* __restrict__ A,
   }
 }
 
+__global__ __launch_bounds__(256) void k_back_step(const double* __restrict__ A, int lda, int n, int kb,
+                                                   const double* __restrict__ Linv, double* __restrict__ y,
+                                                   double* __restrict__ x) {
+  back_step(A, lda, n, kb, Linv, y, x);
+}
+
+// The same step for k right-hand sides at once: blockIdx.y = vector (y, x of vector v at v * ldy, v * ldx).
+// Every vector takes k_back_step's arithmetic in k_back_step's order: k = 1 is bit-identical to it.
+__global__ __launch_bounds__(256) void k_back_step_multi(const double* __restrict__ A, int lda, int n, int kb,
+                                                         const double* __restrict__ Linv, double* __restrict__ y, int ldy,
+                                                         double* __restrict__ x, int ldx) {
+  back_step(A, lda, n, kb, Linv, y + (size_t)blockIdx.y * ldy, x + (size_t)blockIdx.y * ldx);
+}
+
+// Forward substitution y = L^-1 b against a stored factor, k vectors (blockIdx.y = vector), one 64-row block step:
+//   y_k = Linv_k b_k            (every workgroup forms it; workgroup 0 writes it to y)
+//   b_j -= L[j][k-cols] y_k     for the rows j >= k0 + nb, one wavefront per row (lane = column, butterfly sum),
+//                               16 rows per workgroup.
+// b is read only in block k and written only below it, y is written only in block k: no workgroup reads what
+// another one writes in the same launch.
+__global__ __launch_bounds__(256) void k_fwd_step_multi(const double* __restrict__ A, int lda, int n, int kb,
+                                                        const double* __restrict__ Linv, double* __restrict__ b, int ldb,
+                                                        double* __restrict__ y, int ldy) {
+  __shared__ double bk[NB], yk[NB], part[4][NB];
+  b += (size_t)blockIdx.y * ldb;
+  y += (size_t)blockIdx.y * ldy;
+  const int k0 = kb * NB;
+  const int nb = min(NB, n - k0);
+  const int tid = threadIdx.x;
+  if (tid < NB) bk[tid] = (tid < nb) ? b[k0 + tid] : 0.0;
+  __syncthreads();
+  {
+    // y_k[i] = sum_r Linv[i][r] b_k[r] : 4 column chunks of 16 per row i
+    const int i = tid & 63, ch = tid >> 6;
+    const double* Z = Linv + (size_t)kb * NB * NB;
+    double s = 0.0;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) { const int r = ch * 16 + q; s += Z[i * NB + r] * bk[r]; }
+    part[ch][i] = s;
+  }
+  __syncthreads();
+  if (tid < NB) {
+    const double s = (part[0][tid] + part[1][tid]) + (part[2][tid] + part[3][tid]);
+    yk[tid] = s;
+    if (blockIdx.x == 0 && tid < nb) y[k0 + tid] = s;
+  }
+  __syncthreads();
+  const int lane = tid & 63, wv = tid >> 6;
+  const double yl = lane < nb ? yk[lane] : 0.0;
+  for (int q = 0; q < 4; ++q) {
+    const int j = k0 + nb + blockIdx.x * 16 + wv * 4 + q;   // wave-uniform
+    if (j >= n) break;
+    const double t = lane < nb ? A[(size_t)j * lda + k0 + lane] * yl : 0.0;
+    const double s = wave_sum_butterfly(t);
+    if (lane == 0) b[j] -= s;
+  }
+}
+
 }  // namespace
 
 size_t dense_cholesky_workspace(int n) {
@@ -184,12 +243,11 @@ size_t dense_cholesky_workspace(int n) {
   return (size_t)std::max(1, nblk) * NB * NB + (size_t)n + 8;
 }
 
-void dense_cholesky_solve(int n, double* A, int lda, double* b, double* work, double* fail_flag, hipStream_t st) {
+void dense_cholesky_factor(int n, int k, double* A, int lda, double* work, double* fail_flag, hipStream_t st) {
   if (n <= 0) return;
-  const int nrows = n + 1;  // row n = right-hand side (b must alias A + n*lda)
+  const int nrows = n + k;  // rows n .. n+k-1 = right-hand sides, forward-substituted in place
   const int nblk = (n + NB - 1) / NB;
   double* Linv = work;
-  double* x = work + (size_t)nblk * NB * NB;
   for (int kb = 0; kb < nblk; ++kb) {
     const int k0 = kb * NB;
     const int nb = (n - k0 < NB) ? (n - k0) : NB;
@@ -203,6 +261,38 @@ void dense_cholesky_solve(int n, double* A, int lda, double* b, double* work, do
       k_syrk<<<grid, 256, 0, st>>>(A, lda, nrows, k0, nb);
     }
   }
+}
+
+void dense_cholesky_back_substitute(int n, const double* A, int lda, const double* work, int k, double* Y, int ldy,
+                                    double* X, int ldx, hipStream_t st) {
+  if (n <= 0 || k <= 0) return;
+  const int nblk = (n + NB - 1) / NB;
+  for (int kb = nblk - 1; kb >= 0; --kb) {
+    const int k0 = kb * NB;
+    dim3 grid(k0 > 0 ? (k0 + 255) / 256 : 1, k);
+    k_back_step_multi<<<grid, 256, 0, st>>>(A, lda, n, kb, work, Y, ldy, X, ldx);
+  }
+}
+
+void dense_cholesky_solve_factored(int n, const double* A, int lda, const double* work, int k, double* B, int ldb,
+                                   double* T, double* X, int ldx, hipStream_t st) {
+  if (n <= 0 || k <= 0) return;
+  const int nblk = (n + NB - 1) / NB;
+  for (int kb = 0; kb < nblk; ++kb) {
+    const int below = n - std::min(n, (kb + 1) * NB);
+    dim3 grid(below > 0 ? (below + 15) / 16 : 1, k);
+    k_fwd_step_multi<<<grid, 256, 0, st>>>(A, lda, n, kb, work, B, ldb, T, n);
+  }
+  dense_cholesky_back_substitute(n, A, lda, work, k, T, n, X, ldx, st);
+}
+
+void dense_cholesky_solve(int n, double* A, int lda, double* b, double* work, double* fail_flag, hipStream_t st) {
+  if (n <= 0) return;
+  // row n = right-hand side (b must alias A + n*lda): the factorisation leaves y = L^-1 b there
+  dense_cholesky_factor(n, 1, A, lda, work, fail_flag, st);
+  const int nblk = (n + NB - 1) / NB;
+  double* Linv = work;
+  double* x = work + (size_t)nblk * NB * NB;
   double* y = A + (size_t)n * lda;
   for (int kb = nblk - 1; kb >= 0; --kb) {
     const int k0 = kb * NB;

@@ -1,0 +1,491 @@
+// rotation_averaging.hip -- RobustRotationEstimator (global_pose_estimation/robust_rotation_estimator.{h,cc}; pybind
+// sfm.cc:1749-1780): L1 ADMM regression on the view graph, then IRLS, all on the device in FP64.
+//
+// The reference solves with A (one 3-row block per edge: -I at view i, +I at view j, no column for a fixed view) through
+// Eigen's SimplicialLDLT of the 3N x 3N matrix A'WA.  Every edge's weight is the same for its three rows, so
+//   A'WA = L_w (x) I_3,   A'W e = the three columns gathered per view,
+// with L_w the weighted graph Laplacian restricted to the free views: ONE N x N SPD factorisation (dense_cholesky.hip, the
+// BA's K3 kernels) with three right-hand sides, 27x fewer flops than the 3N x 3N one.  The L1 stage factors L once and runs
+// every ADMM solve against that factor (dense_cholesky_solve_factored); the IRLS stage assembles L_w and its three
+// right-hand-side rows into one (N + 3) x lda array and factors it per iteration (forward substitution out of the panel
+// steps, then dense_cholesky_back_substitute).
+//
+// Determinism: no atomics.  The Laplacian is assembled from host-built CSR lists (per free view: incident edges in edge
+// order; per unordered free-view pair: its edges in edge order), the norms of the ADMM stopping test and the step sizes are
+// block partials summed by one workgroup in block order.  Two runs on one input are bit-identical.
+//
+// The per-edge residual e_ij = MultiplyRotations(-r_j, MultiplyRotations(r_ij, r_i)) and the update
+// r_i <- MultiplyRotations(r_i, delta_i) go through ceres' conversions (ransac_device.h) with the intermediate angle-axis
+// round trip the reference takes (math/rotation.cc:56-66).
+#include "ransac_device.h"
+#include "ba_kernels.h"
+#include "wave_reduce.h"
+#include "theia_hip_internal.h"
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <numeric>
+#include <vector>
+
+#define HIP_TRY(expr)                                                                             \
+  do {                                                                                            \
+    hipError_t e_ = (expr);                                                                       \
+    if (e_ != hipSuccess) return thip::set_error(THEIA_HIP_ERR_INTERNAL, "%s: %s", #expr, hipGetErrorString(e_)); \
+  } while (0)
+
+namespace thip {
+namespace {
+
+constexpr int kThreads = 256;
+
+// MultiplyRotations(a, b): angle-axis -> matrices, product, matrix -> angle-axis (row-major matrices throughout)
+__device__ __forceinline__ void multiply_rotations(const double* a, const double* b, double* out) {
+  double Ra[9], Rb[9], R[9];
+  rsc::angle_axis_to_rot(a, Ra);
+  rsc::angle_axis_to_rot(b, Rb);
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) R[3 * r + c] = (Ra[3 * r] * Rb[c] + Ra[3 * r + 1] * Rb[3 + c]) + Ra[3 * r + 2] * Rb[6 + c];
+  rsc::rot_to_angle_axis(R, out);
+}
+
+// Sum of v over the workgroup in a fixed tree order; the result is valid in thread 0.
+__device__ __forceinline__ double block_sum(double v, double* red) {
+  const int tid = threadIdx.x;
+  red[tid] = v;
+  __syncthreads();
+  for (int s = kThreads / 2; s > 0; s >>= 1) {
+    if (tid < s) red[tid] += red[tid + s];
+    __syncthreads();
+  }
+  const double r = red[0];
+  __syncthreads();
+  return r;
+}
+
+// ComputeResiduals (robust_rotation_estimator.cc:268-284) and the IRLS weight of every edge (:200-206):
+// w = sigma / (|e|^2 + sigma^2)^2.  part[block] = sum of |e|^2 over the block's edges.
+__global__ __launch_bounds__(kThreads) void k_residual(int E, const int2* __restrict__ edges, const double* __restrict__ rel,
+                                                       const double* __restrict__ aa, double sigma, double* __restrict__ res,
+                                                       double* __restrict__ w, double* __restrict__ part) {
+  __shared__ double red[kThreads];
+  const int e = blockIdx.x * kThreads + threadIdx.x;
+  double sq = 0.0;
+  if (e < E) {
+    const int2 ij = edges[e];
+    const double ri[3] = {aa[3 * ij.x], aa[3 * ij.x + 1], aa[3 * ij.x + 2]};
+    const double nrj[3] = {-aa[3 * ij.y], -aa[3 * ij.y + 1], -aa[3 * ij.y + 2]};
+    const double rij[3] = {rel[3 * (size_t)e], rel[3 * (size_t)e + 1], rel[3 * (size_t)e + 2]};
+    double t[3], r[3];
+    multiply_rotations(rij, ri, t);
+    multiply_rotations(nrj, t, r);
+    res[3 * (size_t)e] = r[0]; res[3 * (size_t)e + 1] = r[1]; res[3 * (size_t)e + 2] = r[2];
+    sq = (r[0] * r[0] + r[1] * r[1]) + r[2] * r[2];
+    const double tmp = sq + sigma * sigma;
+    w[e] = sigma / (tmp * tmp);
+  }
+  const double s = block_sum(sq, red);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// The lower triangle of L_w and the rows of A'W e, into the zeroed (m + 3) x lda array:
+//   thread t < m       : free view t -- diagonal sum of w over its incident edges, rhs row c = sum of sign * w * e_c
+//   thread t = m + p   : pair p = (a > b) -- A[a][b] = -sum of w over the pair's edges
+// inc[k] = 2 * edge + (1 if the view is the edge's second view, i.e. +I).  w == nullptr: unit weights (A'A, A'e).
+__global__ __launch_bounds__(kThreads) void k_assemble(int m, int P, int lda, const int* __restrict__ inc_off,
+                                                       const int* __restrict__ inc, const int* __restrict__ pair_off,
+                                                       const int* __restrict__ pair_edge, const int2* __restrict__ pair_rc,
+                                                       const double* __restrict__ w, const double* __restrict__ res,
+                                                       double* __restrict__ A) {
+  const int t = blockIdx.x * kThreads + threadIdx.x;
+  if (t < m) {
+    double d = 0.0, g0 = 0.0, g1 = 0.0, g2 = 0.0;
+    for (int k = inc_off[t]; k < inc_off[t + 1]; ++k) {
+      const int e = inc[k] >> 1;
+      const double we = w ? w[e] : 1.0;
+      const double sw = (inc[k] & 1) ? we : -we;
+      d += we;
+      g0 += sw * res[3 * (size_t)e]; g1 += sw * res[3 * (size_t)e + 1]; g2 += sw * res[3 * (size_t)e + 2];
+    }
+    A[(size_t)t * lda + t] = d;
+    A[(size_t)m * lda + t] = g0;
+    A[(size_t)(m + 1) * lda + t] = g1;
+    A[(size_t)(m + 2) * lda + t] = g2;
+  } else if (t < m + P) {
+    const int p = t - m;
+    double s = 0.0;
+    for (int k = pair_off[p]; k < pair_off[p + 1]; ++k) s += w ? w[pair_edge[k]] : 1.0;
+    const int2 rc = pair_rc[p];
+    A[(size_t)rc.x * lda + rc.y] = -s;
+  }
+}
+
+// ADMM x-update right-hand side (l1_solver.h:128): g = A' (b + z - u), [3][m].
+__global__ __launch_bounds__(kThreads) void k_admm_rhs(int m, const int* __restrict__ inc_off, const int* __restrict__ inc,
+                                                       const double* __restrict__ b, const double* __restrict__ z,
+                                                       const double* __restrict__ u, double* __restrict__ g) {
+  const int v = blockIdx.x * kThreads + threadIdx.x;
+  if (v >= m) return;
+  double g0 = 0.0, g1 = 0.0, g2 = 0.0;
+  for (int k = inc_off[v]; k < inc_off[v + 1]; ++k) {
+    const size_t e3 = 3 * (size_t)(inc[k] >> 1);
+    const double q0 = (b[e3] + z[e3]) - u[e3], q1 = (b[e3 + 1] + z[e3 + 1]) - u[e3 + 1], q2 = (b[e3 + 2] + z[e3 + 2]) - u[e3 + 2];
+    if (inc[k] & 1) { g0 += q0; g1 += q1; g2 += q2; } else { g0 -= q0; g1 -= q1; g2 -= q2; }
+  }
+  g[v] = g0; g[m + v] = g1; g[2 * m + v] = g2;
+}
+
+// ADMM z / u updates of one iteration (l1_solver.h:135-145) per edge row, and the block partials of
+// |A x - z - b|^2, |A x|^2, |z|^2 (:148-150) into part[block][3].
+__global__ __launch_bounds__(kThreads) void k_admm_edge(int E, int m, const int2* __restrict__ edges, const int* __restrict__ idx,
+                                                        const double* __restrict__ x, const double* __restrict__ b,
+                                                        double* __restrict__ z, double* __restrict__ zold, double* __restrict__ u,
+                                                        double alpha, double kappa, double* __restrict__ part) {
+  __shared__ double red[kThreads];
+  const int e = blockIdx.x * kThreads + threadIdx.x;
+  double rr = 0.0, aa = 0.0, zz = 0.0;
+  if (e < E) {
+    const int2 ij = edges[e];
+    const int a = idx[ij.x], c = idx[ij.y];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const size_t q = 3 * (size_t)e + k;
+      const double xi = a >= 0 ? x[(size_t)k * m + a] : 0.0, xj = c >= 0 ? x[(size_t)k * m + c] : 0.0;
+      const double ax = xj - xi;
+      const double bq = b[q], zq = z[q], uq = u[q];
+      const double ax_hat = alpha * ax + (1.0 - alpha) * (zq + bq);
+      const double v = (ax_hat - bq) + uq;
+      const double zn = fmax(0.0, v - kappa) - fmax(0.0, -v - kappa);
+      zold[q] = zq;
+      z[q] = zn;
+      u[q] = uq + ((ax_hat - zn) - bq);
+      const double r = (ax - zn) - bq;
+      rr += r * r; aa += ax * ax; zz += zn * zn;
+    }
+  }
+  const double s0 = block_sum(rr, red), s1 = block_sum(aa, red), s2 = block_sum(zz, red);
+  if (threadIdx.x == 0) { part[3 * blockIdx.x] = s0; part[3 * blockIdx.x + 1] = s1; part[3 * blockIdx.x + 2] = s2; }
+}
+
+// Dual residual and dual tolerance terms (l1_solver.h:151-156): |rho A'(z - z_old)|^2 and |rho A' u|^2, part[block][2].
+__global__ __launch_bounds__(kThreads) void k_admm_view(int m, const int* __restrict__ inc_off, const int* __restrict__ inc,
+                                                        const double* __restrict__ z, const double* __restrict__ zold,
+                                                        const double* __restrict__ u, double rho, double* __restrict__ part) {
+  __shared__ double red[kThreads];
+  const int v = blockIdx.x * kThreads + threadIdx.x;
+  double ss = 0.0, tt = 0.0;
+  if (v < m) {
+    double s[3] = {0.0, 0.0, 0.0}, t[3] = {0.0, 0.0, 0.0};
+    for (int k = inc_off[v]; k < inc_off[v + 1]; ++k) {
+      const size_t e3 = 3 * (size_t)(inc[k] >> 1);
+      const bool plus = inc[k] & 1;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const double d = z[e3 + c] - zold[e3 + c];
+        s[c] += plus ? d : -d;
+        t[c] += plus ? u[e3 + c] : -u[e3 + c];
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const double sc = -rho * s[c], tc = rho * t[c];
+      ss += sc * sc; tt += tc * tc;
+    }
+  }
+  const double s0 = block_sum(ss, red), s1 = block_sum(tt, red);
+  if (threadIdx.x == 0) { part[2 * blockIdx.x] = s0; part[2 * blockIdx.x + 1] = s1; }
+}
+
+// UpdateGlobalRotations (:252-266): r_v <- MultiplyRotations(r_v, delta_v) for the free views, and the block partials of
+// |delta_v| for ComputeAverageStepSize (:286-294).
+__global__ __launch_bounds__(kThreads) void k_update(int m, const int* __restrict__ free_view, const double* __restrict__ x,
+                                                     double* __restrict__ aa, double* __restrict__ part) {
+  __shared__ double red[kThreads];
+  const int v = blockIdx.x * kThreads + threadIdx.x;
+  double step = 0.0;
+  if (v < m) {
+    const int id = free_view[v];
+    const double d[3] = {x[v], x[(size_t)m + v], x[2 * (size_t)m + v]};
+    const double r[3] = {aa[3 * (size_t)id], aa[3 * (size_t)id + 1], aa[3 * (size_t)id + 2]};
+    double o[3];
+    multiply_rotations(r, d, o);
+    aa[3 * (size_t)id] = o[0]; aa[3 * (size_t)id + 1] = o[1]; aa[3 * (size_t)id + 2] = o[2];
+    step = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+  }
+  const double s = block_sum(step, red);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// Second stage of every reduction: out[c] = sum over blocks of part[block][c], one workgroup, fixed order.
+__global__ __launch_bounds__(kThreads) void k_reduce(const double* __restrict__ part, int nblk, int ncol, double* __restrict__ out) {
+  __shared__ double red[kThreads];
+  for (int c = 0; c < ncol; ++c) {
+    double s = 0.0;
+    for (int b = threadIdx.x; b < nblk; b += kThreads) s += part[(size_t)b * ncol + c];
+    s = block_sum(s, red);
+    if (threadIdx.x == 0) out[c] = s;
+  }
+}
+
+template <class T>
+struct DevBuf {
+  T* p = nullptr;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { if (p) (void)hipFree(p); }
+  int alloc(size_t n) {
+    if (hipMalloc((void**)&p, std::max<size_t>(1, n) * sizeof(T)) != hipSuccess) {
+      (void)hipGetLastError();
+      p = nullptr;
+      return set_error(THEIA_HIP_ERR_OUT_OF_MEMORY, "hipMalloc(%zu) failed", n * sizeof(T));
+    }
+    return 0;
+  }
+  int up(const void* src, size_t n) {
+    int rc = alloc(n);
+    if (rc) return rc;
+    if (n && hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess)
+      return set_error(THEIA_HIP_ERR_INTERNAL, "hipMemcpy H2D failed");
+    return 0;
+  }
+};
+
+int find_root(std::vector<int>& parent, int v) {
+  while (parent[v] != v) { parent[v] = parent[parent[v]]; v = parent[v]; }
+  return v;
+}
+
+double ms_since(std::chrono::steady_clock::time_point t0) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+int grid_of(int n) { return std::max(1, (n + kThreads - 1) / kThreads); }
+
+}  // namespace
+}  // namespace thip
+
+using namespace thip;
+
+extern "C" int theia_hip_robust_rotation_averaging(int32_t num_views, double* orientations, const uint8_t* fixed,
+                                                   int32_t num_edges, const int32_t* edges, const double* relative_rotations,
+                                                   const theia_rotation_options* o, theia_rotation_summary* summary) {
+  const auto t_start = std::chrono::steady_clock::now();
+  const int n = num_views, E = num_edges;
+  if (n < 1 || !orientations) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "no views");
+  if (E < 1 || !edges || !relative_rotations)   // CHECK_GT(relative_rotations_.size(), 0) (robust_rotation_estimator.cc:68)
+    return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "no relative rotation constraints");
+  if (!o || !summary) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "null options or summary");
+  if (o->max_num_l1_iterations < 0 || o->max_num_irls_iterations < 0 || !(o->irls_loss_parameter_sigma > 0.0))
+    return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "bad options");
+  for (int e = 0; e < E; ++e)
+    if (edges[2 * e] < 0 || edges[2 * e] >= n || edges[2 * e + 1] < 0 || edges[2 * e + 1] >= n)
+      return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "edge %d names a view out of range", e);
+  *summary = theia_rotation_summary{};
+
+  // fixed views (none flagged: view 0), free-view numbering in view order
+  std::vector<uint8_t> fix(n, 0);
+  bool any = false;
+  for (int v = 0; v < n && fixed; ++v) { fix[v] = fixed[v] ? 1 : 0; any = any || fix[v]; }
+  if (!any) fix[0] = 1;
+  // every connected component needs a fixed view, else A'A is singular (the L1Solver constructor's CHECK)
+  std::vector<int> parent(n);
+  std::iota(parent.begin(), parent.end(), 0);
+  for (int e = 0; e < E; ++e) {
+    const int a = find_root(parent, edges[2 * e]), b = find_root(parent, edges[2 * e + 1]);
+    if (a != b) parent[std::max(a, b)] = std::min(a, b);
+  }
+  std::vector<uint8_t> anchored(n, 0);
+  for (int v = 0; v < n; ++v) if (fix[v]) anchored[find_root(parent, v)] = 1;
+  for (int v = 0; v < n; ++v)
+    if (!anchored[find_root(parent, v)])
+      return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "view %d lies in a connected component without a fixed view", v);
+  std::vector<int> idx(n, -1), free_view;
+  for (int v = 0; v < n; ++v) if (!fix[v]) { idx[v] = (int)free_view.size(); free_view.push_back(v); }
+  const int m = (int)free_view.size();
+  if (m == 0) { summary->setup_ms = ms_since(t_start); return 0; }   // nothing moves
+
+  // CSR of the incident edges per free view (edge order) and of the edges per unordered free-view pair (edge order);
+  // self-loops have a zero row in A and are left out of both
+  std::vector<int> inc_off(m + 1, 0), inc;
+  std::vector<std::pair<int64_t, int>> pe;   // (pair key, edge)
+  for (int e = 0; e < E; ++e) {
+    const int i = edges[2 * e], j = edges[2 * e + 1];
+    if (i == j) continue;
+    if (idx[i] >= 0) ++inc_off[idx[i] + 1];
+    if (idx[j] >= 0) ++inc_off[idx[j] + 1];
+    if (idx[i] >= 0 && idx[j] >= 0) {
+      const int a = std::max(idx[i], idx[j]), b = std::min(idx[i], idx[j]);
+      pe.emplace_back((int64_t)a * m + b, e);
+    }
+  }
+  for (int v = 0; v < m; ++v) inc_off[v + 1] += inc_off[v];
+  inc.resize(inc_off[m]);
+  {
+    std::vector<int> fill(inc_off.begin(), inc_off.end() - 1);
+    for (int e = 0; e < E; ++e) {
+      const int i = edges[2 * e], j = edges[2 * e + 1];
+      if (i == j) continue;
+      if (idx[i] >= 0) inc[fill[idx[i]]++] = 2 * e;
+      if (idx[j] >= 0) inc[fill[idx[j]]++] = 2 * e + 1;
+    }
+  }
+  std::sort(pe.begin(), pe.end());
+  std::vector<int> pair_off(1, 0), pair_edge(pe.size());
+  std::vector<int2> pair_rc;
+  for (size_t k = 0; k < pe.size(); ++k) {
+    if (k == 0 || pe[k].first != pe[k - 1].first) {
+      if (k) pair_off.push_back((int)k);
+      pair_rc.push_back(make_int2((int)(pe[k].first / m), (int)(pe[k].first % m)));
+    }
+    pair_edge[k] = pe[k].second;
+  }
+  pair_off.push_back((int)pe.size());
+  const int P = (int)pair_rc.size();
+
+  int rc = thip::ensure_device();
+  if (rc) return rc;
+  const int lda = m + 3;
+  const int nbE = grid_of(E), nbV = grid_of(m);
+  DevBuf<double> d_aa, d_rel, d_res, d_w, d_A, d_work, d_flag, d_b, d_z, d_u, d_zold, d_g, d_T, d_x, d_part, d_sums;
+  DevBuf<int2> d_edges, d_pair_rc;
+  DevBuf<int> d_idx, d_free, d_inc_off, d_inc, d_pair_off, d_pair_edge;
+  const size_t dense = (size_t)(m + 3) * lda;
+  if ((rc = d_A.alloc(dense)) || (rc = d_work.alloc(dense_cholesky_workspace(m))) || (rc = d_flag.alloc(1)) ||
+      (rc = d_aa.up(orientations, 3 * (size_t)n)) || (rc = d_rel.up(relative_rotations, 3 * (size_t)E)) ||
+      (rc = d_edges.up(edges, E)) || (rc = d_idx.up(idx.data(), n)) || (rc = d_free.up(free_view.data(), m)) ||
+      (rc = d_inc_off.up(inc_off.data(), m + 1)) || (rc = d_inc.up(inc.data(), inc.size())) ||
+      (rc = d_pair_off.up(pair_off.data(), pair_off.size())) || (rc = d_pair_edge.up(pair_edge.data(), pair_edge.size())) ||
+      (rc = d_pair_rc.up(pair_rc.data(), pair_rc.size())) || (rc = d_res.alloc(3 * (size_t)E)) || (rc = d_w.alloc(E)) ||
+      (rc = d_b.alloc(3 * (size_t)E)) || (rc = d_z.alloc(3 * (size_t)E)) || (rc = d_u.alloc(3 * (size_t)E)) ||
+      (rc = d_zold.alloc(3 * (size_t)E)) || (rc = d_g.alloc(3 * (size_t)m)) || (rc = d_T.alloc(3 * (size_t)m)) ||
+      (rc = d_x.alloc(3 * (size_t)m)) || (rc = d_part.alloc(3 * (size_t)std::max(nbE, nbV))) || (rc = d_sums.alloc(8)))
+    return rc;
+  hipStream_t st = nullptr;
+  const double sigma = o->irls_loss_parameter_sigma;
+  double sums[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  // residuals and weights of the current orientations, |e|^2 -> sums[6]
+  auto residuals = [&]() {
+    k_residual<<<nbE, kThreads, 0, st>>>(E, d_edges.p, d_rel.p, d_aa.p, sigma, d_res.p, d_w.p, d_part.p);
+    k_reduce<<<1, kThreads, 0, st>>>(d_part.p, nbE, 1, d_sums.p + 6);
+  };
+  // update with d_x, new residuals; returns the average step size (sums[5] / m)
+  auto update = [&](double* avg) -> int {
+    k_update<<<nbV, kThreads, 0, st>>>(m, d_free.p, d_x.p, d_aa.p, d_part.p);
+    k_reduce<<<1, kThreads, 0, st>>>(d_part.p, nbV, 1, d_sums.p + 5);
+    residuals();
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(sums, d_sums.p, sizeof(sums), hipMemcpyDeviceToHost));
+    *avg = sums[5] / m;
+    return 0;
+  };
+  auto factor_failed = [&](bool* failed) -> int {
+    double flag = 0.0;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(&flag, d_flag.p, sizeof(double), hipMemcpyDeviceToHost));
+    *failed = flag != 0.0;
+    return 0;
+  };
+  auto give_back = [&]() -> int {
+    HIP_TRY(hipMemcpy(orientations, d_aa.p, sizeof(double) * 3 * (size_t)n, hipMemcpyDeviceToHost));
+    return 0;
+  };
+
+  // ---- L1 stage (SolveL1Regression, :164-185; L1Solver, math/l1_solver.h): factor A'A = L (x) I_3 once
+  HIP_TRY(hipMemsetAsync(d_A.p, 0, sizeof(double) * dense, st));
+  HIP_TRY(hipMemsetAsync(d_flag.p, 0, sizeof(double), st));
+  HIP_TRY(hipMemsetAsync(d_x.p, 0, sizeof(double) * 3 * m, st));
+  residuals();
+  k_assemble<<<grid_of(m + P), kThreads, 0, st>>>(m, P, lda, d_inc_off.p, d_inc.p, d_pair_off.p, d_pair_edge.p, d_pair_rc.p,
+                                                 nullptr, d_res.p, d_A.p);
+  dense_cholesky_factor(m, 1, d_A.p, lda, d_work.p, d_flag.p, st);   // row m (A'e, unused) rides along
+  bool failed = false;
+  if ((rc = factor_failed(&failed))) return rc;
+  HIP_TRY(hipMemcpy(sums, d_sums.p, sizeof(sums), hipMemcpyDeviceToHost));
+  summary->setup_ms = ms_since(t_start);
+  if (failed) return set_error(THEIA_HIP_ERR_INTERNAL, "the Cholesky factorisation of A'A failed");
+  const auto t_l1 = std::chrono::steady_clock::now();
+  const double rho = 1.0, alpha = 1.0, abs_tol = 1e-4, rel_tol = 1e-2;
+  const double primal_abs_eps = std::sqrt(3.0 * E) * abs_tol, dual_abs_eps = std::sqrt(3.0 * m) * abs_tol;
+  int max_admm = 5;
+  for (int pass = 0; pass < o->max_num_l1_iterations; ++pass) {
+    // L1Solver::Solve(residual, &step): z = u = 0, b = residual
+    HIP_TRY(hipMemcpyAsync(d_b.p, d_res.p, sizeof(double) * 3 * E, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemsetAsync(d_z.p, 0, sizeof(double) * 3 * E, st));
+    HIP_TRY(hipMemsetAsync(d_u.p, 0, sizeof(double) * 3 * E, st));
+    const double rhs_norm = std::sqrt(sums[6]);
+    for (int it = 0; it < max_admm; ++it) {
+      k_admm_rhs<<<nbV, kThreads, 0, st>>>(m, d_inc_off.p, d_inc.p, d_b.p, d_z.p, d_u.p, d_g.p);
+      dense_cholesky_solve_factored(m, d_A.p, lda, d_work.p, 3, d_g.p, m, d_T.p, d_x.p, m, st);
+      k_admm_edge<<<nbE, kThreads, 0, st>>>(E, m, d_edges.p, d_idx.p, d_x.p, d_b.p, d_z.p, d_zold.p, d_u.p, alpha, 1.0 / rho, d_part.p);
+      k_reduce<<<1, kThreads, 0, st>>>(d_part.p, nbE, 3, d_sums.p);
+      k_admm_view<<<nbV, kThreads, 0, st>>>(m, d_inc_off.p, d_inc.p, d_z.p, d_zold.p, d_u.p, rho, d_part.p);
+      k_reduce<<<1, kThreads, 0, st>>>(d_part.p, nbV, 2, d_sums.p + 3);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipMemcpy(sums, d_sums.p, sizeof(double) * 5, hipMemcpyDeviceToHost));
+      ++summary->admm_iterations;
+      const double r_norm = std::sqrt(sums[0]), s_norm = std::sqrt(sums[3]);
+      const double max_norm = std::max({std::sqrt(sums[1]), std::sqrt(sums[2]), rhs_norm});
+      const double primal_eps = primal_abs_eps + rel_tol * max_norm;
+      const double dual_eps = dual_abs_eps + rel_tol * std::sqrt(sums[4]);
+      if (r_norm < primal_eps && s_norm < dual_eps) break;
+    }
+    double avg = 0.0;
+    if ((rc = update(&avg))) return rc;
+    ++summary->l1_iterations;
+    if (avg <= o->l1_step_convergence_threshold) break;
+    max_admm *= 2;
+  }
+  summary->l1_ms = ms_since(t_l1);
+
+  // ---- IRLS stage (SolveIRLS, :187-250): per iteration factor L_w with the three rows of A'W e forward-substituted
+  const auto t_irls = std::chrono::steady_clock::now();
+  for (int it = 0; it < o->max_num_irls_iterations; ++it) {
+    HIP_TRY(hipMemsetAsync(d_A.p, 0, sizeof(double) * dense, st));
+    k_assemble<<<grid_of(m + P), kThreads, 0, st>>>(m, P, lda, d_inc_off.p, d_inc.p, d_pair_off.p, d_pair_edge.p, d_pair_rc.p,
+                                                   d_w.p, d_res.p, d_A.p);
+    dense_cholesky_factor(m, 3, d_A.p, lda, d_work.p, d_flag.p, st);
+    if ((rc = factor_failed(&failed))) return rc;
+    if (failed) {
+      summary->irls_ms = ms_since(t_irls);
+      summary->final_squared_residual = sums[6];
+      if ((rc = give_back())) return rc;
+      return set_error(THEIA_HIP_ERR_INTERNAL, "the Cholesky factorisation of A'WA failed in IRLS iteration %d", it);
+    }
+    dense_cholesky_back_substitute(m, d_A.p, lda, d_work.p, 3, d_A.p + (size_t)m * lda, lda, d_x.p, m, st);
+    double avg = 0.0;
+    if ((rc = update(&avg))) return rc;
+    ++summary->irls_iterations;
+    if (avg < o->irls_step_convergence_threshold) break;
+  }
+  summary->irls_ms = ms_since(t_irls);
+  summary->final_squared_residual = sums[6];
+  return give_back();
+}
+
+// Introspection for the parity tests: factor A once, then solve the k right-hand sides against the factor
+// (dense_cholesky_solve_factored: the forward and backward kernels of the ADMM solves).
+extern "C" int theia_hip_dense_spd_solve_multi(int32_t n, const double* A, int32_t k, const double* B, double* X) {
+  if (n < 0 || k < 1 || (n > 0 && (!A || !B || !X))) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "bad argument");
+  if (n == 0) return 0;
+  int rc = thip::ensure_device();
+  if (rc) return rc;
+  const int lda = n + 1;   // row n: the factorisation's right-hand-side row (zero, unused)
+  DevBuf<double> dA, dw, dflag, dB, dT, dX;
+  if ((rc = dA.alloc((size_t)(n + 1) * lda)) || (rc = dw.alloc(dense_cholesky_workspace(n))) || (rc = dflag.alloc(1)) ||
+      (rc = dB.up(B, (size_t)k * n)) || (rc = dT.alloc((size_t)k * n)) || (rc = dX.alloc((size_t)k * n)))
+    return rc;
+  HIP_TRY(hipMemset(dA.p, 0, sizeof(double) * (size_t)(n + 1) * lda));
+  HIP_TRY(hipMemcpy2D(dA.p, sizeof(double) * lda, A, sizeof(double) * n, sizeof(double) * n, n, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(dflag.p, 0, sizeof(double)));
+  dense_cholesky_factor(n, 1, dA.p, lda, dw.p, dflag.p, nullptr);
+  dense_cholesky_solve_factored(n, dA.p, lda, dw.p, k, dB.p, n, dT.p, dX.p, n, nullptr);
+  HIP_TRY(hipGetLastError());
+  double flag = 0.0;
+  HIP_TRY(hipMemcpy(X, dX.p, sizeof(double) * (size_t)k * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&flag, dflag.p, sizeof(double), hipMemcpyDeviceToHost));
+  if (flag != 0.0) return set_error(THEIA_HIP_ERR_INTERNAL, "matrix is not positive definite");
+  return 0;
+}

@@ -20,6 +20,8 @@ import numpy as np
 from . import _capi as capi
 from . import ba as _ba
 from .synth import angle_axis_to_matrix
+from .global_pose import (GlobalRotationEstimatorType, RobustRotationEstimator,  # noqa: F401  (pyTheia's names)
+                          RobustRotationEstimatorOptions)
 
 kInvalidViewId = 0xFFFFFFFF
 
