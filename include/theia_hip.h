@@ -468,6 +468,39 @@ int theia_hip_dense_spd_solve(int32_t n, const double* A, const double* b, doubl
  * B [k][n] into X [k][n] against the stored factor.  THEIA_HIP_ERR_INTERNAL when a pivot is not positive. */
 int theia_hip_dense_spd_solve_multi(int32_t n, const double* A, int32_t k, const double* B, double* X);
 
+/* K3 on a tile structure the caller chooses (introspection for the K3 tests): the level-scheduled tile-sparse Cholesky
+ * (chol_plan_create / chol_plan_solve) the BA runs, built for the given 64 x 64 tile co-visibility.
+ * A: n x n SPD, row-major with leading dimension lda >= n.  Of the buffer only the factor's structure tiles (the declared
+ * ones plus fill) at their physical lower position are read, and of a diagonal tile only its lower triangle: the strict
+ * upper triangle is never read, so the assembly does not have to write it.
+ * tile_adj [nt][nt] (nt = ceil(n / 64)), symmetric (the diagonal is ignored), or NULL = dense.
+ * mode 0: A uploaded verbatim, the rhs as row n, the solution in place (the BA's layout when lda == n).
+ * mode 1: as mode 0, but the solution goes to a separate buffer (the non-in-place back-substitution).
+ * mode 2: a device buffer filled with NaN, chol_plan_clear, then A's lower structure tiles (tile_adj + the diagonal
+ *         tiles) and the rhs ADDED on the device: the BA's clear-then-accumulate order.
+ * info (optional): the path the plan took.  tile_order / tile_level [nt] (optional): the plan's elimination order
+ * (the tile at each position) and the level of each position (identity / 0 .. nt-1 on the dense path).
+ * THEIA_HIP_ERR_INTERNAL when a pivot is not positive; THEIA_HIP_ERR_INVALID_ARGUMENT for a bad n / lda / mode or an
+ * asymmetric tile_adj (checked before the device is touched). */
+typedef struct theia_k3_info {
+  int32_t dense;             /* 1 = the plan fell back to the dense panel chain */
+  int32_t levels, num_symm_tiles, num_deferred_targets, num_deferred_partials, split_level, num_shared_tiles;
+  double flops;
+} theia_k3_info;
+int theia_hip_tile_sparse_spd_solve(int32_t n, int32_t lda, const uint8_t* tile_adj, int32_t mode, const double* A,
+                                    const double* b, double* x, theia_k3_info* info, int32_t* tile_order,
+                                    int32_t* tile_level);
+/* The sharded plan (chol_plan_create_sharded) of num_ranks ranks, emulated in one process on one device.  Rank r holds
+ * its partial system A [r] (n x n, lda = n) and b [r]; tile_class [r][nt]: 0 shared, 1 this rank's, 2 another rank's.
+ * Per rank: the plan, phase 0 on its own partial sums; then the tiles of chol_plan_shared_tiles and the whole rhs row
+ * summed over the ranks (in rank order, the same sum on every rank); then phase 1.  x [r]: rank r's raw solution (its
+ * own private columns and the shared ones are meaningful).  THEIA_HIP_ERR_INVALID_ARGUMENT for tile classes that are
+ * inconsistent across the ranks, THEIA_HIP_ERR_INTERNAL when the ranks' shared-tile lists differ or a pivot is not
+ * positive, THEIA_HIP_ERR_UNSUPPORTED when a rank's structure has no level schedule. */
+int theia_hip_tile_sparse_spd_solve_sharded(int32_t n, int32_t num_ranks, const uint8_t* tile_adj_union,
+                                            const uint8_t* tile_class, const double* A, const double* b, double* x,
+                                            theia_k3_info* info);
+
 /* RobustRotationEstimator::EstimateRotations (global_pose_estimation/robust_rotation_estimator.cc:66-110; pybind
  * sfm.cc:1749-1780, the ROBUST_L1L2 global rotation estimator of the global pipeline): L1 ADMM regression on the view
  * graph (math/l1_solver.h), then IRLS with the weight sigma / (|e|^2 + sigma^2)^2 per edge, through one N x N Laplacian

@@ -166,6 +166,16 @@ class RotationSummary(C.Structure):
                 ("l1_ms", C.c_double), ("irls_ms", C.c_double)]
 
 
+class K3Info(C.Structure):
+    """theia_k3_info."""
+    _fields_ = [("dense", C.c_int32), ("levels", C.c_int32), ("num_symm_tiles", C.c_int32),
+                ("num_deferred_targets", C.c_int32), ("num_deferred_partials", C.c_int32), ("split_level", C.c_int32),
+                ("num_shared_tiles", C.c_int32), ("flops", C.c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p)
 
 # every symbol include/theia_hip.h declares (checked by tests/test_capi_symbols.py)
@@ -175,7 +185,7 @@ EXPORTED_SYMBOLS = [
     "theia_hip_ba_reset_parameters", "theia_hip_estimate_tracks", "theia_hip_ba_set_shard", "theia_hip_ba_snapshot_parameters", "theia_hip_ba_restore_parameters", "theia_hip_ba_set_options", "theia_hip_ba_run", "theia_hip_ba_download",
     "theia_hip_ba_destroy", "theia_hip_ba_covariance", "theia_hip_ba_evaluate", "theia_hip_ba_evaluate_ex", "theia_hip_ba_reduced_system",
     "theia_hip_ba_set_allreduce", "theia_hip_ba_set_inner_global", "theia_hip_ba_plan_info", "theia_hip_rccl_unique_id", "theia_hip_rccl_comm_create",
-    "theia_hip_optimize_relative_position_batch", "theia_hip_rccl_comm_destroy", "theia_hip_rccl_comm_count", "theia_hip_ba_set_rccl", "theia_hip_dense_spd_solve", "theia_hip_dense_spd_solve_multi", "theia_hip_robust_rotation_averaging", "theia_ransac_params_default",
+    "theia_hip_optimize_relative_position_batch", "theia_hip_rccl_comm_destroy", "theia_hip_rccl_comm_count", "theia_hip_ba_set_rccl", "theia_hip_dense_spd_solve", "theia_hip_dense_spd_solve_multi", "theia_hip_tile_sparse_spd_solve", "theia_hip_tile_sparse_spd_solve_sharded", "theia_hip_robust_rotation_averaging", "theia_ransac_params_default",
     "theia_hip_ransac_estimate_batch", "theia_hip_five_point_relative_pose",
     "theia_hip_pose_from_three_points", "theia_hip_sqpnp", "theia_hip_dls_pnp", "theia_hip_dls_macaulay_terms", "theia_hip_four_point_pose_and_focal_length", "theia_hip_four_point_focal_length_radial_distortion", "theia_hip_four_point_focal_length_radial_distortion_ex", "theia_hip_release_scratch", "theia_hip_guided_knn", "theia_hip_randint_stream", "theia_hip_selftest_wave_primitives",
     "theia_hip_rng_seed", "theia_hip_rng_rand_int", "theia_hip_rng_rand_double", "theia_hip_rng_discard", "theia_hip_ransac_estimate_streams",
@@ -221,6 +231,10 @@ def lib():
     L.theia_ba_options_default.argtypes = [C.POINTER(BaOptions)]
     L.theia_hip_dense_spd_solve.argtypes = [C.c_int32, c_double_p, c_double_p, c_double_p]
     L.theia_hip_dense_spd_solve_multi.argtypes = [C.c_int32, c_double_p, C.c_int32, c_double_p, c_double_p]
+    L.theia_hip_tile_sparse_spd_solve.argtypes = [C.c_int32, C.c_int32, c_uint8_p, C.c_int32, c_double_p, c_double_p,
+                                                  c_double_p, C.POINTER(K3Info), c_int32_p, c_int32_p]
+    L.theia_hip_tile_sparse_spd_solve_sharded.argtypes = [C.c_int32, C.c_int32, c_uint8_p, c_uint8_p, c_double_p,
+                                                          c_double_p, c_double_p, C.POINTER(K3Info)]
     L.theia_hip_robust_rotation_averaging.argtypes = [C.c_int32, c_double_p, c_uint8_p, C.c_int32, c_int32_p, c_double_p,
                                                       C.POINTER(RotationOptions), C.POINTER(RotationSummary)]
     _lib = L

@@ -164,6 +164,37 @@ def dense_spd_solve(A, b):
     return x
 
 
+def tile_sparse_spd_solve(A, b, tile_adj=None, mode=0):
+    """K3 on a chosen tile structure (theia_hip_tile_sparse_spd_solve).  A: n x lda host buffer (lda = A.shape[1] >= n),
+    lower triangle read; tile_adj: [nt][nt] 0/1 or None (dense).  Returns (x, info dict, tile_order, tile_level);
+    raises TheiaHipError (INTERNAL when a pivot is not positive)."""
+    A = np.ascontiguousarray(A, dtype=np.float64); b = np.ascontiguousarray(b, dtype=np.float64)
+    n, lda = A.shape[0], A.shape[1]
+    nt = (n + 63) // 64
+    adj = None if tile_adj is None else np.ascontiguousarray(tile_adj, dtype=np.uint8)
+    x = np.empty(n)
+    info = capi.K3Info()
+    order = np.empty(max(nt, 1), np.int32); level = np.empty(max(nt, 1), np.int32)
+    capi.check(capi.lib().theia_hip_tile_sparse_spd_solve(n, lda, capi.ptr(adj, C.c_uint8), mode, capi.ptr(A, C.c_double),
+                                                          capi.ptr(b, C.c_double), capi.ptr(x, C.c_double), C.byref(info),
+                                                          capi.ptr(order, C.c_int32), capi.ptr(level, C.c_int32)))
+    return x, info.as_dict(), order[:nt], level[:nt]
+
+
+def tile_sparse_spd_solve_sharded(A, b, tile_adj, tile_class):
+    """The sharded K3 plan of R ranks emulated on one device (theia_hip_tile_sparse_spd_solve_sharded).
+    A: [R][n][n] partial systems, b: [R][n], tile_class: [R][nt].  Returns (x [R][n], list of R info dicts)."""
+    A = np.ascontiguousarray(A, dtype=np.float64); b = np.ascontiguousarray(b, dtype=np.float64)
+    R, n = A.shape[0], A.shape[1]
+    adj = np.ascontiguousarray(tile_adj, dtype=np.uint8); cls = np.ascontiguousarray(tile_class, dtype=np.uint8)
+    x = np.empty((R, n))
+    info = (capi.K3Info * R)()
+    capi.check(capi.lib().theia_hip_tile_sparse_spd_solve_sharded(n, R, capi.ptr(adj, C.c_uint8), capi.ptr(cls, C.c_uint8),
+                                                                  capi.ptr(A, C.c_double), capi.ptr(b, C.c_double),
+                                                                  capi.ptr(x, C.c_double), info))
+    return x, [i.as_dict() for i in info]
+
+
 def solve(problem, options, trace_capacity=256):
     """theia_hip_ba_solve: parameters of `problem` are updated in place."""
     s = capi.BaSummary()

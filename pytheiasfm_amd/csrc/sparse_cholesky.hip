@@ -17,12 +17,14 @@
 // triangle are first mirrored from the lower one).
 #include "ba_kernels.h"
 #include "cholesky_device.h"
+#include "theia_hip_internal.h"
 
 #include <algorithm>
 #include <cstdlib>
 #include <cstdio>
 #include <functional>
 #include <map>
+#include <memory>
 #include <vector>
 
 namespace thip {
@@ -496,6 +498,7 @@ struct CholPlan {
   // after it; shared_tiles = the (tile row, tile column) positions the all-reduce has to sum.  lev_split = 0 otherwise.
   int lev_split = 0;
   std::vector<int> shared_tiles;
+  std::vector<int> perm, pos_level;   // elimination order (tile at each position) and the level of each position
   int* prog = nullptr;   // device
   double* scratch = nullptr;   // device: partial tiles of the deferred updates
   ~CholPlan() { if (prog) (void)hipFree(prog); if (scratch) (void)hipFree(scratch); }
@@ -606,6 +609,8 @@ CholPlan* chol_plan_create_impl(int n, const uint8_t* adj_in, const uint8_t* til
   if (best.ntiles >= (long long)nt * (nt + 1) / 2 || best.nlev >= nt) return pl;   // nothing to gain: dense path
   pl->dense = false;
   pl->nlev = best.nlev;
+  pl->perm = perm;
+  pl->pos_level = best.level;
 
   auto r0 = [&](int I) { return I == nt ? n : perm[I] * NB; };                 // I == nt: the rhs row
   auto hh = [&](int I) { return I == nt ? 1 : std::min(NB, n - perm[I] * NB); };
@@ -693,7 +698,7 @@ CholPlan* chol_plan_create_impl(int n, const uint8_t* adj_in, const uint8_t* til
     prog.insert(prog.end(), srcs.begin(), srcs.end());
     pl->def_red_off = (int)prog.size(); pl->n_def_red = (int)red.size() / 7;
     prog.insert(prog.end(), red.begin(), red.end());
-    if (hipMalloc((void**)&pl->scratch, sizeof(double) * (size_t)slot * NB * NB) != hipSuccess) { pl->scratch = nullptr; pl->dense = true; pl->lev.clear(); return pl; }
+    if (hipMalloc((void**)&pl->scratch, sizeof(double) * (size_t)slot * NB * NB) != hipSuccess) { pl->scratch = nullptr; pl->dense = true; pl->lev.clear(); pl->perm.clear(); pl->pos_level.clear(); return pl; }
   }
   // tiles of the factor structure that sit in the physical upper triangle
   pl->symm_off = (int)prog.size();
@@ -737,6 +742,7 @@ CholPlan* chol_plan_create_impl(int n, const uint8_t* adj_in, const uint8_t* til
       hipMemcpy(pl->prog, prog.data(), sizeof(int) * prog.size(), hipMemcpyHostToDevice) != hipSuccess) {
     pl->dense = true;   // dense schedule instead (same solution)
     pl->lev.clear();
+    pl->perm.clear(); pl->pos_level.clear();
   }
   return pl;
 }
@@ -823,3 +829,204 @@ int chol_plan_split_level(const CholPlan* pl) { return pl && !pl->dense ? pl->le
 const std::vector<int>& chol_plan_shared_tiles(const CholPlan* pl) { return pl->shared_tiles; }
 
 }  // namespace thip
+
+// ------------------------------------------------------------------ introspection (the K3 tests)
+// K3 on a tile structure the caller chooses: theia_hip_tile_sparse_spd_solve[_sharded] (include/theia_hip.h).
+namespace thip {
+namespace {
+
+#define K3_TRY(expr)                                                                                      \
+  do {                                                                                                    \
+    hipError_t e_ = (expr);                                                                               \
+    if (e_ != hipSuccess) return set_error(THEIA_HIP_ERR_INTERNAL, "%s: %s", #expr, hipGetErrorString(e_)); \
+  } while (0)
+
+template <class T>
+struct K3Buf {
+  T* p = nullptr;
+  K3Buf() = default;
+  K3Buf(const K3Buf&) = delete;
+  K3Buf& operator=(const K3Buf&) = delete;
+  ~K3Buf() { if (p) (void)hipFree(p); }
+  int alloc(size_t n) {
+    if (hipMalloc((void**)&p, std::max<size_t>(1, n) * sizeof(T)) != hipSuccess) {
+      (void)hipGetLastError();
+      p = nullptr;
+      return set_error(THEIA_HIP_ERR_OUT_OF_MEMORY, "hipMalloc(%zu) failed", n * sizeof(T));
+    }
+    return 0;
+  }
+};
+
+__global__ __launch_bounds__(256) void k_k3_fill(double* __restrict__ p, size_t count, double v) {
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < count; e += (size_t)gridDim.x * 256) p[e] = v;
+}
+
+// items {r0, h, c0, w, diag}: dst tile += src tile (accumulate != 0) or dst tile = src tile; diag: lower triangle only
+__global__ __launch_bounds__(256) void k_k3_tiles(double* __restrict__ dst, const double* __restrict__ src, int lda,
+                                                  const int* __restrict__ items, int accumulate) {
+  const int* it = items + 5 * blockIdx.x;
+  const int r0 = it[0], h = it[1], c0 = it[2], w = it[3], diag = it[4];
+  for (int e = threadIdx.x; e < NB * NB; e += 256) {
+    const int r = e >> 6, c = e & 63;
+    if (r >= h || c >= w || (diag && c > r)) continue;
+    const size_t o = (size_t)(r0 + r) * lda + c0 + c;
+    dst[o] = accumulate ? dst[o] + src[o] : src[o];
+  }
+}
+
+int k3_tiles(double* dst, const double* src, int lda, const std::vector<int>& items, int accumulate) {
+  if (items.empty()) return 0;
+  K3Buf<int> d;
+  int rc = d.alloc(items.size());
+  if (rc) return rc;
+  K3_TRY(hipMemcpy(d.p, items.data(), sizeof(int) * items.size(), hipMemcpyHostToDevice));
+  k_k3_tiles<<<(int)(items.size() / 5), 256>>>(dst, src, lda, d.p, accumulate);
+  K3_TRY(hipGetLastError());
+  K3_TRY(hipDeviceSynchronize());
+  return 0;
+}
+
+// tile (rt, ct) of the n x n matrix; rt < 0: column tile ct of the rhs row (row n)
+void k3_item(std::vector<int>& v, int n, int rt, int ct, int diag) {
+  v.push_back(rt < 0 ? n : rt * NB); v.push_back(rt < 0 ? 1 : std::min(NB, n - rt * NB));
+  v.push_back(ct * NB); v.push_back(std::min(NB, n - ct * NB)); v.push_back(diag);
+}
+
+bool k3_adj_symmetric(int nt, const uint8_t* adj) {
+  for (int i = 0; i < nt; ++i)
+    for (int j = 0; j < i; ++j)
+      if ((adj[(size_t)i * nt + j] != 0) != (adj[(size_t)j * nt + i] != 0)) return false;
+  return true;
+}
+
+void k3_fill_info(const CholPlan* pl, theia_k3_info* info) {
+  if (!info) return;
+  info->dense = pl->dense ? 1 : 0;
+  info->levels = chol_plan_levels(pl);
+  info->num_symm_tiles = pl->dense ? 0 : pl->nsymm;
+  info->num_deferred_targets = pl->dense ? 0 : pl->n_def_red;
+  info->num_deferred_partials = pl->dense ? 0 : pl->n_def_part;
+  info->split_level = chol_plan_split_level(pl);
+  info->num_shared_tiles = (int32_t)(pl->shared_tiles.size() / 2);
+  info->flops = chol_plan_flops(pl);
+}
+
+}  // namespace
+}  // namespace thip
+
+using namespace thip;
+
+extern "C" int theia_hip_tile_sparse_spd_solve(int32_t n, int32_t lda, const uint8_t* tile_adj, int32_t mode, const double* A,
+                                               const double* b, double* x, theia_k3_info* info, int32_t* tile_order,
+                                               int32_t* tile_level) {
+  if (n <= 0 || lda < n || mode < 0 || mode > 2 || !A || !b || !x)
+    return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "tile_sparse_spd_solve: bad argument (n = %d, lda = %d, mode = %d)", n, lda, mode);
+  const int nt = (n + NB - 1) / NB;
+  if (tile_adj && !k3_adj_symmetric(nt, tile_adj))
+    return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "tile_sparse_spd_solve: the tile adjacency is not symmetric");
+  int rc = ensure_device();
+  if (rc) return rc;
+  CholPlan* pl = chol_plan_create(n, tile_adj);
+  std::unique_ptr<CholPlan, void (*)(CholPlan*)> hold(pl, chol_plan_destroy);
+  k3_fill_info(pl, info);
+  for (int i = 0; i < nt; ++i) {
+    if (tile_order) tile_order[i] = pl->dense ? i : pl->perm[i];
+    if (tile_level) tile_level[i] = pl->dense ? i : pl->pos_level[i];
+  }
+  const size_t cnt = (size_t)(n + 1) * lda;
+  K3Buf<double> dA, dw, dflag, dx, dstage;
+  if ((rc = dA.alloc(cnt)) || (rc = dw.alloc(dense_cholesky_workspace(n))) || (rc = dflag.alloc(1)) || (rc = dx.alloc(n))) return rc;
+  K3_TRY(hipMemset(dflag.p, 0, sizeof(double)));
+  const double nan = __builtin_nan("");
+  k_k3_fill<<<64, 256>>>(dx.p, (size_t)n, nan);
+  if (mode < 2) {
+    K3_TRY(hipMemcpy(dA.p, A, sizeof(double) * (size_t)n * lda, hipMemcpyHostToDevice));
+    K3_TRY(hipMemcpy(dA.p + (size_t)n * lda, b, sizeof(double) * n, hipMemcpyHostToDevice));
+  } else {
+    // the BA's order: a buffer with anything in it, the per-iteration clear, then the assembly adds into the structure
+    // tiles (lower triangle of the diagonal tiles) and the rhs
+    if ((rc = dstage.alloc(cnt))) return rc;
+    k_k3_fill<<<1024, 256>>>(dA.p, cnt, nan);
+    K3_TRY(hipMemcpy(dstage.p, A, sizeof(double) * (size_t)n * lda, hipMemcpyHostToDevice));
+    K3_TRY(hipMemcpy(dstage.p + (size_t)n * lda, b, sizeof(double) * n, hipMemcpyHostToDevice));
+    if (!chol_plan_clear(pl, dA.p, lda, nullptr, dA.p + (size_t)n * lda, (size_t)n)) K3_TRY(hipMemset(dA.p, 0, sizeof(double) * cnt));
+    std::vector<int> items;
+    for (int i = 0; i < nt; ++i)
+      for (int j = 0; j <= i; ++j)
+        if (i == j || !tile_adj || tile_adj[(size_t)i * nt + j]) k3_item(items, n, i, j, i == j);
+    for (int j = 0; j < nt; ++j) k3_item(items, n, -1, j, 0);
+    if ((rc = k3_tiles(dA.p, dstage.p, lda, items, 1))) return rc;
+  }
+  K3_TRY(hipGetLastError());
+  chol_plan_solve(pl, dA.p, lda, mode == 1 ? dx.p : dA.p + (size_t)n * lda, dw.p, dflag.p, nullptr);
+  K3_TRY(hipGetLastError());
+  K3_TRY(hipDeviceSynchronize());
+  double flag = 0.0;
+  K3_TRY(hipMemcpy(x, mode == 1 ? dx.p : dA.p + (size_t)n * lda, sizeof(double) * n, hipMemcpyDeviceToHost));
+  K3_TRY(hipMemcpy(&flag, dflag.p, sizeof(double), hipMemcpyDeviceToHost));
+  if (flag != 0.0) return set_error(THEIA_HIP_ERR_INTERNAL, "matrix is not positive definite");
+  return 0;
+}
+
+extern "C" int theia_hip_tile_sparse_spd_solve_sharded(int32_t n, int32_t num_ranks, const uint8_t* tile_adj_union,
+                                                       const uint8_t* tile_class, const double* A, const double* b, double* x,
+                                                       theia_k3_info* info) {
+  if (n <= 0 || num_ranks < 1 || num_ranks > 64 || !tile_adj_union || !tile_class || !A || !b || !x)
+    return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "tile_sparse_spd_solve_sharded: bad argument (n = %d, %d ranks)", n, num_ranks);
+  const int nt = (n + NB - 1) / NB, R = num_ranks;
+  if (!k3_adj_symmetric(nt, tile_adj_union))
+    return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "tile_sparse_spd_solve_sharded: the tile adjacency is not symmetric");
+  // a tile is shared on every rank, or private to exactly one rank and another rank's on all the others
+  for (int t = 0; t < nt; ++t) {
+    int c[3] = {0, 0, 0};
+    for (int r = 0; r < R; ++r) {
+      const uint8_t v = tile_class[(size_t)r * nt + t];
+      if (v > 2) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "tile_sparse_spd_solve_sharded: tile class %d", (int)v);
+      c[v]++;
+    }
+    if (!(c[0] == R || (c[1] == 1 && c[2] == R - 1)))
+      return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "tile_sparse_spd_solve_sharded: tile %d has inconsistent classes across the ranks", t);
+  }
+  int rc = ensure_device();
+  if (rc) return rc;
+  std::vector<std::unique_ptr<CholPlan, void (*)(CholPlan*)>> plans;
+  for (int r = 0; r < R; ++r) {
+    plans.emplace_back(chol_plan_create_sharded(n, tile_adj_union, tile_class + (size_t)r * nt), chol_plan_destroy);
+    if (!plans.back()) return set_error(THEIA_HIP_ERR_UNSUPPORTED, "rank %d: no level schedule for this structure", r);
+    k3_fill_info(plans.back().get(), info ? info + r : nullptr);
+  }
+  const std::vector<int>& st = chol_plan_shared_tiles(plans[0].get());
+  for (int r = 1; r < R; ++r)
+    if (chol_plan_shared_tiles(plans[r].get()) != st) return set_error(THEIA_HIP_ERR_INTERNAL, "rank %d: the shared-tile list differs from rank 0's", r);
+  const size_t cnt = (size_t)(n + 1) * n;
+  std::vector<K3Buf<double>> dA(R), dw(R);
+  K3Buf<double> dsum, dflag;
+  if ((rc = dsum.alloc(cnt)) || (rc = dflag.alloc(R))) return rc;
+  K3_TRY(hipMemset(dflag.p, 0, sizeof(double) * R));
+  for (int r = 0; r < R; ++r) {
+    if ((rc = dA[r].alloc(cnt)) || (rc = dw[r].alloc(dense_cholesky_workspace(n)))) return rc;
+    K3_TRY(hipMemcpy(dA[r].p, A + (size_t)r * n * n, sizeof(double) * (size_t)n * n, hipMemcpyHostToDevice));
+    K3_TRY(hipMemcpy(dA[r].p + (size_t)n * n, b + (size_t)r * n, sizeof(double) * n, hipMemcpyHostToDevice));
+    chol_plan_solve_phase(plans[r].get(), 0, dA[r].p, n, dA[r].p + (size_t)n * n, dw[r].p, dflag.p + r, nullptr);
+  }
+  K3_TRY(hipGetLastError());
+  K3_TRY(hipDeviceSynchronize());
+  // the all-reduce: the shared tiles and the whole rhs row, summed in rank order, the same sum handed to every rank
+  std::vector<int> items;
+  for (size_t k = 0; k + 1 < st.size(); k += 2) k3_item(items, n, st[k], st[k + 1], 0);
+  for (int j = 0; j < nt; ++j) k3_item(items, n, -1, j, 0);
+  if ((rc = k3_tiles(dsum.p, dA[0].p, n, items, 0))) return rc;
+  for (int r = 1; r < R; ++r) if ((rc = k3_tiles(dsum.p, dA[r].p, n, items, 1))) return rc;
+  for (int r = 0; r < R; ++r) if ((rc = k3_tiles(dA[r].p, dsum.p, n, items, 0))) return rc;
+  for (int r = 0; r < R; ++r)
+    chol_plan_solve_phase(plans[r].get(), 1, dA[r].p, n, dA[r].p + (size_t)n * n, dw[r].p, dflag.p + r, nullptr);
+  K3_TRY(hipGetLastError());
+  K3_TRY(hipDeviceSynchronize());
+  std::vector<double> flag(R);
+  for (int r = 0; r < R; ++r) K3_TRY(hipMemcpy(x + (size_t)r * n, dA[r].p + (size_t)n * n, sizeof(double) * n, hipMemcpyDeviceToHost));
+  K3_TRY(hipMemcpy(flag.data(), dflag.p, sizeof(double) * R, hipMemcpyDeviceToHost));
+  for (int r = 0; r < R; ++r)
+    if (flag[r] != 0.0) return set_error(THEIA_HIP_ERR_INTERNAL, "rank %d: matrix is not positive definite", r);
+  return 0;
+}

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from pytheiasfm_amd import _capi as capi, ba, sfm, synth
+from tests import k3_systems as k3s
 from tests import oracle_lib as ol
 
 pytestmark = pytest.mark.gpu
@@ -417,6 +418,7 @@ def test_dense_cholesky_kernel_against_numpy(n):
     x = ba.dense_spd_solve(np.tril(A), b)   # only the lower triangle is read
     xr = np.linalg.solve(A, b)
     assert np.abs(x - xr).max() <= 1e-9 * np.abs(xr).max() * max(1.0, np.linalg.cond(A) * 1e-6)
+    assert k3s.eta(A, x, b) <= k3s.eta_bound(n)   # backward error, long-double residual
     with pytest.raises(capi.TheiaHipError):
         Abad = A.copy(); Abad[n // 2, n // 2] = -1.0
         ba.dense_spd_solve(np.tril(Abad), b)

@@ -7,6 +7,7 @@ import pytest
 
 from pytheiasfm_amd import _capi as capi
 from pytheiasfm_amd import global_pose, sfm
+from tests import k3_systems as k3s
 from tests import rotation_averaging_ref as ref
 from tests import rotation_scenes as rs
 
@@ -94,6 +95,7 @@ def test_multi_rhs_solve_against_numpy(n):
                                                       capi.ptr(X, C.c_double)))
         Xr = np.linalg.solve(A, B.T).T
         assert np.abs(X - Xr).max() <= 1e-12 * np.abs(Xr).max()
+        assert max(k3s.eta(A, X[i], B[i]) for i in range(k)) <= k3s.eta_bound(n)   # backward error, long-double residual
         if k == 1:
             x1 = np.empty(n)
             b1 = np.ascontiguousarray(B[0])
