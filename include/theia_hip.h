@@ -523,6 +523,33 @@ int theia_hip_robust_rotation_averaging(int32_t num_views, double* orientations,
                                         const int32_t* edges, const double* relative_rotations,
                                         const theia_rotation_options* options, theia_rotation_summary* summary);
 
+/* LeastUnsquaredDeviationPositionEstimator::EstimatePositions (global_pose_estimation/
+ * least_unsquared_deviation_position_estimator.cc:75-213; pybind sfm.cc:1196-1204, 1707-1726, the default
+ * LEAST_UNSQUARED_DEVIATION position stage of the global pipeline): per pair e = (i, j) the rows c_j - c_i - s_e d_e with
+ * d_e = R_i' relative_translation_e and the bound s_e >= 1, solved by ConstrainedL1Solver's ADMM
+ * (math/constrained_l1_solver.cc:49-187) with the scales eliminated: one dense 3m x 3m Cholesky of the Schur complement
+ * (m = free views), factored once, then up to max_num_iterations x-updates against it; the stopping test runs on the
+ * device (csrc/lud_positions.hip).  orientations [num_views][3] angle-axis (world -> camera); fixed [num_views] non-zero =
+ * held at the origin, or NULL (view 0 is held -- the reference holds the first view its unordered_set yields); edges
+ * [num_edges][2] = (i, j) with relative_translations [num_edges][3] = TwoViewInfo::position_2; positions_out [num_views][3].
+ * THEIA_HIP_ERR_INVALID_ARGUMENT (the reference's CHECK failures; nothing launched, outputs untouched): no edge, an edge
+ * naming a view out of range, a connected component of the view graph without a held view (a view without edges counts),
+ * max_num_iterations <= 0, rho <= 0 or a non-finite option.  THEIA_HIP_ERR_INTERNAL: the factorisation failed (positions
+ * untouched).  THEIA_HIP_ERR_OUT_OF_MEMORY: the dense (3m + 1)^2 array of doubles does not fit on the device
+ * (5 000 free views take 1.8 GB, 20 000 take 29 GB). */
+typedef struct theia_lud_options {   /* ConstrainedL1Solver::Options (constrained_l1_solver.h:64-74) */
+  int32_t max_num_iterations, reserved;                 /* 1000 */
+  double rho, alpha, absolute_tolerance, relative_tolerance;   /* 10, 1.2, 1e-4, 1e-2 */
+} theia_lud_options;
+typedef struct theia_lud_summary {
+  int32_t admm_iterations, converged;   /* converged: the stopping test passed within max_num_iterations */
+  double r_norm, s_norm, primal_eps, dual_eps;   /* of the last iteration */
+  double setup_ms, factor_ms, admm_ms;
+} theia_lud_summary;
+int theia_hip_lud_positions(int32_t num_views, const double* orientations, const uint8_t* fixed, int32_t num_edges,
+                            const int32_t* edges, const double* relative_translations, const theia_lud_options* options,
+                            double* positions_out, theia_lud_summary* summary);
+
 /* Multi-GPU (one process per GPU): tracks are sharded by the caller; each
  * rank's handle holds its shard plus ALL cameras.  The reduced camera system
  * (and the scalar reductions) are summed across ranks through this callback,

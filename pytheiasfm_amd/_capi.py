@@ -166,6 +166,19 @@ class RotationSummary(C.Structure):
                 ("l1_ms", C.c_double), ("irls_ms", C.c_double)]
 
 
+class LudOptions(C.Structure):
+    """theia_lud_options."""
+    _fields_ = [("max_num_iterations", C.c_int32), ("reserved", C.c_int32), ("rho", C.c_double), ("alpha", C.c_double),
+                ("absolute_tolerance", C.c_double), ("relative_tolerance", C.c_double)]
+
+
+class LudSummary(C.Structure):
+    """theia_lud_summary."""
+    _fields_ = [("admm_iterations", C.c_int32), ("converged", C.c_int32), ("r_norm", C.c_double), ("s_norm", C.c_double),
+                ("primal_eps", C.c_double), ("dual_eps", C.c_double), ("setup_ms", C.c_double), ("factor_ms", C.c_double),
+                ("admm_ms", C.c_double)]
+
+
 class K3Info(C.Structure):
     """theia_k3_info."""
     _fields_ = [("dense", C.c_int32), ("levels", C.c_int32), ("num_symm_tiles", C.c_int32),
@@ -185,7 +198,7 @@ EXPORTED_SYMBOLS = [
     "theia_hip_ba_reset_parameters", "theia_hip_estimate_tracks", "theia_hip_ba_set_shard", "theia_hip_ba_snapshot_parameters", "theia_hip_ba_restore_parameters", "theia_hip_ba_set_options", "theia_hip_ba_run", "theia_hip_ba_download",
     "theia_hip_ba_destroy", "theia_hip_ba_covariance", "theia_hip_ba_evaluate", "theia_hip_ba_evaluate_ex", "theia_hip_ba_reduced_system",
     "theia_hip_ba_set_allreduce", "theia_hip_ba_set_inner_global", "theia_hip_ba_plan_info", "theia_hip_rccl_unique_id", "theia_hip_rccl_comm_create",
-    "theia_hip_optimize_relative_position_batch", "theia_hip_rccl_comm_destroy", "theia_hip_rccl_comm_count", "theia_hip_ba_set_rccl", "theia_hip_dense_spd_solve", "theia_hip_dense_spd_solve_multi", "theia_hip_tile_sparse_spd_solve", "theia_hip_tile_sparse_spd_solve_sharded", "theia_hip_robust_rotation_averaging", "theia_ransac_params_default",
+    "theia_hip_optimize_relative_position_batch", "theia_hip_rccl_comm_destroy", "theia_hip_rccl_comm_count", "theia_hip_ba_set_rccl", "theia_hip_dense_spd_solve", "theia_hip_dense_spd_solve_multi", "theia_hip_tile_sparse_spd_solve", "theia_hip_tile_sparse_spd_solve_sharded", "theia_hip_robust_rotation_averaging", "theia_hip_lud_positions", "theia_ransac_params_default",
     "theia_hip_ransac_estimate_batch", "theia_hip_five_point_relative_pose",
     "theia_hip_pose_from_three_points", "theia_hip_sqpnp", "theia_hip_dls_pnp", "theia_hip_dls_macaulay_terms", "theia_hip_four_point_pose_and_focal_length", "theia_hip_four_point_focal_length_radial_distortion", "theia_hip_four_point_focal_length_radial_distortion_ex", "theia_hip_release_scratch", "theia_hip_guided_knn", "theia_hip_randint_stream", "theia_hip_selftest_wave_primitives",
     "theia_hip_rng_seed", "theia_hip_rng_rand_int", "theia_hip_rng_rand_double", "theia_hip_rng_discard", "theia_hip_ransac_estimate_streams",
@@ -237,6 +250,8 @@ def lib():
                                                           c_double_p, c_double_p, C.POINTER(K3Info)]
     L.theia_hip_robust_rotation_averaging.argtypes = [C.c_int32, c_double_p, c_uint8_p, C.c_int32, c_int32_p, c_double_p,
                                                       C.POINTER(RotationOptions), C.POINTER(RotationSummary)]
+    L.theia_hip_lud_positions.argtypes = [C.c_int32, c_double_p, c_uint8_p, C.c_int32, c_int32_p, c_double_p,
+                                          C.POINTER(LudOptions), c_double_p, C.POINTER(LudSummary)]
     _lib = L
     return L
 

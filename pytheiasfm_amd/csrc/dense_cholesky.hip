@@ -186,9 +186,11 @@ __global__ __launch_bounds__(256) void k_back_step(const double* __restrict__ A,
 
 // The same step for k right-hand sides at once: blockIdx.y = vector (y, x of vector v at v * ldy, v * ldx).
 // Every vector takes k_back_step's arithmetic in k_back_step's order: k = 1 is bit-identical to it.
+// skip (optional): the step returns at once while *skip is non-zero (a device-side stopping test, lud_positions.hip).
 __global__ __launch_bounds__(256) void k_back_step_multi(const double* __restrict__ A, int lda, int n, int kb,
                                                          const double* __restrict__ Linv, double* __restrict__ y, int ldy,
-                                                         double* __restrict__ x, int ldx) {
+                                                         double* __restrict__ x, int ldx, const int* __restrict__ skip) {
+  if (skip && *skip) return;
   back_step(A, lda, n, kb, Linv, y + (size_t)blockIdx.y * ldy, x + (size_t)blockIdx.y * ldx);
 }
 
@@ -200,8 +202,9 @@ __global__ __launch_bounds__(256) void k_back_step_multi(const double* __restric
 // another one writes in the same launch.
 __global__ __launch_bounds__(256) void k_fwd_step_multi(const double* __restrict__ A, int lda, int n, int kb,
                                                         const double* __restrict__ Linv, double* __restrict__ b, int ldb,
-                                                        double* __restrict__ y, int ldy) {
+                                                        double* __restrict__ y, int ldy, const int* __restrict__ skip) {
   __shared__ double bk[NB], yk[NB], part[4][NB];
+  if (skip && *skip) return;
   b += (size_t)blockIdx.y * ldb;
   y += (size_t)blockIdx.y * ldy;
   const int k0 = kb * NB;
@@ -264,26 +267,26 @@ void dense_cholesky_factor(int n, int k, double* A, int lda, double* work, doubl
 }
 
 void dense_cholesky_back_substitute(int n, const double* A, int lda, const double* work, int k, double* Y, int ldy,
-                                    double* X, int ldx, hipStream_t st) {
+                                    double* X, int ldx, hipStream_t st, const int* skip) {
   if (n <= 0 || k <= 0) return;
   const int nblk = (n + NB - 1) / NB;
   for (int kb = nblk - 1; kb >= 0; --kb) {
     const int k0 = kb * NB;
     dim3 grid(k0 > 0 ? (k0 + 255) / 256 : 1, k);
-    k_back_step_multi<<<grid, 256, 0, st>>>(A, lda, n, kb, work, Y, ldy, X, ldx);
+    k_back_step_multi<<<grid, 256, 0, st>>>(A, lda, n, kb, work, Y, ldy, X, ldx, skip);
   }
 }
 
 void dense_cholesky_solve_factored(int n, const double* A, int lda, const double* work, int k, double* B, int ldb,
-                                   double* T, double* X, int ldx, hipStream_t st) {
+                                   double* T, double* X, int ldx, hipStream_t st, const int* skip) {
   if (n <= 0 || k <= 0) return;
   const int nblk = (n + NB - 1) / NB;
   for (int kb = 0; kb < nblk; ++kb) {
     const int below = n - std::min(n, (kb + 1) * NB);
     dim3 grid(below > 0 ? (below + 15) / 16 : 1, k);
-    k_fwd_step_multi<<<grid, 256, 0, st>>>(A, lda, n, kb, work, B, ldb, T, n);
+    k_fwd_step_multi<<<grid, 256, 0, st>>>(A, lda, n, kb, work, B, ldb, T, n, skip);
   }
-  dense_cholesky_back_substitute(n, A, lda, work, k, T, n, X, ldx, st);
+  dense_cholesky_back_substitute(n, A, lda, work, k, T, n, X, ldx, st, skip);
 }
 
 void dense_cholesky_solve(int n, double* A, int lda, double* b, double* work, double* fail_flag, hipStream_t st) {

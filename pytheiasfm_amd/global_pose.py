@@ -1,9 +1,12 @@
 """Host-side mirror of pyTheia's global rotation estimation (pytheia.sfm.RobustRotationEstimator,
-src/pytheia/sfm/sfm.cc:1749-1780 -> global_pose_estimation/robust_rotation_estimator.{h,cc}).
+src/pytheia/sfm/sfm.cc:1749-1780 -> global_pose_estimation/robust_rotation_estimator.{h,cc}) and position estimation
+(pytheia.sfm.LeastUnsquaredDeviationPositionEstimator, sfm.cc:1707-1726 ->
+global_pose_estimation/least_unsquared_deviation_position_estimator.{h,cc}).
 
 The solve runs on the device through theia_hip_robust_rotation_averaging (csrc/rotation_averaging.hip).  The object
 keeps the reference's state across calls: constraints accumulate over EstimateRotations / AddRelativeRotationConstraint
-calls on one object, and the view fixed by default on the first call stays fixed on later ones.
+calls on one object, and the view fixed by default on the first call stays fixed on later ones.  The positions run
+through theia_hip_lud_positions (csrc/lud_positions.hip).
 """
 import enum
 import math
@@ -107,3 +110,102 @@ class RobustRotationEstimator:
         self.last_success = rc == 0
         self.last_summary = s
         return {v: out[k].copy() for k, v in enumerate(ids)}
+
+
+class GlobalPositionEstimatorType(enum.IntEnum):  # reconstruction_estimator_options.h:80-85 (pybind sfm.cc:1196-1204)
+    NONLINEAR = 0
+    LINEAR_TRIPLET = 1
+    LEAST_UNSQUARED_DEVIATION = 2
+    LIGT = 3
+
+
+class LeastUnsquaredDeviationPositionEstimatorOptions:  # least_unsquared_deviation_position_estimator.h:60-69
+    def __init__(self):
+        self.max_num_iterations = 400
+        self.max_num_reweighted_iterations = 10
+        self.convergence_criterion = 1e-4
+
+
+class ConstrainedL1SolverOptions:  # math/constrained_l1_solver.h:64-74: what the estimator actually solves with
+    def __init__(self):
+        self.max_num_iterations = 1000
+        self.rho = 10.0
+        self.alpha = 1.2
+        self.absolute_tolerance = 1e-4
+        self.relative_tolerance = 1e-2
+
+    def to_c(self):
+        o = capi.LudOptions()
+        o.max_num_iterations = int(self.max_num_iterations)
+        o.rho = float(self.rho)
+        o.alpha = float(self.alpha)
+        o.absolute_tolerance = float(self.absolute_tolerance)
+        o.relative_tolerance = float(self.relative_tolerance)
+        return o
+
+
+def lud_positions(orientations, edges, relative_translations, fixed=None, options=None, positions_out=None):
+    """The C-ABI on arrays: orientations [n][3] angle-axis, edges [E][2] view indices, relative_translations [E][3]
+    (TwoViewInfo::position_2), fixed: [n] booleans or None (view 0 held), options: ConstrainedL1SolverOptions.
+    Returns (return code, positions [n][3], LudSummary); on a refusal the positions are positions_out (or zeros) as
+    passed in, untouched."""
+    o = (options or ConstrainedL1SolverOptions()).to_c()
+    aa = np.ascontiguousarray(np.asarray(orientations, dtype=np.float64).reshape(-1, 3))
+    e = np.ascontiguousarray(np.asarray(edges, dtype=np.int32).reshape(-1, 2))
+    t = np.ascontiguousarray(np.asarray(relative_translations, dtype=np.float64).reshape(-1, 3))
+    f = None if fixed is None else np.ascontiguousarray(np.asarray(fixed, dtype=bool).astype(np.uint8))
+    if f is not None and f.shape != (aa.shape[0],):
+        raise ValueError("fixed must have one entry per view")
+    if t.shape[0] != e.shape[0]:
+        raise ValueError("one relative translation per edge")
+    out = np.zeros((aa.shape[0], 3)) if positions_out is None else positions_out
+    if out.shape != (aa.shape[0], 3) or out.dtype != np.float64 or not out.flags["C_CONTIGUOUS"]:
+        raise ValueError("positions_out must be a C-contiguous float64 [n][3] array")
+    s = capi.LudSummary()
+    rc = capi.lib().theia_hip_lud_positions(aa.shape[0], capi.ptr(aa, capi.C.c_double), capi.ptr(f, capi.C.c_uint8),
+                                            e.shape[0], capi.ptr(e, capi.C.c_int32), capi.ptr(t, capi.C.c_double),
+                                            capi.C.byref(o), capi.ptr(out, capi.C.c_double), capi.C.byref(s))
+    return rc, out, s
+
+
+class LeastUnsquaredDeviationPositionEstimator:
+    """LeastUnsquaredDeviationPositionEstimator(options) with EstimatePositions(view_pairs, orientations) -> dict, as
+    pyTheia binds it.  view_pairs: {(id1, id2): TwoViewInfo} (position_2 is read); orientations: {view_id: angle-axis}.
+
+    The views are those of the pairs whose two views both have an orientation, in the order the pairs first name them;
+    the first of them is held at the origin (the reference holds the first view of its unordered_set: the positions
+    differ by a translation only).  A pair naming a view without an orientation is refused, as the
+    reference's CHECK on the factorisation fails for it (its scale column stays empty)."""
+
+    def __init__(self, options):
+        # the constructor's CHECK_GTs are the only readers of these options: the reference solves with
+        # ConstrainedL1Solver::Options at their defaults (:108-110) and so does this mirror
+        if not options.max_num_iterations > 0:
+            raise capi.TheiaHipError(capi.THEIA_HIP_ERR_INVALID_ARGUMENT, "max_num_iterations must be > 0")
+        if not options.max_num_reweighted_iterations > 0:
+            raise capi.TheiaHipError(capi.THEIA_HIP_ERR_INVALID_ARGUMENT, "max_num_reweighted_iterations must be > 0")
+        self.options = options
+        self.solver_options = ConstrainedL1SolverOptions()
+        self.last_summary = None
+
+    def EstimatePositions(self, view_pairs, orientations):
+        if not view_pairs:
+            raise capi.TheiaHipError(capi.THEIA_HIP_ERR_INVALID_ARGUMENT, "no view pairs")
+        ids = {}
+        for a, b in view_pairs:
+            if int(a) in orientations and int(b) in orientations:
+                ids.setdefault(int(a), len(ids))
+                ids.setdefault(int(b), len(ids))
+        for a, b in view_pairs:
+            if int(a) not in ids or int(b) not in ids:
+                raise capi.TheiaHipError(capi.THEIA_HIP_ERR_INVALID_ARGUMENT,
+                                         f"view pair ({a}, {b}) names a view without an orientation")
+        views = list(ids)
+        edges = np.array([(ids[int(a)], ids[int(b)]) for a, b in view_pairs], dtype=np.int32)
+        rel = np.array([np.asarray(info.position_2, dtype=np.float64).reshape(3) for info in view_pairs.values()])
+        aa = np.array([np.asarray(orientations[v], dtype=np.float64).reshape(3) for v in views])
+        fixed = np.arange(len(views)) == 0
+        rc, pos, s = lud_positions(aa, edges, rel, fixed, self.solver_options)
+        capi.check(rc)
+        self.last_summary = s
+        return {v: pos[k].copy() for k, v in enumerate(views)}
