@@ -886,6 +886,25 @@ int theia_hip_randint_stream(uint32_t seed, int32_t n, int32_t lo, int32_t hi, i
  * wavefronts; *mismatches = lanes whose bits differ (0 on a device / compiler the library is right for).  No reference
  * counterpart: a maintainer's first call on new hardware. */
 int theia_hip_selftest_wave_primitives(int32_t count, int32_t* mismatches);
+/* Self-checks of the team linear algebra of the minimal solvers (csrc/selftest_team_solvers.hip): each runs the team routine in
+ * its production launch shape and the one-thread routine it is bit-identical to on `count` caller-supplied inputs and returns
+ * both results, for the tests to compare.  No reference counterpart.  THEIA_HIP_ERR_INVALID_ARGUMENT for a bad variant / team /
+ * n, count < 1 or a null pointer.  The output buffers are read as well: records the kernels do not write keep their contents.
+ * eig_team: variant 0 = eig_team<8, false> (k_fit5_b), n in [1, 10]; 1 = eig_team<8, true> (k_upnp_b, k_p4pfr_b), n in
+ * [1, 13]; 2 = eig_team<32, true, 4> with V = X = the matrix's global slot and the rows {0, 9, 3, 1} kept (k_dls_b_team),
+ * n in [10, 27]; against eig_general_t<10, false>, <13, true>, <27, true>.  A [count][n][n] row-major; active [count]: 0 =
+ * the team returns at once and neither record is written.  Record per matrix, 1 + 2 n + 2 n^2 doubles: ok | wr [n] | wi [n]
+ * | H [n][n] (the Schur form; the one-thread H of a second run without vectors) | V [n][n] (variant 2, team: the 4 kept
+ * rows, 4 x n).  One-thread ok = -1: its runs with and without vectors disagreed. */
+int theia_hip_selftest_eig_team(int32_t variant, int32_t n, int32_t count, const double* A, const int32_t* active,
+                                double* team_out, double* single_out);
+/* svd9_team<team> (team 5: k_sqp_b / k_hom_b, 9: the earlier shape), with V accumulated or not, against svd_sq<9>.  A
+ * [count][9][9]; record per matrix, 171 doubles: U [81] | S [9] | V [81] (the team's V only when with_v). */
+int theia_hip_selftest_svd9_team(int32_t team, int32_t with_v, int32_t count, const double* A, double* team_out,
+                                 double* single_out);
+/* five_point_pre_team<16> (k_fit5_a_team) against five_point_pre.  corr [count][5][4] = (x1, y1, x2, y2); record per
+ * problem, 137 doubles: ok | N [9][4] | M [10][10] (N and M only when ok). */
+int theia_hip_selftest_five_point_pre_team(int32_t count, const double* corr, double* team_out, double* single_out);
 
 /* The batch entry points above keep their device workspace and the pinned host blocks of their per-round transfers in
  * process-wide caches between calls (up to 6 GiB of device memory and 2 GiB of pinned host memory); the buffers of a

@@ -201,6 +201,7 @@ EXPORTED_SYMBOLS = [
     "theia_hip_optimize_relative_position_batch", "theia_hip_rccl_comm_destroy", "theia_hip_rccl_comm_count", "theia_hip_ba_set_rccl", "theia_hip_dense_spd_solve", "theia_hip_dense_spd_solve_multi", "theia_hip_tile_sparse_spd_solve", "theia_hip_tile_sparse_spd_solve_sharded", "theia_hip_robust_rotation_averaging", "theia_hip_lud_positions", "theia_ransac_params_default",
     "theia_hip_ransac_estimate_batch", "theia_hip_five_point_relative_pose",
     "theia_hip_pose_from_three_points", "theia_hip_sqpnp", "theia_hip_dls_pnp", "theia_hip_dls_macaulay_terms", "theia_hip_four_point_pose_and_focal_length", "theia_hip_four_point_focal_length_radial_distortion", "theia_hip_four_point_focal_length_radial_distortion_ex", "theia_hip_release_scratch", "theia_hip_guided_knn", "theia_hip_randint_stream", "theia_hip_selftest_wave_primitives",
+    "theia_hip_selftest_eig_team", "theia_hip_selftest_svd9_team", "theia_hip_selftest_five_point_pre_team",
     "theia_hip_rng_seed", "theia_hip_rng_rand_int", "theia_hip_rng_rand_double", "theia_hip_rng_discard", "theia_hip_ransac_estimate_streams",
 ]
 
@@ -252,6 +253,9 @@ def lib():
                                                       C.POINTER(RotationOptions), C.POINTER(RotationSummary)]
     L.theia_hip_lud_positions.argtypes = [C.c_int32, c_double_p, c_uint8_p, C.c_int32, c_int32_p, c_double_p,
                                           C.POINTER(LudOptions), c_double_p, C.POINTER(LudSummary)]
+    L.theia_hip_selftest_eig_team.argtypes = [C.c_int32, C.c_int32, C.c_int32, c_double_p, c_int32_p, c_double_p, c_double_p]
+    L.theia_hip_selftest_svd9_team.argtypes = [C.c_int32, C.c_int32, C.c_int32, c_double_p, c_double_p, c_double_p]
+    L.theia_hip_selftest_five_point_pre_team.argtypes = [C.c_int32, c_double_p, c_double_p, c_double_p]
     _lib = L
     return L
 

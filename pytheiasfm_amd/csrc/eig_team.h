@@ -163,6 +163,11 @@ __device__ __forceinline__ bool eig_team(int nn, double* __restrict__ H, double*
   double norm = 0.0;
   for (int i = 0; i < nn; ++i)
     for (int j = (i - 1 > 0 ? i - 1 : 0); j < nn; ++j) norm += fabs(HH(i, j));
+  if (norm == 0.0) {   // the zero matrix (eig_general_t): eigenvalues 0, V (Vk) as accumulated = the identity (its kept rows)
+    for (int i = tl; i < nn; i += TEAM) { wr[i] = 0.0; wi[i] = 0.0; }
+    team_sync();
+    return true;
+  }
   int iter = 0, total_iter = 0;
   while (n >= low) {
     // Converged roots are peeled off in an inner loop until THIS team is due for a sweep (or done): the teams of a wave then
@@ -358,7 +363,6 @@ __device__ __forceinline__ bool eig_team(int nn, double* __restrict__ H, double*
   }
   team_sync();
   EIG_STAMP(2);
-  if (norm == 0.0) return true;
   // ---- back-substitution: one lane per eigenvalue column.  The sequential routine overwrites column n of H with the
   // vector while columns < n still hold the triangular form; here the vectors go to X so that the columns are independent
   // (column n reads T(i, j) for j <= n only through H, and its own entries through X).

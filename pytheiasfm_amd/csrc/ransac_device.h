@@ -134,6 +134,10 @@ RDEV bool eig_general_t(int nn, double* H, double* wr, double* wi, double* V) {
   double norm = 0.0;
   for (int i = 0; i < nn; ++i)
     for (int j = (i - 1 > 0 ? i - 1 : 0); j < nn; ++j) norm += fabs(HH(i, j));
+  if (norm == 0.0) {   // the zero matrix: every deflation test would read 0 < eps * 0 and the sweeps run on 0 / 0
+    for (int i = 0; i < nn; ++i) { wr[i] = 0.0; wi[i] = 0.0; }
+    return true;        // V: the accumulation's identity
+  }
   int iter = 0, total_iter = 0;
   while (n >= low) {
     int l = n;
@@ -251,7 +255,6 @@ RDEV bool eig_general_t(int nn, double* H, double* wr, double* wi, double* V) {
     }
   }
   if (!V) return true;
-  if (norm == 0.0) return true;
   // back-substitution for the REAL eigenvectors of the quasi-triangular form
   for (n = nn - 1; n >= 0; --n) {
     p = wr[n]; q = wi[n];
