@@ -550,6 +550,66 @@ int theia_hip_lud_positions(int32_t num_views, const double* orientations, const
                             const int32_t* edges, const double* relative_translations, const theia_lud_options* options,
                             double* positions_out, theia_lud_summary* summary);
 
+/* FilterViewPairsFromRelativeTranslation (sfm/filter_view_pairs_from_relative_translation.cc:264-312, step 6 of the global
+ * pipeline, sfm/global_reconstruction_estimator.cc:126-138; options: filter_view_pairs_from_relative_translation.h:48-66):
+ * Wilson & Snavely's 1DSfM outlier test on the device (csrc/view_pair_filters.hip).  The translations are rotated into the
+ * global frame (:67-84), their mean and variance give num_iterations random axes (:178-217), every axis orders the views by
+ * the greedy minimum-feedback-arc-set heuristic of :86-160 (one workgroup per axis), and a pair whose projections
+ * contradict the orderings by more than translation_projection_tolerance * num_iterations in total is removed (:236-305).
+ * pairs [n_pairs][2] = (first, second) view indices, each unordered pair at most once; orientations [n_views][3] angle-axis;
+ * position_2 [n_pairs][3] = TwoViewInfo::position_2.
+ * Axes: three RandGaussian(mean[k], variance[k]) per iteration in the order x, y, z, iteration after iteration, from *rng,
+ * which is left where the draws end (the reference with num_threads = 1); with axes_in they are used as given and rng is
+ * neither read nor advanced.
+ * Where the reference's result depends on the order of its hash maps, the rule here is: the lowest view index among the
+ * sources, the lowest view index among equal scores, initial weights summed in pair order, iterations added in order.
+ * Fewer than two pairs: the reference's variance is 0 / 0, its axes are NaN and no pair is judged; here nothing is
+ * launched, removed and bad_weight are zeroed, the other outputs are left untouched, and rng still advances by the draws.
+ * THEIA_HIP_ERR_INVALID_ARGUMENT (nothing launched, outputs and rng untouched): a view index out of range, a pair naming one
+ * view twice, an unordered pair listed twice, num_iterations <= 0, a negative or NaN tolerance, rng and axes_in both NULL.
+ * THEIA_HIP_ERR_OUT_OF_MEMORY: the workspace, O(num_iterations x (n_pairs + n_views)): 24 bytes per iteration and pair,
+ * 4 per iteration and view, and 28 more per iteration and view beyond THEIA_MFAS_LDS_MAX_VIEWS views.
+ * THEIA_MFAS_LDS_MAX_VIEWS: up to this many views (named by a pair or not) the ordering keeps its per-view state in the
+ * CU's LDS; with more it runs out of a global workspace.  Same results on both routes. */
+#define THEIA_MFAS_LDS_MAX_VIEWS 5632
+struct theia_rng_state;
+typedef struct theia_translation_filter_options {   /* filter_view_pairs_from_relative_translation.h:48-66 */
+  int32_t num_iterations, reserved;                 /* 48 */
+  double translation_projection_tolerance;          /* 0.08 */
+} theia_translation_filter_options;
+int theia_hip_filter_view_pairs_from_relative_translation(
+    int32_t n_views, int32_t n_pairs, const int32_t* pairs /*[n_pairs][2]*/,
+    const double* orientations /*[n_views][3]*/, const double* position_2 /*[n_pairs][3]*/,
+    const theia_translation_filter_options* opt /* NULL = the defaults above */,
+    struct theia_rng_state* rng /* declared below; drawn from and advanced; may be NULL when axes_in is given */,
+    const double* axes_in     /* optional [num_iterations][3], unit vectors: used instead of drawing */,
+    uint8_t* removed          /* [n_pairs] */,
+    double* bad_weight        /* optional [n_pairs] */,
+    int32_t* order            /* optional [num_iterations][n_views], -1 for a view no pair names */,
+    double* axes_out          /* optional [num_iterations][3] */,
+    double* rotated           /* optional [n_pairs][3]: the translations in the global frame */);
+
+/* Host-side account of the calling thread's last theia_hip_filter_view_pairs_from_relative_translation call that launched
+ * (development and timing aid, scripts/gpu_time_translation_filter.py): wall times of its stages, the ordering steps
+ * that took a source and those that took the arg-max of the score (summed over the iterations), and the route taken. */
+typedef struct theia_translation_filter_stats {
+  double setup_ms, rotate_project_ms, order_ms, weights_ms, total_ms;   /* set-up = checks, CSR, allocation, upload */
+  int64_t source_steps, argmax_steps;
+  int32_t lds_route, order_threads;   /* 1: per-view state in LDS, 0: global workspace; lanes per ordering workgroup */
+} theia_translation_filter_stats;
+int theia_hip_translation_filter_last_stats(theia_translation_filter_stats* out);
+
+/* FilterViewPairsFromOrientation (sfm/filter_view_pairs_from_orientation.cc:65-103, step 4 of the global pipeline): a pair
+ * stays when |MultiplyRotations(-rotation_2, MultiplyRotations(r_second, -r_first))|^2 <= DegToRad(max degrees)^2 (:46-63);
+ * a pair naming a view without an orientation (has_orientation[view] == 0; NULL = every view has one) is removed (:73-82).
+ * removed [n_pairs].  THEIA_HIP_ERR_INVALID_ARGUMENT (nothing launched, removed untouched): a view index out of range, a
+ * pair naming one view twice, an unordered pair listed twice, a negative or NaN angle (the reference's CHECK_GE). */
+int theia_hip_filter_view_pairs_from_orientation(
+    int32_t n_views, int32_t n_pairs, const int32_t* pairs, const double* orientations,
+    const uint8_t* has_orientation /* optional [n_views]: a pair naming a view without one is removed */,
+    const double* rotation_2 /*[n_pairs][3]*/, double max_relative_rotation_difference_degrees,
+    uint8_t* removed);
+
 /* Multi-GPU (one process per GPU): tracks are sharded by the caller; each
  * rank's handle holds its shard plus ALL cameras.  The reduced camera system
  * (and the scalar reductions) are summed across ranks through this callback,
@@ -790,11 +850,15 @@ typedef struct theia_rng_state {
 
 /* Host only (no GPU).  seed = RandomNumberGenerator(seed) / Seed(seed): resets mt and pos only.  rand_int = n draws of
  * RandInt(lo, hi) (uniform_int_distribution<int>, libstdc++'s Lemire reduction), rand_double = n draws of RandDouble(lo, hi)
- * (generate_canonical<double, 53>: two words per draw), discard = `words` raw 32-bit outputs.  An argument error (NULL state,
+ * (generate_canonical<double, 53>: two words per draw), discard = `words` raw 32-bit outputs.  rand_gaussian = n draws of
+ * RandGaussian(mean, std_dev) (util/random.cc:87-91: a fresh std::normal_distribution<double> per draw, so the polar pair's
+ * second value is dropped; four words per trial, trials rejected until 0 < r2 <= 1; the number of words a draw takes does
+ * not depend on mean or std_dev, which are not range-checked, as in the reference).  An argument error (NULL state,
  * pos outside [0, 624], n < 0, lo > hi) leaves the state untouched. */
 int theia_hip_rng_seed(theia_rng_state* state, uint32_t seed);
 int theia_hip_rng_rand_int(theia_rng_state* state, int32_t lo, int32_t hi, int32_t n, int32_t* out);
 int theia_hip_rng_rand_double(theia_rng_state* state, double lo, double hi, int32_t n, double* out);
+int theia_hip_rng_rand_gaussian(theia_rng_state* state, double mean, double std_dev, int32_t n, double* out);
 int theia_hip_rng_discard(theia_rng_state* state, uint64_t words);
 
 typedef struct theia_ransac_streams {

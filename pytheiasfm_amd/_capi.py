@@ -179,6 +179,22 @@ class LudSummary(C.Structure):
                 ("admm_ms", C.c_double)]
 
 
+# theia_hip.h THEIA_MFAS_LDS_MAX_VIEWS: up to this many views the 1DSfM ordering keeps its per-view state in LDS
+MFAS_LDS_MAX_VIEWS = 5632
+
+
+class TranslationFilterOptions(C.Structure):
+    """theia_translation_filter_options."""
+    _fields_ = [("num_iterations", C.c_int32), ("reserved", C.c_int32), ("translation_projection_tolerance", C.c_double)]
+
+
+class TranslationFilterStats(C.Structure):
+    """theia_translation_filter_stats."""
+    _fields_ = [("setup_ms", C.c_double), ("rotate_project_ms", C.c_double), ("order_ms", C.c_double),
+                ("weights_ms", C.c_double), ("total_ms", C.c_double), ("source_steps", C.c_int64),
+                ("argmax_steps", C.c_int64), ("lds_route", C.c_int32), ("order_threads", C.c_int32)]
+
+
 class K3Info(C.Structure):
     """theia_k3_info."""
     _fields_ = [("dense", C.c_int32), ("levels", C.c_int32), ("num_symm_tiles", C.c_int32),
@@ -198,11 +214,11 @@ EXPORTED_SYMBOLS = [
     "theia_hip_ba_reset_parameters", "theia_hip_estimate_tracks", "theia_hip_ba_set_shard", "theia_hip_ba_snapshot_parameters", "theia_hip_ba_restore_parameters", "theia_hip_ba_set_options", "theia_hip_ba_run", "theia_hip_ba_download",
     "theia_hip_ba_destroy", "theia_hip_ba_covariance", "theia_hip_ba_evaluate", "theia_hip_ba_evaluate_ex", "theia_hip_ba_reduced_system",
     "theia_hip_ba_set_allreduce", "theia_hip_ba_set_inner_global", "theia_hip_ba_plan_info", "theia_hip_rccl_unique_id", "theia_hip_rccl_comm_create",
-    "theia_hip_optimize_relative_position_batch", "theia_hip_rccl_comm_destroy", "theia_hip_rccl_comm_count", "theia_hip_ba_set_rccl", "theia_hip_dense_spd_solve", "theia_hip_dense_spd_solve_multi", "theia_hip_tile_sparse_spd_solve", "theia_hip_tile_sparse_spd_solve_sharded", "theia_hip_robust_rotation_averaging", "theia_hip_lud_positions", "theia_ransac_params_default",
+    "theia_hip_optimize_relative_position_batch", "theia_hip_rccl_comm_destroy", "theia_hip_rccl_comm_count", "theia_hip_ba_set_rccl", "theia_hip_dense_spd_solve", "theia_hip_dense_spd_solve_multi", "theia_hip_tile_sparse_spd_solve", "theia_hip_tile_sparse_spd_solve_sharded", "theia_hip_robust_rotation_averaging", "theia_hip_lud_positions", "theia_hip_filter_view_pairs_from_relative_translation", "theia_hip_translation_filter_last_stats", "theia_hip_filter_view_pairs_from_orientation", "theia_ransac_params_default",
     "theia_hip_ransac_estimate_batch", "theia_hip_five_point_relative_pose",
     "theia_hip_pose_from_three_points", "theia_hip_sqpnp", "theia_hip_dls_pnp", "theia_hip_dls_macaulay_terms", "theia_hip_four_point_pose_and_focal_length", "theia_hip_four_point_focal_length_radial_distortion", "theia_hip_four_point_focal_length_radial_distortion_ex", "theia_hip_release_scratch", "theia_hip_guided_knn", "theia_hip_randint_stream", "theia_hip_selftest_wave_primitives",
     "theia_hip_selftest_eig_team", "theia_hip_selftest_svd9_team", "theia_hip_selftest_five_point_pre_team",
-    "theia_hip_rng_seed", "theia_hip_rng_rand_int", "theia_hip_rng_rand_double", "theia_hip_rng_discard", "theia_hip_ransac_estimate_streams",
+    "theia_hip_rng_seed", "theia_hip_rng_rand_int", "theia_hip_rng_rand_double", "theia_hip_rng_rand_gaussian", "theia_hip_rng_discard", "theia_hip_ransac_estimate_streams",
 ]
 
 _lib = None
@@ -253,6 +269,12 @@ def lib():
                                                       C.POINTER(RotationOptions), C.POINTER(RotationSummary)]
     L.theia_hip_lud_positions.argtypes = [C.c_int32, c_double_p, c_uint8_p, C.c_int32, c_int32_p, c_double_p,
                                           C.POINTER(LudOptions), c_double_p, C.POINTER(LudSummary)]
+    L.theia_hip_filter_view_pairs_from_relative_translation.argtypes = [
+        C.c_int32, C.c_int32, c_int32_p, c_double_p, c_double_p, C.POINTER(TranslationFilterOptions), C.POINTER(RngState),
+        c_double_p, c_uint8_p, c_double_p, c_int32_p, c_double_p, c_double_p]
+    L.theia_hip_translation_filter_last_stats.argtypes = [C.POINTER(TranslationFilterStats)]
+    L.theia_hip_filter_view_pairs_from_orientation.argtypes = [C.c_int32, C.c_int32, c_int32_p, c_double_p, c_uint8_p,
+                                                               c_double_p, C.c_double, c_uint8_p]
     L.theia_hip_selftest_eig_team.argtypes = [C.c_int32, C.c_int32, C.c_int32, c_double_p, c_int32_p, c_double_p, c_double_p]
     L.theia_hip_selftest_svd9_team.argtypes = [C.c_int32, C.c_int32, C.c_int32, c_double_p, c_double_p, c_double_p]
     L.theia_hip_selftest_five_point_pre_team.argtypes = [C.c_int32, c_double_p, c_double_p, c_double_p]

@@ -1320,6 +1320,19 @@ struct Mt19937 {
     if (ret >= 1.0) ret = std::nextafter(1.0, 0.0);
     return ret * (hi - lo) + lo;
   }
+  // libstdc++ std::normal_distribution<double>(mean, std_dev) on a FRESH distribution object, as RandomNumberGenerator::RandGaussian
+  // makes one per call (util/random.cc:87-91): Marsaglia's polar method on two generate_canonical<double, 53> per trial, rejected
+  // until 0 < r2 <= 1; the call returns the pair's y value and the saved x value dies with the object
+  double rand_gaussian(double mean, double std_dev) {
+    double x, y, r2;
+    do {
+      x = 2.0 * rand_double(0.0, 1.0) - 1.0;
+      y = 2.0 * rand_double(0.0, 1.0) - 1.0;
+      r2 = x * x + y * y;
+    } while (r2 > 1.0 || r2 == 0.0);
+    const double mult = std::sqrt(-2.0 * std::log(r2) / r2);
+    return (y * mult) * std_dev + mean;
+  }
   int rand_int(int lo, int hi) {
     const uint32_t urange = (uint32_t)hi - (uint32_t)lo;
     uint32_t ret;
@@ -2399,6 +2412,16 @@ int theia_hip_rng_rand_double(theia_rng_state* state, double lo, double hi, int3
   Mt19937 g;
   rng_load(g, *state);
   for (int32_t i = 0; i < n; ++i) out[i] = g.rand_double(lo, hi);
+  rng_store(*state, g);
+  return 0;
+}
+
+int theia_hip_rng_rand_gaussian(theia_rng_state* state, double mean, double std_dev, int32_t n, double* out) {
+  if (!rng_state_ok(state)) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "null state or pos outside [0, 624]");
+  if (n < 0 || (n > 0 && !out)) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "bad argument");
+  Mt19937 g;
+  rng_load(g, *state);
+  for (int32_t i = 0; i < n; ++i) out[i] = g.rand_gaussian(mean, std_dev);
   rng_store(*state, g);
   return 0;
 }

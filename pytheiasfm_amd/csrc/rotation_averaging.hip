@@ -18,6 +18,7 @@
 // r_i <- MultiplyRotations(r_i, delta_i) go through ceres' conversions (ransac_device.h) with the intermediate angle-axis
 // round trip the reference takes (math/rotation.cc:56-66).
 #include "ransac_device.h"
+#include "rotation_compose.h"
 #include "ba_kernels.h"
 #include "wave_reduce.h"
 #include "theia_hip_internal.h"
@@ -38,18 +39,6 @@ namespace thip {
 namespace {
 
 constexpr int kThreads = 256;
-
-// MultiplyRotations(a, b): angle-axis -> matrices, product, matrix -> angle-axis (row-major matrices throughout)
-__device__ __forceinline__ void multiply_rotations(const double* a, const double* b, double* out) {
-  double Ra[9], Rb[9], R[9];
-  rsc::angle_axis_to_rot(a, Ra);
-  rsc::angle_axis_to_rot(b, Rb);
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) R[3 * r + c] = (Ra[3 * r] * Rb[c] + Ra[3 * r + 1] * Rb[3 + c]) + Ra[3 * r + 2] * Rb[6 + c];
-  rsc::rot_to_angle_axis(R, out);
-}
 
 // Sum of v over the workgroup in a fixed tree order; the result is valid in thread 0.
 __device__ __forceinline__ double block_sum(double v, double* red) {

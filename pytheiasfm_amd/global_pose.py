@@ -7,7 +7,13 @@ The solve runs on the device through theia_hip_robust_rotation_averaging (csrc/r
 keeps the reference's state across calls: constraints accumulate over EstimateRotations / AddRelativeRotationConstraint
 calls on one object, and the view fixed by default on the first call stays fixed on later ones.  The positions run
 through theia_hip_lud_positions (csrc/lud_positions.hip).
+
+Between them sit the two view-graph filters (sfm/filter_view_pairs_from_orientation.{h,cc} after the rotations,
+sfm/filter_view_pairs_from_relative_translation.{h,cc}, the 1DSfM test, before the positions): csrc/view_pair_filters.hip
+behind filter_pairs_from_orientation / filter_translations_1dsfm on arrays and FilterViewPairsFromOrientation /
+FilterViewPairsFromRelativeTranslation on the {(id1, id2): TwoViewInfo} dict that stands in for the ViewGraph.
 """
+import ctypes as C
 import enum
 import math
 
@@ -209,3 +215,131 @@ class LeastUnsquaredDeviationPositionEstimator:
         capi.check(rc)
         self.last_summary = s
         return {v: pos[k].copy() for k, v in enumerate(views)}
+
+
+class FilterViewPairsFromRelativeTranslationOptions:  # filter_view_pairs_from_relative_translation.h:48-66
+    def __init__(self):
+        self.rng = None           # a ransac.RandomNumberGenerator; None: a generator seeded from the clock per call
+        self.num_threads = 1      # held and ignored: the iterations are workgroups of one launch
+        self.num_iterations = 48
+        self.translation_projection_tolerance = 0.08
+
+    def to_c(self):
+        o = capi.TranslationFilterOptions()
+        o.num_iterations = int(self.num_iterations)
+        o.translation_projection_tolerance = float(self.translation_projection_tolerance)
+        return o
+
+
+def _pair_arrays(pairs, per_pair, what):
+    e = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+    t = np.ascontiguousarray(np.asarray(per_pair, dtype=np.float64).reshape(-1, 3))
+    if t.shape[0] != e.shape[0]:
+        raise ValueError(f"one {what} per pair")
+    return e, t
+
+
+def filter_translations_1dsfm(orientations, pairs, position_2, options=None, rng_state=None, axes=None, want=()):
+    """theia_hip_filter_view_pairs_from_relative_translation on arrays: orientations [n][3] angle-axis, pairs [E][2] view
+    indices (every unordered pair at most once), position_2 [E][3].  rng_state: the capi.RngState the axes are drawn
+    from and that the call advances; axes: [num_iterations][3] unit vectors used instead.  want: names of the optional
+    outputs to fetch, out of "bad_weight", "order", "axes", "rotated".  Returns (return code, removed [E] bool, dict of
+    the outputs asked for); on a refusal removed is all False and the dict is empty."""
+    o = (options or FilterViewPairsFromRelativeTranslationOptions()).to_c()
+    aa = np.ascontiguousarray(np.asarray(orientations, dtype=np.float64).reshape(-1, 3))
+    e, t = _pair_arrays(pairs, position_2, "position_2")
+    n, E, iters = aa.shape[0], e.shape[0], max(0, o.num_iterations)
+    ax = None
+    if axes is not None:
+        ax = np.ascontiguousarray(np.asarray(axes, dtype=np.float64).reshape(-1, 3))
+        if ax.shape[0] != iters:
+            raise ValueError("one axis per iteration")
+    unknown = set(want) - {"bad_weight", "order", "axes", "rotated"}
+    if unknown:
+        raise ValueError(f"unknown outputs {sorted(unknown)}")
+    removed = np.zeros(E, dtype=np.uint8)
+    bufs = dict(bad_weight=np.zeros(E), order=np.full((iters, n), -1, dtype=np.int32), axes=np.full((iters, 3), np.nan),
+                rotated=np.zeros((E, 3)))
+    arg = lambda k, ct: capi.ptr(bufs[k] if k in want else None, ct)
+    rc = capi.lib().theia_hip_filter_view_pairs_from_relative_translation(
+        n, E, capi.ptr(e, C.c_int32), capi.ptr(aa, C.c_double), capi.ptr(t, C.c_double), C.byref(o),
+        None if rng_state is None else C.byref(rng_state), capi.ptr(ax, C.c_double), capi.ptr(removed, C.c_uint8),
+        arg("bad_weight", C.c_double), arg("order", C.c_int32), arg("axes", C.c_double), arg("rotated", C.c_double))
+    return rc, removed.astype(bool), ({k: bufs[k] for k in want} if rc == 0 else {})
+
+
+def translation_filter_last_stats():
+    """theia_hip_translation_filter_last_stats of the calling thread, as a dict."""
+    s = capi.TranslationFilterStats()
+    capi.check(capi.lib().theia_hip_translation_filter_last_stats(C.byref(s)))
+    return {name: getattr(s, name) for name, _ in s._fields_}
+
+
+def filter_pairs_from_orientation(orientations, pairs, rotation_2, max_relative_rotation_difference_degrees,
+                                  has_orientation=None):
+    """theia_hip_filter_view_pairs_from_orientation on arrays: rotation_2 [E][3] = TwoViewInfo::rotation_2,
+    has_orientation: [n] booleans or None.  Returns (return code, removed [E] bool)."""
+    aa = np.ascontiguousarray(np.asarray(orientations, dtype=np.float64).reshape(-1, 3))
+    e, r = _pair_arrays(pairs, rotation_2, "rotation_2")
+    h = None if has_orientation is None else np.ascontiguousarray(np.asarray(has_orientation, dtype=bool).astype(np.uint8))
+    if h is not None and h.shape != (aa.shape[0],):
+        raise ValueError("has_orientation must have one entry per view")
+    removed = np.zeros(e.shape[0], dtype=np.uint8)
+    rc = capi.lib().theia_hip_filter_view_pairs_from_orientation(
+        aa.shape[0], e.shape[0], capi.ptr(e, C.c_int32), capi.ptr(aa, C.c_double), capi.ptr(h, C.c_uint8),
+        capi.ptr(r, C.c_double), float(max_relative_rotation_difference_degrees), capi.ptr(removed, C.c_uint8))
+    return rc, removed.astype(bool)
+
+
+def _graph_views(view_pairs):
+    """The views the pairs name, in increasing id: the filters' "lowest view index" is the lowest view id."""
+    views = sorted({int(v) for pair in view_pairs for v in pair})
+    return views, {v: k for k, v in enumerate(views)}
+
+
+def FilterViewPairsFromRelativeTranslation(options, orientations, view_pairs):
+    """FilterViewPairsFromRelativeTranslation(options, orientations, view_graph) with the {(id1, id2): TwoViewInfo} dict
+    in the ViewGraph's place: the removed pairs are deleted from it and their number is returned.  The axes come from
+    options.rng, i.e. the calling thread's generator, which is left where the draws end; options.rng = None seeds that
+    generator from the clock first, as the reference's per-thread RandomNumberGenerator() does."""
+    from . import ransac
+    views, pos = _graph_views(view_pairs)
+    keys = list(view_pairs)
+    aa = np.zeros((len(views), 3))
+    for a, _ in keys:   # FindOrDie(orientations, view_pair.first.first): only a pair's first view is looked up
+        if int(a) not in orientations:
+            raise capi.TheiaHipError(capi.THEIA_HIP_ERR_INVALID_ARGUMENT, f"view {a} has no orientation")
+    for v in views:
+        if v in orientations:
+            aa[pos[v]] = np.asarray(orientations[v], dtype=np.float64).reshape(3)
+    pairs = np.array([(pos[int(a)], pos[int(b)]) for a, b in keys], dtype=np.int32).reshape(-1, 2)
+    rel = np.array([np.asarray(view_pairs[k].position_2, dtype=np.float64).reshape(3) for k in keys]).reshape(-1, 3)
+    rng = options.rng if options.rng is not None else ransac.RandomNumberGenerator()
+    rc, removed, _ = filter_translations_1dsfm(aa, pairs, rel, options, rng_state=rng.thread_state())
+    capi.check(rc)
+    for k, gone in zip(keys, removed):
+        if gone:
+            del view_pairs[k]
+    return int(removed.sum())
+
+
+def FilterViewPairsFromOrientation(orientations, max_relative_rotation_difference_degrees, view_pairs):
+    """FilterViewPairsFromOrientation(orientations, max degrees, view_graph) on the dict: a pair whose rotation_2
+    disagrees with the two orientations by more than the angle, or that names a view without an orientation, is deleted;
+    returns how many were."""
+    views, pos = _graph_views(view_pairs)
+    keys = list(view_pairs)
+    aa = np.zeros((len(views), 3))
+    has = np.zeros(len(views), dtype=bool)
+    for v in views:
+        if v in orientations:
+            aa[pos[v]] = np.asarray(orientations[v], dtype=np.float64).reshape(3)
+            has[pos[v]] = True
+    pairs = np.array([(pos[int(a)], pos[int(b)]) for a, b in keys], dtype=np.int32).reshape(-1, 2)
+    rel = np.array([np.asarray(view_pairs[k].rotation_2, dtype=np.float64).reshape(3) for k in keys]).reshape(-1, 3)
+    rc, removed = filter_pairs_from_orientation(aa, pairs, rel, max_relative_rotation_difference_degrees, has)
+    capi.check(rc)
+    for k, gone in zip(keys, removed):
+        if gone:
+            del view_pairs[k]
+    return int(removed.sum())

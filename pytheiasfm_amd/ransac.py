@@ -81,6 +81,11 @@ class RandomNumberGenerator:
         capi.check(_sig().theia_hip_rng_rand_double(C.byref(self.thread_state()), float(lower), float(upper), 1, C.byref(out)))
         return out.value
 
+    def RandGaussian(self, mean, std_dev):
+        out = C.c_double(0.0)
+        capi.check(_sig().theia_hip_rng_rand_gaussian(C.byref(self.thread_state()), float(mean), float(std_dev), 1, C.byref(out)))
+        return out.value
+
     def Discard(self, words):
         capi.check(_sig().theia_hip_rng_discard(C.byref(self.thread_state()), int(words)))
 
@@ -184,6 +189,7 @@ def _sig():
         L.theia_hip_rng_seed.argtypes = [C.POINTER(capi.RngState), C.c_uint32]
         L.theia_hip_rng_rand_int.argtypes = [C.POINTER(capi.RngState), C.c_int32, C.c_int32, C.c_int32, capi.c_int32_p]
         L.theia_hip_rng_rand_double.argtypes = [C.POINTER(capi.RngState), C.c_double, C.c_double, C.c_int32, capi.c_double_p]
+        L.theia_hip_rng_rand_gaussian.argtypes = [C.POINTER(capi.RngState), C.c_double, C.c_double, C.c_int32, capi.c_double_p]
         L.theia_hip_rng_discard.argtypes = [C.POINTER(capi.RngState), C.c_uint64]
         L._ransac_ready = True
     return L

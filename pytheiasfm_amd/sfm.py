@@ -22,7 +22,9 @@ from . import ba as _ba
 from .synth import angle_axis_to_matrix
 from .global_pose import (GlobalRotationEstimatorType, RobustRotationEstimator,  # noqa: F401  (pyTheia's names)
                           RobustRotationEstimatorOptions, GlobalPositionEstimatorType,
-                          LeastUnsquaredDeviationPositionEstimator, LeastUnsquaredDeviationPositionEstimatorOptions)
+                          LeastUnsquaredDeviationPositionEstimator, LeastUnsquaredDeviationPositionEstimatorOptions,
+                          FilterViewPairsFromOrientation, FilterViewPairsFromRelativeTranslation,
+                          FilterViewPairsFromRelativeTranslationOptions)
 
 kInvalidViewId = 0xFFFFFFFF
 
