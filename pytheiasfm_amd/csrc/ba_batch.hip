@@ -13,18 +13,12 @@
 // 6 x 6 system whose model-cost change is  y'g - y'Hy/2.  Lane = observation
 // (stride 64); the 6 x 6 normal equations are wave-reduced in a fixed order.
 #include "ba_device.h"
-#include "theia_hip_internal.h"
+#include "device_util.h"
 
 #include <chrono>
 #include <cmath>
 #include <cstring>
 #include <vector>
-
-#define HIP_TRY(expr)                                                                             \
-  do {                                                                                            \
-    hipError_t e_ = (expr);                                                                       \
-    if (e_ != hipSuccess) return thip::set_error(THEIA_HIP_ERR_INTERNAL, "%s: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
 
 namespace thip {
 namespace {
@@ -650,24 +644,6 @@ __global__ __launch_bounds__(64) void k_track_triangulate(TrackBatch B, const do
   status[p] = 0;
 }
 
-template <typename T>
-struct Dev {
-  T* p = nullptr;
-  ~Dev() { if (p) (void)hipFree(p); }
-  int alloc(size_t n) {
-    if (hipMalloc((void**)&p, std::max<size_t>(1, n) * sizeof(T)) != hipSuccess)
-      return set_error(THEIA_HIP_ERR_OUT_OF_MEMORY, "hipMalloc(%zu) failed", n * sizeof(T));
-    return 0;
-  }
-  int up(const void* src, size_t n) {
-    int rc = alloc(n);
-    if (rc) return rc;
-    if (n && hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess)
-      return set_error(THEIA_HIP_ERR_INTERNAL, "hipMemcpy H2D failed");
-    return 0;
-  }
-};
-
 }  // namespace
 
 // device-resident variant for callers inside the library (LO-RANSAC)
@@ -726,7 +702,7 @@ extern "C" int theia_hip_ba_views_batch(const theia_ba_view_batch* b, const thei
     if (m & THEIA_CAM_CONST_TZ) cols |= 0x04;
     mask[i] = (uint8_t)cols;
   }
-  Dev<int64_t> d_off; Dev<double> d_uv, d_si, d_X, d_cam, d_intr; Dev<int> d_model; Dev<uint8_t> d_mask; Dev<char> d_out;
+  DevBuf<int64_t> d_off; DevBuf<double> d_uv, d_si, d_X, d_cam, d_intr; DevBuf<int> d_model; DevBuf<uint8_t> d_mask; DevBuf<char> d_out;
   if ((rc = d_off.up(b->offsets, num + 1)) || (rc = d_uv.up(b->obs_uv, 2 * total)) || (rc = d_X.up(b->points, 4 * total)) ||
       (rc = d_cam.up(b->cam_ext, 6 * (size_t)num)) || (rc = d_intr.up(b->intrinsics, THEIA_MAX_INTRINSICS * (size_t)num)) ||
       (rc = d_model.up(b->model, num)) || (rc = d_mask.up(mask.data(), num)) || (rc = d_out.alloc(views_batch_out_bytes() * num)))
@@ -810,7 +786,7 @@ extern "C" int theia_hip_ba_tracks_batch(const theia_ba_problem* p, const theia_
   const std::vector<double>& uv = G.uv;
   const std::vector<double>& si = G.si;
   const std::vector<int>& oc = G.oc;
-  Dev<int64_t> d_off; Dev<double> d_uv, d_si, d_cam, d_intr, d_pts; Dev<int> d_oc, d_gm, d_cg; Dev<uint8_t> d_pc; Dev<char> d_out;
+  DevBuf<int64_t> d_off; DevBuf<double> d_uv, d_si, d_cam, d_intr, d_pts; DevBuf<int> d_oc, d_gm, d_cg; DevBuf<uint8_t> d_pc; DevBuf<char> d_out;
   if ((rc = d_off.up(off.data(), np + 1)) || (rc = d_uv.up(uv.data(), uv.size())) || (rc = d_oc.up(oc.data(), oc.size())) ||
       (rc = d_cam.up(p->cam_ext, 6 * (size_t)p->num_cameras)) || (rc = d_intr.up(p->intrinsics, THEIA_MAX_INTRINSICS * (size_t)p->num_groups)) ||
       (rc = d_gm.up(p->group_model, p->num_groups)) || (rc = d_cg.up(p->cam_group, p->num_cameras)) ||
@@ -855,7 +831,7 @@ extern "C" int theia_hip_track_statistics(const theia_ba_problem* p, double* mea
   int rc = group_by_point(p, &G);
   if (rc) return rc;
   if ((rc = thip::ensure_device())) return rc;
-  Dev<int64_t> d_off; Dev<double> d_uv, d_cam, d_intr, d_pts, d_err, d_cos; Dev<int> d_oc, d_gm, d_cg, d_nb;
+  DevBuf<int64_t> d_off; DevBuf<double> d_uv, d_cam, d_intr, d_pts, d_err, d_cos; DevBuf<int> d_oc, d_gm, d_cg, d_nb;
   if ((rc = d_off.up(G.off.data(), np + 1)) || (rc = d_uv.up(G.uv.data(), G.uv.size())) || (rc = d_oc.up(G.oc.data(), G.oc.size())) ||
       (rc = d_cam.up(p->cam_ext, 6 * (size_t)p->num_cameras)) || (rc = d_intr.up(p->intrinsics, THEIA_MAX_INTRINSICS * (size_t)p->num_groups)) ||
       (rc = d_gm.up(p->group_model, p->num_groups)) || (rc = d_cg.up(p->cam_group, p->num_cameras)) ||
@@ -899,8 +875,8 @@ extern "C" int theia_hip_estimate_tracks(const theia_ba_problem* p, const double
       for (int k = 0; k < 3; ++k) rays[3 * s + k] = obs_ray_dir[3 * i + k];
     }
   }
-  Dev<int64_t> d_off; Dev<double> d_uv, d_si, d_cam, d_intr, d_pts, d_rays, d_err, d_cos; Dev<int> d_oc, d_gm, d_cg, d_status, d_nb;
-  Dev<uint8_t> d_pc; Dev<char> d_out;
+  DevBuf<int64_t> d_off; DevBuf<double> d_uv, d_si, d_cam, d_intr, d_pts, d_rays, d_err, d_cos; DevBuf<int> d_oc, d_gm, d_cg, d_status, d_nb;
+  DevBuf<uint8_t> d_pc; DevBuf<char> d_out;
   if ((rc = d_off.up(G.off.data(), np + 1)) || (rc = d_uv.up(G.uv.data(), G.uv.size())) || (rc = d_oc.up(G.oc.data(), G.oc.size())) ||
       (rc = d_cam.up(p->cam_ext, 6 * (size_t)p->num_cameras)) || (rc = d_intr.up(p->intrinsics, THEIA_MAX_INTRINSICS * (size_t)p->num_groups)) ||
       (rc = d_gm.up(p->group_model, p->num_groups)) || (rc = d_cg.up(p->cam_group, p->num_cameras)) ||
@@ -926,7 +902,7 @@ extern "C" int theia_hip_estimate_tracks(const theia_ba_problem* p, const double
   // the track BA and the reprojection sweep run on the triangulated tracks only: everything else is "constant"
   std::vector<uint8_t> skip(np);
   for (int i = 0; i < np; ++i) skip[i] = status[i] != 0;
-  Dev<uint8_t> d_skip;
+  DevBuf<uint8_t> d_skip;
   if ((rc = d_skip.up(skip.data(), np))) return rc;
   B.pt_const = d_skip.p;
   std::vector<char> h_out;

@@ -31,18 +31,10 @@
 #include "ba_kernels.h"
 #include "ba_priors.h"
 #include "theia_hip.h"
-#include "theia_hip_internal.h"
+#include "device_util.h"
 
 namespace thip {
 namespace {
-
-#define HIP_TRY(expr)                                                                                       \
-  do {                                                                                                      \
-    hipError_t e_ = (expr);                                                                                 \
-    if (e_ != hipSuccess)                                                                                   \
-      return set_error(e_ == hipErrorOutOfMemory ? THEIA_HIP_ERR_OUT_OF_MEMORY : THEIA_HIP_ERR_NO_DEVICE,   \
-                       "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);         \
-  } while (0)
 
 constexpr int kRec = 48;   // record of one observation: F_ref (2 x 6) | F_oth (2 x 6) | e (2) | r (2) | F_k (2 x 10)
 constexpr int kRecK = 28;  // offset of the intrinsics block
@@ -495,26 +487,16 @@ __global__ void k_id_xnorm(IdProblem P, const double* __restrict__ cam, const do
   if (s != 0.0) atomicAdd(out, s);
 }
 
+// DevBuf::alloc, then the vector's elements on the stream (the vector outlives the copy: synchronised here)
 template <typename T>
-struct Buf {
-  T* p = nullptr;
-  size_t n = 0;
-  ~Buf() { if (p) (void)hipFree(p); }
-  int alloc(size_t count) {
-    n = count;
-    if (hipMalloc((void**)&p, std::max<size_t>(1, count) * sizeof(T)) != hipSuccess)
-      return set_error(THEIA_HIP_ERR_OUT_OF_MEMORY, "hipMalloc(%zu) failed", count * sizeof(T));
-    return 0;
-  }
-  int upload(const std::vector<T>& h, hipStream_t st) {   // (the vector outlives the copy: synchronised here)
-    int rc = alloc(h.size());
-    if (rc) return rc;
-    if (!h.empty() && (hipMemcpyAsync(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, st) != hipSuccess ||
-                       hipStreamSynchronize(st) != hipSuccess))
-      return set_error(THEIA_HIP_ERR_NO_DEVICE, "hipMemcpy failed");
-    return 0;
-  }
-};
+int upload(DevBuf<T>& d, const std::vector<T>& h, hipStream_t st) {
+  int rc = d.alloc(h.size());
+  if (rc) return rc;
+  if (!h.empty() && (hipMemcpyAsync(d.p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, st) != hipSuccess ||
+                     hipStreamSynchronize(st) != hipSuccess))
+    return set_error(THEIA_HIP_ERR_NO_DEVICE, "hipMemcpy failed");
+  return 0;
+}
 
 // free parameters of a model under an OptimizeIntrinsicsType mask (GetSubsetFromOptimizeIntrinsicsType of every
 // *_camera_model.cc), the sizes of the eight models, the bounds of bundle_adjuster.cc:406-427: as ba_solver.hip
@@ -567,11 +549,11 @@ struct IdHandle {
   std::vector<uint8_t> h_pt_observed;   // tracks with at least one observation: their inverse depth must be positive
   struct StreamGuard { hipStream_t s = nullptr; ~StreamGuard() { if (s) (void)hipStreamDestroy(s); } } sg;
   hipStream_t st = nullptr;
-  Buf<double> d_intr[2], d_scale_i, d_colsq_i, d_pvec, d_pinfo, d_bearing, d_uv, d_si, d_cam[2], d_rho[2], d_scale_c, d_scale_r, d_scale_red, d_recs, d_red, d_vinv, d_grho, d_scal, d_radius, d_work, d_colsq_c, d_colsq_r;
-  Buf<int> d_gm, d_cg, d_cred, d_pref, d_ocam, d_opt, d_pobs, d_gred, d_gk, d_pcam, d_pkind;
-  Buf<unsigned> d_gfree;
-  Buf<uint8_t> d_cmask, d_pconst;
-  Buf<int64_t> d_poff;
+  DevBuf<double> d_intr[2], d_scale_i, d_colsq_i, d_pvec, d_pinfo, d_bearing, d_uv, d_si, d_cam[2], d_rho[2], d_scale_c, d_scale_r, d_scale_red, d_recs, d_red, d_vinv, d_grho, d_scal, d_radius, d_work, d_colsq_c, d_colsq_r;
+  DevBuf<int> d_gm, d_cg, d_cred, d_pref, d_ocam, d_opt, d_pobs, d_gred, d_gk, d_pcam, d_pkind;
+  DevBuf<unsigned> d_gfree;
+  DevBuf<uint8_t> d_cmask, d_pconst;
+  DevBuf<int64_t> d_poff;
   IdProblem P;
   CholPlan* plan = nullptr;
   size_t red_count = 0;
@@ -583,7 +565,7 @@ struct IdHandle {
   int run(const theia_ba_options* o, theia_ba_summary* S);
   int download(theia_ba_problem* p);
   // theia_hip_ba_snapshot_parameters / restore_parameters: the current parameters <-> a device-side copy
-  Buf<double> snap_cam, snap_rho, snap_intr;
+  DevBuf<double> snap_cam, snap_rho, snap_intr;
   bool has_snapshot = false;
   int snapshot();
   int restore();
@@ -674,7 +656,7 @@ int IdHandle::create(const theia_ba_problem* p, const theia_ba_options* o) {
   if (p->obs_sqrt_info) std::memcpy(si.data(), p->obs_sqrt_info, sizeof(double) * 2 * nobs);
   // ---- a stream of this object (non-blocking: the entry points stay callable from a thread pool; the legacy stream would
   // serialise against every other stream of the process)
-  HIP_TRY(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
+  HIP_TRYR(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
   st = sg.s;
   h_group_model.assign(p->group_model, p->group_model + ng);
   std::vector<double> hb(p->point_ref_bearing, p->point_ref_bearing + 3 * (size_t)np);
@@ -683,13 +665,13 @@ int IdHandle::create(const theia_ba_problem* p, const theia_ba_options* o) {
   std::vector<int> hoc(p->obs_cam, p->obs_cam + nobs), hop(p->obs_pt, p->obs_pt + nobs);
   red_count = (size_t)n * n + 3 * (size_t)n;   // S | rhs | colsq | gc
   if ((rc = d_intr[0].alloc((size_t)kKW * ng)) || (rc = d_intr[1].alloc((size_t)kKW * ng)) || (rc = d_scale_i.alloc((size_t)kKW * ng)) ||
-      (rc = d_colsq_i.alloc((size_t)kKW * ng)) || (rc = d_gred.upload(grp_red, st)) || (rc = d_gk.upload(grp_k, st)) ||
-      (rc = d_gfree.upload(grp_free, st)) || (rc = d_pcam.upload(prior_cam, st)) || (rc = d_pkind.upload(prior_kind, st)) ||
-      (rc = d_pvec.upload(prior_vec, st)) || (rc = d_pinfo.upload(prior_info, st)) || (rc = d_bearing.upload(hb, st)) || (rc = d_uv.upload(huv, st)) || (rc = d_si.upload(si, st)) ||
+      (rc = d_colsq_i.alloc((size_t)kKW * ng)) || (rc = upload(d_gred, grp_red, st)) || (rc = upload(d_gk, grp_k, st)) ||
+      (rc = upload(d_gfree, grp_free, st)) || (rc = upload(d_pcam, prior_cam, st)) || (rc = upload(d_pkind, prior_kind, st)) ||
+      (rc = upload(d_pvec, prior_vec, st)) || (rc = upload(d_pinfo, prior_info, st)) || (rc = upload(d_bearing, hb, st)) || (rc = upload(d_uv, huv, st)) || (rc = upload(d_si, si, st)) ||
       (rc = d_cam[0].alloc(6 * (size_t)nc)) || (rc = d_cam[1].alloc(6 * (size_t)nc)) || (rc = d_rho[0].alloc(np)) || (rc = d_rho[1].alloc(np)) ||
-      (rc = d_gm.upload(hgm, st)) || (rc = d_cg.upload(hcg, st)) || (rc = d_cred.upload(cam_red, st)) || (rc = d_pref.upload(hpref, st)) ||
-      (rc = d_ocam.upload(hoc, st)) || (rc = d_opt.upload(hop, st)) || (rc = d_pobs.upload(pt_obs, st)) || (rc = d_cmask.upload(cam_mask, st)) ||
-      (rc = d_pconst.upload(pt_const, st)) || (rc = d_poff.upload(pt_off, st)) || (rc = d_scale_c.alloc(6 * (size_t)nc)) ||
+      (rc = upload(d_gm, hgm, st)) || (rc = upload(d_cg, hcg, st)) || (rc = upload(d_cred, cam_red, st)) || (rc = upload(d_pref, hpref, st)) ||
+      (rc = upload(d_ocam, hoc, st)) || (rc = upload(d_opt, hop, st)) || (rc = upload(d_pobs, pt_obs, st)) || (rc = upload(d_cmask, cam_mask, st)) ||
+      (rc = upload(d_pconst, pt_const, st)) || (rc = upload(d_poff, pt_off, st)) || (rc = d_scale_c.alloc(6 * (size_t)nc)) ||
       (rc = d_scale_r.alloc(np)) || (rc = d_scale_red.alloc(std::max(1, n))) || (rc = d_recs.alloc((size_t)kRec * nobs)) ||
       (rc = d_red.alloc(std::max<size_t>(1, red_count))) || (rc = d_vinv.alloc(np)) || (rc = d_grho.alloc(np)) ||
       (rc = d_scal.alloc(ID_SCALARS)) || (rc = d_radius.alloc(1)) || (rc = d_work.alloc(dense_cholesky_workspace(std::max(1, n)))) ||
@@ -739,11 +721,11 @@ int IdHandle::upload_parameters(const theia_ba_problem* p) {
   std::vector<double> hintr(p->intrinsics, p->intrinsics + (size_t)THEIA_MAX_INTRINSICS * ng);
   for (int g = 0; g < ng; ++g) if (grp_red[g] >= 0) id_project_to_bounds_host(h_group_model[g], &hintr[(size_t)g * kKW]);
   for (int k = 0; k < 2; ++k) {
-    if (ng) HIP_TRY(hipMemcpyAsync(d_intr[k].p, hintr.data(), sizeof(double) * hintr.size(), hipMemcpyHostToDevice, st));
-    if (nc) HIP_TRY(hipMemcpyAsync(d_cam[k].p, p->cam_ext, sizeof(double) * 6 * (size_t)nc, hipMemcpyHostToDevice, st));
-    if (np) HIP_TRY(hipMemcpyAsync(d_rho[k].p, p->point_inverse_depth, sizeof(double) * (size_t)np, hipMemcpyHostToDevice, st));
+    if (ng) HIP_TRYR(hipMemcpyAsync(d_intr[k].p, hintr.data(), sizeof(double) * hintr.size(), hipMemcpyHostToDevice, st));
+    if (nc) HIP_TRYR(hipMemcpyAsync(d_cam[k].p, p->cam_ext, sizeof(double) * 6 * (size_t)nc, hipMemcpyHostToDevice, st));
+    if (np) HIP_TRYR(hipMemcpyAsync(d_rho[k].p, p->point_inverse_depth, sizeof(double) * (size_t)np, hipMemcpyHostToDevice, st));
   }
-  HIP_TRY(hipStreamSynchronize(st));   // the sources are the caller's (and a local) arrays
+  HIP_TRYR(hipStreamSynchronize(st));   // the sources are the caller's (and a local) arrays
   cur = 0;
   return 0;
 }
@@ -758,21 +740,21 @@ int IdHandle::run(const theia_ba_options* o, theia_ba_summary* S) {
   S->time_linearize = S->time_solve_reduced = S->time_backsub = 0.0; S->time_kernel_linearize = 0.0; S->num_linearize_launches = 0;
   P.loss_type = o->loss_function_type; P.loss_width = o->robust_loss_width;
   if (cur != 0) {   // the state of a previous run: continue from it in slot 0
-    if (ng) HIP_TRY(hipMemcpyAsync(d_intr[0].p, d_intr[1].p, sizeof(double) * (size_t)kKW * ng, hipMemcpyDeviceToDevice, st));
-    if (nc) HIP_TRY(hipMemcpyAsync(d_cam[0].p, d_cam[1].p, sizeof(double) * 6 * (size_t)nc, hipMemcpyDeviceToDevice, st));
-    if (np) HIP_TRY(hipMemcpyAsync(d_rho[0].p, d_rho[1].p, sizeof(double) * (size_t)np, hipMemcpyDeviceToDevice, st));
+    if (ng) HIP_TRYR(hipMemcpyAsync(d_intr[0].p, d_intr[1].p, sizeof(double) * (size_t)kKW * ng, hipMemcpyDeviceToDevice, st));
+    if (nc) HIP_TRYR(hipMemcpyAsync(d_cam[0].p, d_cam[1].p, sizeof(double) * 6 * (size_t)nc, hipMemcpyDeviceToDevice, st));
+    if (np) HIP_TRYR(hipMemcpyAsync(d_rho[0].p, d_rho[1].p, sizeof(double) * (size_t)np, hipMemcpyDeviceToDevice, st));
     cur = 0;
   }
   const int ob = (int)((nobs + 255) / 256), tb = (np + 63) / 64, cb = (std::max(nc, ng) + 63) / 64, pb = (npri + 63) / 64;
   double* dS = d_red.p; double* drhs = dS + (size_t)n * n; double* dcolsq = drhs + n; double* dgc = dcolsq + n;
   double hs[ID_SCALARS];
   auto read_scal = [&]() -> int {
-    HIP_TRY(hipMemcpyAsync(hs, d_scal.p, sizeof(hs), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRYR(hipMemcpyAsync(hs, d_scal.p, sizeof(hs), hipMemcpyDeviceToHost, st));
+    HIP_TRYR(hipStreamSynchronize(st));
     return 0;
   };
   auto cost_at = [&](const double* cam, const double* rho, const double* intr, double* cost, bool* ok) -> int {
-    HIP_TRY(hipMemsetAsync(d_scal.p, 0, sizeof(hs), st));
+    HIP_TRYR(hipMemsetAsync(d_scal.p, 0, sizeof(hs), st));
     if (nobs) k_id_obs<<<ob, 256, 0, st>>>(P, cam, rho, intr, 0, nullptr, d_scal.p, nullptr, nullptr, nullptr);
     if (npri) k_id_priors<<<pb, 64, 0, st>>>(P, cam, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, d_scal.p);
     int r2 = read_scal();
@@ -781,10 +763,10 @@ int IdHandle::run(const theia_ba_options* o, theia_ba_summary* S) {
     return 0;
   };
   // ---- Jacobi scaling (once): squared column norms of the unscaled Jacobian at the start
-  HIP_TRY(hipMemsetAsync(d_colsq_c.p, 0, sizeof(double) * 6 * nc, st));
-  HIP_TRY(hipMemsetAsync(d_colsq_r.p, 0, sizeof(double) * np, st));
-  HIP_TRY(hipMemsetAsync(d_scal.p, 0, sizeof(hs), st));
-  HIP_TRY(hipMemsetAsync(d_colsq_i.p, 0, sizeof(double) * std::max<size_t>(1, (size_t)kKW * ng), st));
+  HIP_TRYR(hipMemsetAsync(d_colsq_c.p, 0, sizeof(double) * 6 * nc, st));
+  HIP_TRYR(hipMemsetAsync(d_colsq_r.p, 0, sizeof(double) * np, st));
+  HIP_TRYR(hipMemsetAsync(d_scal.p, 0, sizeof(hs), st));
+  HIP_TRYR(hipMemsetAsync(d_colsq_i.p, 0, sizeof(double) * std::max<size_t>(1, (size_t)kKW * ng), st));
   if (nobs) k_id_obs<<<ob, 256, 0, st>>>(P, d_cam[0].p, d_rho[0].p, d_intr[0].p, 2, nullptr, d_scal.p, d_colsq_c.p, d_colsq_r.p, d_colsq_i.p);
   if (npri) k_id_priors<<<pb, 64, 0, st>>>(P, d_cam[0].p, 2, nullptr, nullptr, nullptr, nullptr, d_colsq_c.p, nullptr, d_scal.p);
   k_id_make_scale<<<(6 * nc + 255) / 256, 256, 0, st>>>(6 * nc, d_colsq_c.p, d_scale_c.p);
@@ -793,7 +775,7 @@ int IdHandle::run(const theia_ba_options* o, theia_ba_summary* S) {
   if (n) k_id_scale_red<<<cb, 64, 0, st>>>(P, d_scale_red.p);
   // |x| of the variable blocks
   auto xnorm_of = [&](const double* cam, const double* rho, const double* intr, double* out) -> int {
-    HIP_TRY(hipMemsetAsync(d_scal.p, 0, sizeof(hs), st));
+    HIP_TRYR(hipMemsetAsync(d_scal.p, 0, sizeof(hs), st));
     k_id_xnorm<<<(std::max(std::max(nc, np), ng) + 255) / 256, 256, 0, st>>>(P, cam, rho, intr, d_scal.p);
     int r2 = read_scal();
     if (r2) return r2;
@@ -802,11 +784,11 @@ int IdHandle::run(const theia_ba_options* o, theia_ba_summary* S) {
   };
   double radius = 1e4, decrease_factor = 2.0, x_cost = 0.0, gmax = 0.0, x_norm = 0.0, fixed_cost = 0.0;
   auto linearize = [&]() -> int {   // records, reduced system with the damping of `radius`, gradient max
-    HIP_TRY(hipMemcpyAsync(d_radius.p, &radius, sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRYR(hipMemcpyAsync(d_radius.p, &radius, sizeof(double), hipMemcpyHostToDevice, st));
     // only the tiles the plan's assembly and factorisation touch are cleared (the whole n x n buffer with the dense plan)
     if (!(n > 0 && chol_plan_clear(plan, dS, n, st, drhs, 3 * (size_t)n)))
-      HIP_TRY(hipMemsetAsync(d_red.p, 0, sizeof(double) * std::max<size_t>(1, red_count), st));
-    HIP_TRY(hipMemsetAsync(d_scal.p, 0, sizeof(hs), st));
+      HIP_TRYR(hipMemsetAsync(d_red.p, 0, sizeof(double) * std::max<size_t>(1, red_count), st));
+    HIP_TRYR(hipMemsetAsync(d_scal.p, 0, sizeof(hs), st));
     if (nobs) k_id_obs<<<ob, 256, 0, st>>>(P, d_cam[cur].p, d_rho[cur].p, d_intr[cur].p, 1, d_recs.p, d_scal.p, nullptr, nullptr, nullptr);
     if (np) k_id_track<<<np, 64, 0, st>>>(P, d_recs.p, d_radius.p, dS, drhs, dgc, dcolsq, d_vinv.p, d_grho.p, d_scal.p);
     if (npri) k_id_priors<<<pb, 64, 0, st>>>(P, d_cam[cur].p, 1, dS, drhs, dgc, dcolsq, nullptr, nullptr, d_scal.p);
@@ -836,7 +818,7 @@ int IdHandle::run(const theia_ba_options* o, theia_ba_summary* S) {
     if (!fresh && (rc = linearize())) return rc;   // same point, new radius: the damping sits inside the Schur complement
     fresh = false;
     const int nxt = 1 - cur;
-    HIP_TRY(hipMemsetAsync(d_scal.p, 0, sizeof(hs), st));
+    HIP_TRYR(hipMemsetAsync(d_scal.p, 0, sizeof(hs), st));
     if (n) chol_plan_solve(plan, dS, n, drhs, d_work.p, d_scal.p + ID_NOTPD, st);
     if (nc) k_id_cam_update<<<(nc + 63) / 64, 64, 0, st>>>(P, d_cam[cur].p, drhs, d_cam[nxt].p, d_scal.p);
     if (ng) k_id_intr_update<<<(ng + 63) / 64, 64, 0, st>>>(P, d_intr[cur].p, drhs, d_intr[nxt].p, d_scal.p);
@@ -877,7 +859,7 @@ int IdHandle::run(const theia_ba_options* o, theia_ba_summary* S) {
   }
   S->num_iterations = iter; S->termination_type = term; S->success = term != THEIA_TERM_FAILURE;
   S->final_cost = minimum_cost + fixed_cost;
-  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRYR(hipStreamSynchronize(st));
   S->solve_time_in_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
   S->setup_time_in_seconds = 0.0;
   return 0;
@@ -886,18 +868,18 @@ int IdHandle::run(const theia_ba_options* o, theia_ba_summary* S) {
 int IdHandle::snapshot() {
   int rc;
   if ((rc = snap_cam.alloc((size_t)6 * std::max(1, nc))) || (rc = snap_rho.alloc((size_t)std::max(1, np))) || (rc = snap_intr.alloc((size_t)kKW * std::max(1, ng)))) return rc;
-  if (nc) HIP_TRY(hipMemcpyAsync(snap_cam.p, d_cam[cur].p, sizeof(double) * 6 * (size_t)nc, hipMemcpyDeviceToDevice, st));
-  if (np) HIP_TRY(hipMemcpyAsync(snap_rho.p, d_rho[cur].p, sizeof(double) * (size_t)np, hipMemcpyDeviceToDevice, st));
-  if (ng) HIP_TRY(hipMemcpyAsync(snap_intr.p, d_intr[cur].p, sizeof(double) * (size_t)kKW * ng, hipMemcpyDeviceToDevice, st));
+  if (nc) HIP_TRYR(hipMemcpyAsync(snap_cam.p, d_cam[cur].p, sizeof(double) * 6 * (size_t)nc, hipMemcpyDeviceToDevice, st));
+  if (np) HIP_TRYR(hipMemcpyAsync(snap_rho.p, d_rho[cur].p, sizeof(double) * (size_t)np, hipMemcpyDeviceToDevice, st));
+  if (ng) HIP_TRYR(hipMemcpyAsync(snap_intr.p, d_intr[cur].p, sizeof(double) * (size_t)kKW * ng, hipMemcpyDeviceToDevice, st));
   has_snapshot = true;
   return 0;
 }
 int IdHandle::restore() {
   if (!has_snapshot) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "restore_parameters without a snapshot");
   for (int k = 0; k < 2; ++k) {
-    if (nc) HIP_TRY(hipMemcpyAsync(d_cam[k].p, snap_cam.p, sizeof(double) * 6 * (size_t)nc, hipMemcpyDeviceToDevice, st));
-    if (np) HIP_TRY(hipMemcpyAsync(d_rho[k].p, snap_rho.p, sizeof(double) * (size_t)np, hipMemcpyDeviceToDevice, st));
-    if (ng) HIP_TRY(hipMemcpyAsync(d_intr[k].p, snap_intr.p, sizeof(double) * (size_t)kKW * ng, hipMemcpyDeviceToDevice, st));
+    if (nc) HIP_TRYR(hipMemcpyAsync(d_cam[k].p, snap_cam.p, sizeof(double) * 6 * (size_t)nc, hipMemcpyDeviceToDevice, st));
+    if (np) HIP_TRYR(hipMemcpyAsync(d_rho[k].p, snap_rho.p, sizeof(double) * (size_t)np, hipMemcpyDeviceToDevice, st));
+    if (ng) HIP_TRYR(hipMemcpyAsync(d_intr[k].p, snap_intr.p, sizeof(double) * (size_t)kKW * ng, hipMemcpyDeviceToDevice, st));
   }
   cur = 0;
   return 0;
@@ -906,10 +888,10 @@ int IdHandle::restore() {
 int IdHandle::download(theia_ba_problem* p) {
   if (p->num_cameras != nc || p->num_points != np || p->num_groups != ng)
     return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "problem shape differs from the handle's");
-  if (ngv) HIP_TRY(hipMemcpyAsync(p->intrinsics, d_intr[cur].p, sizeof(double) * (size_t)kKW * ng, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(p->cam_ext, d_cam[cur].p, sizeof(double) * 6 * nc, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(p->point_inverse_depth, d_rho[cur].p, sizeof(double) * np, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
+  if (ngv) HIP_TRYR(hipMemcpyAsync(p->intrinsics, d_intr[cur].p, sizeof(double) * (size_t)kKW * ng, hipMemcpyDeviceToHost, st));
+  HIP_TRYR(hipMemcpyAsync(p->cam_ext, d_cam[cur].p, sizeof(double) * 6 * nc, hipMemcpyDeviceToHost, st));
+  HIP_TRYR(hipMemcpyAsync(p->point_inverse_depth, d_rho[cur].p, sizeof(double) * np, hipMemcpyDeviceToHost, st));
+  HIP_TRYR(hipStreamSynchronize(st));
   return 0;
 }
 

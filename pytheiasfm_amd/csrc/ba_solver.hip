@@ -32,7 +32,7 @@
 
 #include "ba_kernels.h"
 #include "theia_hip.h"
-#include "theia_hip_internal.h"
+#include "device_util.h"
 #include "pools.h"
 #include "host_team.h"
 
@@ -49,15 +49,6 @@ int set_error(int code, const char* fmt, ...) {
   g_last_error = buf;
   return code;
 }
-
-#define HIP_TRY(expr)                                                                   \
-  do {                                                                                  \
-    hipError_t e_ = (expr);                                                             \
-    if (e_ != hipSuccess)                                                               \
-      return set_error(e_ == hipErrorOutOfMemory ? THEIA_HIP_ERR_OUT_OF_MEMORY         \
-                                                 : THEIA_HIP_ERR_NO_DEVICE,            \
-                       "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
 
 static double now_s() {
   return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -102,17 +93,17 @@ struct StageScope {   // the arena (the handle's: it lives until the uploads are
 };
 
 template <typename T>
-struct DevBuf {
+struct PoolBuf {
   // Blocks come from the library's device cache (pools.h): creating a handle makes ~80 allocations, and at a million
   // observations hipMalloc + hipFree were ~15 ms of a 100 ms create().  A cached block is handed out without a device
   // synchronisation, so the owner makes sure no kernel still uses a buffer when it goes back (the handle's destructor
   // waits for its stream; a re-allocation waits for the device).
   T* p = nullptr;
   size_t n = 0, bytes = 0;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { if (p) dev_pool().give(p, bytes); }
+  PoolBuf() = default;
+  PoolBuf(const PoolBuf&) = delete;
+  PoolBuf& operator=(const PoolBuf&) = delete;
+  ~PoolBuf() { if (p) dev_pool().give(p, bytes); }
   int alloc(size_t count) {
     if (p) { (void)hipDeviceSynchronize(); dev_pool().give(p, bytes); p = nullptr; bytes = 0; }
     n = count;
@@ -133,8 +124,8 @@ struct DevBuf {
       StageArena* a = stage_arena();
       if (!pinned && a && a->stream == st && count * sizeof(T) <= ((size_t)32 << 20))
         if (const void* staged = a->put(src, count * sizeof(T))) { src = static_cast<const T*>(staged); pinned = true; }
-      HIP_TRY(hipMemcpyAsync(p, src, count * sizeof(T), hipMemcpyHostToDevice, st));
-      if (!pinned) HIP_TRY(hipStreamSynchronize(st));
+      HIP_TRYR(hipMemcpyAsync(p, src, count * sizeof(T), hipMemcpyHostToDevice, st));
+      if (!pinned) HIP_TRYR(hipStreamSynchronize(st));
     }
     return 0;
   }
@@ -151,13 +142,13 @@ struct theia_ba_handle_s {
   int64_t nobs = 0, nobs_main = 0;
   int ntiles_main = 0, ntiles_eval = 0, ntiles_all = 0;  // linearize tiles < + long-track eval tiles < + fixed tiles
   int long_nobs = 0, long_ntracks = 0;
-  DevBuf<int> long_obs_index, long_obs_slot, long_track_start, long_track_pt;
-  DevBuf<double> long_scratch;
+  PoolBuf<int> long_obs_index, long_obs_slot, long_track_start, long_track_pt;
+  PoolBuf<double> long_scratch;
   hipStream_t stream = nullptr;
   static constexpr int kMaxChunk = 8;   // LM iterations enqueued per host synchronisation
   hipEvent_t ev[kMaxChunk][6] = {};
-  DevBuf<char> lm_state;                // LmState (device): radius, cost, counters, termination
-  DevBuf<char> lm_ctl;                  // LmCtl (device): per-run tolerances, caps, trace pointers
+  PoolBuf<char> lm_state;                // LmState (device): radius, cost, counters, termination
+  PoolBuf<char> lm_ctl;                  // LmCtl (device): per-run tolerances, caps, trace pointers
   hipGraph_t graph = nullptr;           // one captured LM iteration (no all-reduce callback, no phase timing)
   hipGraphExec_t graph_exec = nullptr;
   bool graph_failed = false;
@@ -165,8 +156,8 @@ struct theia_ba_handle_s {
     if (graph_exec) { (void)hipGraphExecDestroy(graph_exec); graph_exec = nullptr; }
     if (graph) { (void)hipGraphDestroy(graph); graph = nullptr; }
   }
-  DevBuf<double> tr_cost, tr_g, tr_step, tr_radius;
-  DevBuf<int> tr_acc;
+  PoolBuf<double> tr_cost, tr_g, tr_step, tr_radius;
+  PoolBuf<int> tr_acc;
   // host-side bookkeeping
   HBuf<int64_t> perm;              // sorted obs index -> original obs index (a block of the pinned host cache: no page faults)
   std::vector<int> cam_red, grp_red, grp_k;
@@ -180,56 +171,56 @@ struct theia_ba_handle_s {
   std::vector<uint8_t> cam_mask, pt_const;
   int ni = 0, ngv = 0;
   // device buffers
-  DevBuf<double> snap_cam, snap_pts, snap_intr;   // theia_hip_ba_snapshot_parameters
-  DevBuf<double> xnorm_part;
+  PoolBuf<double> snap_cam, snap_pts, snap_intr;   // theia_hip_ba_snapshot_parameters
+  PoolBuf<double> xnorm_part;
   bool has_snapshot = false;
-  DevBuf<double> cam[2], pts[2], intr[2], scale_c, scale_p, ones_c, ones_p, colsq_c0, colsq_p0;
-  DevBuf<double> scale_i, ones_i, colsq_i0, scale_red;
-  DevBuf<int> d_grp_red, d_grp_k;
-  DevBuf<unsigned> d_grp_free, d_red_free;
+  PoolBuf<double> cam[2], pts[2], intr[2], scale_c, scale_p, ones_c, ones_p, colsq_c0, colsq_p0;
+  PoolBuf<double> scale_i, ones_i, colsq_i0, scale_red;
+  PoolBuf<int> d_grp_red, d_grp_k;
+  PoolBuf<unsigned> d_grp_free, d_red_free;
   int intr_rows = 10;            // intrinsics rows per gather record (ba_kernels.hip RecI): 10, or 4 compact rows
-  DevBuf<int> group_model, cam_group, d_cam_red, obs_cam, obs_pt, tile_start, tile_count, f2s, fmaxflag;
-  DevBuf<uint8_t> d_cam_mask, d_pt_const;
-  DevBuf<double2> obs_uv, obs_si;
-  DevBuf<uint8_t> obs_kind;
-  DevBuf<double> reduce, Vinv, gp, tile_part, red_part, scalB, chol_work, stop_flag;
-  DevBuf<double> rec;                       // per-observation records of the gather-based Schur assembly
-  DevBuf<int> diag_items, cam_obs, blk_items, slot_obs, slot_pt;
-  DevBuf<int> prior_cam, prior_kind;        // camera priors in use (compact list)
+  PoolBuf<int> group_model, cam_group, d_cam_red, obs_cam, obs_pt, tile_start, tile_count, f2s, fmaxflag;
+  PoolBuf<uint8_t> d_cam_mask, d_pt_const;
+  PoolBuf<double2> obs_uv, obs_si;
+  PoolBuf<uint8_t> obs_kind;
+  PoolBuf<double> reduce, Vinv, gp, tile_part, red_part, scalB, chol_work, stop_flag;
+  PoolBuf<double> rec;                       // per-observation records of the gather-based Schur assembly
+  PoolBuf<int> diag_items, cam_obs, blk_items, slot_obs, slot_pt;
+  PoolBuf<int> prior_cam, prior_kind;        // camera priors in use (compact list)
   // inner iterations (ba_inner.hip): observation lists by camera / group / track, a third parameter buffer the sweep
   // works on, its scalars {step^2, |x|^2, cost, invalid}, the gate flag
   bool inner = false;
-  DevBuf<int> in_cam_off, in_cam_idx, in_grp_off, in_grp_idx, in_trk_off, in_gate, in_grp_bar;
-  DevBuf<double> in_grp_part;   // partial sums of the intrinsics sweep, inner_group_wgs() workgroups per group
-  DevBuf<double> in_cam, in_pts, in_intr, in_scal, in_part;
+  PoolBuf<int> in_cam_off, in_cam_idx, in_grp_off, in_grp_idx, in_trk_off, in_gate, in_grp_bar;
+  PoolBuf<double> in_grp_part;   // partial sums of the intrinsics sweep, inner_group_wgs() workgroups per group
+  PoolBuf<double> in_cam, in_pts, in_intr, in_scal, in_part;
   // inner iterations of a SHARDED solve (theia_hip_ba_set_inner_global): every rank sweeps all cameras and intrinsics groups
   // over the FULL observation set (the same sums on every rank: no exchange of their results), its own tracks afterwards
   bool inner_global = false;
   int g_np = 0, g_npriors = 0;
   int64_t g_nobs = 0;
-  DevBuf<double2> g_uv, g_si;
-  DevBuf<int> g_cam, g_pt, g_cam_off, g_cam_idx, g_grp_off, g_grp_idx, g_pidx, g_prior_cam, g_prior_kind;
-  DevBuf<uint8_t> g_kind;
-  DevBuf<double> g_pts, g_prior_vec, g_prior_info, g_stage;
+  PoolBuf<double2> g_uv, g_si;
+  PoolBuf<int> g_cam, g_pt, g_cam_off, g_cam_idx, g_grp_off, g_grp_idx, g_pidx, g_prior_cam, g_prior_kind;
+  PoolBuf<uint8_t> g_kind;
+  PoolBuf<double> g_pts, g_prior_vec, g_prior_info, g_stage;
   int in_ntracks = 0;
-  DevBuf<double> prior_vec, prior_info;
+  PoolBuf<double> prior_vec, prior_info;
   int n_priors = 0;
-  DevBuf<int2> blk_pairs;
-  DevBuf<int> pt_sum_slot;   // [np] pseudo-record of a track's summed intrinsics fields, -1 = none (build_gather_lists_intr)
-  DevBuf<uint8_t> slot_in_sum;   // [#records] the observation's track is summed
-  DevBuf<uint8_t> pt_sum_cnt;    // [np] number of summed groups (pseudo-records) of a track
-  DevBuf<int> sum_group;         // [#pseudo-records] reduced group index
+  PoolBuf<int2> blk_pairs;
+  PoolBuf<int> pt_sum_slot;   // [np] pseudo-record of a track's summed intrinsics fields, -1 = none (build_gather_lists_intr)
+  PoolBuf<uint8_t> slot_in_sum;   // [#records] the observation's track is summed
+  PoolBuf<uint8_t> pt_sum_cnt;    // [np] number of summed groups (pseudo-records) of a track
+  PoolBuf<int> sum_group;         // [#pseudo-records] reduced group index
   int sum_base = 0;              // first pseudo-record slot
   int n_trk_sums = 0;
   int n_diag_items = 0, n_blk_items = 0;
   // fused linearise + Schur plan (ba_fused.hip)
   bool use_fused = false;
   unsigned model_mask = 0xffu;          // camera models present in the problem
-  DevBuf<FusedRun> fruns;
-  DevBuf<int> frun_cams, frun_stage, tile_trk_end, sum_items, sum_src, frun_order, frun_next;
-  DevBuf<unsigned short> frun_tgt;
-  DevBuf<uint8_t> obs_lc, obs_tl;
-  DevBuf<double> fpart, camrot, camrot_cand, camdir;
+  PoolBuf<FusedRun> fruns;
+  PoolBuf<int> frun_cams, frun_stage, tile_trk_end, sum_items, sum_src, frun_order, frun_next;
+  PoolBuf<unsigned short> frun_tgt;
+  PoolBuf<uint8_t> obs_lc, obs_tl;
+  PoolBuf<double> fpart, camrot, camrot_cand, camdir;
   int n_fruns = 0, n_sum_items = 0;
   double* h_scal = nullptr;  // pinned: [scalA(16) | scalB(16) | stop flag out / in (2) | spare]
   char* h_state = nullptr;   // pinned: LmState read-back
@@ -247,14 +238,14 @@ struct theia_ba_handle_s {
   CholPlan* plan = nullptr;
   bool plan_is_global = true;
   // multi-rank: only the structurally non-zero lower 64x64 tiles of S travel through the all-reduce
-  DevBuf<int2> pack_tiles;
-  DevBuf<double> pack_buf;
+  PoolBuf<int2> pack_tiles;
+  PoolBuf<double> pack_buf;
   int shard_rank = -1, shard_world = 0;   // theia_hip_ba_set_shard
   // distributed K3 of a sharded solve (sync_plan): every rank factors the tile columns only its own tracks touch before the
   // all-reduce, which then carries the shared tiles only; tile_cls: 0 shared, 1 this rank's, 2 another rank's
   bool dist_k3 = false;
   std::vector<uint8_t> tile_adj_local, tile_cls, tile_touch;   // tile_touch: this rank's observations / priors write into the tile column
-  DevBuf<uint8_t> d_tile_cls;
+  PoolBuf<uint8_t> d_tile_cls;
   int n_pack_tiles = 0;
 
   StageArena stage;                     // pinned staging of create()'s small uploads (released after the first run)
@@ -732,7 +723,7 @@ int upload_parameters(theia_ba_handle_s* h, const theia_ba_problem* p) {
     if (!count) return 0;
     const double* from = src;
     // (staged up to 64 MB per array -- C4's points are 16 MB; larger arrays go from the caller's memory and are waited for,
-    // like DevBuf::upload's cap: pinned blocks count against the 2 GiB pinned cache until the arena is released)
+    // like PoolBuf::upload's cap: pinned blocks count against the 2 GiB pinned cache until the arena is released)
     const bool fits = count * sizeof(double) <= ((size_t)64 << 20);
     double* st = (staged && fits) ? static_cast<double*>(a->reserve(count * sizeof(double))) : nullptr;
     if (st) {
@@ -742,8 +733,8 @@ int upload_parameters(theia_ba_handle_s* h, const theia_ba_problem* p) {
       if (staged && fits) (void)hipGetLastError();   // the host does not pin that much: the caller's array is the source, and is waited for
       must_wait = true;
     }
-    HIP_TRY(hipMemcpyAsync(dst0, from, sizeof(double) * count, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(dst1, dst0, sizeof(double) * count, hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRYR(hipMemcpyAsync(dst0, from, sizeof(double) * count, hipMemcpyHostToDevice, h->stream));
+    HIP_TRYR(hipMemcpyAsync(dst1, dst0, sizeof(double) * count, hipMemcpyDeviceToDevice, h->stream));
     return 0;
   };
   int rc;
@@ -753,9 +744,9 @@ int upload_parameters(theia_ba_handle_s* h, const theia_ba_problem* p) {
     std::vector<double> hk(p->intrinsics, p->intrinsics + (size_t)THEIA_MAX_INTRINSICS * h->ng);
     for (int g = 0; g < h->ng; ++g) if (h->grp_red[g] >= 0) project_intrinsics_to_bounds(p->group_model[g], &hk[(size_t)g * THEIA_MAX_INTRINSICS]);
     if ((rc = up(h->intr[0].p, h->intr[1].p, hk.data(), hk.size()))) return rc;
-    if (must_wait) HIP_TRY(hipStreamSynchronize(h->stream));   // (hk is a local)
+    if (must_wait) HIP_TRYR(hipStreamSynchronize(h->stream));   // (hk is a local)
   }
-  if (must_wait) HIP_TRY(hipStreamSynchronize(h->stream));
+  if (must_wait) HIP_TRYR(hipStreamSynchronize(h->stream));
   h->cur = 0;
   h->P.intr = h->intr[0].p; h->P.intr_cand = h->intr[1].p;
   h->have_scale = false; h->camrot_valid = false;
@@ -784,11 +775,11 @@ int cost_of_tiles(theia_ba_handle_s* h, int tile0, int ntiles, const double* cam
   if (ntiles == 0) return 0;
   DevProblem Q = h->P;
   Q.tile_start = h->tile_start.p + tile0; Q.tile_count = h->tile_count.p + tile0; Q.ntiles = ntiles;
-  HIP_TRY(hipMemsetAsync(h->scalB.p, 0, sizeof(double) * 16, h->stream));
+  HIP_TRYR(hipMemsetAsync(h->scalB.p, 0, sizeof(double) * 16, h->stream));
   launch_cost_only(Q, cam, pts, h->tile_part.p, h->scalB.p, h->stream);
   launch_reduce_tiles(ntiles, h->tile_part.p, 2, h->f2s.p + 16, h->fmaxflag.p + 16, h->scalB.p, h->stream);
-  HIP_TRY(hipMemcpyAsync(h->h_scal + 16, h->scalB.p, sizeof(double) * 16, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRYR(hipMemcpyAsync(h->h_scal + 16, h->scalB.p, sizeof(double) * 16, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRYR(hipStreamSynchronize(h->stream));
   *cost = h->h_scal[16 + SB_COST]; *invalid = h->h_scal[16 + SB_INVALID];
   return 0;
 }
@@ -800,9 +791,9 @@ int cost_of_tiles(theia_ba_handle_s* h, int tile0, int ntiles, const double* cam
 int compute_scale(theia_ba_handle_s* h) {
   DevProblem Q = h->P;
   Q.scale_c = h->ones_c.p; Q.scale_p = h->ones_p.p;
-  if (h->colsq_c0.n) HIP_TRY(hipMemsetAsync(h->colsq_c0.p, 0, sizeof(double) * h->colsq_c0.n, h->stream));
-  if (h->colsq_p0.n) HIP_TRY(hipMemsetAsync(h->colsq_p0.p, 0, sizeof(double) * h->colsq_p0.n, h->stream));
-  if (h->colsq_i0.n) HIP_TRY(hipMemsetAsync(h->colsq_i0.p, 0, sizeof(double) * h->colsq_i0.n, h->stream));
+  if (h->colsq_c0.n) HIP_TRYR(hipMemsetAsync(h->colsq_c0.p, 0, sizeof(double) * h->colsq_c0.n, h->stream));
+  if (h->colsq_p0.n) HIP_TRYR(hipMemsetAsync(h->colsq_p0.p, 0, sizeof(double) * h->colsq_p0.n, h->stream));
+  if (h->colsq_i0.n) HIP_TRYR(hipMemsetAsync(h->colsq_i0.p, 0, sizeof(double) * h->colsq_i0.n, h->stream));
   Q.scale_i = h->ones_i.p;
   Q.intr = h->intr[h->cur].p;
   launch_colnorm(Q, h->cam[h->cur].p, h->pts[h->cur].p, h->colsq_c0.p, h->colsq_p0.p, h->colsq_i0.p, h->stream);
@@ -838,8 +829,8 @@ int enqueue_linearize(theia_ba_handle_s* h, int slot = 0) {
   if (h->n > 0 && !(h->allreduce && h->n_pack_tiles == 0) &&
       chol_plan_clear(h->plan, h->rb.S, h->n, h->stream, h->rb.rhs, h->reduce.n - (size_t)h->n * h->n)) {
   } else
-    HIP_TRY(hipMemsetAsync(h->reduce.p, 0, sizeof(double) * h->reduce.n, h->stream));
-  if (slot >= 0) HIP_TRY(hipEventRecord(h->ev[slot][4], h->stream));
+    HIP_TRYR(hipMemsetAsync(h->reduce.p, 0, sizeof(double) * h->reduce.n, h->stream));
+  if (slot >= 0) HIP_TRYR(hipEventRecord(h->ev[slot][4], h->stream));
   // the state's per-camera blocks (k_cam_prep) are still current after the first body: an accepted step copies the candidate's
   // blocks over them (k_lm_accept), a rejected one leaves the state where it was.  Not with inner iterations (the accepted
   // point may be the swept one, and the sweep reuses the candidate's blocks) and not with free intrinsics.
@@ -847,7 +838,7 @@ int enqueue_linearize(theia_ba_handle_s* h, int slot = 0) {
   h->P.camrot_current = keep_blocks && h->camrot_valid;
   launch_linearize(h->P, h->cam[h->cur].p, h->pts[h->cur].p, radius, h->rb, h->Vinv.p, h->gp.p, h->tile_part.p, h->stream);
   h->camrot_valid = keep_blocks;
-  if (slot >= 0) HIP_TRY(hipEventRecord(h->ev[slot][5], h->stream));
+  if (slot >= 0) HIP_TRYR(hipEventRecord(h->ev[slot][5], h->stream));
   // without an all-reduce (and without phase timing) the tile reduction rides in k_finalize_rcs: one launch less
   const bool fuse_reduce = !h->allreduce && slot < 0 && h->ntiles_main > 0;
   if (h->ntiles_main && !fuse_reduce) launch_reduce_tiles(h->ntiles_main, h->tile_part.p, 4, h->f2s.p, h->fmaxflag.p, h->rb.scal, h->stream, h->red_part.p);
@@ -897,7 +888,7 @@ int enqueue_solve_and_backsub(theia_ba_handle_s* h, int slot = 0, bool defer_red
     if (rcy) return rcy;
   } else
   chol_plan_solve(h->plan, h->rb.S, h->n, h->rb.rhs, h->chol_work.p, h->rb.scal + SC_NOTPD, h->stream);
-  if (slot >= 0) HIP_TRY(hipEventRecord(h->ev[slot][2], h->stream));
+  if (slot >= 0) HIP_TRYR(hipEventRecord(h->ev[slot][2], h->stream));
   const int nxt = 1 - h->cur;
   launch_cam_update(h->P, h->cam[h->cur].p, yc, h->cam[nxt].p, h->ni ? h->intr[nxt].p : nullptr,
                     h->scalB.p + SB_STEPSQ_CAM, h->scalB.p + SB_XNORMSQ_CAM, h->stream, h->scalB.p);
@@ -918,11 +909,11 @@ int sync_plan(theia_ba_handle_s* h) {
   if (h->tile_adj_local.size() != cnt) h->tile_adj_local = h->tile_adj;   // this rank's own structure (tile_adj becomes the union)
   std::vector<double> a(cnt);
   for (size_t i = 0; i < cnt; ++i) a[i] = h->tile_adj_local[i];
-  HIP_TRY(hipMemcpyAsync(h->reduce.p, a.data(), sizeof(double) * cnt, hipMemcpyHostToDevice, h->stream));
+  HIP_TRYR(hipMemcpyAsync(h->reduce.p, a.data(), sizeof(double) * cnt, hipMemcpyHostToDevice, h->stream));
   int rc = do_allreduce(h, h->reduce.p, cnt, THEIA_REDUCE_MAX);
   if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(a.data(), h->reduce.p, sizeof(double) * cnt, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRYR(hipMemcpyAsync(a.data(), h->reduce.p, sizeof(double) * cnt, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRYR(hipStreamSynchronize(h->stream));
   for (size_t i = 0; i < cnt; ++i) h->tile_adj[i] = a[i] != 0.0 ? 1 : 0;
   h->drop_graph();
   if (h->plan) chol_plan_destroy(h->plan);
@@ -934,22 +925,22 @@ int sync_plan(theia_ba_handle_s* h) {
   if (geom && h->ni == 0 && nt > 2 && !getenv("THEIA_HIP_K3_REPLICATED")) {
     std::vector<double> t(nt + 1, 0.0);
     for (int i = 0; i < nt; ++i) t[i] = (i < (int)h->tile_touch.size() && h->tile_touch[i]) ? 1.0 : 0.0;
-    HIP_TRY(hipMemcpyAsync(h->reduce.p, t.data(), sizeof(double) * nt, hipMemcpyHostToDevice, h->stream));
+    HIP_TRYR(hipMemcpyAsync(h->reduce.p, t.data(), sizeof(double) * nt, hipMemcpyHostToDevice, h->stream));
     if ((rc = do_allreduce(h, h->reduce.p, (size_t)nt, THEIA_REDUCE_SUM))) return rc;
     std::vector<double> c(nt);
-    HIP_TRY(hipMemcpyAsync(c.data(), h->reduce.p, sizeof(double) * nt, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRYR(hipMemcpyAsync(c.data(), h->reduce.p, sizeof(double) * nt, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRYR(hipStreamSynchronize(h->stream));
     h->tile_cls.assign(nt, 0);
     int nmine = 0;
     for (int i = 0; i < nt; ++i)
       if (c[i] == 1.0) { h->tile_cls[i] = t[i] != 0.0 ? 1 : 2; nmine += t[i] != 0.0; }
     CholPlan* pl = chol_plan_create_sharded(h->n, h->tile_adj.data(), h->tile_cls.data());
     double bad = pl ? 0.0 : 1.0;      // agreed between the ranks: one rank without a level schedule keeps everybody replicated
-    HIP_TRY(hipMemcpyAsync(h->reduce.p, &bad, sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRYR(hipMemcpyAsync(h->reduce.p, &bad, sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRYR(hipStreamSynchronize(h->stream));
     if ((rc = do_allreduce(h, h->reduce.p, 1, THEIA_REDUCE_MAX))) { if (pl) chol_plan_destroy(pl); return rc; }
-    HIP_TRY(hipMemcpyAsync(&bad, h->reduce.p, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRYR(hipMemcpyAsync(&bad, h->reduce.p, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRYR(hipStreamSynchronize(h->stream));
     if (bad == 0.0) {
       h->plan = pl; h->dist_k3 = true;
       if ((rc = h->d_tile_cls.upload(h->tile_cls, h->stream))) return rc;
@@ -966,7 +957,7 @@ int sync_plan(theia_ba_handle_s* h) {
     fprintf(stderr, "theia_hip distributed K3: not taken (shard geometry %d/%d, %d intrinsics columns, %d tiles)\n", h->shard_rank, h->shard_world, h->ni, nt);
   if (!h->plan) h->plan = chol_plan_create(h->n, h->tile_adj.data());
   h->plan_is_global = true;
-  HIP_TRY(hipMemsetAsync(h->reduce.p, 0, sizeof(double) * h->reduce.n, h->stream));   // tiles only the old plan touched
+  HIP_TRYR(hipMemsetAsync(h->reduce.p, 0, sizeof(double) * h->reduce.n, h->stream));   // tiles only the old plan touched
   {
     std::vector<int2> tiles;
     if (h->dist_k3) {
@@ -981,7 +972,7 @@ int sync_plan(theia_ba_handle_s* h) {
     int rc2 = h->pack_tiles.upload(tiles, h->stream);
     if (!rc2) rc2 = h->pack_buf.alloc((size_t)tiles.size() * 4096 + 3 * (size_t)h->n + 8 + kMaxShardSlots);
     if (rc2) return rc2;
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRYR(hipStreamSynchronize(h->stream));
   }
   return 0;
 }
@@ -1914,13 +1905,13 @@ static int ba_create_impl(const theia_ba_problem* p, const theia_ba_options* o, 
   h->opt = *o;
   h->nc = p->num_cameras; h->ng = p->num_groups; h->np = p->num_points; h->nobs = p->num_obs;
   h->pd = o->use_homogeneous_point_parametrization ? 3 : 4;
-  HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  HIP_TRYR(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
   h->stage.stream = h->stream;
   StageScope stage_scope(&h->stage);
   PoolStreamScope pool_scope(h->stream);   // blocks that go back to the caches inside this call are tagged with an event on it
-  for (auto& row : h->ev) for (auto& e : row) HIP_TRY(hipEventCreate(&e));
-  HIP_TRY(hipHostMalloc((void**)&h->h_scal, sizeof(double) * 40, hipHostMallocDefault));
-  HIP_TRY(hipHostMalloc((void**)&h->h_state, 1024, hipHostMallocDefault));
+  for (auto& row : h->ev) for (auto& e : row) HIP_TRYR(hipEventCreate(&e));
+  HIP_TRYR(hipHostMalloc((void**)&h->h_scal, sizeof(double) * 40, hipHostMallocDefault));
+  HIP_TRYR(hipHostMalloc((void**)&h->h_state, 1024, hipHostMallocDefault));
   static_assert(sizeof(LmState) <= 1024, "pinned read-back block too small");
 
   // THEIA_HIP_CREATE_TIMING=1: wall time of the create() stages on stderr
@@ -2355,7 +2346,7 @@ static int ba_create_impl(const theia_ba_problem* p, const theia_ba_options* o, 
   }
   AL(colsq_i0, (size_t)THEIA_MAX_INTRINSICS * h->ng); AL(scale_red, (size_t)std::max(1, h->n));
   AL(ones_c, (size_t)6 * h->nc); AL(ones_p, (size_t)h->pd * h->np); AL(scale_c, (size_t)6 * h->nc); AL(scale_p, (size_t)h->pd * h->np);
-  for (DevBuf<double>* b : {&h->ones_c, &h->ones_p, &h->scale_c, &h->scale_p})   // filled on the device
+  for (PoolBuf<double>* b : {&h->ones_c, &h->ones_p, &h->scale_c, &h->scale_p})   // filled on the device
     if (b->n) k_fill_value<<<(unsigned)std::min<size_t>(1024, (b->n + 255) / 256), 256, 0, st>>>(b->p, b->n, 1.0);
   AL(colsq_c0, (size_t)6 * h->nc); AL(colsq_p0, (size_t)h->pd * h->np);
   {
@@ -2364,14 +2355,14 @@ static int ba_create_impl(const theia_ba_problem* p, const theia_ba_options* o, 
   }
   const size_t nn = (size_t)h->n * h->n;
   AL(reduce, nn + 3 * (size_t)h->n + SC_COUNT);
-  if (h->reduce.n) HIP_TRY(hipMemsetAsync(h->reduce.p, 0, sizeof(double) * h->reduce.n, st));
+  if (h->reduce.n) HIP_TRYR(hipMemsetAsync(h->reduce.p, 0, sizeof(double) * h->reduce.n, st));
   h->rb.base = h->reduce.p; h->rb.count = h->reduce.n;
   h->rb.S = h->reduce.p; h->rb.rhs = h->rb.S + nn; h->rb.colsq = h->rb.rhs + h->n; h->rb.gc = h->rb.colsq + h->n;
   h->rb.scal = h->rb.gc + h->n;
   AL(Vinv, (size_t)(h->pd * (h->pd + 1) / 2) * h->np); AL(gp, (size_t)h->pd * h->np);
   // constant points are never written: the Schur readers rebuild T = W V^-1 from these arrays and need zeros there
-  if (h->Vinv.n) HIP_TRY(hipMemsetAsync(h->Vinv.p, 0, sizeof(double) * h->Vinv.n, st));
-  if (h->gp.n) HIP_TRY(hipMemsetAsync(h->gp.p, 0, sizeof(double) * h->gp.n, st));
+  if (h->Vinv.n) HIP_TRYR(hipMemsetAsync(h->Vinv.p, 0, sizeof(double) * h->Vinv.n, st));
+  if (h->gp.n) HIP_TRYR(hipMemsetAsync(h->gp.p, 0, sizeof(double) * h->gp.n, st));
   AL(tile_part, (size_t)5 * std::max(1, h->ntiles_all)); AL(scalB, 16); AL(red_part, (size_t)8 * kReduceBlocks);
   AL(chol_work, dense_cholesky_workspace(h->n));
   AL(lm_state, sizeof(LmState)); AL(lm_ctl, sizeof(LmCtl));
@@ -2496,10 +2487,10 @@ static int ba_create_impl(const theia_ba_problem* p, const theia_ba_options* o, 
   if (rc) return rc;
   if (h->n_priors) {   // priors on constant cameras: residual blocks without variable parameters
     double pf = 0.0;
-    HIP_TRY(hipMemsetAsync(h->scalB.p, 0, sizeof(double) * 16, h->stream));
+    HIP_TRYR(hipMemsetAsync(h->scalB.p, 0, sizeof(double) * 16, h->stream));
     launch_cam_priors(h->P, PRIOR_FIXED, h->cam[0].p, nullptr, nullptr, nullptr, nullptr, h->scalB.p, nullptr, h->stream);
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipMemcpy(&pf, h->scalB.p, sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRYR(hipStreamSynchronize(h->stream));
+    HIP_TRYR(hipMemcpy(&pf, h->scalB.p, sizeof(double), hipMemcpyDeviceToHost));
     fc += pf;
   }
   h->fixed_cost = fc;
@@ -2532,9 +2523,9 @@ int theia_hip_ba_snapshot_parameters(theia_ba_handle h) {
   int rc;
   if ((rc = h->snap_cam.alloc(h->cam[0].n)) || (rc = h->snap_pts.alloc(h->pts[0].n)) || (rc = h->snap_intr.alloc(h->intr[0].n))) return rc;
   const int c = h->cur;
-  if (h->cam[c].n) HIP_TRY(hipMemcpyAsync(h->snap_cam.p, h->cam[c].p, sizeof(double) * h->cam[c].n, hipMemcpyDeviceToDevice, h->stream));
-  if (h->pts[c].n) HIP_TRY(hipMemcpyAsync(h->snap_pts.p, h->pts[c].p, sizeof(double) * h->pts[c].n, hipMemcpyDeviceToDevice, h->stream));
-  if (h->intr[c].n) HIP_TRY(hipMemcpyAsync(h->snap_intr.p, h->intr[c].p, sizeof(double) * h->intr[c].n, hipMemcpyDeviceToDevice, h->stream));
+  if (h->cam[c].n) HIP_TRYR(hipMemcpyAsync(h->snap_cam.p, h->cam[c].p, sizeof(double) * h->cam[c].n, hipMemcpyDeviceToDevice, h->stream));
+  if (h->pts[c].n) HIP_TRYR(hipMemcpyAsync(h->snap_pts.p, h->pts[c].p, sizeof(double) * h->pts[c].n, hipMemcpyDeviceToDevice, h->stream));
+  if (h->intr[c].n) HIP_TRYR(hipMemcpyAsync(h->snap_intr.p, h->intr[c].p, sizeof(double) * h->intr[c].n, hipMemcpyDeviceToDevice, h->stream));
   h->has_snapshot = true;
   return 0;
 }
@@ -2545,9 +2536,9 @@ int theia_hip_ba_restore_parameters(theia_ba_handle h) {
   if (!h->has_snapshot) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "no snapshot taken on this handle");
   release_stage_if_idle(h);
   for (int k = 0; k < 2; ++k) {
-    if (h->cam[k].n) HIP_TRY(hipMemcpyAsync(h->cam[k].p, h->snap_cam.p, sizeof(double) * h->cam[k].n, hipMemcpyDeviceToDevice, h->stream));
-    if (h->pts[k].n) HIP_TRY(hipMemcpyAsync(h->pts[k].p, h->snap_pts.p, sizeof(double) * h->pts[k].n, hipMemcpyDeviceToDevice, h->stream));
-    if (h->intr[k].n) HIP_TRY(hipMemcpyAsync(h->intr[k].p, h->snap_intr.p, sizeof(double) * h->intr[k].n, hipMemcpyDeviceToDevice, h->stream));
+    if (h->cam[k].n) HIP_TRYR(hipMemcpyAsync(h->cam[k].p, h->snap_cam.p, sizeof(double) * h->cam[k].n, hipMemcpyDeviceToDevice, h->stream));
+    if (h->pts[k].n) HIP_TRYR(hipMemcpyAsync(h->pts[k].p, h->snap_pts.p, sizeof(double) * h->pts[k].n, hipMemcpyDeviceToDevice, h->stream));
+    if (h->intr[k].n) HIP_TRYR(hipMemcpyAsync(h->intr[k].p, h->snap_intr.p, sizeof(double) * h->intr[k].n, hipMemcpyDeviceToDevice, h->stream));
   }
   h->cur = 0;
   h->P.intr = h->intr[0].p; h->P.intr_cand = h->intr[1].p;
@@ -2652,7 +2643,7 @@ int theia_hip_ba_set_inner_global(theia_ba_handle h, const theia_ba_problem* ful
   else if ((rc = h->g_si.alloc(0))) return rc;
   if (full->obs_kind) { if ((rc = h->g_kind.upload(full->obs_kind, (size_t)nobs, st, false))) return rc; }
   else if ((rc = h->g_kind.alloc(0))) return rc;
-  HIP_TRY(hipStreamSynchronize(st));   // the sources above are local vectors and the caller's arrays
+  HIP_TRYR(hipStreamSynchronize(st));   // the sources above are local vectors and the caller's arrays
   h->inner_global = true;
   return 0;
 }
@@ -2678,11 +2669,11 @@ int theia_hip_ba_download(theia_ba_handle h, theia_ba_problem* p) {
   if (!h || !p) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "null argument");
   if (h->idh) return thip::id_handle_download(h->idh, p);
   // caller-owned (pageable) destinations: drain the stream, then blocking copies
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRYR(hipStreamSynchronize(h->stream));
   h->stage.release();
-  if (h->nc) HIP_TRY(hipMemcpy(p->cam_ext, h->cam[h->cur].p, sizeof(double) * 6 * h->nc, hipMemcpyDeviceToHost));
-  if (h->np) HIP_TRY(hipMemcpy(p->points, h->pts[h->cur].p, sizeof(double) * 4 * h->np, hipMemcpyDeviceToHost));
-  if (h->ng && h->ni) HIP_TRY(hipMemcpy(p->intrinsics, h->intr[h->cur].p, sizeof(double) * THEIA_MAX_INTRINSICS * h->ng, hipMemcpyDeviceToHost));
+  if (h->nc) HIP_TRYR(hipMemcpy(p->cam_ext, h->cam[h->cur].p, sizeof(double) * 6 * h->nc, hipMemcpyDeviceToHost));
+  if (h->np) HIP_TRYR(hipMemcpy(p->points, h->pts[h->cur].p, sizeof(double) * 4 * h->np, hipMemcpyDeviceToHost));
+  if (h->ng && h->ni) HIP_TRYR(hipMemcpy(p->intrinsics, h->intr[h->cur].p, sizeof(double) * THEIA_MAX_INTRINSICS * h->ng, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -2725,7 +2716,7 @@ int theia_hip_ba_run(theia_ba_handle h, theia_ba_summary* S) {
   // lifetime would need a synchronisation before the first iteration
   k_lm_init_state<<<1, 1, 0, h->stream>>>(dst, st);
   // |x| of the variable blocks at the start: summed on the device (points per shard, all-reduced)
-  HIP_TRY(hipMemsetAsync(h->scalB.p, 0, sizeof(double) * 16, h->stream));
+  HIP_TRYR(hipMemsetAsync(h->scalB.p, 0, sizeof(double) * 16, h->stream));
   if (h->xnorm_part.n < 2 * (size_t)kXnormBlocks && (rc = h->xnorm_part.alloc(2 * kXnormBlocks))) return rc;
   k_xnorm_partial<<<kXnormBlocks, 256, 0, h->stream>>>(h->P, h->cam[0].p, h->pts[0].p, h->intr[0].p, h->xnorm_part.p);
   k_xnorm_reduce<<<1, 1, 0, h->stream>>>(h->xnorm_part.p, kXnormBlocks, h->scalB.p);
@@ -2752,18 +2743,18 @@ int theia_hip_ba_run(theia_ba_handle h, theia_ba_summary* S) {
   // one LM iteration ("body"): linearise + Schur, solve, trial step, step control, accept
   auto enqueue_body = [&](int slot) -> int {
     int r;
-    if (slot >= 0) HIP_TRY(hipEventRecord(h->ev[slot][0], h->stream));
+    if (slot >= 0) HIP_TRYR(hipEventRecord(h->ev[slot][0], h->stream));
     if ((r = enqueue_linearize(h, slot))) return r;
-    if (slot >= 0) HIP_TRY(hipEventRecord(h->ev[slot][1], h->stream));
+    if (slot >= 0) HIP_TRYR(hipEventRecord(h->ev[slot][1], h->stream));
     const bool fuse = !h->allreduce && !inner && slot < 0 && h->ntiles_main > 0;   // tile reduction inside the control kernel
     if ((r = enqueue_solve_and_backsub(h, slot, fuse))) return r;
     if (inner) {
       // DoInnerIterationsIfNeeded: one sweep of block coordinate descent on a copy of the candidate, its cost and its
       // distance from x; every kernel returns at once when the gate is closed (step invalid, inner iterations off, done)
       k_inner_gate<<<1, 1, 0, h->stream>>>(dst, h->rb.scal, h->scalB.p, h->in_gate.p);
-      HIP_TRY(hipMemcpyAsync(h->in_cam.p, h->cam[nxt].p, sizeof(double) * 6 * h->nc, hipMemcpyDeviceToDevice, h->stream));
-      HIP_TRY(hipMemcpyAsync(h->in_pts.p, h->pts[nxt].p, sizeof(double) * 4 * h->np, hipMemcpyDeviceToDevice, h->stream));
-      HIP_TRY(hipMemcpyAsync(h->in_intr.p, (h->ni ? h->intr[nxt].p : h->intr[0].p), sizeof(double) * THEIA_MAX_INTRINSICS * h->ng, hipMemcpyDeviceToDevice, h->stream));
+      HIP_TRYR(hipMemcpyAsync(h->in_cam.p, h->cam[nxt].p, sizeof(double) * 6 * h->nc, hipMemcpyDeviceToDevice, h->stream));
+      HIP_TRYR(hipMemcpyAsync(h->in_pts.p, h->pts[nxt].p, sizeof(double) * 4 * h->np, hipMemcpyDeviceToDevice, h->stream));
+      HIP_TRYR(hipMemcpyAsync(h->in_intr.p, (h->ni ? h->intr[nxt].p : h->intr[0].p), sizeof(double) * THEIA_MAX_INTRINSICS * h->ng, hipMemcpyDeviceToDevice, h->stream));
       InnerArgs IA;
       IA.P = h->P;
       IA.cam_obs_off = h->in_cam_off.p; IA.cam_obs_idx = h->in_cam_idx.p; IA.grp_obs_off = h->in_grp_off.p; IA.grp_obs_idx = h->in_grp_idx.p;
@@ -2772,7 +2763,7 @@ int theia_hip_ba_run(theia_ba_handle h, theia_ba_summary* S) {
       IA.grp_part = h->in_grp_part.p; IA.grp_bar = h->in_grp_bar.p; IA.grp_wgs = h->in_grp_part.p ? inner_group_wgs(h->ng) : 1;
       if (h->allreduce && h->inner_global) {
         // the full candidate point set: every shard's points at their global indices, summed over the ranks
-        HIP_TRY(hipMemsetAsync(h->g_pts.p, 0, sizeof(double) * 4 * (size_t)h->g_np, h->stream));
+        HIP_TRYR(hipMemsetAsync(h->g_pts.p, 0, sizeof(double) * 4 * (size_t)h->g_np, h->stream));
         launch_inner_scatter_points(h->np, h->in_pts.p, h->g_pidx.p, h->g_pts.p, h->stream);
         if ((r = do_allreduce(h, h->g_pts.p, (size_t)4 * h->g_np, THEIA_REDUCE_SUM))) return r;
         InnerArgs IG = IA;      // cameras and groups over the full observation set, identically on every rank
@@ -2809,7 +2800,7 @@ int theia_hip_ba_run(theia_ba_handle h, theia_ba_summary* S) {
       launch_inner_norms_cost(IA, h->cam[0].p, h->pts[0].p, h->intr[0].p, h->in_scal.p, h->in_part.p, h->stream);   // step norms + cost, two launches
       }
     }
-    if (slot >= 0) HIP_TRY(hipEventRecord(h->ev[slot][3], h->stream));
+    if (slot >= 0) HIP_TRYR(hipEventRecord(h->ev[slot][3], h->stream));
     if (fuse && h->ntiles_main > 4 * kReduceBlocks) {
       launch_reduce_tiles_stage1(h->ntiles_main, h->tile_part.p, 5, h->fmaxflag.p + 8, h->red_part.p, h->stream);
       k_reduce_control<<<1, 1024, 0, h->stream>>>(kReduceBlocks, h->red_part.p, h->f2s.p + 8, h->fmaxflag.p + 8, dst, h->rb.scal, h->scalB.p, dctl);
@@ -2861,10 +2852,10 @@ int theia_hip_ba_run(theia_ba_handle h, theia_ba_summary* S) {
       if (h->allreduce && bodies_enqueued > 0) {
         if (h->stop_flag.n < 8 && (rc = h->stop_flag.alloc(8))) return rc;
         h->h_scal[32] = expired;
-        HIP_TRY(hipMemcpyAsync(h->stop_flag.p, h->h_scal + 32, sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIP_TRYR(hipMemcpyAsync(h->stop_flag.p, h->h_scal + 32, sizeof(double), hipMemcpyHostToDevice, h->stream));
         if ((rc = do_allreduce(h, h->stop_flag.p, 1, THEIA_REDUCE_MAX))) return rc;
-        HIP_TRY(hipMemcpyAsync(h->h_scal + 33, h->stop_flag.p, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
+        HIP_TRYR(hipMemcpyAsync(h->h_scal + 33, h->stop_flag.p, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRYR(hipStreamSynchronize(h->stream));
         expired = h->h_scal[33];
       }
       if (expired != 0.0) { st.term = THEIA_TERM_NO_CONVERGENCE; break; }
@@ -2872,15 +2863,15 @@ int theia_hip_ba_run(theia_ba_handle h, theia_ba_summary* S) {
     const int nb = (int)std::min<long long>(chunk, bodies_max - bodies_enqueued);
     if (nb <= 0) break;
     for (int b = 0; b < nb; ++b) {
-      if (use_graph) HIP_TRY(hipGraphLaunch(h->graph_exec, h->stream));
+      if (use_graph) HIP_TRYR(hipGraphLaunch(h->graph_exec, h->stream));
       else if ((rc = enqueue_body(timing ? b : -1))) return rc;
     }
     bodies_enqueued += nb;
-    HIP_TRY(hipGetLastError());   // a rejected launch configuration would otherwise go unnoticed
+    HIP_TRYR(hipGetLastError());   // a rejected launch configuration would otherwise go unnoticed
     // read-back through the handle's pinned block: an asynchronous copy needs a peer that outlives the call (HIP may
     // pin pageable pages and run the DMA later; stack temporaries were the round-1 corruption)
-    HIP_TRY(hipMemcpyAsync(h->h_state, dst, sizeof(st), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRYR(hipMemcpyAsync(h->h_state, dst, sizeof(st), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRYR(hipStreamSynchronize(h->stream));
     std::memcpy(&st, h->h_state, sizeof(st));
     const int ran = (int)std::min<long long>(nb, std::max<long long>(0, (long long)st.bodies - (bodies_enqueued - nb)));
     for (int b = 0; timing && b < ran; ++b) {
@@ -2897,11 +2888,11 @@ int theia_hip_ba_run(theia_ba_handle h, theia_ba_summary* S) {
     const int k = std::min(st.trace_size, S->trace_capacity);
     S->trace_size = k;
     if (k) {
-      HIP_TRY(hipMemcpy(S->trace_cost, h->tr_cost.p, sizeof(double) * k, hipMemcpyDeviceToHost));
-      if (S->trace_gradient_max_norm) HIP_TRY(hipMemcpy(S->trace_gradient_max_norm, h->tr_g.p, sizeof(double) * k, hipMemcpyDeviceToHost));
-      if (S->trace_step_norm) HIP_TRY(hipMemcpy(S->trace_step_norm, h->tr_step.p, sizeof(double) * k, hipMemcpyDeviceToHost));
-      if (S->trace_radius) HIP_TRY(hipMemcpy(S->trace_radius, h->tr_radius.p, sizeof(double) * k, hipMemcpyDeviceToHost));
-      if (S->trace_accepted) HIP_TRY(hipMemcpy(S->trace_accepted, h->tr_acc.p, sizeof(int) * k, hipMemcpyDeviceToHost));
+      HIP_TRYR(hipMemcpy(S->trace_cost, h->tr_cost.p, sizeof(double) * k, hipMemcpyDeviceToHost));
+      if (S->trace_gradient_max_norm) HIP_TRYR(hipMemcpy(S->trace_gradient_max_norm, h->tr_g.p, sizeof(double) * k, hipMemcpyDeviceToHost));
+      if (S->trace_step_norm) HIP_TRYR(hipMemcpy(S->trace_step_norm, h->tr_step.p, sizeof(double) * k, hipMemcpyDeviceToHost));
+      if (S->trace_radius) HIP_TRYR(hipMemcpy(S->trace_radius, h->tr_radius.p, sizeof(double) * k, hipMemcpyDeviceToHost));
+      if (S->trace_accepted) HIP_TRYR(hipMemcpy(S->trace_accepted, h->tr_acc.p, sizeof(int) * k, hipMemcpyDeviceToHost));
     }
   }
   if (O.verbose)
@@ -2953,7 +2944,7 @@ int theia_hip_ba_evaluate_ex(theia_ba_handle h, double* cost, double* residuals,
   if (!h) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "null handle");
   release_stage_if_idle(h);
   const int pd = h->pd;
-  DevBuf<double> dr, djc, djp, dji; DevBuf<uint8_t> dv;
+  PoolBuf<double> dr, djc, djp, dji; PoolBuf<uint8_t> dv;
   int rc;
   const size_t nm = (size_t)h->nobs_main;
   if ((rc = dr.alloc(2 * nm)) || (rc = djc.alloc(12 * nm)) || (rc = djp.alloc(2 * pd * nm)) || (rc = dv.alloc(nm))) return rc;
@@ -2963,21 +2954,21 @@ int theia_hip_ba_evaluate_ex(theia_ba_handle h, double* cost, double* residuals,
   Q.scale_c = h->ones_c.p; Q.scale_p = h->ones_p.p;
   Q.ntiles = h->ntiles_eval;
   Q.scale_i = h->ones_i.p; Q.intr = h->intr[h->cur].p;
-  HIP_TRY(hipMemsetAsync(h->scalB.p, 0, sizeof(double) * 16, h->stream));
+  HIP_TRYR(hipMemsetAsync(h->scalB.p, 0, sizeof(double) * 16, h->stream));
   launch_evaluate(Q, h->cam[h->cur].p, h->pts[h->cur].p, dr.p, djc.p, djp.p, dv.p, h->tile_part.p, h->stream, want_ji ? dji.p : nullptr);
   if (h->ntiles_eval) launch_reduce_tiles(h->ntiles_eval, h->tile_part.p, 2, h->f2s.p + 16, h->fmaxflag.p + 16, h->scalB.p, h->stream);
   launch_cam_priors(Q, PRIOR_COST, h->cam[h->cur].p, nullptr, nullptr, nullptr, nullptr, h->scalB.p + SB_COST, nullptr, h->stream);
   std::vector<double> hr(2 * nm), hjc(12 * nm), hjp(2 * pd * nm); std::vector<uint8_t> hv(nm);
   if (nm) {
-    HIP_TRY(hipMemcpyAsync(hr.data(), dr.p, sizeof(double) * hr.size(), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(hjc.data(), djc.p, sizeof(double) * hjc.size(), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(hjp.data(), djp.p, sizeof(double) * hjp.size(), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(hv.data(), dv.p, hv.size(), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRYR(hipMemcpyAsync(hr.data(), dr.p, sizeof(double) * hr.size(), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRYR(hipMemcpyAsync(hjc.data(), djc.p, sizeof(double) * hjc.size(), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRYR(hipMemcpyAsync(hjp.data(), djp.p, sizeof(double) * hjp.size(), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRYR(hipMemcpyAsync(hv.data(), dv.p, hv.size(), hipMemcpyDeviceToHost, h->stream));
   }
   std::vector<double> hji;
-  if (want_ji && nm) { hji.resize(20 * nm); HIP_TRY(hipMemcpyAsync(hji.data(), dji.p, sizeof(double) * hji.size(), hipMemcpyDeviceToHost, h->stream)); }
-  HIP_TRY(hipMemcpyAsync(h->h_scal + 16, h->scalB.p, sizeof(double) * 16, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (want_ji && nm) { hji.resize(20 * nm); HIP_TRYR(hipMemcpyAsync(hji.data(), dji.p, sizeof(double) * hji.size(), hipMemcpyDeviceToHost, h->stream)); }
+  HIP_TRYR(hipMemcpyAsync(h->h_scal + 16, h->scalB.p, sizeof(double) * 16, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRYR(hipStreamSynchronize(h->stream));
   if (cost) *cost = h->h_scal[16 + SB_COST] + h->fixed_cost;
   if (jac_intr) std::fill(jac_intr, jac_intr + 20 * h->nobs, 0.0);
   if (want_ji) for (size_t s2 = 0; s2 < nm; ++s2) std::copy(&hji[20 * s2], &hji[20 * s2] + 20, jac_intr + 20 * h->perm[s2]);
@@ -3027,17 +3018,17 @@ int theia_hip_ba_covariance(theia_ba_handle h, double* point_cov, double* cam_co
   LmState st;
   std::memset(&st, 0, sizeof(st));
   st.radius = 1e300;   // no LM damping: D = clamp(diag) / radius vanishes against the diagonal
-  HIP_TRY(hipMemcpyAsync(h->lm_state.p, &st, sizeof(st), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRYR(hipMemcpyAsync(h->lm_state.p, &st, sizeof(st), hipMemcpyHostToDevice, h->stream));
+  HIP_TRYR(hipStreamSynchronize(h->stream));
   const double* radius = &reinterpret_cast<const LmState*>(h->lm_state.p)->radius;
-  HIP_TRY(hipMemsetAsync(h->reduce.p, 0, sizeof(double) * h->reduce.n, h->stream));
-  if (h->Vinv.n) HIP_TRY(hipMemsetAsync(h->Vinv.p, 0, sizeof(double) * h->Vinv.n, h->stream));
+  HIP_TRYR(hipMemsetAsync(h->reduce.p, 0, sizeof(double) * h->reduce.n, h->stream));
+  if (h->Vinv.n) HIP_TRYR(hipMemsetAsync(h->Vinv.p, 0, sizeof(double) * h->Vinv.n, h->stream));
   launch_linearize(Q, h->cam[h->cur].p, h->pts[h->cur].p, radius, h->rb, h->Vinv.p, h->gp.p, h->tile_part.p, h->stream);
   launch_long_linearize(Q, h->cam[h->cur].p, h->pts[h->cur].p, radius, h->rb, h->Vinv.p, h->gp.p, h->long_scratch.p, h->stream);
   if (point_cov) {
     std::vector<double> vi((size_t)NT * h->np);
-    if (h->np) HIP_TRY(hipMemcpyAsync(vi.data(), h->Vinv.p, sizeof(double) * vi.size(), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->np) HIP_TRYR(hipMemcpyAsync(vi.data(), h->Vinv.p, sizeof(double) * vi.size(), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRYR(hipStreamSynchronize(h->stream));
     for (int q = 0; q < h->np; ++q)
       for (int a = 0; a < pd; ++a)
         for (int b = 0; b < pd; ++b)
@@ -3046,8 +3037,8 @@ int theia_hip_ba_covariance(theia_ba_handle h, double* point_cov, double* cam_co
   if (cam_cov) {
     const int n = h->n;
     std::vector<double> S((size_t)n * n);
-    if (n) HIP_TRY(hipMemcpyAsync(S.data(), h->rb.S, sizeof(double) * S.size(), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (n) HIP_TRYR(hipMemcpyAsync(S.data(), h->rb.S, sizeof(double) * S.size(), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRYR(hipStreamSynchronize(h->stream));
     std::fill(cam_cov, cam_cov + 36 * (size_t)h->nc, 0.0);
     if (h->ni) {
       // Optimised intrinsics: with every point constant J'J is an ARROW per intrinsics group -- [G_g  B^T; B  D], D block diagonal
@@ -3060,7 +3051,7 @@ int theia_hip_ba_covariance(theia_ba_handle h, double* point_cov, double* cam_co
       for (int i = 0; i < ni; ++i)
         for (int j = 0; j < 10; ++j) { const int gs = 10 * (i / 10), r = std::max(i, gs + j), q = std::min(i, gs + j); G[(size_t)i * 10 + j] = S[(size_t)r * n + q]; }
       std::vector<int> cg((size_t)std::max(1, h->nc));
-      if (h->nc) HIP_TRY(hipMemcpy(cg.data(), h->cam_group.p, sizeof(int) * h->nc, hipMemcpyDeviceToHost));
+      if (h->nc) HIP_TRYR(hipMemcpy(cg.data(), h->cam_group.p, sizeof(int) * h->nc, hipMemcpyDeviceToHost));
       auto chol_inv = [](const double* A, int m, double* Ainv) -> bool {   // inverse of an SPD m x m matrix (m <= 10), row-major
         double L[100], Li[100];
         for (int i = 0; i < m; ++i)
@@ -3185,18 +3176,18 @@ int theia_hip_dense_spd_solve(int32_t n, const double* A, const double* b, doubl
   if (n == 0) return 0;
   int rc = thip::ensure_device();
   if (rc) return rc;
-  DevBuf<double> dA, dw, dflag;
+  PoolBuf<double> dA, dw, dflag;
   if ((rc = dA.alloc((size_t)n * n + n)) || (rc = dw.alloc(dense_cholesky_workspace(n))) || (rc = dflag.alloc(1))) return rc;
-  HIP_TRY(hipMemcpy(dA.p, A, sizeof(double) * (size_t)n * n, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dA.p + (size_t)n * n, b, sizeof(double) * n, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemset(dflag.p, 0, sizeof(double)));
+  HIP_TRYR(hipMemcpy(dA.p, A, sizeof(double) * (size_t)n * n, hipMemcpyHostToDevice));
+  HIP_TRYR(hipMemcpy(dA.p + (size_t)n * n, b, sizeof(double) * n, hipMemcpyHostToDevice));
+  HIP_TRYR(hipMemset(dflag.p, 0, sizeof(double)));
   dense_cholesky_solve(n, dA.p, n, dA.p + (size_t)n * n, dw.p, dflag.p, nullptr);
   double flag = 0.0;
   if (getenv("THEIA_HIP_DEBUG_FACTOR")) {  // development aid: hand back the factor in place of A
-    HIP_TRY(hipMemcpy(const_cast<double*>(A), dA.p, sizeof(double) * (size_t)n * n, hipMemcpyDeviceToHost));
+    HIP_TRYR(hipMemcpy(const_cast<double*>(A), dA.p, sizeof(double) * (size_t)n * n, hipMemcpyDeviceToHost));
   }
-  HIP_TRY(hipMemcpy(x, dA.p + (size_t)n * n, sizeof(double) * n, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(&flag, dflag.p, sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRYR(hipMemcpy(x, dA.p + (size_t)n * n, sizeof(double) * n, hipMemcpyDeviceToHost));
+  HIP_TRYR(hipMemcpy(&flag, dflag.p, sizeof(double), hipMemcpyDeviceToHost));
   if (flag != 0.0) return set_error(THEIA_HIP_ERR_INTERNAL, "matrix is not positive definite");
   return 0;
 }
@@ -3210,18 +3201,18 @@ int theia_hip_ba_reduced_system(theia_ba_handle h, double radius, int32_t* n_out
     LmState st;
     std::memset(&st, 0, sizeof(st));
     st.radius = radius;
-    HIP_TRY(hipMemcpyAsync(h->lm_state.p, &st, sizeof(st), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));   // `st` is a stack object
+    HIP_TRYR(hipMemcpyAsync(h->lm_state.p, &st, sizeof(st), hipMemcpyHostToDevice, h->stream));
+    HIP_TRYR(hipStreamSynchronize(h->stream));   // `st` is a stack object
   }
   rc = enqueue_linearize(h);
   if (rc) return rc;
   const int n = h->n;
   *n_out = n;
   if ((int64_t)n * n > capacity) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "capacity too small for %d x %d", n, n);
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRYR(hipStreamSynchronize(h->stream));
   if (n) {
-    HIP_TRY(hipMemcpy(S, h->rb.S, sizeof(double) * (size_t)n * n, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(rhs, h->rb.rhs, sizeof(double) * n, hipMemcpyDeviceToHost));
+    HIP_TRYR(hipMemcpy(S, h->rb.S, sizeof(double) * (size_t)n * n, hipMemcpyDeviceToHost));
+    HIP_TRYR(hipMemcpy(rhs, h->rb.rhs, sizeof(double) * n, hipMemcpyDeviceToHost));
   }
   for (int i = 0; i < n; ++i) for (int j = i + 1; j < n; ++j) S[(size_t)i * n + j] = S[(size_t)j * n + i];
   return 0;

@@ -10,17 +10,11 @@
 // every lane's distance summed over the dimensions IN SEQUENCE in float (no FMA: the file is built with -ffp-contract=off) --
 // the order the oracle uses; Eigen's squaredNorm() sums in packets, unpinned (stated in DESIGN.md) -- then the lanes' two best
 // are merged by a butterfly under the (distance, position) order of the reference's pair comparison.
-#include "theia_hip_internal.h"
+#include "device_util.h"
 
 #include <algorithm>
 #include <cfloat>
 #include <vector>
-
-#define HIP_TRY(expr)                                                                             \
-  do {                                                                                            \
-    hipError_t e_ = (expr);                                                                       \
-    if (e_ != hipSuccess) return thip::set_error(THEIA_HIP_ERR_INTERNAL, "%s: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
 
 namespace thip {
 namespace {
@@ -72,19 +66,6 @@ __global__ __launch_bounds__(256) void k_guided_knn(int nq, const int* __restric
   }
 }
 
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  int up(const void* src, size_t n) {
-    if (hipMalloc((void**)&p, std::max<size_t>(1, n) * sizeof(T)) != hipSuccess)
-      return set_error(THEIA_HIP_ERR_OUT_OF_MEMORY, "hipMalloc(%zu) failed", n * sizeof(T));
-    if (n && src && hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess)
-      return set_error(THEIA_HIP_ERR_INTERNAL, "hipMemcpy H2D failed");
-    return 0;
-  }
-};
-
 }  // namespace
 }  // namespace thip
 
@@ -111,7 +92,7 @@ extern "C" int theia_hip_guided_knn(int32_t num_groups, const int64_t* q_off, co
   DevBuf<int> d_qg, d_qi, d_ci, d_ni; DevBuf<int64_t> d_co; DevBuf<float> d_d1, d_d2, d_nd;
   if ((rc = d_qg.up(qg.data(), qg.size())) || (rc = d_qi.up(q_idx, (size_t)nq)) || (rc = d_ci.up(c_idx, (size_t)ncand)) ||
       (rc = d_co.up(c_off, (size_t)num_groups + 1)) || (rc = d_d1.up(desc1, (size_t)n1 * dim)) || (rc = d_d2.up(desc2, (size_t)n2 * dim)) ||
-      (rc = d_nd.up(nullptr, 2 * (size_t)nq)) || (rc = d_ni.up(nullptr, 2 * (size_t)nq)))
+      (rc = d_nd.alloc(2 * (size_t)nq)) || (rc = d_ni.alloc(2 * (size_t)nq)))
     return rc;
   k_guided_knn<<<(unsigned)((nq + 3) / 4), 256, 0, nullptr>>>((int)nq, d_qg.p, d_qi.p, d_co.p, d_ci.p, dim, d_d1.p, d_d2.p, d_nd.p, d_ni.p);
   HIP_TRY(hipGetLastError());

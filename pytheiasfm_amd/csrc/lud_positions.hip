@@ -25,19 +25,13 @@
 #include "ransac_device.h"
 #include "ba_kernels.h"
 #include "wave_reduce.h"
-#include "theia_hip_internal.h"
+#include "device_util.h"
+#include "view_graph_plan.h"
 
 #include <algorithm>
 #include <chrono>
 #include <cmath>
-#include <numeric>
 #include <vector>
-
-#define HIP_TRY(expr)                                                                             \
-  do {                                                                                            \
-    hipError_t e_ = (expr);                                                                       \
-    if (e_ != hipSuccess) return thip::set_error(THEIA_HIP_ERR_INTERNAL, "%s: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
 
 namespace thip {
 namespace {
@@ -51,20 +45,6 @@ struct LudState {
   int done, iterations, pad0, pad1;
   double r_norm, s_norm, primal_eps, dual_eps;
 };
-
-// Sum of v over the workgroup in a fixed tree order; the result is valid in thread 0.
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  const int tid = threadIdx.x;
-  red[tid] = v;
-  __syncthreads();
-  for (int s = kThreads / 2; s > 0; s >>= 1) {
-    if (tid < s) red[tid] += red[tid + s];
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
-}
 
 // GetRotatedTranslation (:63-70): d_e = R_i' position_2 (ceres angle-axis -> matrix), and D_e = |d_e|^2 + 1.
 __global__ __launch_bounds__(kThreads) void k_setup(int E, const int2* __restrict__ edges, const double* __restrict__ aa,
@@ -90,7 +70,7 @@ __device__ __forceinline__ double m_entry(const double* d, double De, int r, int
 // The lower triangle of S into the zeroed array (row-major, leading dimension lda):
 //   thread t < m       : free view t -- its 3 x 3 diagonal block, sum of M_e over its incident edges
 //   thread t = m + p   : pair p = (a > b) -- block (a, b) = -sum of M_e over the pair's edges
-// inc[k] = 2 * edge + (1 if the view is the edge's second view).
+// inc, pair_edge, pair_rc: view_graph_plan.h.
 __global__ __launch_bounds__(kThreads) void k_assemble(int m, int P, int lda, const int* __restrict__ inc_off,
                                                        const int* __restrict__ inc, const int* __restrict__ pair_off,
                                                        const int* __restrict__ pair_edge, const int2* __restrict__ pair_rc,
@@ -213,8 +193,8 @@ __global__ __launch_bounds__(kThreads) void k_edge(int E, const int2* __restrict
     const double tc = rho * (un[3] - ((de[0] * un[0] + de[1] * un[1]) + de[2] * un[2]));
     ss = sc * sc; tt = tc * tc;
   }
-  const double s0 = block_sum(rr, red), s1 = block_sum(aa, red), s2 = block_sum(zz, red);
-  const double s3 = block_sum(ss, red), s4 = block_sum(tt, red);
+  const double s0 = block_sum<kThreads>(rr, red), s1 = block_sum<kThreads>(aa, red), s2 = block_sum<kThreads>(zz, red);
+  const double s3 = block_sum<kThreads>(ss, red), s4 = block_sum<kThreads>(tt, red);
   if (threadIdx.x == 0) {
     double* p = part + 5 * (size_t)blockIdx.x;
     p[0] = s0; p[1] = s1; p[2] = s2; p[3] = s3; p[4] = s4;
@@ -269,12 +249,12 @@ __global__ __launch_bounds__(kThreads) void k_test(const double* __restrict__ pa
   for (int c = 0; c < 5; ++c) {
     double s = 0.0;
     for (int b = threadIdx.x; b < nbE; b += kThreads) s += part_e[5 * (size_t)b + c];
-    sum[c] = block_sum(s, red);
+    sum[c] = block_sum<kThreads>(s, red);
   }
   for (int c = 0; c < 2; ++c) {
     double s = 0.0;
     for (int b = threadIdx.x; b < nbV; b += kThreads) s += part_v[2 * (size_t)b + c];
-    sum[5 + c] = block_sum(s, red);
+    sum[5 + c] = block_sum<kThreads>(s, red);
   }
   if (threadIdx.x == 0) {
     const double r_norm = sqrt(sum[0]);
@@ -287,41 +267,6 @@ __global__ __launch_bounds__(kThreads) void k_test(const double* __restrict__ pa
     if (r_norm < primal_eps && s_norm < dual_eps) st->done = 1;
   }
 }
-
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  int alloc(size_t n) {
-    if (hipMalloc((void**)&p, std::max<size_t>(1, n) * sizeof(T)) != hipSuccess) {
-      (void)hipGetLastError();
-      p = nullptr;
-      return set_error(THEIA_HIP_ERR_OUT_OF_MEMORY, "hipMalloc(%zu) failed", n * sizeof(T));
-    }
-    return 0;
-  }
-  int up(const void* src, size_t n) {
-    int rc = alloc(n);
-    if (rc) return rc;
-    if (n && hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess)
-      return set_error(THEIA_HIP_ERR_INTERNAL, "hipMemcpy H2D failed");
-    return 0;
-  }
-};
-
-int find_root(std::vector<int>& parent, int v) {
-  while (parent[v] != v) { parent[v] = parent[parent[v]]; v = parent[v]; }
-  return v;
-}
-
-double ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
-int grid_of(int n) { return std::max(1, (n + kThreads - 1) / kThreads); }
 
 }  // namespace
 }  // namespace thip
@@ -340,74 +285,16 @@ extern "C" int theia_hip_lud_positions(int32_t num_views, const double* orientat
   if (o->max_num_iterations <= 0 || !(o->rho > 0.0) || !std::isfinite(o->rho) || !std::isfinite(o->alpha) ||
       !std::isfinite(o->absolute_tolerance) || !std::isfinite(o->relative_tolerance))
     return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "bad options");
-  for (int e = 0; e < E; ++e)
-    if (edges[2 * e] < 0 || edges[2 * e] >= n || edges[2 * e + 1] < 0 || edges[2 * e + 1] >= n)
-      return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "edge %d names a view out of range", e);
-
-  // held views (none flagged: view 0), free-view numbering in view order
-  std::vector<uint8_t> fix(n, 0);
-  bool any = false;
-  for (int v = 0; v < n && fixed; ++v) { fix[v] = fixed[v] ? 1 : 0; any = any || fix[v]; }
-  if (!any) fix[0] = 1;
   // every connected component needs a held view, else S (and the reference's A'A) is singular
-  std::vector<int> parent(n);
-  std::iota(parent.begin(), parent.end(), 0);
-  for (int e = 0; e < E; ++e) {
-    const int a = find_root(parent, edges[2 * e]), b = find_root(parent, edges[2 * e + 1]);
-    if (a != b) parent[std::max(a, b)] = std::min(a, b);
-  }
-  std::vector<uint8_t> anchored(n, 0);
-  for (int v = 0; v < n; ++v) if (fix[v]) anchored[find_root(parent, v)] = 1;
-  for (int v = 0; v < n; ++v)
-    if (!anchored[find_root(parent, v)])
-      return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "view %d lies in a connected component without a held view", v);
-  std::vector<int> idx(n, -1), free_view;
-  for (int v = 0; v < n; ++v) if (!fix[v]) { idx[v] = (int)free_view.size(); free_view.push_back(v); }
-  const int m = (int)free_view.size();
+  ViewGraphPlan g;
+  int rc = build_view_graph_plan(n, fixed, E, edges, "held", &g);
+  if (rc) return rc;
+  const int m = g.m, P = g.P;
   const int n3 = 3 * m;
 
-  // CSR of the incident edges per free view (edge order) and of the edges per unordered free-view pair (edge order);
-  // a self-loop's position terms cancel and it is left out of both
-  std::vector<int> inc_off(m + 1, 0), inc;
-  std::vector<std::pair<int64_t, int>> pe;   // (pair key, edge)
-  for (int e = 0; e < E; ++e) {
-    const int i = edges[2 * e], j = edges[2 * e + 1];
-    if (i == j) continue;
-    if (idx[i] >= 0) ++inc_off[idx[i] + 1];
-    if (idx[j] >= 0) ++inc_off[idx[j] + 1];
-    if (idx[i] >= 0 && idx[j] >= 0) {
-      const int a = std::max(idx[i], idx[j]), b = std::min(idx[i], idx[j]);
-      pe.emplace_back((int64_t)a * m + b, e);
-    }
-  }
-  for (int v = 0; v < m; ++v) inc_off[v + 1] += inc_off[v];
-  inc.resize(inc_off[m]);
-  {
-    std::vector<int> fill(inc_off.begin(), inc_off.end() - 1);
-    for (int e = 0; e < E; ++e) {
-      const int i = edges[2 * e], j = edges[2 * e + 1];
-      if (i == j) continue;
-      if (idx[i] >= 0) inc[fill[idx[i]]++] = 2 * e;
-      if (idx[j] >= 0) inc[fill[idx[j]]++] = 2 * e + 1;
-    }
-  }
-  std::stable_sort(pe.begin(), pe.end());
-  std::vector<int> pair_off(1, 0), pair_edge(pe.size());
-  std::vector<int2> pair_rc;
-  for (size_t k = 0; k < pe.size(); ++k) {
-    if (k == 0 || pe[k].first != pe[k - 1].first) {
-      if (k) pair_off.push_back((int)k);
-      pair_rc.push_back(make_int2((int)(pe[k].first / m), (int)(pe[k].first % m)));
-    }
-    pair_edge[k] = pe[k].second;
-  }
-  pair_off.push_back((int)pe.size());
-  const int P = (int)pair_rc.size();
-
-  int rc = thip::ensure_device();
-  if (rc) return rc;
+  if ((rc = thip::ensure_device())) return rc;
   const int lda = n3 + 1;   // row n3: the factorisation's right-hand-side row (zero, unused)
-  const int nbE = grid_of(E), nbV = std::max(1, (m + kViewsPerBlock - 1) / kViewsPerBlock);
+  const int nbE = grid_of(E, kThreads), nbV = std::max(1, (m + kViewsPerBlock - 1) / kViewsPerBlock);
   DevBuf<double> d_aa, d_rel, d_d, d_D, d_S, d_work, d_flag, d_z, d_u, d_dz, d_g, d_T, d_x, d_pe, d_pv;
   DevBuf<int2> d_edges, d_pair_rc;
   DevBuf<int> d_idx, d_inc_off, d_inc, d_pair_off, d_pair_edge;
@@ -415,9 +302,9 @@ extern "C" int theia_hip_lud_positions(int32_t num_views, const double* orientat
   const size_t dense = (size_t)(n3 + 1) * lda;
   if ((rc = d_S.alloc(dense)) || (rc = d_work.alloc(dense_cholesky_workspace(n3))) || (rc = d_flag.alloc(1)) ||
       (rc = d_aa.up(orientations, 3 * (size_t)n)) || (rc = d_rel.up(relative_translations, 3 * (size_t)E)) ||
-      (rc = d_edges.up(edges, E)) || (rc = d_idx.up(idx.data(), n)) || (rc = d_inc_off.up(inc_off.data(), m + 1)) ||
-      (rc = d_inc.up(inc.data(), inc.size())) || (rc = d_pair_off.up(pair_off.data(), pair_off.size())) ||
-      (rc = d_pair_edge.up(pair_edge.data(), pair_edge.size())) || (rc = d_pair_rc.up(pair_rc.data(), pair_rc.size())) ||
+      (rc = d_edges.up(edges, E)) || (rc = d_idx.up(g.idx.data(), n)) || (rc = d_inc_off.up(g.inc_off.data(), m + 1)) ||
+      (rc = d_inc.up(g.inc.data(), g.inc.size())) || (rc = d_pair_off.up(g.pair_off.data(), g.pair_off.size())) ||
+      (rc = d_pair_edge.up(g.pair_edge.data(), g.pair_edge.size())) || (rc = d_pair_rc.up(g.pair_rc.data(), g.pair_rc.size())) ||
       (rc = d_d.alloc(3 * (size_t)E)) || (rc = d_D.alloc(E)) || (rc = d_z.alloc(4 * (size_t)E)) ||
       (rc = d_u.alloc(4 * (size_t)E)) || (rc = d_dz.alloc(4 * (size_t)E)) || (rc = d_g.alloc(n3)) ||
       (rc = d_T.alloc(n3)) || (rc = d_x.alloc(n3)) || (rc = d_pe.alloc(5 * (size_t)nbE)) ||
@@ -434,8 +321,8 @@ extern "C" int theia_hip_lud_positions(int32_t num_views, const double* orientat
   HIP_TRY(hipMemsetAsync(d_u.p, 0, sizeof(double) * 4 * (size_t)E, st));
   HIP_TRY(hipMemsetAsync(d_st.p, 0, sizeof(LudState), st));
   k_setup<<<nbE, kThreads, 0, st>>>(E, d_edges.p, d_aa.p, d_rel.p, d_d.p, d_D.p);
-  k_assemble<<<grid_of(m + P), kThreads, 0, st>>>(m, P, lda, d_inc_off.p, d_inc.p, d_pair_off.p, d_pair_edge.p,
-                                                 d_pair_rc.p, d_d.p, d_D.p, d_S.p);
+  k_assemble<<<grid_of(m + P, kThreads), kThreads, 0, st>>>(m, P, lda, d_inc_off.p, d_inc.p, d_pair_off.p, d_pair_edge.p,
+                                                           d_pair_rc.p, d_d.p, d_D.p, d_S.p);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(st));
   sm.setup_ms = ms_since(t_start);
@@ -483,7 +370,7 @@ extern "C" int theia_hip_lud_positions(int32_t num_views, const double* orientat
   sm.converged = hs.done;
   sm.r_norm = hs.r_norm; sm.s_norm = hs.s_norm; sm.primal_eps = hs.primal_eps; sm.dual_eps = hs.dual_eps;
   for (int v = 0; v < n; ++v)
-    for (int c = 0; c < 3; ++c) positions_out[3 * (size_t)v + c] = idx[v] >= 0 ? x[3 * (size_t)idx[v] + c] : 0.0;
+    for (int c = 0; c < 3; ++c) positions_out[3 * (size_t)v + c] = g.idx[v] >= 0 ? x[3 * (size_t)g.idx[v] + c] : 0.0;
   *summary = sm;
   return 0;
 }

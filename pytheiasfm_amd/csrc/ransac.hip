@@ -38,7 +38,7 @@
 #include <functional>
 #include <thread>
 
-#include "theia_hip_internal.h"
+#include "device_util.h"
 #include "host_team.h"
 #include "pools.h"
 
@@ -1494,14 +1494,6 @@ struct StreamInit {
   const uint8_t* p4pfr_first;
   const dls::GlibcRand* dls_start;   // NULL unless the estimator is DLS / gDLS
 };
-
-#define HIP_TRYR(expr)                                                                               \
-  do {                                                                                               \
-    hipError_t e_ = (expr);                                                                          \
-    if (e_ != hipSuccess)                                                                            \
-      return set_error(e_ == hipErrorOutOfMemory ? THEIA_HIP_ERR_OUT_OF_MEMORY : THEIA_HIP_ERR_NO_DEVICE, \
-                       "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);   \
-  } while (0)
 
 }  // namespace
 }  // namespace thip

@@ -19,19 +19,13 @@
 #include "ransac_device.h"
 #include "wave_reduce.h"
 #include "eig_team.h"
-#include "theia_hip_internal.h"
+#include "device_util.h"
 
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
 #include <cstdlib>
 #include <vector>
-
-#define HIP_TRY(expr)                                                                             \
-  do {                                                                                            \
-    hipError_t e_ = (expr);                                                                       \
-    if (e_ != hipSuccess) return thip::set_error(THEIA_HIP_ERR_INTERNAL, "%s: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
 
 namespace thip {
 namespace {
@@ -135,24 +129,6 @@ void host_angle_axis_to_rot(const double* aa, double* R) {
     R[2] = aa[1]; R[5] = -aa[0]; R[8] = 1.0;
   }
 }
-
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  int alloc(size_t n) {
-    if (hipMalloc((void**)&p, std::max<size_t>(1, n) * sizeof(T)) != hipSuccess)
-      return set_error(THEIA_HIP_ERR_OUT_OF_MEMORY, "hipMalloc(%zu) failed", n * sizeof(T));
-    return 0;
-  }
-  int up(const void* src, size_t n) {
-    int rc = alloc(n);
-    if (rc) return rc;
-    if (n && hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess)
-      return set_error(THEIA_HIP_ERR_INTERNAL, "hipMemcpy H2D failed");
-    return 0;
-  }
-};
 
 }  // namespace
 }  // namespace thip

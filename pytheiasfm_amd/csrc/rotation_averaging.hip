@@ -21,38 +21,18 @@
 #include "rotation_compose.h"
 #include "ba_kernels.h"
 #include "wave_reduce.h"
-#include "theia_hip_internal.h"
+#include "device_util.h"
+#include "view_graph_plan.h"
 
 #include <algorithm>
 #include <chrono>
 #include <cmath>
-#include <numeric>
 #include <vector>
-
-#define HIP_TRY(expr)                                                                             \
-  do {                                                                                            \
-    hipError_t e_ = (expr);                                                                       \
-    if (e_ != hipSuccess) return thip::set_error(THEIA_HIP_ERR_INTERNAL, "%s: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
 
 namespace thip {
 namespace {
 
 constexpr int kThreads = 256;
-
-// Sum of v over the workgroup in a fixed tree order; the result is valid in thread 0.
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  const int tid = threadIdx.x;
-  red[tid] = v;
-  __syncthreads();
-  for (int s = kThreads / 2; s > 0; s >>= 1) {
-    if (tid < s) red[tid] += red[tid + s];
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
-}
 
 // ComputeResiduals (robust_rotation_estimator.cc:268-284) and the IRLS weight of every edge (:200-206):
 // w = sigma / (|e|^2 + sigma^2)^2.  part[block] = sum of |e|^2 over the block's edges.
@@ -75,14 +55,14 @@ __global__ __launch_bounds__(kThreads) void k_residual(int E, const int2* __rest
     const double tmp = sq + sigma * sigma;
     w[e] = sigma / (tmp * tmp);
   }
-  const double s = block_sum(sq, red);
+  const double s = block_sum<kThreads>(sq, red);
   if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
 // The lower triangle of L_w and the rows of A'W e, into the zeroed (m + 3) x lda array:
 //   thread t < m       : free view t -- diagonal sum of w over its incident edges, rhs row c = sum of sign * w * e_c
 //   thread t = m + p   : pair p = (a > b) -- A[a][b] = -sum of w over the pair's edges
-// inc[k] = 2 * edge + (1 if the view is the edge's second view, i.e. +I).  w == nullptr: unit weights (A'A, A'e).
+// inc, pair_edge, pair_rc: view_graph_plan.h.  w == nullptr: unit weights (A'A, A'e).
 __global__ __launch_bounds__(kThreads) void k_assemble(int m, int P, int lda, const int* __restrict__ inc_off,
                                                        const int* __restrict__ inc, const int* __restrict__ pair_off,
                                                        const int* __restrict__ pair_edge, const int2* __restrict__ pair_rc,
@@ -154,7 +134,7 @@ __global__ __launch_bounds__(kThreads) void k_admm_edge(int E, int m, const int2
       rr += r * r; aa += ax * ax; zz += zn * zn;
     }
   }
-  const double s0 = block_sum(rr, red), s1 = block_sum(aa, red), s2 = block_sum(zz, red);
+  const double s0 = block_sum<kThreads>(rr, red), s1 = block_sum<kThreads>(aa, red), s2 = block_sum<kThreads>(zz, red);
   if (threadIdx.x == 0) { part[3 * blockIdx.x] = s0; part[3 * blockIdx.x + 1] = s1; part[3 * blockIdx.x + 2] = s2; }
 }
 
@@ -183,7 +163,7 @@ __global__ __launch_bounds__(kThreads) void k_admm_view(int m, const int* __rest
       ss += sc * sc; tt += tc * tc;
     }
   }
-  const double s0 = block_sum(ss, red), s1 = block_sum(tt, red);
+  const double s0 = block_sum<kThreads>(ss, red), s1 = block_sum<kThreads>(tt, red);
   if (threadIdx.x == 0) { part[2 * blockIdx.x] = s0; part[2 * blockIdx.x + 1] = s1; }
 }
 
@@ -203,7 +183,7 @@ __global__ __launch_bounds__(kThreads) void k_update(int m, const int* __restric
     aa[3 * (size_t)id] = o[0]; aa[3 * (size_t)id + 1] = o[1]; aa[3 * (size_t)id + 2] = o[2];
     step = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
   }
-  const double s = block_sum(step, red);
+  const double s = block_sum<kThreads>(step, red);
   if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
@@ -213,45 +193,10 @@ __global__ __launch_bounds__(kThreads) void k_reduce(const double* __restrict__ 
   for (int c = 0; c < ncol; ++c) {
     double s = 0.0;
     for (int b = threadIdx.x; b < nblk; b += kThreads) s += part[(size_t)b * ncol + c];
-    s = block_sum(s, red);
+    s = block_sum<kThreads>(s, red);
     if (threadIdx.x == 0) out[c] = s;
   }
 }
-
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  int alloc(size_t n) {
-    if (hipMalloc((void**)&p, std::max<size_t>(1, n) * sizeof(T)) != hipSuccess) {
-      (void)hipGetLastError();
-      p = nullptr;
-      return set_error(THEIA_HIP_ERR_OUT_OF_MEMORY, "hipMalloc(%zu) failed", n * sizeof(T));
-    }
-    return 0;
-  }
-  int up(const void* src, size_t n) {
-    int rc = alloc(n);
-    if (rc) return rc;
-    if (n && hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess)
-      return set_error(THEIA_HIP_ERR_INTERNAL, "hipMemcpy H2D failed");
-    return 0;
-  }
-};
-
-int find_root(std::vector<int>& parent, int v) {
-  while (parent[v] != v) { parent[v] = parent[parent[v]]; v = parent[v]; }
-  return v;
-}
-
-double ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
-int grid_of(int n) { return std::max(1, (n + kThreads - 1) / kThreads); }
 
 }  // namespace
 }  // namespace thip
@@ -269,85 +214,27 @@ extern "C" int theia_hip_robust_rotation_averaging(int32_t num_views, double* or
   if (!o || !summary) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "null options or summary");
   if (o->max_num_l1_iterations < 0 || o->max_num_irls_iterations < 0 || !(o->irls_loss_parameter_sigma > 0.0))
     return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "bad options");
-  for (int e = 0; e < E; ++e)
-    if (edges[2 * e] < 0 || edges[2 * e] >= n || edges[2 * e + 1] < 0 || edges[2 * e + 1] >= n)
-      return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "edge %d names a view out of range", e);
-  *summary = theia_rotation_summary{};
-
-  // fixed views (none flagged: view 0), free-view numbering in view order
-  std::vector<uint8_t> fix(n, 0);
-  bool any = false;
-  for (int v = 0; v < n && fixed; ++v) { fix[v] = fixed[v] ? 1 : 0; any = any || fix[v]; }
-  if (!any) fix[0] = 1;
   // every connected component needs a fixed view, else A'A is singular (the L1Solver constructor's CHECK)
-  std::vector<int> parent(n);
-  std::iota(parent.begin(), parent.end(), 0);
-  for (int e = 0; e < E; ++e) {
-    const int a = find_root(parent, edges[2 * e]), b = find_root(parent, edges[2 * e + 1]);
-    if (a != b) parent[std::max(a, b)] = std::min(a, b);
-  }
-  std::vector<uint8_t> anchored(n, 0);
-  for (int v = 0; v < n; ++v) if (fix[v]) anchored[find_root(parent, v)] = 1;
-  for (int v = 0; v < n; ++v)
-    if (!anchored[find_root(parent, v)])
-      return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "view %d lies in a connected component without a fixed view", v);
-  std::vector<int> idx(n, -1), free_view;
-  for (int v = 0; v < n; ++v) if (!fix[v]) { idx[v] = (int)free_view.size(); free_view.push_back(v); }
-  const int m = (int)free_view.size();
+  ViewGraphPlan g;
+  int rc = build_view_graph_plan(n, fixed, E, edges, "fixed", &g);
+  if (rc) return rc;
+  *summary = theia_rotation_summary{};
+  const int m = g.m, P = g.P;
   if (m == 0) { summary->setup_ms = ms_since(t_start); return 0; }   // nothing moves
 
-  // CSR of the incident edges per free view (edge order) and of the edges per unordered free-view pair (edge order);
-  // self-loops have a zero row in A and are left out of both
-  std::vector<int> inc_off(m + 1, 0), inc;
-  std::vector<std::pair<int64_t, int>> pe;   // (pair key, edge)
-  for (int e = 0; e < E; ++e) {
-    const int i = edges[2 * e], j = edges[2 * e + 1];
-    if (i == j) continue;
-    if (idx[i] >= 0) ++inc_off[idx[i] + 1];
-    if (idx[j] >= 0) ++inc_off[idx[j] + 1];
-    if (idx[i] >= 0 && idx[j] >= 0) {
-      const int a = std::max(idx[i], idx[j]), b = std::min(idx[i], idx[j]);
-      pe.emplace_back((int64_t)a * m + b, e);
-    }
-  }
-  for (int v = 0; v < m; ++v) inc_off[v + 1] += inc_off[v];
-  inc.resize(inc_off[m]);
-  {
-    std::vector<int> fill(inc_off.begin(), inc_off.end() - 1);
-    for (int e = 0; e < E; ++e) {
-      const int i = edges[2 * e], j = edges[2 * e + 1];
-      if (i == j) continue;
-      if (idx[i] >= 0) inc[fill[idx[i]]++] = 2 * e;
-      if (idx[j] >= 0) inc[fill[idx[j]]++] = 2 * e + 1;
-    }
-  }
-  std::sort(pe.begin(), pe.end());
-  std::vector<int> pair_off(1, 0), pair_edge(pe.size());
-  std::vector<int2> pair_rc;
-  for (size_t k = 0; k < pe.size(); ++k) {
-    if (k == 0 || pe[k].first != pe[k - 1].first) {
-      if (k) pair_off.push_back((int)k);
-      pair_rc.push_back(make_int2((int)(pe[k].first / m), (int)(pe[k].first % m)));
-    }
-    pair_edge[k] = pe[k].second;
-  }
-  pair_off.push_back((int)pe.size());
-  const int P = (int)pair_rc.size();
-
-  int rc = thip::ensure_device();
-  if (rc) return rc;
+  if ((rc = thip::ensure_device())) return rc;
   const int lda = m + 3;
-  const int nbE = grid_of(E), nbV = grid_of(m);
+  const int nbE = grid_of(E, kThreads), nbV = grid_of(m, kThreads);
   DevBuf<double> d_aa, d_rel, d_res, d_w, d_A, d_work, d_flag, d_b, d_z, d_u, d_zold, d_g, d_T, d_x, d_part, d_sums;
   DevBuf<int2> d_edges, d_pair_rc;
   DevBuf<int> d_idx, d_free, d_inc_off, d_inc, d_pair_off, d_pair_edge;
   const size_t dense = (size_t)(m + 3) * lda;
   if ((rc = d_A.alloc(dense)) || (rc = d_work.alloc(dense_cholesky_workspace(m))) || (rc = d_flag.alloc(1)) ||
       (rc = d_aa.up(orientations, 3 * (size_t)n)) || (rc = d_rel.up(relative_rotations, 3 * (size_t)E)) ||
-      (rc = d_edges.up(edges, E)) || (rc = d_idx.up(idx.data(), n)) || (rc = d_free.up(free_view.data(), m)) ||
-      (rc = d_inc_off.up(inc_off.data(), m + 1)) || (rc = d_inc.up(inc.data(), inc.size())) ||
-      (rc = d_pair_off.up(pair_off.data(), pair_off.size())) || (rc = d_pair_edge.up(pair_edge.data(), pair_edge.size())) ||
-      (rc = d_pair_rc.up(pair_rc.data(), pair_rc.size())) || (rc = d_res.alloc(3 * (size_t)E)) || (rc = d_w.alloc(E)) ||
+      (rc = d_edges.up(edges, E)) || (rc = d_idx.up(g.idx.data(), n)) || (rc = d_free.up(g.free_view.data(), m)) ||
+      (rc = d_inc_off.up(g.inc_off.data(), m + 1)) || (rc = d_inc.up(g.inc.data(), g.inc.size())) ||
+      (rc = d_pair_off.up(g.pair_off.data(), g.pair_off.size())) || (rc = d_pair_edge.up(g.pair_edge.data(), g.pair_edge.size())) ||
+      (rc = d_pair_rc.up(g.pair_rc.data(), g.pair_rc.size())) || (rc = d_res.alloc(3 * (size_t)E)) || (rc = d_w.alloc(E)) ||
       (rc = d_b.alloc(3 * (size_t)E)) || (rc = d_z.alloc(3 * (size_t)E)) || (rc = d_u.alloc(3 * (size_t)E)) ||
       (rc = d_zold.alloc(3 * (size_t)E)) || (rc = d_g.alloc(3 * (size_t)m)) || (rc = d_T.alloc(3 * (size_t)m)) ||
       (rc = d_x.alloc(3 * (size_t)m)) || (rc = d_part.alloc(3 * (size_t)std::max(nbE, nbV))) || (rc = d_sums.alloc(8)))
@@ -387,8 +274,8 @@ extern "C" int theia_hip_robust_rotation_averaging(int32_t num_views, double* or
   HIP_TRY(hipMemsetAsync(d_flag.p, 0, sizeof(double), st));
   HIP_TRY(hipMemsetAsync(d_x.p, 0, sizeof(double) * 3 * m, st));
   residuals();
-  k_assemble<<<grid_of(m + P), kThreads, 0, st>>>(m, P, lda, d_inc_off.p, d_inc.p, d_pair_off.p, d_pair_edge.p, d_pair_rc.p,
-                                                 nullptr, d_res.p, d_A.p);
+  k_assemble<<<grid_of(m + P, kThreads), kThreads, 0, st>>>(m, P, lda, d_inc_off.p, d_inc.p, d_pair_off.p, d_pair_edge.p,
+                                                           d_pair_rc.p, nullptr, d_res.p, d_A.p);
   dense_cholesky_factor(m, 1, d_A.p, lda, d_work.p, d_flag.p, st);   // row m (A'e, unused) rides along
   bool failed = false;
   if ((rc = factor_failed(&failed))) return rc;
@@ -433,8 +320,8 @@ extern "C" int theia_hip_robust_rotation_averaging(int32_t num_views, double* or
   const auto t_irls = std::chrono::steady_clock::now();
   for (int it = 0; it < o->max_num_irls_iterations; ++it) {
     HIP_TRY(hipMemsetAsync(d_A.p, 0, sizeof(double) * dense, st));
-    k_assemble<<<grid_of(m + P), kThreads, 0, st>>>(m, P, lda, d_inc_off.p, d_inc.p, d_pair_off.p, d_pair_edge.p, d_pair_rc.p,
-                                                   d_w.p, d_res.p, d_A.p);
+    k_assemble<<<grid_of(m + P, kThreads), kThreads, 0, st>>>(m, P, lda, d_inc_off.p, d_inc.p, d_pair_off.p, d_pair_edge.p,
+                                                             d_pair_rc.p, d_w.p, d_res.p, d_A.p);
     dense_cholesky_factor(m, 3, d_A.p, lda, d_work.p, d_flag.p, st);
     if ((rc = factor_failed(&failed))) return rc;
     if (failed) {

@@ -9,37 +9,13 @@
 #include "svd_team.h"
 #include "fit5_team.h"
 #include "dls_device.h"
-#include "theia_hip_internal.h"
+#include "device_util.h"
 
 #include <algorithm>
 #include <vector>
 
-#define HIP_TRY(expr)                                                                             \
-  do {                                                                                            \
-    hipError_t e_ = (expr);                                                                       \
-    if (e_ != hipSuccess) return thip::set_error(THEIA_HIP_ERR_INTERNAL, "%s: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
-
 namespace thip {
 namespace {
-
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  int alloc(size_t n) {
-    if (hipMalloc((void**)&p, std::max<size_t>(1, n) * sizeof(T)) != hipSuccess)
-      return set_error(THEIA_HIP_ERR_OUT_OF_MEMORY, "hipMalloc(%zu) failed", n * sizeof(T));
-    return 0;
-  }
-  int up(const void* src, size_t n) {
-    int rc = alloc(n);
-    if (rc) return rc;
-    if (n && hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess)
-      return set_error(THEIA_HIP_ERR_INTERNAL, "hipMemcpy H2D failed");
-    return 0;
-  }
-};
 
 // ---- eigen-decomposition.  Record per matrix (doubles): ok | wr [n] | wi [n] | H [n][n] (the Schur form) | V [n][n]
 // (the kept rows only, NR x n, when NR > 0).

@@ -17,7 +17,7 @@
 // triangle are first mirrored from the lower one).
 #include "ba_kernels.h"
 #include "cholesky_device.h"
-#include "theia_hip_internal.h"
+#include "device_util.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -835,29 +835,6 @@ const std::vector<int>& chol_plan_shared_tiles(const CholPlan* pl) { return pl->
 namespace thip {
 namespace {
 
-#define K3_TRY(expr)                                                                                      \
-  do {                                                                                                    \
-    hipError_t e_ = (expr);                                                                               \
-    if (e_ != hipSuccess) return set_error(THEIA_HIP_ERR_INTERNAL, "%s: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
-
-template <class T>
-struct K3Buf {
-  T* p = nullptr;
-  K3Buf() = default;
-  K3Buf(const K3Buf&) = delete;
-  K3Buf& operator=(const K3Buf&) = delete;
-  ~K3Buf() { if (p) (void)hipFree(p); }
-  int alloc(size_t n) {
-    if (hipMalloc((void**)&p, std::max<size_t>(1, n) * sizeof(T)) != hipSuccess) {
-      (void)hipGetLastError();
-      p = nullptr;
-      return set_error(THEIA_HIP_ERR_OUT_OF_MEMORY, "hipMalloc(%zu) failed", n * sizeof(T));
-    }
-    return 0;
-  }
-};
-
 __global__ __launch_bounds__(256) void k_k3_fill(double* __restrict__ p, size_t count, double v) {
   for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < count; e += (size_t)gridDim.x * 256) p[e] = v;
 }
@@ -877,13 +854,13 @@ __global__ __launch_bounds__(256) void k_k3_tiles(double* __restrict__ dst, cons
 
 int k3_tiles(double* dst, const double* src, int lda, const std::vector<int>& items, int accumulate) {
   if (items.empty()) return 0;
-  K3Buf<int> d;
+  DevBuf<int> d;
   int rc = d.alloc(items.size());
   if (rc) return rc;
-  K3_TRY(hipMemcpy(d.p, items.data(), sizeof(int) * items.size(), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d.p, items.data(), sizeof(int) * items.size(), hipMemcpyHostToDevice));
   k_k3_tiles<<<(int)(items.size() / 5), 256>>>(dst, src, lda, d.p, accumulate);
-  K3_TRY(hipGetLastError());
-  K3_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
   return 0;
 }
 
@@ -935,22 +912,22 @@ extern "C" int theia_hip_tile_sparse_spd_solve(int32_t n, int32_t lda, const uin
     if (tile_level) tile_level[i] = pl->dense ? i : pl->pos_level[i];
   }
   const size_t cnt = (size_t)(n + 1) * lda;
-  K3Buf<double> dA, dw, dflag, dx, dstage;
+  DevBuf<double> dA, dw, dflag, dx, dstage;
   if ((rc = dA.alloc(cnt)) || (rc = dw.alloc(dense_cholesky_workspace(n))) || (rc = dflag.alloc(1)) || (rc = dx.alloc(n))) return rc;
-  K3_TRY(hipMemset(dflag.p, 0, sizeof(double)));
+  HIP_TRY(hipMemset(dflag.p, 0, sizeof(double)));
   const double nan = __builtin_nan("");
   k_k3_fill<<<64, 256>>>(dx.p, (size_t)n, nan);
   if (mode < 2) {
-    K3_TRY(hipMemcpy(dA.p, A, sizeof(double) * (size_t)n * lda, hipMemcpyHostToDevice));
-    K3_TRY(hipMemcpy(dA.p + (size_t)n * lda, b, sizeof(double) * n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dA.p, A, sizeof(double) * (size_t)n * lda, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dA.p + (size_t)n * lda, b, sizeof(double) * n, hipMemcpyHostToDevice));
   } else {
     // the BA's order: a buffer with anything in it, the per-iteration clear, then the assembly adds into the structure
     // tiles (lower triangle of the diagonal tiles) and the rhs
     if ((rc = dstage.alloc(cnt))) return rc;
     k_k3_fill<<<1024, 256>>>(dA.p, cnt, nan);
-    K3_TRY(hipMemcpy(dstage.p, A, sizeof(double) * (size_t)n * lda, hipMemcpyHostToDevice));
-    K3_TRY(hipMemcpy(dstage.p + (size_t)n * lda, b, sizeof(double) * n, hipMemcpyHostToDevice));
-    if (!chol_plan_clear(pl, dA.p, lda, nullptr, dA.p + (size_t)n * lda, (size_t)n)) K3_TRY(hipMemset(dA.p, 0, sizeof(double) * cnt));
+    HIP_TRY(hipMemcpy(dstage.p, A, sizeof(double) * (size_t)n * lda, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dstage.p + (size_t)n * lda, b, sizeof(double) * n, hipMemcpyHostToDevice));
+    if (!chol_plan_clear(pl, dA.p, lda, nullptr, dA.p + (size_t)n * lda, (size_t)n)) HIP_TRY(hipMemset(dA.p, 0, sizeof(double) * cnt));
     std::vector<int> items;
     for (int i = 0; i < nt; ++i)
       for (int j = 0; j <= i; ++j)
@@ -958,13 +935,13 @@ extern "C" int theia_hip_tile_sparse_spd_solve(int32_t n, int32_t lda, const uin
     for (int j = 0; j < nt; ++j) k3_item(items, n, -1, j, 0);
     if ((rc = k3_tiles(dA.p, dstage.p, lda, items, 1))) return rc;
   }
-  K3_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   chol_plan_solve(pl, dA.p, lda, mode == 1 ? dx.p : dA.p + (size_t)n * lda, dw.p, dflag.p, nullptr);
-  K3_TRY(hipGetLastError());
-  K3_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
   double flag = 0.0;
-  K3_TRY(hipMemcpy(x, mode == 1 ? dx.p : dA.p + (size_t)n * lda, sizeof(double) * n, hipMemcpyDeviceToHost));
-  K3_TRY(hipMemcpy(&flag, dflag.p, sizeof(double), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(x, mode == 1 ? dx.p : dA.p + (size_t)n * lda, sizeof(double) * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&flag, dflag.p, sizeof(double), hipMemcpyDeviceToHost));
   if (flag != 0.0) return set_error(THEIA_HIP_ERR_INTERNAL, "matrix is not positive definite");
   return 0;
 }
@@ -1000,18 +977,18 @@ extern "C" int theia_hip_tile_sparse_spd_solve_sharded(int32_t n, int32_t num_ra
   for (int r = 1; r < R; ++r)
     if (chol_plan_shared_tiles(plans[r].get()) != st) return set_error(THEIA_HIP_ERR_INTERNAL, "rank %d: the shared-tile list differs from rank 0's", r);
   const size_t cnt = (size_t)(n + 1) * n;
-  std::vector<K3Buf<double>> dA(R), dw(R);
-  K3Buf<double> dsum, dflag;
+  std::vector<DevBuf<double>> dA(R), dw(R);
+  DevBuf<double> dsum, dflag;
   if ((rc = dsum.alloc(cnt)) || (rc = dflag.alloc(R))) return rc;
-  K3_TRY(hipMemset(dflag.p, 0, sizeof(double) * R));
+  HIP_TRY(hipMemset(dflag.p, 0, sizeof(double) * R));
   for (int r = 0; r < R; ++r) {
     if ((rc = dA[r].alloc(cnt)) || (rc = dw[r].alloc(dense_cholesky_workspace(n)))) return rc;
-    K3_TRY(hipMemcpy(dA[r].p, A + (size_t)r * n * n, sizeof(double) * (size_t)n * n, hipMemcpyHostToDevice));
-    K3_TRY(hipMemcpy(dA[r].p + (size_t)n * n, b + (size_t)r * n, sizeof(double) * n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dA[r].p, A + (size_t)r * n * n, sizeof(double) * (size_t)n * n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dA[r].p + (size_t)n * n, b + (size_t)r * n, sizeof(double) * n, hipMemcpyHostToDevice));
     chol_plan_solve_phase(plans[r].get(), 0, dA[r].p, n, dA[r].p + (size_t)n * n, dw[r].p, dflag.p + r, nullptr);
   }
-  K3_TRY(hipGetLastError());
-  K3_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
   // the all-reduce: the shared tiles and the whole rhs row, summed in rank order, the same sum handed to every rank
   std::vector<int> items;
   for (size_t k = 0; k + 1 < st.size(); k += 2) k3_item(items, n, st[k], st[k + 1], 0);
@@ -1021,11 +998,11 @@ extern "C" int theia_hip_tile_sparse_spd_solve_sharded(int32_t n, int32_t num_ra
   for (int r = 0; r < R; ++r) if ((rc = k3_tiles(dA[r].p, dsum.p, n, items, 0))) return rc;
   for (int r = 0; r < R; ++r)
     chol_plan_solve_phase(plans[r].get(), 1, dA[r].p, n, dA[r].p + (size_t)n * n, dw[r].p, dflag.p + r, nullptr);
-  K3_TRY(hipGetLastError());
-  K3_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
   std::vector<double> flag(R);
-  for (int r = 0; r < R; ++r) K3_TRY(hipMemcpy(x + (size_t)r * n, dA[r].p + (size_t)n * n, sizeof(double) * n, hipMemcpyDeviceToHost));
-  K3_TRY(hipMemcpy(flag.data(), dflag.p, sizeof(double) * R, hipMemcpyDeviceToHost));
+  for (int r = 0; r < R; ++r) HIP_TRY(hipMemcpy(x + (size_t)r * n, dA[r].p + (size_t)n * n, sizeof(double) * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(flag.data(), dflag.p, sizeof(double) * R, hipMemcpyDeviceToHost));
   for (int r = 0; r < R; ++r)
     if (flag[r] != 0.0) return set_error(THEIA_HIP_ERR_INTERNAL, "rank %d: matrix is not positive definite", r);
   return 0;

@@ -15,18 +15,12 @@
 // (stride 64); the reduced system is wave-reduced; every lane keeps the same scalar state.
 #include "ba_device.h"
 #include "wave_reduce.h"
-#include "theia_hip_internal.h"
+#include "device_util.h"
 
 #include <chrono>
 #include <cmath>
 #include <cstring>
 #include <vector>
-
-#define HIP_TRY(expr)                                                                             \
-  do {                                                                                            \
-    hipError_t e_ = (expr);                                                                       \
-    if (e_ != hipSuccess) return thip::set_error(THEIA_HIP_ERR_INTERNAL, "%s: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
 
 namespace thip {
 namespace {
@@ -419,24 +413,6 @@ __global__ __launch_bounds__(64) void k_two_view_ba(TvBatch B, TvOut* __restrict
   }
 }
 
-template <typename T>
-struct Dev {
-  T* p = nullptr;
-  ~Dev() { if (p) (void)hipFree(p); }
-  int alloc(size_t n) {
-    if (hipMalloc((void**)&p, std::max<size_t>(1, n) * sizeof(T)) != hipSuccess)
-      return set_error(THEIA_HIP_ERR_OUT_OF_MEMORY, "hipMalloc(%zu) failed", n * sizeof(T));
-    return 0;
-  }
-  int up(const void* src, size_t n) {
-    int rc = alloc(n);
-    if (rc) return rc;
-    if (n && hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess)
-      return set_error(THEIA_HIP_ERR_INTERNAL, "hipMemcpy H2D failed");
-    return 0;
-  }
-};
-
 }  // namespace
 }  // namespace thip
 
@@ -463,7 +439,7 @@ extern "C" int theia_hip_ba_two_views_batch(const theia_ba_two_view_full_batch* 
   if (o->max_num_iterations < 0) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "negative max_num_iterations");
   int rc = thip::ensure_device();
   if (rc) return rc;
-  Dev<int64_t> d_off; Dev<double> d_corr, d_cam, d_intr, d_X, d_Xc, d_sp; Dev<int> d_model; Dev<uint8_t> d_kc; Dev<TvOut> d_out;
+  DevBuf<int64_t> d_off; DevBuf<double> d_corr, d_cam, d_intr, d_X, d_Xc, d_sp; DevBuf<int> d_model; DevBuf<uint8_t> d_kc; DevBuf<TvOut> d_out;
   if ((rc = d_off.up(b->offsets, num + 1)) || (rc = d_corr.up(b->correspondences, 4 * total)) || (rc = d_X.up(b->points, 4 * total)) ||
       (rc = d_cam.up(b->cam_ext, 12 * (size_t)num)) || (rc = d_intr.up(b->intrinsics, 2 * THEIA_MAX_INTRINSICS * (size_t)num)) ||
       (rc = d_model.up(b->model, 2 * (size_t)num)) || (rc = d_kc.up(b->const_intrinsics, 2 * (size_t)num)) ||

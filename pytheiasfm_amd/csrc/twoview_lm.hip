@@ -19,17 +19,11 @@
 #include "ba_device.h"
 #include "wave_reduce.h"
 #include "ransac_device.h"
-#include "theia_hip_internal.h"
+#include "device_util.h"
 
 #include <chrono>
 #include <cmath>
 #include <vector>
-
-#define HIP_TRY(expr)                                                                             \
-  do {                                                                                            \
-    hipError_t e_ = (expr);                                                                       \
-    if (e_ != hipSuccess) return thip::set_error(THEIA_HIP_ERR_INTERNAL, "%s: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
 
 namespace thip {
 namespace {
@@ -900,24 +894,6 @@ __global__ __launch_bounds__(256) void k_fundamental_lm(FundBatch B, TwoViewOut*
   }
 }
 
-template <typename T>
-struct Dev {
-  T* p = nullptr;
-  ~Dev() { if (p) (void)hipFree(p); }
-  int alloc(size_t n) {
-    if (hipMalloc((void**)&p, std::max<size_t>(1, n) * sizeof(T)) != hipSuccess)
-      return set_error(THEIA_HIP_ERR_OUT_OF_MEMORY, "hipMalloc(%zu) failed", n * sizeof(T));
-    return 0;
-  }
-  int up(const void* src, size_t n) {
-    int rc = alloc(n);
-    if (rc) return rc;
-    if (n && hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess)
-      return set_error(THEIA_HIP_ERR_INTERNAL, "hipMemcpy H2D failed");
-    return 0;
-  }
-};
-
 }  // namespace
 
 // device-resident variant for callers inside the library (LO-RANSAC); d_out = views_batch_out_bytes() per problem
@@ -981,7 +957,7 @@ extern "C" int theia_hip_ba_two_views_angular_batch(const theia_ba_two_view_batc
     return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "unknown linear_solver %d", b->linear_solver);
   int rc = thip::ensure_device();
   if (rc) return rc;
-  Dev<int64_t> d_off; Dev<double> d_corr, d_pose; Dev<char> d_out;
+  DevBuf<int64_t> d_off; DevBuf<double> d_corr, d_pose; DevBuf<char> d_out;
   if ((rc = d_off.up(b->offsets, num + 1)) || (rc = d_corr.up(b->correspondences, 4 * total)) ||
       (rc = d_pose.up(b->rotation_position, 6 * (size_t)num)) || (rc = d_out.alloc(sizeof(TwoViewOut) * num)))
     return rc;
@@ -1024,7 +1000,7 @@ extern "C" int theia_hip_optimize_homography_batch(int32_t num_problems, const i
   for (int p = 0; p < num; ++p)
     for (int i = 0; i < 3; ++i)
       for (int j = 0; j < 3; ++j) hcm[(size_t)p * 9 + i + 3 * j] = homographies[(size_t)p * 9 + 3 * i + j];
-  Dev<int64_t> d_off; Dev<double> d_corr, d_H; Dev<char> d_out;
+  DevBuf<int64_t> d_off; DevBuf<double> d_corr, d_H; DevBuf<char> d_out;
   if ((rc = d_off.up(offsets, num + 1)) || (rc = d_corr.up(correspondences, 4 * total)) || (rc = d_H.up(hcm.data(), hcm.size())) ||
       (rc = d_out.alloc(sizeof(TwoViewOut) * num)))
     return rc;
@@ -1067,7 +1043,7 @@ extern "C" int theia_hip_optimize_fundamental_matrix_batch(int32_t num_problems,
   if (o->max_num_iterations < 0) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "negative max_num_iterations");
   int rc = thip::ensure_device();
   if (rc) return rc;
-  Dev<int64_t> d_off; Dev<double> d_corr, d_F; Dev<char> d_out;
+  DevBuf<int64_t> d_off; DevBuf<double> d_corr, d_F; DevBuf<char> d_out;
   if ((rc = d_off.up(offsets, num + 1)) || (rc = d_corr.up(correspondences, 4 * total)) ||
       (rc = d_F.up(fundamental_matrices, 9 * (size_t)num)) || (rc = d_out.alloc(sizeof(TwoViewOut) * num)))
     return rc;

@@ -34,7 +34,7 @@
 #include "ransac_device.h"
 #include "rotation_compose.h"
 #include "wave_reduce.h"
-#include "theia_hip_internal.h"
+#include "device_util.h"
 
 #include <algorithm>
 #include <chrono>
@@ -42,12 +42,6 @@
 #include <cstring>
 #include <limits>
 #include <vector>
-
-#define HIP_TRY(expr)                                                                             \
-  do {                                                                                            \
-    hipError_t e_ = (expr);                                                                       \
-    if (e_ != hipSuccess) return thip::set_error(THEIA_HIP_ERR_INTERNAL, "%s: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
 
 extern "C" int theia_hip_rng_rand_gaussian(theia_rng_state* state, double mean, double std_dev, int32_t n, double* out);
 
@@ -61,20 +55,6 @@ constexpr int kMfasLdsMaxViews = THEIA_MFAS_LDS_MAX_VIEWS;   // the switch point
 constexpr int kMfasStateBytes = 28;                          // key 8, incoming 8, outgoing 8, in-degree 4
 constexpr unsigned kSecondBit = 0x80000000u;                 // adjacency entry: the list's owner is the pair's second view
 static_assert((size_t)kMfasLdsMaxViews * kMfasStateBytes + 3 * kMfasMaxWaves * 4 <= 160 * 1024, "the CU has 160 KiB of LDS");
-
-// Sum of v over the workgroup in a fixed tree order; the result is valid in thread 0.
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  const int tid = threadIdx.x;
-  red[tid] = v;
-  __syncthreads();
-  for (int s = kThreads / 2; s > 0; s >>= 1) {
-    if (tid < s) red[tid] += red[tid + s];
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
-}
 
 // ceres/rotation.h AngleAxisRotatePoint: Rodrigues for theta^2 > DBL_EPSILON, else pt + aa x pt.
 __device__ __forceinline__ void angle_axis_rotate_point(const double* aa, const double* pt, double* out) {
@@ -109,7 +89,7 @@ __global__ __launch_bounds__(kThreads) void k_rotate(int E, const int2* __restri
     angle_axis_rotate_point(w, t, r);
     rot[3 * (size_t)e] = r[0]; rot[3 * (size_t)e + 1] = r[1]; rot[3 * (size_t)e + 2] = r[2];
   }
-  const double s0 = block_sum(r[0], red), s1 = block_sum(r[1], red), s2 = block_sum(r[2], red);
+  const double s0 = block_sum<kThreads>(r[0], red), s1 = block_sum<kThreads>(r[1], red), s2 = block_sum<kThreads>(r[2], red);
   if (threadIdx.x == 0) { part[3 * blockIdx.x] = s0; part[3 * blockIdx.x + 1] = s1; part[3 * blockIdx.x + 2] = s2; }
 }
 
@@ -126,7 +106,7 @@ __global__ __launch_bounds__(kThreads) void k_sq_dev(int E, const double* __rest
       d[k] = v * v;
     }
   }
-  const double s0 = block_sum(d[0], red), s1 = block_sum(d[1], red), s2 = block_sum(d[2], red);
+  const double s0 = block_sum<kThreads>(d[0], red), s1 = block_sum<kThreads>(d[1], red), s2 = block_sum<kThreads>(d[2], red);
   if (threadIdx.x == 0) { part[3 * blockIdx.x] = s0; part[3 * blockIdx.x + 1] = s1; part[3 * blockIdx.x + 2] = s2; }
 }
 
@@ -137,7 +117,7 @@ __global__ __launch_bounds__(kThreads) void k_reduce3(int nb, const double* __re
   for (int k = 0; k < 3; ++k) {
     double s = 0.0;
     for (int b = threadIdx.x; b < nb; b += kThreads) s += part[3 * (size_t)b + k];
-    const double t = block_sum(s, red);
+    const double t = block_sum<kThreads>(s, red);
     if (threadIdx.x == 0) out[k] = t / divisor;
   }
 }
@@ -308,36 +288,6 @@ __global__ __launch_bounds__(kThreads) void k_orientation_filter(int E, const in
   removed[e] = sq <= sq_max ? 0 : 1;
 }
 
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  int alloc(size_t n) {
-    if (hipMalloc((void**)&p, std::max<size_t>(1, n) * sizeof(T)) != hipSuccess) {
-      (void)hipGetLastError();
-      p = nullptr;
-      return set_error(THEIA_HIP_ERR_OUT_OF_MEMORY, "hipMalloc(%zu) failed", n * sizeof(T));
-    }
-    return 0;
-  }
-  int up(const void* src, size_t n) {
-    int rc = alloc(n);
-    if (rc) return rc;
-    if (n && hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess)
-      return set_error(THEIA_HIP_ERR_INTERNAL, "hipMemcpy H2D failed");
-    return 0;
-  }
-};
-
-double ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
-int grid_of(size_t n) { return (int)std::max<size_t>(1, (n + kThreads - 1) / kThreads); }
-
 // What both filters refuse in their pair list: a view out of range, a self-pair, an unordered pair named twice.
 int check_pairs(int n_views, int n_pairs, const int32_t* pairs) {
   std::vector<uint64_t> keys((size_t)n_pairs);
@@ -412,7 +362,7 @@ extern "C" int theia_hip_filter_view_pairs_from_relative_translation(
   }
   const bool lds = N <= kMfasLdsMaxViews;
   const size_t slots = 2 * (size_t)E;
-  const int nbE = grid_of(E);
+  const int nbE = grid_of(E, kThreads);
 
   if ((rc = thip::ensure_device())) return rc;
   DevBuf<int2> d_pairs;
@@ -458,7 +408,7 @@ extern "C" int theia_hip_filter_view_pairs_from_relative_translation(
     *rng = local;
   }
   HIP_TRY(hipMemcpyAsync(d_axes.p, axes.data(), sizeof(double) * axes.size(), hipMemcpyHostToDevice, st));
-  k_project<<<grid_of(3 * (size_t)E), kThreads, 0, st>>>(E, iters, d_rot.p, d_axes.p, d_adj_pair.p, d_proj.p, d_padj.p);
+  k_project<<<grid_of(3 * (size_t)E, kThreads), kThreads, 0, st>>>(E, iters, d_rot.p, d_axes.p, d_adj_pair.p, d_proj.p, d_padj.p);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(st));
   stats.rotate_project_ms = ms_since(t_rotate);
@@ -533,8 +483,8 @@ extern "C" int theia_hip_filter_view_pairs_from_orientation(int32_t n_views, int
   if ((rc = d_pairs.up(pairs, E)) || (rc = d_aa.up(orientations, 3 * (size_t)N)) || (rc = d_rel.up(rotation_2, 3 * (size_t)E)) ||
       (has_orientation && (rc = d_has.up(has_orientation, N))) || (rc = d_removed.alloc(E)))
     return rc;
-  k_orientation_filter<<<grid_of(E), kThreads>>>(E, d_pairs.p, d_aa.p, has_orientation ? d_has.p : nullptr, d_rel.p, rad * rad,
-                                                d_removed.p);
+  k_orientation_filter<<<grid_of(E, kThreads), kThreads>>>(E, d_pairs.p, d_aa.p, has_orientation ? d_has.p : nullptr, d_rel.p, rad * rad,
+                                                          d_removed.p);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(removed, d_removed.p, (size_t)E, hipMemcpyDeviceToHost));
   return 0;

@@ -104,5 +104,21 @@ __device__ __forceinline__ double wave_max_abs(double v) {
   return __builtin_amdgcn_ballot_w64(valid) != 0ull ? __hiloint2double((int)hm, (int)lm) : -1.0;
 }
 
+// Sum of v over a workgroup of THREADS (a power of two) in a fixed tree order -- halving strides over red[THREADS] in LDS;
+// the result is valid in thread 0.  The global-pose stages' tests restate this order on the host and compare bits.
+template <int THREADS>
+__device__ __forceinline__ double block_sum(double v, double* red) {
+  const int tid = threadIdx.x;
+  red[tid] = v;
+  __syncthreads();
+  for (int s = THREADS / 2; s > 0; s >>= 1) {
+    if (tid < s) red[tid] += red[tid + s];
+    __syncthreads();
+  }
+  const double r = red[0];
+  __syncthreads();
+  return r;
+}
+
 }  // namespace thip
 #endif
