@@ -159,11 +159,13 @@ __device__ unsigned long long g_fused_stamps[16];
 
 // Phase L of one wave tile on prefetched registers: the linearisation (lin5, ba_fused_lin.h), the track sums, V^-1, the record
 // and the slot table.
-template <int PD, unsigned MODELS, int LOSSK, bool STAMPS>
+// FIRST (the first linearisation of a solve, k_lin_schur<.., FIRST = true>): P carries UNIT scales, the Jacobi scaling of the
+// track's point columns is made here from the track sums and written to scale_out (the solve's scale_p).
+template <int PD, unsigned MODELS, int LOSSK, bool STAMPS, bool FIRST = false>
 THIP_DEV void fused_phase_l5(const DevProblem& P, const LanePre<PD>& c, const double* __restrict__ s_cam, int W, int tile, bool tile_ok,
                              int wv, int lane, double inv_radius, double* __restrict__ Vinv, double* __restrict__ tile_part,
                              double* __restrict__ s_rec, uint8_t* __restrict__ s_tslot, unsigned* __restrict__ s_tmask,
-                             unsigned long long (&stamps)[12]) {
+                             unsigned long long (&stamps)[12], double* __restrict__ scale_out = nullptr) {
   Stamp<STAMPS> sl;
   sl.start();
   constexpr int NT = PD * (PD + 1) / 2;
@@ -218,6 +220,24 @@ THIP_DEV void fused_phase_l5(const DevProblem& P, const LanePre<PD>& c, const do
   }
   if constexpr (STAMPS) { asm volatile("" :: "v"(tot[0]), "v"(tot[NT + PD - 1]), "v"(tmask)); }
   sl.lap(stamps, 3);
+  double spn[PD];   // the point's Jacobi scaling: the state's, or (FIRST) the one made here
+#pragma unroll
+  for (int a = 0; a < PD; ++a) spn[a] = c.sp[a];
+  if constexpr (FIRST) {
+    // tot's diagonal is the squared column norm k_colnorm sums (same rows: loss-corrected, zero for a constant point, for an
+    // observation that is not evaluated and for an inactive lane), the rule is k_make_scale's.  The sums were made with unit
+    // scales: E, V and g take the scaling now -- (s_a s_b) V_ab, s_a g_a -- before the LM diagonal and the inverse.
+    // Same bits in every lane of the track (tot is).
+#pragma unroll
+    for (int a = 0; a < PD; ++a) spn[a] = 1.0 / (1.0 + sqrt(tot[lidx(a, a)]));
+#pragma unroll
+    for (int a = 0; a < PD; ++a) {
+#pragma unroll
+      for (int b = 0; b <= a; ++b) tot[lidx(a, b)] *= spn[a] * spn[b];
+      tot[NT + a] *= spn[a];
+      Jt[a] *= spn[a]; Jt[PD + a] *= spn[a];
+    }
+  }
   double V[NT], Vi[NT], g[PD];
 #pragma unroll
   for (int k = 0; k < NT; ++k) V[k] = tot[k];
@@ -252,11 +272,15 @@ THIP_DEV void fused_phase_l5(const DevProblem& P, const LanePre<PD>& c, const do
   sl.lap(stamps, 4);
   if (active && sg.head) {
     s_tmask[c.tl] = tmask;
+    if constexpr (FIRST) {
+#pragma unroll
+      for (int a = 0; a < PD; ++a) scale_out[(size_t)PD * c.p + a] = spn[a];
+    }
     if (!c.pconst) {
 #pragma unroll
       for (int k = 0; k < NT; ++k) Vinv[(size_t)NT * c.p + k] = Vi[k];
 #pragma unroll
-      for (int a = 0; a < PD; ++a) gmax = fmax(gmax, fabs(g[a] / c.sp[a]));
+      for (int a = 0; a < PD; ++a) gmax = fmax(gmax, fabs(g[a] / spn[a]));
     }
   }
   if (active && is_tgt) {
@@ -303,10 +327,14 @@ THIP_DEV void fused_phase_l5(const DevProblem& P, const LanePre<PD>& c, const do
 }
 
 // tile_part layout as k_lin_obs: [ntiles][4] = {cost, gmax_points, invalid, notpd}
-template <int PD, int TPS, unsigned MODELS, int LOSSK, bool STAMPS = false>
+// FIRST: the first linearisation of a solve that folds the Jacobi scaling in (launch_linearize_fused_first): P carries unit
+// scales and the per-camera blocks are the unit-scale ones, the point scales are made in phase L and written to scale_out;
+// the camera scales follow from the column norms this launch sums (k_scale_from_colsq), the reduced system is rescaled.
+template <int PD, int TPS, unsigned MODELS, int LOSSK, bool STAMPS = false, bool FIRST = false>
 __global__ __launch_bounds__(64 * TPS, THIP_FUSED_WAVES) void k_lin_schur(DevProblem P, const double* __restrict__ pts,
                                                            const double* __restrict__ radius_p,
-                                                           double* __restrict__ Vinv, double* __restrict__ tile_part) {
+                                                           double* __restrict__ Vinv, double* __restrict__ tile_part,
+                                                           double* __restrict__ scale_out = nullptr) {
   constexpr int RD = rec_doubles<PD>();
   constexpr int SUB = TPS * kWave;                    // observations per sub-chunk
   constexpr int SUBT = TPS * kFusedTileTracks;        // tracks per sub-chunk
@@ -383,7 +411,7 @@ __global__ __launch_bounds__(64 * TPS, THIP_FUSED_WAVES) void k_lin_schur(DevPro
     const int scn = min(sc + 1, nsc - 1);   // (the last sub-chunk reloads itself: unconditional loads, nothing is used)
     pre_level1<PD, TPS>(P, run, scn, wv, lane, ntile, ntile_ok, nxt);
     if (P.fused_dbg & 16) __builtin_amdgcn_s_setprio(1);   // development: issue priority to the latency-bound phase
-    fused_phase_l5<PD, MODELS, LOSSK, STAMPS>(P, cur, s_cam, run.W, tile, tile_ok, wv, lane, inv_radius, Vinv, tile_part, s_rec, s_tslot, s_tmask, stamps);
+    fused_phase_l5<PD, MODELS, LOSSK, STAMPS, FIRST>(P, cur, s_cam, run.W, tile, tile_ok, wv, lane, inv_radius, Vinv, tile_part, s_rec, s_tslot, s_tmask, stamps, scale_out);
     sk.lap(stamps, 1);
     pre_level2<PD>(P, pts, nxt);
     if (P.fused_dbg & 16) __builtin_amdgcn_s_setprio(0);
@@ -793,6 +821,18 @@ __global__ __launch_bounds__(256) void k_schur_sum(int nitems, const int* __rest
   }
 }
 
+// The camera part of the Jacobi scaling from the column norms the first launch summed (rb.colsq by reduced index, unit
+// scales): k_make_scale's rule on the free columns of the variable cameras; 1 on a frozen column or a constant camera, whose
+// norm is zero (their scale is never applied: k_cam_prep, k_build_scale_red and k_cam_update test the mask first).
+__global__ __launch_bounds__(256) void k_scale_from_colsq(DevProblem P, const double* __restrict__ colsq, double* __restrict__ scale_c) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= 6 * P.nc) return;
+  const int c = i / 6, q = i - 6 * c;
+  const int rc = P.cam_red[c];
+  const bool free_col = rc >= 0 && !((P.cam_mask[c] >> q) & 1u);
+  scale_c[i] = free_col ? 1.0 / (1.0 + sqrt(colsq[P.ni + 6 * rc + q])) : 1.0;
+}
+
 }  // namespace
 
 void launch_cam_prep(const DevProblem& P, const double* cam, const double* intr, double* camrot, hipStream_t st, const double* ycam) {
@@ -838,6 +878,31 @@ void launch_linearize_fused(const DevProblem& P, const double* cam, const double
   if (P.n_sum_items)
     k_schur_sum<<<(P.n_sum_items + 3) / 4, 256, 0, st>>>(P.n_sum_items, P.sum_items, P.sum_src, P.fpart, rb.S, P.n, rb.rhs,
                                                          rb.gc, rb.colsq, P.frun_next);
+}
+
+void launch_linearize_fused_first(const DevProblem& P, const double* ones_c, const double* ones_p, double* scale_c, double* scale_p,
+                                  double* scale_red, const double* cam, const double* pts, const double* radius,
+                                  const ReduceBuf& rb, double* Vinv, double* tile_part, hipStream_t st) {
+  if (P.n_fruns == 0 || P.n_sum_items == 0) return;
+  DevProblem Q = P;
+  Q.scale_c = ones_c; Q.scale_p = ones_p;
+  launch_cam_prep(Q, cam, Q.intr, Q.camrot, st);
+  static const int wgs = [] { const char* e = getenv("THEIA_HIP_FUSED_WGS"); return e ? std::max(1, atoi(e)) : 512; }();
+  const int grid = std::min(P.n_fruns, wgs);
+  const bool trig = (P.model_mask & ~kModelsNoTrig) != 0;
+  const int lk = loss_class(P.loss_type);
+#define THIP_LS1(PD_, M_) do { \
+    if (lk == 0) k_lin_schur<PD_, 4, M_, 0, false, true><<<grid, 256, 0, st>>>(Q, pts, radius, Vinv, tile_part, scale_p); \
+    else if (lk == 1) k_lin_schur<PD_, 4, M_, 1, false, true><<<grid, 256, 0, st>>>(Q, pts, radius, Vinv, tile_part, scale_p); \
+    else k_lin_schur<PD_, 4, M_, 2, false, true><<<grid, 256, 0, st>>>(Q, pts, radius, Vinv, tile_part, scale_p); } while (0)
+  if (P.pd == 3) { if (trig) THIP_LS1(3, kModelsAll); else THIP_LS1(3, kModelsNoTrig); }
+  else { if (trig) THIP_LS1(4, kModelsAll); else THIP_LS1(4, kModelsNoTrig); }
+#undef THIP_LS1
+  k_schur_sum<<<(P.n_sum_items + 3) / 4, 256, 0, st>>>(P.n_sum_items, P.sum_items, P.sum_src, P.fpart, rb.S, P.n, rb.rhs, rb.gc, rb.colsq, P.frun_next);
+  k_scale_from_colsq<<<(6 * P.nc + 255) / 256, 256, 0, st>>>(P, rb.colsq, scale_c);
+  DevProblem R = P;
+  R.scale_c = scale_c;
+  launch_build_scale_red(R, scale_red, st);
 }
 
 // K4 + K5 over the runs of the fused plan (k_backsub_runs); false: not applicable (the caller takes k_backsub)

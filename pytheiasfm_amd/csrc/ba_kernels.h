@@ -193,6 +193,12 @@ void launch_linearize(const DevProblem& P, const double* cam, const double* pts,
 // fused path: k_cam_prep + k_lin_schur + k_schur_sum (S blocks are WRITTEN, the buffer must be clear where nothing lands)
 void launch_linearize_fused(const DevProblem& P, const double* cam, const double* pts, const double* radius /* device */,
                             const ReduceBuf& rb, double* Vinv, double* tile_part, hipStream_t st);
+// the first linearisation of a solve with the Jacobi scaling folded in (no separate column-norm pass): P is the solve's view,
+// the kernels run on unit scales and leave scale_p, scale_c and scale_red; the reduced system in rb is the UNIT-camera-scale
+// one until the caller has rescaled it (chol_plan_rescale with scale_red), and P.camrot holds unit-scale blocks
+void launch_linearize_fused_first(const DevProblem& P, const double* ones_c, const double* ones_p, double* scale_c, double* scale_p,
+                                  double* scale_red, const double* cam, const double* pts, const double* radius /* device */,
+                                  const ReduceBuf& rb, double* Vinv, double* tile_part, hipStream_t st);
 void launch_linearize_fused_intr(const DevProblem& P, const double* cam, const double* pts, const double* radius /* device */,
                                  const ReduceBuf& rb, double* Vinv, double* tile_part, hipStream_t st);
 // colsq_c[nc][6] / colsq_i[ng][10] += the squared column norms k_sum_items left by reduced index (Jacobi scaling)
@@ -274,6 +280,8 @@ void chol_plan_destroy(CholPlan* plan);
 // zero the tiles of A the plan's assembly / factorisation touch; false = dense plan (the caller clears everything)
 // tail / tail_count: a vector of doubles to zero in the same launch (null / 0: none)
 bool chol_plan_clear(const CholPlan* plan, double* A, int lda, hipStream_t st, double* tail = nullptr, size_t tail_count = 0);
+// S <- D S D, rhs <- D rhs, gc <- D gc, colsq <- D^2 colsq over the tiles chol_plan_clear clears (D = diag(s), n entries)
+void chol_plan_rescale(const CholPlan* plan, double* A, int lda, int n, const double* s, double* rhs, double* colsq, double* gc, hipStream_t st);
 int chol_plan_levels(const CholPlan* plan);
 double chol_plan_flops(const CholPlan* plan);   // FP64 flops of one solve on the plan (n^3 / 3 for the dense schedule)
 void chol_plan_solve(const CholPlan* plan, double* A, int lda, double* b, double* work, double* fail_flag, hipStream_t st);

@@ -818,10 +818,24 @@ int compute_scale(theia_ba_handle_s* h) {
   return 0;
 }
 
+// Where the Jacobi scaling is folded into the first linearisation of a run (enqueue_linearize(.., first_fold = true)) instead
+// of taking compute_scale()'s pass of its own.  The fold applies to: the fused plan without free intrinsics (k_lin_schur),
+// on one rank (the norms need no all-reduce), with every track inside a wave tile (no slow-path tracks), without camera
+// priors (their rows add to the column norms after the launch), with a reduced system to rescale, and with direct launches
+// (the opt-in graph replay would capture the first body as the replayed one).  Inner iterations take the fold too.
+// Everything else keeps the separate pass; THEIA_HIP_SCALE_PASS=1 forces it.
+bool scale_fold_applies(const theia_ba_handle_s* h) {
+  const char* pass = getenv("THEIA_HIP_SCALE_PASS");
+  const char* genv = getenv("THEIA_HIP_LM_GRAPH");
+  return h->use_fused && h->ni == 0 && h->n_fruns > 0 && h->n_sum_items > 0 && h->n > 0 && h->ntiles_main > 0 && !h->allreduce &&
+         h->long_ntracks == 0 && h->n_priors == 0 && !(genv && genv[0] == '1') && !(pass && pass[0] == '1');
+}
+
 // enqueue: clear, linearize + Schur, tile reduction, (all-reduce), LM diagonal.
 // The trust-region radius is read from the device-resident LM state.
 // slot < 0: no phase-timing events (graph capture, or timing not requested)
-int enqueue_linearize(theia_ba_handle_s* h, int slot = 0) {
+// first_fold: the first linearisation of a run where scale_fold_applies(): it also makes the Jacobi scaling
+int enqueue_linearize(theia_ba_handle_s* h, int slot = 0, bool first_fold = false) {
   const double* radius = &reinterpret_cast<const LmState*>(h->lm_state.p)->radius;
   h->P.intr = h->intr[h->cur].p; h->P.intr_cand = h->intr[1 - h->cur].p;
   // clear the reduced system: the tiles the K3 plan knows (assembly + fill) and the vector tail; everything else in
@@ -836,6 +850,16 @@ int enqueue_linearize(theia_ba_handle_s* h, int slot = 0) {
   // point may be the swept one, and the sweep reuses the candidate's blocks) and not with free intrinsics.
   const bool keep_blocks = h->use_fused && h->ni == 0 && !h->inner && !getenv("THEIA_HIP_CAM_PREP_ALWAYS");
   h->P.camrot_current = keep_blocks && h->camrot_valid;
+  if (first_fold) {
+    // unit scales in, scale_p / scale_c / scale_red out; the camera scaling factors out of the Schur complement exactly
+    // (S(D) = D S(I) D, rhs(D) = D rhs(I), the same for g_c and the column norms), so the assembled system is rescaled
+    // before the LM diagonal, and the state's per-camera blocks are rebuilt with the solve's scales for the back-substitution
+    launch_linearize_fused_first(h->P, h->ones_c.p, h->ones_p.p, h->scale_c.p, h->scale_p.p, h->scale_red.p, h->cam[h->cur].p,
+                                 h->pts[h->cur].p, radius, h->rb, h->Vinv.p, h->tile_part.p, h->stream);
+    chol_plan_rescale(h->plan, h->rb.S, h->n, h->n, h->scale_red.p, h->rb.rhs, h->rb.colsq, h->rb.gc, h->stream);
+    launch_cam_prep(h->P, h->cam[h->cur].p, h->P.intr, h->P.camrot, h->stream);
+    h->have_scale = true;
+  } else
   launch_linearize(h->P, h->cam[h->cur].p, h->pts[h->cur].p, radius, h->rb, h->Vinv.p, h->gp.p, h->tile_part.p, h->stream);
   h->camrot_valid = keep_blocks;
   if (slot >= 0) HIP_TRYR(hipEventRecord(h->ev[slot][5], h->stream));
@@ -2698,8 +2722,8 @@ int theia_hip_ba_run(theia_ba_handle h, theia_ba_summary* S) {
   int rc = h->plan_is_global ? 0 : sync_plan(h);
   if (rc) return rc;
   h->cur = 0;   // state = buffer 0, candidate = buffer 1 (accepted steps are copied back on the device)
-  rc = compute_scale(h);
-  if (rc) return rc;
+  const bool fold = scale_fold_applies(h);   // the first body makes the Jacobi scaling itself
+  if (!fold && (rc = compute_scale(h))) return rc;
   // device-resident LM state, control block and trace
   LmState st;
   std::memset(&st, 0, sizeof(st));
@@ -2741,10 +2765,10 @@ int theia_hip_ba_run(theia_ba_handle h, theia_ba_summary* S) {
   const LmCtl* dctl = reinterpret_cast<const LmCtl*>(h->lm_ctl.p);
   const int nxt = 1;
   // one LM iteration ("body"): linearise + Schur, solve, trial step, step control, accept
-  auto enqueue_body = [&](int slot) -> int {
+  auto enqueue_body = [&](int slot, bool first_fold = false) -> int {
     int r;
     if (slot >= 0) HIP_TRYR(hipEventRecord(h->ev[slot][0], h->stream));
-    if ((r = enqueue_linearize(h, slot))) return r;
+    if ((r = enqueue_linearize(h, slot, first_fold))) return r;
     if (slot >= 0) HIP_TRYR(hipEventRecord(h->ev[slot][1], h->stream));
     const bool fuse = !h->allreduce && !inner && slot < 0 && h->ntiles_main > 0;   // tile reduction inside the control kernel
     if ((r = enqueue_solve_and_backsub(h, slot, fuse))) return r;
@@ -2864,7 +2888,7 @@ int theia_hip_ba_run(theia_ba_handle h, theia_ba_summary* S) {
     if (nb <= 0) break;
     for (int b = 0; b < nb; ++b) {
       if (use_graph) HIP_TRYR(hipGraphLaunch(h->graph_exec, h->stream));
-      else if ((rc = enqueue_body(timing ? b : -1))) return rc;
+      else if ((rc = enqueue_body(timing ? b : -1, fold && bodies_enqueued == 0 && b == 0))) return rc;   // (a host-side fact: bodies are enqueued ahead of the device)
     }
     bodies_enqueued += nb;
     HIP_TRYR(hipGetLastError());   // a rejected launch configuration would otherwise go unnoticed
@@ -3195,7 +3219,8 @@ int theia_hip_dense_spd_solve(int32_t n, const double* A, const double* b, doubl
 int theia_hip_ba_reduced_system(theia_ba_handle h, double radius, int32_t* n_out, double* S, double* rhs, int64_t capacity) {
   if (h && h->idh) return set_error(THEIA_HIP_ERR_UNSUPPORTED, "inverse-depth handle: the reduced-system dump is not built in this mode");
   if (!h || !n_out) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "null argument");
-  int rc = compute_scale(h);
+  const bool fold = scale_fold_applies(h);   // the route run() takes for its first linearisation
+  int rc = fold ? 0 : compute_scale(h);
   if (rc) return rc;
   {
     LmState st;
@@ -3204,7 +3229,7 @@ int theia_hip_ba_reduced_system(theia_ba_handle h, double radius, int32_t* n_out
     HIP_TRYR(hipMemcpyAsync(h->lm_state.p, &st, sizeof(st), hipMemcpyHostToDevice, h->stream));
     HIP_TRYR(hipStreamSynchronize(h->stream));   // `st` is a stack object
   }
-  rc = enqueue_linearize(h);
+  rc = enqueue_linearize(h, 0, fold);
   if (rc) return rc;
   const int n = h->n;
   *n_out = n;

@@ -774,6 +774,43 @@ bool chol_plan_clear(const CholPlan* pl, double* A, int lda, hipStream_t st, dou
   return true;
 }
 
+namespace {
+// D S D of the assembled system, D = diag(s): blocks [0, ntiles) take one structure tile each (the clear list; every tile of
+// the n x n buffer, row-major, when there is none), the blocks beyond take the vectors behind the matrix, 1024 rows each:
+// rhs_i *= s_i, gc_i *= s_i, colsq_i *= s_i^2.
+__global__ __launch_bounds__(256) void k_sp_rescale(double* __restrict__ A, int lda, const int* __restrict__ items, int ntiles, int n,
+                                                    const double* __restrict__ s, double* __restrict__ rhs,
+                                                    double* __restrict__ colsq, double* __restrict__ gc) {
+  if ((int)blockIdx.x >= ntiles) {
+    const int b0 = ((int)blockIdx.x - ntiles) * 1024;
+    for (int i = b0 + (int)threadIdx.x; i < n && i < b0 + 1024; i += 256) {
+      const double si = s[i];
+      rhs[i] *= si; gc[i] *= si; colsq[i] *= si * si;
+    }
+    return;
+  }
+  int r0, h, c0, w;
+  if (items) { const int* it = items + 4 * blockIdx.x; r0 = it[0]; h = it[1]; c0 = it[2]; w = it[3]; }
+  else {
+    const int nt = (n + NB - 1) / NB;
+    r0 = NB * ((int)blockIdx.x / nt); c0 = NB * ((int)blockIdx.x % nt);
+    h = min(NB, n - r0); w = min(NB, n - c0);
+  }
+  for (int e = threadIdx.x; e < NB * NB; e += 256) {
+    const int r = e >> 6, c = e & 63;
+    if (r < h && c < w) A[(size_t)(r0 + r) * lda + c0 + c] *= s[r0 + r] * s[c0 + c];
+  }
+}
+}  // namespace
+
+void chol_plan_rescale(const CholPlan* pl, double* A, int lda, int n, const double* s, double* rhs, double* colsq, double* gc, hipStream_t st) {
+  if (n <= 0) return;
+  const bool tiles = pl && !pl->dense && pl->nclear > 0;   // (as chol_plan_clear: otherwise the whole buffer was cleared, and is walked)
+  const int nt = (n + NB - 1) / NB;
+  const int ntiles = tiles ? pl->nclear : nt * nt;
+  k_sp_rescale<<<ntiles + (n + 1023) / 1024, 256, 0, st>>>(A, lda, tiles ? pl->prog + pl->clear_off : nullptr, ntiles, n, s, rhs, colsq, gc);
+}
+
 void chol_plan_destroy(CholPlan* pl) { delete pl; }
 double chol_plan_flops(const CholPlan* pl) {
   if (!pl) return 0.0;
