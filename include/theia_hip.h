@@ -550,6 +550,67 @@ int theia_hip_lud_positions(int32_t num_views, const double* orientations, const
                             const int32_t* edges, const double* relative_translations, const theia_lud_options* options,
                             double* positions_out, theia_lud_summary* summary);
 
+/* LiGTPositionEstimator::EstimatePositions (global_pose_estimation/LiGT_position_estimator.cc:160-470, options
+ * LiGT_position_estimator.h:70-82; pybind sfm.cc:1728-1747, the LIGT position stage of the global pipeline, which skips the pairwise
+ * translation optimisation and the 1DSfM filter for it, global_reconstruction_estimator.cc:190-208): positions from the
+ * global orientations and the tracks' normalised features (csrc/ligt_positions.hip).  Per track of >= 3 observations the
+ * base pair maximises theta^2_ij = |[f_j]x R_j R_i' f_i|^2 (:227-255), every other observation gives one 3-row constraint
+ * B c_v1 + C c_v2 + D c_v3 = 0 (:257-289, :307-351), the normal equations H = sum [B C D]' [B C D] are summed on the 3 x 3
+ * blocks of the views (:94-121, :356-401) without the held view, and the positions are the unit eigenvector of H's
+ * smallest eigenvalue: one dense Cholesky of H + mu I, mu = n eps max diag H (the shift moves no eigenvector), then inverse
+ * iteration from x = 1 / sqrt(n) until |x_new - sign(x_new . x) x|_2 <= eigensolver_threshold or max_power_iterations
+ * (the reference declares both options and reads neither: it takes BDCSVD or Spectra's shift-invert, :190-207).  The sign
+ * is voted by the view pairs (:432-470): +1 when (R_first (c_second - c_first) / |.|) . relative_translation > 0, else -1,
+ * over the pairs whose two views are in the system; a negative total flips every position.  num_edges = 0: no vote.
+ * orientations [num_views][3] angle-axis (world -> camera); track t holds the observations track_offsets[t] ..
+ * track_offsets[t + 1] - 1 of obs_view / obs_feature ((x, y) of hnormalized(PixelToNormalizedCoordinates(pixel))).
+ * Where the reference depends on the order of its hash maps or threads, the rule here is: tracks in the caller's order
+ * and observations in the caller's order within a track; the base pair is the first maximal pair in lexicographic (i, j)
+ * order (strict >, from 0); a track with fewer than 3 observations, or whose best theta^2 is not positive (0 or NaN; the
+ * reference reads a default-constructed pair there), is skipped and enters no view into the system; the held view (index
+ * -1, at the origin) is v1 of the first track used; the other views are indexed in the order of the reference's
+ * insertions, v1, v2, v3 per constraint, constraints in (track, observation) order; every entry of H is summed in (track,
+ * observation) order by one owner, B'B, B'D and D'D within their track first, without floating-point atomics: two runs are
+ * bit-identical.  theta^2 of the pair search is evaluated as |R_i' f_i x R_j' f_j|^2, equal for orthonormal R; the
+ * observation of v3 itself, whose B = C = D vanish, is counted as a constraint and adds nothing.
+ * positions_out [num_views][3] and estimated_out [num_views]: a view of the system gets its position (the held view
+ * zeros) and 1; a view outside it gets 0 and its positions_out row is left untouched.  Optional outputs: base_pairs_out
+ * [num_tracks][2] observation indices within the track (-1 -1: skipped); system_out [3 (m - 1)]^2 row-major, H before
+ * the shift, both triangles (m = summary->num_views_in_system; size it for num_views); system_index_out [num_views]: the
+ * view's block in H, -1 held, -2 not in the system.
+ * THEIA_HIP_ERR_INVALID_ARGUMENT (nothing launched, outputs untouched; checked before the device is touched): a view index
+ * out of range, decreasing track_offsets, a track naming one view twice, a view pair out of range,
+ * max_power_iterations <= 0, a non-positive or non-finite eigensolver_threshold, no track with 3 observations; the same
+ * code, outputs untouched, after the pair search when every track was skipped for its theta^2.
+ * THEIA_HIP_ERR_OUT_OF_MEMORY: the dense (3 (m - 1) + 1)^2 array of doubles (twice with system_out), or the 72 bytes per
+ * 3 x 3 item (three per used track and three per constraint), do not fit on the device.  THEIA_HIP_ERR_INTERNAL: the
+ * factorisation failed even with the shift (outputs untouched, summary holds the shift). */
+typedef struct theia_ligt_options {   /* LiGTPositionEstimator::Options (LiGT_position_estimator.h:70-82) */
+  int32_t max_power_iterations, reserved;   /* 1000 */
+  double eigensolver_threshold;             /* 1e-8 */
+} theia_ligt_options;
+typedef struct theia_ligt_summary {
+  int32_t num_views_in_system;   /* m: the held view and the 3 (m - 1) unknowns' views */
+  int32_t tracks_used, tracks_skipped;
+  int32_t num_constraints;       /* len - 1 per used track, as the reference counts its triplets */
+  int32_t iterations, converged; /* converged: the step test passed within max_power_iterations */
+  int32_t sign_votes, flipped;   /* the total of the +1 / -1 votes; 1 = every position was negated */
+  double eigenvalue;             /* the last iterate's Rayleigh quotient minus the shift */
+  double shift;                  /* mu */
+  double setup_ms, assemble_ms, factor_ms, eig_ms;   /* set-up = checks, uploads, pair search, plan */
+} theia_ligt_summary;
+int theia_hip_ligt_positions(
+    int32_t num_views, const double* orientations /*[num_views][3] angle-axis, world -> camera*/,
+    int32_t num_tracks, const int32_t* track_offsets /*[num_tracks+1]*/,
+    const int32_t* obs_view /*[num_obs]*/, const double* obs_feature /*[num_obs][2], normalised*/,
+    int32_t num_edges, const int32_t* edges /*[num_edges][2]*/,
+    const double* relative_translations /*[num_edges][3]; 0 edges = no sign vote*/,
+    const theia_ligt_options* options /*NULL = defaults*/,
+    double* positions_out /*[num_views][3]*/, uint8_t* estimated_out /*[num_views]*/,
+    int32_t* base_pairs_out /*optional [num_tracks][2]*/,
+    double* system_out /*optional*/, int32_t* system_index_out /*optional [num_views]*/,
+    theia_ligt_summary* summary);
+
 /* FilterViewPairsFromRelativeTranslation (sfm/filter_view_pairs_from_relative_translation.cc:264-312, step 6 of the global
  * pipeline, sfm/global_reconstruction_estimator.cc:126-138; options: filter_view_pairs_from_relative_translation.h:48-66):
  * Wilson & Snavely's 1DSfM outlier test on the device (csrc/view_pair_filters.hip).  The translations are rotated into the

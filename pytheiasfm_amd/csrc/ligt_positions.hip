@@ -1,0 +1,601 @@
+// ligt_positions.hip -- LiGTPositionEstimator (global_pose_estimation/LiGT_position_estimator.cc:160-470; Cai et al.,
+// "A Pose-only Solution to Visual Reconstruction and Navigation"): global positions from the global orientations and the
+// tracks' normalised features alone, on the device in FP64.
+//
+// Per track of at least three observations the base pair (v1, v3) is the observation pair of largest
+//   theta^2_ij = |[f_j]x R_j R_i' f_i|^2                                                   (GetBestBaseViews, :227-255)
+// and every other observation (v2, f2) of the track gives one constraint B c_v1 + C c_v2 + D c_v3 = 0 on the camera
+// positions (CalculateBCDForTrack, :257-289):
+//   C = [f1]x R31 f3 a32' R_v2,   a32 = ([R32 f3]x f2)' [f2]x,   B = |[f2]x R32 f3|^2 [f1]x R_v1,   D = -(B + C)
+// with R31 = R_v1 R_v3', R32 = R_v2 R_v3'.  The normal equations H = sum [B C D]' [B C D] on the 3 x 3 blocks of
+// (v1, v2, v3), without the rows and columns of the held view (:94-121, :356-401), are a dense view-by-view matrix of
+// the shape of the BA's reduced camera system; the positions are the eigenvector of H's smallest eigenvalue.
+//
+// Stages:
+//   k_rotations   one thread per view: the rotation matrix, once
+//   k_rays        one thread per observation: the world ray R_v' f.  R is orthonormal, so theta^2_ij = |ray_i x ray_j|^2
+//                 up to rounding, and the pair search needs no matrix at all
+//   k_base_pairs  one wavefront per track: the lanes stride over the len (len - 1) / 2 pairs in lexicographic (i, j)
+//                 order, each keeps its first maximum, and the wave's arg-max takes the lowest pair index among equals
+//                 (wave_reduce.h); base_pairs = observation indices within the track, -1 -1 = track skipped
+//   plan (host)   after the 8-byte-per-track download: the view indexing in the reference's insertion order and, per
+//                 3 x 3 block of H's lower triangle, the list of the items that feed it, in (track, observation) order
+//   k_items       one thread per used track: B, C, D of every constraint in registers; B'B, B'D and D'D of a track all
+//                 land on the (v1, v3) blocks and are summed within the track first -- three items per track, and three
+//                 per constraint (C'C, B'C, C'D)
+//   k_blocks      one thread per non-empty block: adds its items in order, writes the lower triangle
+//   k_shift       mu = kShiftMultiple n eps max diag H on the diagonal (H's smallest eigenvalue is a rounding error of
+//                 either sign on noise-free data; the shift moves no eigenvector)
+//   dense_cholesky_factor once, then per inverse iteration dense_cholesky_solve_factored and k_iterate: normalise,
+//                 |x_new - s x_old|_2 with s = sign(x_new . x_old), and the stop flag on the device (the pattern of
+//                 lud_positions.hip: the host reads the flag once per chunk of iterations)
+//   k_sign_vote   one launch over the view pairs (FlipSignOfPositionsIfNecessary, :432-470): integer votes, block sums,
+//                 one integer atomic per workgroup
+//
+// Determinism: no floating-point atomics.  Every entry of H is a sum in (track, observation) order by one owner, every
+// norm a fixed tree (block_sum), the votes are integers.  Two runs on one input are bit-identical.
+#include "ransac_device.h"
+#include "ba_kernels.h"
+#include "wave_reduce.h"
+#include "device_util.h"
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cfloat>
+#include <vector>
+
+namespace thip {
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kTracksPerBlock = kThreads / 64;   // k_base_pairs: one wavefront per track
+constexpr int kChunk = 4;                        // inverse iterations enqueued between two reads of the `done` flag
+// mu = kShiftMultiple * n * eps * max diag H (DESIGN.md 3.6f has the rule and the scenes it was chosen on)
+constexpr double kShiftMultiple = 1.0;
+
+struct LigtState {
+  int done, converged, iterations, pad;
+  double diff, eigenvalue, shift, max_diag;
+};
+
+__global__ __launch_bounds__(kThreads) void k_rotations(int n, const double* __restrict__ aa, double* __restrict__ R) {
+  const int v = blockIdx.x * kThreads + threadIdx.x;
+  if (v >= n) return;
+  double r[9];
+  rsc::angle_axis_to_rot(aa + 3 * (size_t)v, r);
+#pragma unroll
+  for (int k = 0; k < 9; ++k) R[9 * (size_t)v + k] = r[k];
+}
+
+__global__ __launch_bounds__(kThreads) void k_rays(int num_obs, const int* __restrict__ obs_view,
+                                                   const double* __restrict__ feat, const double* __restrict__ R,
+                                                   double* __restrict__ ray) {
+  const int o = blockIdx.x * kThreads + threadIdx.x;
+  if (o >= num_obs) return;
+  const double* r = R + 9 * (size_t)obs_view[o];
+  const double x = feat[2 * (size_t)o], y = feat[2 * (size_t)o + 1];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) ray[3 * (size_t)o + c] = (r[c] * x + r[3 + c] * y) + r[6 + c];
+}
+
+__device__ __forceinline__ void cross3(const double* a, const double* b, double* c) {
+  c[0] = a[1] * b[2] - a[2] * b[1];
+  c[1] = a[2] * b[0] - a[0] * b[2];
+  c[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// first pair index of row i among the pairs (i, j > i) of L observations
+__device__ __forceinline__ long long pair_row_start(long long i, long long L) { return i * (2 * L - i - 1) / 2; }
+
+__global__ __launch_bounds__(kThreads) void k_base_pairs(int num_tracks, const int* __restrict__ off,
+                                                         const double* __restrict__ ray, int2* __restrict__ base) {
+  const int t = blockIdx.x * kTracksPerBlock + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (t >= num_tracks) return;   // wave-uniform
+  const int o0 = off[t];
+  const long long L = off[t + 1] - o0;
+  if (L < 3) {
+    if (lane == 0) base[t] = make_int2(-1, -1);
+    return;
+  }
+  const long long P = L * (L - 1) / 2;
+  double best = -1.0;        // no candidate: 0 and NaN never beat the reference's starting value 0 under `>`
+  long long best_p = P;
+  if (lane < P) {
+    // decode this lane's first pair, then advance by 64 pairs per step
+    long long p = lane;
+    const double s = 2.0 * (double)L - 1.0;
+    long long i = (long long)((s - sqrt(fmax(0.0, s * s - 8.0 * (double)p))) * 0.5);
+    i = max(0LL, min(i, L - 2));
+    while (i > 0 && pair_row_start(i, L) > p) --i;
+    while (i < L - 2 && pair_row_start(i + 1, L) <= p) ++i;
+    long long j = i + 1 + (p - pair_row_start(i, L));
+    double th_best = 0.0;
+    for (; p < P; p += 64) {
+      const double* ri = ray + 3 * (size_t)(o0 + i);
+      const double* rj = ray + 3 * (size_t)(o0 + j);
+      double c[3];
+      cross3(ri, rj, c);
+      const double th = (c[0] * c[0] + c[1] * c[1]) + c[2] * c[2];
+      if (th > th_best) { th_best = th; best = th; best_p = p; }
+      j += 64;
+      while (j >= L && i < L - 2) { ++i; j = j - L + i + 1; }
+    }
+  }
+  const double m = wave_max_abs(best);   // -1.0 when no lane holds a positive theta^2
+  // the lowest pair index among the lanes that hold the maximum: min p = ~max(~p), high word first
+  const bool mine = m > 0.0 && best == m;
+  const unsigned hi = mine ? ~(unsigned)((unsigned long long)best_p >> 32) : 0u;
+  const unsigned hm = wave_max_u32(hi);
+  const unsigned lo = (mine && hi == hm) ? ~(unsigned)((unsigned long long)best_p & 0xffffffffull) : 0u;
+  const unsigned lm = wave_max_u32(lo);
+  if (lane == 0) {
+    if (!(m > 0.0)) {
+      base[t] = make_int2(-1, -1);
+    } else {
+      const long long p = (long long)(((unsigned long long)(~hm) << 32) | (unsigned long long)(~lm));
+      const double s = 2.0 * (double)L - 1.0;
+      long long i = (long long)((s - sqrt(fmax(0.0, s * s - 8.0 * (double)p))) * 0.5);
+      i = max(0LL, min(i, L - 2));
+      while (i > 0 && pair_row_start(i, L) > p) --i;
+      while (i < L - 2 && pair_row_start(i + 1, L) <= p) ++i;
+      base[t] = make_int2((int)i, (int)(i + 1 + (p - pair_row_start(i, L))));
+    }
+  }
+}
+
+// out = X' Y (3 x 3, row-major)
+__device__ __forceinline__ void atb(const double* X, const double* Y, double* out) {
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[3 * r + c] = (X[r] * Y[c] + X[3 + r] * Y[3 + c]) + X[6 + r] * Y[6 + c];
+}
+
+__device__ __forceinline__ void store9(double* __restrict__ dst, const double* v) {
+#pragma unroll
+  for (int k = 0; k < 9; ++k) dst[k] = v[k];
+}
+
+// One thread per used track.  Items of track t from item_base[t]: [0] sum B'B, [1] sum B'D, [2] sum D'D, then per
+// constraint (every observation but the two of the base pair, in order) C'C, B'C, C'D.  The observation of v3 itself
+// gives B = C = D = 0 in exact arithmetic and is no constraint here.
+__global__ __launch_bounds__(kThreads) void k_items(int num_tracks, const int* __restrict__ off,
+                                                    const int* __restrict__ obs_view, const double* __restrict__ feat,
+                                                    const double* __restrict__ R, const double* __restrict__ ray,
+                                                    const int2* __restrict__ base, const long long* __restrict__ item_base,
+                                                    double* __restrict__ items) {
+  const int t = blockIdx.x * kThreads + threadIdx.x;
+  if (t >= num_tracks) return;
+  const long long ib = item_base[t];
+  if (ib < 0) return;
+  const int o0 = off[t], L = off[t + 1] - o0;
+  const int bi = base[t].x, bj = base[t].y;
+  const double f1[3] = {feat[2 * (size_t)(o0 + bi)], feat[2 * (size_t)(o0 + bi) + 1], 1.0};
+  const double* R1 = R + 9 * (size_t)obs_view[o0 + bi];
+  const double z3[3] = {ray[3 * (size_t)(o0 + bj)], ray[3 * (size_t)(o0 + bj) + 1], ray[3 * (size_t)(o0 + bj) + 2]};
+  // u = [f1]x R31 f3 = f1 x (R1 z3),  M1 = [f1]x R1
+  double g[3], u[3], M1[9];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) g[r] = (R1[3 * r] * z3[0] + R1[3 * r + 1] * z3[1]) + R1[3 * r + 2] * z3[2];
+  cross3(f1, g, u);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const double col[3] = {R1[c], R1[3 + c], R1[6 + c]};
+    double m[3];
+    cross3(f1, col, m);
+    M1[c] = m[0]; M1[3 + c] = m[1]; M1[6 + c] = m[2];
+  }
+  double S11[9], S13[9], S33[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) { S11[k] = 0.0; S13[k] = 0.0; S33[k] = 0.0; }
+  double* out = items + 9 * (size_t)(ib + 3);
+  for (int k = 0; k < L; ++k) {
+    if (k == bi || k == bj) continue;
+    const double f2[3] = {feat[2 * (size_t)(o0 + k)], feat[2 * (size_t)(o0 + k) + 1], 1.0};
+    const double* R2 = R + 9 * (size_t)obs_view[o0 + k];
+    double h[3], q[3], a32[3], w[3], e[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) h[r] = (R2[3 * r] * z3[0] + R2[3 * r + 1] * z3[1]) + R2[3 * r + 2] * z3[2];   // R32 f3
+    cross3(h, f2, q);      // [R32 f3]x f2
+    cross3(q, f2, a32);    // (q' [f2]x)'
+#pragma unroll
+    for (int c = 0; c < 3; ++c) w[c] = (a32[0] * R2[c] + a32[1] * R2[3 + c]) + a32[2] * R2[6 + c];   // a32' R2
+    cross3(f2, h, e);
+    const double th = (e[0] * e[0] + e[1] * e[1]) + e[2] * e[2];
+    double B[9], Cm[9], D[9], T[9];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        B[3 * r + c] = th * M1[3 * r + c];
+        Cm[3 * r + c] = u[r] * w[c];
+        D[3 * r + c] = -(B[3 * r + c] + Cm[3 * r + c]);
+      }
+    atb(B, B, T);
+#pragma unroll
+    for (int q9 = 0; q9 < 9; ++q9) S11[q9] += T[q9];
+    atb(B, D, T);
+#pragma unroll
+    for (int q9 = 0; q9 < 9; ++q9) S13[q9] += T[q9];
+    atb(D, D, T);
+#pragma unroll
+    for (int q9 = 0; q9 < 9; ++q9) S33[q9] += T[q9];
+    atb(Cm, Cm, T); store9(out, T);
+    atb(B, Cm, T); store9(out + 9, T);
+    atb(Cm, D, T); store9(out + 18, T);
+    out += 27;
+  }
+  double* head = items + 9 * (size_t)ib;
+  store9(head, S11); store9(head + 9, S13); store9(head + 18, S33);
+}
+
+// One thread per non-empty block of H's lower triangle: its items in (track, observation) order.  seg_item = item
+// index * 2 + (1: the item is added transposed).  A diagonal block writes its own lower triangle only.
+__global__ __launch_bounds__(kThreads) void k_blocks(int num_blocks, const int2* __restrict__ block_rc,
+                                                     const long long* __restrict__ seg_off, const int* __restrict__ seg_item,
+                                                     const double* __restrict__ items, int lda, double* __restrict__ H) {
+  const int b = blockIdx.x * kThreads + threadIdx.x;
+  if (b >= num_blocks) return;
+  double acc[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (long long k = seg_off[b]; k < seg_off[b + 1]; ++k) {
+    const int it = seg_item[k];
+    const double* v = items + 9 * (size_t)(it >> 1);
+    if (it & 1) {
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) acc[3 * r + c] += v[3 * c + r];
+    } else {
+#pragma unroll
+      for (int q = 0; q < 9; ++q) acc[q] += v[q];
+    }
+  }
+  const int2 rc = block_rc[b];
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      if (rc.x != rc.y || c <= r) H[(size_t)(3 * rc.x + r) * lda + 3 * rc.y + c] = acc[3 * r + c];
+}
+
+// system_out: both triangles of the n x n system from the lower triangle (before the shift)
+__global__ __launch_bounds__(kThreads) void k_full_system(int n, int lda, const double* __restrict__ H,
+                                                          double* __restrict__ full) {
+  const size_t k = (size_t)blockIdx.x * kThreads + threadIdx.x;
+  if (k >= (size_t)n * n) return;
+  const int r = (int)(k / n), c = (int)(k % n);
+  full[k] = r >= c ? H[(size_t)r * lda + c] : H[(size_t)c * lda + r];
+}
+
+// One workgroup: max diag H, then mu = multiple n eps max diag H on the diagonal; x = b = 1 / sqrt(n).
+__global__ __launch_bounds__(kThreads) void k_shift(int n, int lda, double* __restrict__ H, double multiple,
+                                                    double* __restrict__ x, double* __restrict__ b,
+                                                    LigtState* __restrict__ st) {
+  __shared__ double red[kThreads];
+  double m = 0.0;
+  for (int k = threadIdx.x; k < n; k += kThreads) m = fmax(m, H[(size_t)k * lda + k]);
+  red[threadIdx.x] = m;
+  __syncthreads();
+  for (int s = kThreads / 2; s > 0; s >>= 1) {
+    if (threadIdx.x < s) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + s]);
+    __syncthreads();
+  }
+  const double max_diag = red[0];
+  const double mu = ((multiple * (double)n) * DBL_EPSILON) * max_diag;
+  const double x0 = 1.0 / sqrt((double)n);
+  for (int k = threadIdx.x; k < n; k += kThreads) {
+    H[(size_t)k * lda + k] += mu;
+    x[k] = x0; b[k] = x0;
+  }
+  if (threadIdx.x == 0) { st->shift = mu; st->max_diag = max_diag; }
+}
+
+// One workgroup, after y = (H + mu I)^-1 x: x_new = y / |y|, the step |x_new - s x|_2 with s = sign(x_new . x), the
+// Rayleigh quotient of y as the eigenvalue estimate, the iteration count and the stop flag.  b = x_new for the next solve.
+__global__ __launch_bounds__(kThreads) void k_iterate(int n, const double* __restrict__ y, double* __restrict__ x,
+                                                      double* __restrict__ b, double threshold,
+                                                      LigtState* __restrict__ st) {
+  __shared__ double red[kThreads];
+  if (st->done) return;
+  double yy = 0.0, yx = 0.0;
+  for (int k = threadIdx.x; k < n; k += kThreads) { yy += y[k] * y[k]; yx += y[k] * x[k]; }
+  const double syy = block_sum<kThreads>(yy, red), syx = block_sum<kThreads>(yx, red);
+  __shared__ double bc[2];
+  if (threadIdx.x == 0) { bc[0] = sqrt(syy); bc[1] = syx; }
+  __syncthreads();
+  const double norm = bc[0], dot = bc[1];
+  if (!(norm > 0.0) || !isfinite(norm)) {   // a breakdown of the solve: stop, not converged, x stays
+    if (threadIdx.x == 0) { st->iterations += 1; st->done = 1; st->converged = 0; st->diff = norm; }
+    return;
+  }
+  const double s = dot < 0.0 ? -1.0 : 1.0;
+  double dd = 0.0;
+  for (int k = threadIdx.x; k < n; k += kThreads) {
+    const double xn = y[k] / norm, d = xn - s * x[k];
+    dd += d * d;
+    x[k] = xn; b[k] = xn;
+  }
+  const double sdd = block_sum<kThreads>(dd, red);
+  if (threadIdx.x == 0) {
+    const double diff = sqrt(sdd);
+    st->iterations += 1;
+    st->diff = diff;
+    st->eigenvalue = dot / syy - st->shift;
+    if (diff <= threshold) { st->done = 1; st->converged = 1; }
+  }
+}
+
+// VectorsAreSameDirection (:130-139) per view pair whose two views are in the system: +1 when
+// (R_first (c_second - c_first) / |.|) . position_2 > 0, else -1.  idx: -1 held (the origin), -2 not in the system.
+__global__ __launch_bounds__(kThreads) void k_sign_vote(int E, const int2* __restrict__ edges, const int* __restrict__ idx,
+                                                        const double* __restrict__ x, const double* __restrict__ R,
+                                                        const double* __restrict__ rel, int* __restrict__ votes) {
+  __shared__ int red[kThreads];
+  const int e = blockIdx.x * kThreads + threadIdx.x;
+  int vote = 0;
+  if (e < E) {
+    const int2 ij = edges[e];
+    const int a = idx[ij.x], c = idx[ij.y];
+    if (a != -2 && c != -2) {
+      double d[3];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) d[k] = (c >= 0 ? x[3 * (size_t)c + k] : 0.0) - (a >= 0 ? x[3 * (size_t)a + k] : 0.0);
+      const double nrm = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+      if (nrm > 0.0) { d[0] /= nrm; d[1] /= nrm; d[2] /= nrm; }
+      const double* r = R + 9 * (size_t)ij.x;
+      double dot = 0.0;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) dot += ((r[3 * k] * d[0] + r[3 * k + 1] * d[1]) + r[3 * k + 2] * d[2]) * rel[3 * (size_t)e + k];
+      vote = dot > 0.0 ? 1 : -1;
+    }
+  }
+  red[threadIdx.x] = vote;
+  __syncthreads();
+  for (int s = kThreads / 2; s > 0; s >>= 1) {
+    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0 && red[0] != 0) atomicAdd(votes, red[0]);
+}
+
+}  // namespace
+}  // namespace thip
+
+using namespace thip;
+
+extern "C" int theia_hip_ligt_positions(int32_t num_views, const double* orientations, int32_t num_tracks,
+                                        const int32_t* track_offsets, const int32_t* obs_view, const double* obs_feature,
+                                        int32_t num_edges, const int32_t* edges, const double* relative_translations,
+                                        const theia_ligt_options* options, double* positions_out, uint8_t* estimated_out,
+                                        int32_t* base_pairs_out, double* system_out, int32_t* system_index_out,
+                                        theia_ligt_summary* summary) {
+  const auto t_start = std::chrono::steady_clock::now();
+  const int n = num_views, T = num_tracks, E = num_edges;
+  theia_ligt_options o{1000, 0, 1e-8};
+  if (options) o = *options;
+  // ---- refusals, before the device is touched
+  if (n < 1 || !orientations || !positions_out || !estimated_out || !summary)
+    return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "no views, or a null output");
+  if (T < 1 || !track_offsets || !obs_view || !obs_feature) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "no tracks");
+  if (E < 0 || (E > 0 && (!edges || !relative_translations)))
+    return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "view pairs without their arrays");
+  if (o.max_power_iterations <= 0) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "max_power_iterations must be > 0");
+  if (!(o.eigensolver_threshold > 0.0) || !std::isfinite(o.eigensolver_threshold))
+    return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "eigensolver_threshold must be positive and finite");
+  if (track_offsets[0] < 0) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "track_offsets must start at >= 0");
+  for (int t = 0; t < T; ++t)
+    if (track_offsets[t + 1] < track_offsets[t])
+      return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "track_offsets decrease at track %d", t);
+  const int num_obs = track_offsets[T];
+  {
+    std::vector<int> seen(n, -1);
+    bool any_long = false;
+    for (int t = 0; t < T; ++t) {
+      any_long |= track_offsets[t + 1] - track_offsets[t] >= 3;
+      for (int k = track_offsets[t]; k < track_offsets[t + 1]; ++k) {
+        const int v = obs_view[k];
+        if (v < 0 || v >= n) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "observation %d names view %d of %d", k, v, n);
+        if (seen[v] == t) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "track %d names view %d twice", t, v);
+        seen[v] = t;
+      }
+    }
+    for (int e = 0; e < 2 * E; ++e)
+      if (edges[e] < 0 || edges[e] >= n)
+        return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "view pair %d names view %d of %d", e / 2, edges[e], n);
+    if (!any_long) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "no track with three observations: no track used");
+  }
+
+  int rc;
+  if ((rc = thip::ensure_device())) return rc;
+  theia_ligt_summary sm{};
+  hipStream_t st = nullptr;
+  DevBuf<double> d_aa, d_feat, d_R, d_ray;
+  DevBuf<int> d_off, d_obs_view;
+  DevBuf<int2> d_base;
+  if ((rc = d_aa.up(orientations, 3 * (size_t)n)) || (rc = d_off.up(track_offsets, (size_t)T + 1)) ||
+      (rc = d_obs_view.up(obs_view, num_obs)) || (rc = d_feat.up(obs_feature, 2 * (size_t)num_obs)) ||
+      (rc = d_R.alloc(9 * (size_t)n)) || (rc = d_ray.alloc(3 * (size_t)num_obs)) || (rc = d_base.alloc(T)))
+    return rc;
+
+  // ---- set-up: rotations, rays, base pairs, plan
+  k_rotations<<<grid_of(n, kThreads), kThreads, 0, st>>>(n, d_aa.p, d_R.p);
+  k_rays<<<grid_of(num_obs, kThreads), kThreads, 0, st>>>(num_obs, d_obs_view.p, d_feat.p, d_R.p, d_ray.p);
+  k_base_pairs<<<grid_of(T, kTracksPerBlock), kThreads, 0, st>>>(T, d_off.p, d_ray.p, d_base.p);
+  HIP_TRY(hipGetLastError());
+  std::vector<int2> base(T);
+  HIP_TRY(hipMemcpy(base.data(), d_base.p, sizeof(int2) * (size_t)T, hipMemcpyDeviceToHost));
+
+  // the view indexing: v1, v2, v3 per constraint, constraints in (track, observation) order; the first view is held
+  std::vector<int> idx(n, -2);
+  std::vector<long long> item_base(T, -1);
+  int m = 0;
+  long long num_items = 0, num_constraints = 0;
+  for (int t = 0; t < T; ++t) {
+    const int o0 = track_offsets[t], L = track_offsets[t + 1] - o0;
+    const int bi = base[t].x, bj = base[t].y;
+    if (bi < 0) { sm.tracks_skipped += 1; continue; }
+    if (L < 3 || bj <= bi || bj >= L) return set_error(THEIA_HIP_ERR_INTERNAL, "base pair of track %d out of range", t);
+    sm.tracks_used += 1;
+    const int v1 = obs_view[o0 + bi], v3 = obs_view[o0 + bj];
+    for (int k = 0; k < L; ++k) {
+      if (k == bi) continue;
+      const int v2 = obs_view[o0 + k];
+      if (idx[v1] == -2) idx[v1] = m++ - 1;
+      if (idx[v2] == -2) idx[v2] = m++ - 1;
+      if (idx[v3] == -2) idx[v3] = m++ - 1;
+    }
+    item_base[t] = num_items;
+    num_items += 3 + 3 * (long long)(L - 2);
+    num_constraints += L - 1;
+  }
+  if (sm.tracks_used == 0) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "no track has a pair of positive theta^2: no track used");
+  if (num_items >= (1LL << 30)) return set_error(THEIA_HIP_ERR_OUT_OF_MEMORY, "%lld 3 x 3 items: too many constraints", num_items);
+  const int mf = m - 1, n3 = 3 * mf;   // free views
+  sm.num_views_in_system = m;
+  sm.num_constraints = (int32_t)std::min<long long>(num_constraints, INT32_MAX);
+  if (mf < 1) return set_error(THEIA_HIP_ERR_INTERNAL, "a used track with one view");
+
+  // the dense system first: when it does not fit, that is the answer, before the host builds lists of its size
+  const int lda = n3 + 1;   // row n3: the factorisation's right-hand-side row (zero, unused)
+  const size_t dense = (size_t)(n3 + 1) * lda;
+  DevBuf<double> d_H, d_work, d_flag, d_full;
+  if ((rc = d_H.alloc(dense)) || (rc = d_work.alloc(dense_cholesky_workspace(n3))) || (rc = d_flag.alloc(1)) ||
+      (system_out && (rc = d_full.alloc((size_t)n3 * n3))))
+    return rc;
+
+  // the segment list: per block (row >= col, free views) of the lower triangle its items, by a stable counting sort
+  const size_t tri = (size_t)mf * (mf + 1) / 2;
+  std::vector<long long> seg_start(tri + 1, 0);
+  auto block_of = [](int a, int b) { return a >= b ? (size_t)a * (a + 1) / 2 + b : (size_t)b * (b + 1) / 2 + a; };
+  // an item (va, vb) holds X' Y with X on va and Y on vb: it lands on block (idx va, idx vb), transposed when that lies above
+  auto visit = [&](auto&& emit) {
+    for (int t = 0; t < T; ++t) {
+      if (item_base[t] < 0) continue;
+      const int o0 = track_offsets[t], L = track_offsets[t + 1] - o0;
+      const int bi = base[t].x, bj = base[t].y;
+      const int i1 = idx[obs_view[o0 + bi]], i3 = idx[obs_view[o0 + bj]];
+      long long it = item_base[t];
+      emit(i1, i1, it); emit(i1, i3, it + 1); emit(i3, i3, it + 2);
+      it += 3;
+      for (int k = 0; k < L; ++k) {
+        if (k == bi || k == bj) continue;
+        const int i2 = idx[obs_view[o0 + k]];
+        emit(i2, i2, it); emit(i1, i2, it + 1); emit(i2, i3, it + 2);
+        it += 3;
+      }
+    }
+  };
+  visit([&](int a, int b, long long) { if (a >= 0 && b >= 0) seg_start[block_of(a, b) + 1] += 1; });
+  for (size_t k = 0; k < tri; ++k) seg_start[k + 1] += seg_start[k];
+  std::vector<int> seg_item((size_t)std::max<long long>(1, seg_start[tri]));
+  {
+    std::vector<long long> fill(seg_start.begin(), seg_start.end() - 1);
+    visit([&](int a, int b, long long it) {
+      if (a >= 0 && b >= 0) seg_item[(size_t)fill[block_of(a, b)]++] = (int)(2 * it + (a < b ? 1 : 0));
+    });
+  }
+  std::vector<int2> block_rc;
+  std::vector<long long> seg_off(1, 0);
+  for (int a = 0; a < mf; ++a)
+    for (int b = 0; b <= a; ++b) {
+      const size_t k = block_of(a, b);
+      if (seg_start[k + 1] > seg_start[k]) { block_rc.push_back(make_int2(a, b)); seg_off.push_back(seg_start[k + 1]); }
+    }
+  const int num_blocks = (int)block_rc.size();
+
+  DevBuf<double> d_items, d_x, d_b, d_y, d_T, d_rel;
+  DevBuf<long long> d_item_base, d_seg_off;
+  DevBuf<int> d_seg_item, d_idx, d_votes;
+  DevBuf<int2> d_block_rc, d_edges;
+  DevBuf<LigtState> d_st;
+  if ((rc = d_items.alloc(9 * (size_t)num_items)) ||
+      (rc = d_item_base.up(item_base.data(), T)) || (rc = d_seg_off.up(seg_off.data(), seg_off.size())) ||
+      (rc = d_seg_item.up(seg_item.data(), seg_item.size())) || (rc = d_block_rc.up(block_rc.data(), block_rc.size())) ||
+      (rc = d_idx.up(idx.data(), n)) || (rc = d_votes.alloc(1)) || (rc = d_edges.up(edges, E)) ||
+      (rc = d_rel.up(relative_translations, 3 * (size_t)E)) || (rc = d_x.alloc(n3)) || (rc = d_b.alloc(n3)) ||
+      (rc = d_y.alloc(n3)) || (rc = d_T.alloc(n3)) || (rc = d_st.alloc(1)))
+    return rc;
+  HIP_TRY(hipMemsetAsync(d_H.p, 0, sizeof(double) * dense, st));
+  HIP_TRY(hipMemsetAsync(d_flag.p, 0, sizeof(double), st));
+  HIP_TRY(hipMemsetAsync(d_votes.p, 0, sizeof(int), st));
+  HIP_TRY(hipMemsetAsync(d_st.p, 0, sizeof(LigtState), st));
+  HIP_TRY(hipStreamSynchronize(st));
+  sm.setup_ms = ms_since(t_start);
+
+  // ---- assembly
+  const auto t_assemble = std::chrono::steady_clock::now();
+  k_items<<<grid_of(T, kThreads), kThreads, 0, st>>>(T, d_off.p, d_obs_view.p, d_feat.p, d_R.p, d_ray.p, d_base.p,
+                                                    d_item_base.p, d_items.p);
+  k_blocks<<<grid_of(num_blocks, kThreads), kThreads, 0, st>>>(num_blocks, d_block_rc.p, d_seg_off.p, d_seg_item.p,
+                                                              d_items.p, lda, d_H.p);
+  if (system_out)
+    k_full_system<<<grid_of((size_t)n3 * n3, kThreads), kThreads, 0, st>>>(n3, lda, d_H.p, d_full.p);
+  k_shift<<<1, kThreads, 0, st>>>(n3, lda, d_H.p, kShiftMultiple, d_x.p, d_b.p, d_st.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(st));
+  sm.assemble_ms = ms_since(t_assemble);
+
+  // ---- factor H + mu I once
+  const auto t_factor = std::chrono::steady_clock::now();
+  dense_cholesky_factor(n3, 1, d_H.p, lda, d_work.p, d_flag.p, st);
+  HIP_TRY(hipGetLastError());
+  double flag = 0.0;
+  HIP_TRY(hipMemcpy(&flag, d_flag.p, sizeof(double), hipMemcpyDeviceToHost));
+  sm.factor_ms = ms_since(t_factor);
+  LigtState hs{};
+  if (flag != 0.0) {
+    HIP_TRY(hipMemcpy(&hs, d_st.p, sizeof(LigtState), hipMemcpyDeviceToHost));
+    sm.shift = hs.shift;
+    *summary = sm;
+    return set_error(THEIA_HIP_ERR_INTERNAL, "the Cholesky factorisation of H + mu I failed (mu = %g)", hs.shift);
+  }
+
+  // ---- inverse iteration from x = 1 / sqrt(n)
+  const auto t_eig = std::chrono::steady_clock::now();
+  const int* done = &d_st.p->done;
+  for (int enqueued = 0; enqueued < o.max_power_iterations;) {
+    const int chunk = std::min(kChunk, o.max_power_iterations - enqueued);
+    for (int c = 0; c < chunk; ++c) {
+      dense_cholesky_solve_factored(n3, d_H.p, lda, d_work.p, 1, d_b.p, n3, d_T.p, d_y.p, n3, st, done);
+      k_iterate<<<1, kThreads, 0, st>>>(n3, d_y.p, d_x.p, d_b.p, o.eigensolver_threshold, d_st.p);
+    }
+    enqueued += chunk;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(&hs, d_st.p, sizeof(LigtState), hipMemcpyDeviceToHost));
+    if (hs.done) break;
+  }
+  // ---- sign vote and scatter
+  if (E > 0) {
+    k_sign_vote<<<grid_of(E, kThreads), kThreads, 0, st>>>(E, d_edges.p, d_idx.p, d_x.p, d_R.p, d_rel.p, d_votes.p);
+    HIP_TRY(hipGetLastError());
+  }
+  std::vector<double> x(n3);
+  int votes = 0;
+  HIP_TRY(hipMemcpy(x.data(), d_x.p, sizeof(double) * (size_t)n3, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&votes, d_votes.p, sizeof(int), hipMemcpyDeviceToHost));
+  std::vector<double> full;
+  if (system_out) {
+    full.resize((size_t)n3 * n3);
+    HIP_TRY(hipMemcpy(full.data(), d_full.p, sizeof(double) * full.size(), hipMemcpyDeviceToHost));
+  }
+  sm.eig_ms = ms_since(t_eig);
+  sm.iterations = hs.iterations;
+  sm.converged = hs.converged;
+  sm.eigenvalue = hs.eigenvalue;
+  sm.shift = hs.shift;
+  sm.sign_votes = votes;
+  sm.flipped = votes < 0;
+  const double sign = votes < 0 ? -1.0 : 1.0;
+  for (int v = 0; v < n; ++v) {
+    estimated_out[v] = idx[v] != -2;
+    if (idx[v] == -2) continue;
+    for (int c = 0; c < 3; ++c) positions_out[3 * (size_t)v + c] = idx[v] >= 0 ? sign * x[3 * (size_t)idx[v] + c] : 0.0;
+  }
+  if (base_pairs_out)
+    for (int t = 0; t < T; ++t) { base_pairs_out[2 * (size_t)t] = base[t].x; base_pairs_out[2 * (size_t)t + 1] = base[t].y; }
+  if (system_out) std::copy(full.begin(), full.end(), system_out);
+  if (system_index_out) std::copy(idx.begin(), idx.end(), system_index_out);
+  *summary = sm;
+  return 0;
+}

@@ -6,7 +6,9 @@ global_pose_estimation/least_unsquared_deviation_position_estimator.{h,cc}).
 The solve runs on the device through theia_hip_robust_rotation_averaging (csrc/rotation_averaging.hip).  The object
 keeps the reference's state across calls: constraints accumulate over EstimateRotations / AddRelativeRotationConstraint
 calls on one object, and the view fixed by default on the first call stays fixed on later ones.  The positions run
-through theia_hip_lud_positions (csrc/lud_positions.hip).
+through theia_hip_lud_positions (csrc/lud_positions.hip), or, from the tracks' features and without the pairs' relative
+translations, through theia_hip_ligt_positions (pytheia.sfm.LiGTPositionEstimator, sfm.cc:1728-1747 ->
+global_pose_estimation/LiGT_position_estimator.{h,cc}; csrc/ligt_positions.hip).
 
 Between them sit the two view-graph filters (sfm/filter_view_pairs_from_orientation.{h,cc} after the rotations,
 sfm/filter_view_pairs_from_relative_translation.{h,cc}, the 1DSfM test, before the positions): csrc/view_pair_filters.hip
@@ -215,6 +217,149 @@ class LeastUnsquaredDeviationPositionEstimator:
         capi.check(rc)
         self.last_summary = s
         return {v: pos[k].copy() for k, v in enumerate(views)}
+
+
+class LiGTPositionEstimatorOptions:  # LiGT_position_estimator.h:70-82
+    def __init__(self):
+        self.num_threads = 1              # held and ignored: the tracks are lanes and wavefronts of the launches
+        self.max_power_iterations = 1000  # the reference declares these two and reads neither; here they stop the
+        self.eigensolver_threshold = 1e-8  # inverse iteration
+        self.max_num_views_svd = 500      # held and ignored: one dense Cholesky at every size
+
+    def to_c(self):
+        o = capi.LigtOptions()
+        o.max_power_iterations = int(self.max_power_iterations)
+        o.eigensolver_threshold = float(self.eigensolver_threshold)
+        return o
+
+
+def ligt_positions(orientations, track_offsets, obs_view, obs_feature, edges=None, relative_translations=None,
+                   options=None, positions_out=None, want=()):
+    """theia_hip_ligt_positions on arrays: orientations [n][3] angle-axis, track t = observations track_offsets[t] ..
+    track_offsets[t + 1] - 1 of obs_view [N] / obs_feature [N][2] (normalised), edges [E][2] view indices with
+    relative_translations [E][3] (TwoViewInfo::position_2) for the sign vote, or None.  want: names of the optional
+    outputs to fetch, out of "base_pairs", "system", "system_index".  Returns (return code, positions [n][3], estimated
+    [n] bool, LigtSummary, dict of the outputs asked for); a view outside the system keeps its positions_out row (zeros
+    without positions_out); on a refusal nothing is written and the dict is empty."""
+    o = (options or LiGTPositionEstimatorOptions()).to_c()
+    aa = np.ascontiguousarray(np.asarray(orientations, dtype=np.float64).reshape(-1, 3))
+    off = np.ascontiguousarray(np.asarray(track_offsets, dtype=np.int32).reshape(-1))
+    ov = np.ascontiguousarray(np.asarray(obs_view, dtype=np.int32).reshape(-1))
+    of = np.ascontiguousarray(np.asarray(obs_feature, dtype=np.float64).reshape(-1, 2))
+    if off.shape[0] < 1:
+        raise ValueError("track_offsets needs num_tracks + 1 entries")
+    if ov.shape[0] != of.shape[0] or (off.shape[0] > 1 and int(off.max()) > ov.shape[0]):
+        raise ValueError("one view and one feature per observation, and offsets within them")
+    e = np.zeros((0, 2), dtype=np.int32) if edges is None else np.asarray(edges, dtype=np.int32).reshape(-1, 2)
+    t = np.zeros((0, 3)) if relative_translations is None else np.asarray(relative_translations, dtype=np.float64).reshape(-1, 3)
+    e, t = np.ascontiguousarray(e), np.ascontiguousarray(t)
+    if t.shape[0] != e.shape[0]:
+        raise ValueError("one relative translation per edge")
+    unknown = set(want) - {"base_pairs", "system", "system_index"}
+    if unknown:
+        raise ValueError(f"unknown outputs {sorted(unknown)}")
+    n, T = aa.shape[0], off.shape[0] - 1
+    out = np.zeros((n, 3)) if positions_out is None else positions_out
+    if out.shape != (n, 3) or out.dtype != np.float64 or not out.flags["C_CONTIGUOUS"]:
+        raise ValueError("positions_out must be a C-contiguous float64 [n][3] array")
+    est = np.zeros(n, dtype=np.uint8)
+    bufs = {}
+    if "base_pairs" in want:
+        bufs["base_pairs"] = np.full((T, 2), -1, dtype=np.int32)
+    if "system" in want:   # sized for every view in the system; cut to [3 (m - 1)]^2 below
+        bufs["system"] = np.zeros(max(1, 3 * (n - 1)) ** 2)
+    if "system_index" in want:
+        bufs["system_index"] = np.full(n, -2, dtype=np.int32)
+    s = capi.LigtSummary()
+    rc = capi.lib().theia_hip_ligt_positions(
+        n, capi.ptr(aa, C.c_double), T, capi.ptr(off, C.c_int32), capi.ptr(ov, C.c_int32), capi.ptr(of, C.c_double),
+        e.shape[0], capi.ptr(e, C.c_int32), capi.ptr(t, C.c_double), C.byref(o), capi.ptr(out, C.c_double),
+        capi.ptr(est, C.c_uint8), capi.ptr(bufs.get("base_pairs"), C.c_int32), capi.ptr(bufs.get("system"), C.c_double),
+        capi.ptr(bufs.get("system_index"), C.c_int32), C.byref(s))
+    if rc == 0 and "system" in bufs:
+        k = 3 * (s.num_views_in_system - 1)
+        bufs["system"] = bufs["system"][:k * k].reshape(k, k).copy()
+    return rc, out, est.astype(bool), s, (bufs if rc == 0 else {})
+
+
+def _pinhole_normalized(intrinsics, uv):
+    """Camera::PixelToNormalizedCoordinates(pixel).hnormalized() of the pinhole model on arrays
+    (ransac.Camera.pixel_to_normalized, observation by observation): intrinsics [N][>= 7], uv [N][2]."""
+    f, a, sk, cx, cy, k1, k2 = (intrinsics[:, k] for k in range(7))
+    y = (uv[:, 1] - cy) / (f * a)
+    x = (uv[:, 0] - cx - y * sk) / f
+    ux, uy = x.copy(), y.copy()
+    active = np.ones(len(x), dtype=bool)
+    for _ in range(100):
+        if not active.any():
+            break
+        r2 = ux * ux + uy * uy
+        d = 1.0 + r2 * (k1 + k2 * r2)
+        nx, ny = x / d, y / d
+        moved = (np.abs(nx - ux) >= 1e-10) | (np.abs(ny - uy) >= 1e-10)
+        ux = np.where(active, nx, ux); uy = np.where(active, ny, uy)
+        active &= moved
+    return np.column_stack([ux, uy])
+
+
+class LiGTPositionEstimator:
+    """LiGTPositionEstimator(options, reconstruction) with EstimatePositions(view_pairs, orientations) -> dict, as
+    pyTheia binds it.  reconstruction: the array-backed sfm.Reconstruction (obs_view, obs_track and obs_uv are read; ids
+    are dense indices); view_pairs: {(id1, id2): TwoViewInfo}, whose position_2 only votes on the sign; orientations:
+    {view_id: angle-axis}.
+
+    The tracks are taken in increasing id and a track's observations in the order the reconstruction lists them
+    (the reference walks hash containers).  normalized_features [N][2]: the observations'
+    hnormalized(PixelToNormalizedCoordinates(pixel)); without it the pixels of pinhole groups are un-projected here and any
+    other model raises, as ransac.Camera.pixel_to_normalized does.  An observation of a view without an orientation
+    raises (the reference's orientations_.at() throws).  The dict holds the views of the system: those of the tracks
+    that were used."""
+
+    def __init__(self, options, reconstruction, normalized_features=None):
+        if not options.num_threads > 0:   # CHECK_GT(options.num_threads, 0)
+            raise capi.TheiaHipError(capi.THEIA_HIP_ERR_INVALID_ARGUMENT, "num_threads must be > 0")
+        self.options = options
+        self.reconstruction = reconstruction
+        self.normalized_features = normalized_features
+        self.last_summary = None
+
+    def _features(self):
+        r = self.reconstruction
+        if self.normalized_features is not None:
+            f = np.asarray(self.normalized_features, dtype=np.float64).reshape(-1, 2)
+            if f.shape[0] != len(r.obs_view):
+                raise ValueError("one normalized feature per observation")
+            return f
+        groups = np.asarray(r.view_group)[r.obs_view]
+        if np.any(np.asarray(r.group_model)[groups] != 0):
+            raise capi.TheiaHipError(capi.THEIA_HIP_ERR_UNSUPPORTED,
+                                     "pixel_to_normalized mirrors the pinhole model only; pass normalized_features for the others")
+        return _pinhole_normalized(np.asarray(r.group_intrinsics, dtype=np.float64)[groups],
+                                   np.asarray(r.obs_uv, dtype=np.float64).reshape(-1, 2))
+
+    def EstimatePositions(self, view_pairs, orientations):
+        r = self.reconstruction
+        ov = np.asarray(r.obs_view, dtype=np.int64)
+        ot = np.asarray(r.obs_track, dtype=np.int64)
+        feats = self._features()
+        missing = sorted({int(v) for v in np.unique(ov)} - {int(v) for v in orientations})
+        if missing:
+            raise capi.TheiaHipError(capi.THEIA_HIP_ERR_INVALID_ARGUMENT, f"view {missing[0]} has no orientation")
+        views = sorted(int(v) for v in orientations)
+        pos = {v: k for k, v in enumerate(views)}
+        lut = np.full(max(views) + 1 if views else 1, -1, dtype=np.int64)
+        lut[views] = np.arange(len(views))
+        order = np.argsort(ot, kind="stable")   # tracks in increasing id, observations in the reconstruction's order
+        ntracks = r.NumTracks()
+        offsets = np.concatenate([[0], np.cumsum(np.bincount(ot, minlength=ntracks))]).astype(np.int32)
+        keys = [k for k in view_pairs if int(k[0]) in pos and int(k[1]) in pos]
+        edges = np.array([(pos[int(a)], pos[int(b)]) for a, b in keys], dtype=np.int32).reshape(-1, 2)
+        rel = np.array([np.asarray(view_pairs[k].position_2, dtype=np.float64).reshape(3) for k in keys]).reshape(-1, 3)
+        aa = np.array([np.asarray(orientations[v], dtype=np.float64).reshape(3) for v in views]).reshape(-1, 3)
+        rc, p, est, s, _ = ligt_positions(aa, offsets, lut[ov[order]], feats[order], edges, rel, self.options)
+        capi.check(rc)
+        self.last_summary = s
+        return {v: p[k].copy() for k, v in enumerate(views) if est[k]}
 
 
 class FilterViewPairsFromRelativeTranslationOptions:  # filter_view_pairs_from_relative_translation.h:48-66

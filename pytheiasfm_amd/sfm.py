@@ -23,6 +23,7 @@ from .synth import angle_axis_to_matrix
 from .global_pose import (GlobalRotationEstimatorType, RobustRotationEstimator,  # noqa: F401  (pyTheia's names)
                           RobustRotationEstimatorOptions, GlobalPositionEstimatorType,
                           LeastUnsquaredDeviationPositionEstimator, LeastUnsquaredDeviationPositionEstimatorOptions,
+                          LiGTPositionEstimator, LiGTPositionEstimatorOptions,
                           FilterViewPairsFromOrientation, FilterViewPairsFromRelativeTranslation,
                           FilterViewPairsFromRelativeTranslationOptions)
 

@@ -1,0 +1,172 @@
+"""GPU: theia_hip_ligt_positions (csrc/ligt_positions.hip) against the numpy restatement (tests/ligt_positions_ref.py) on
+the scenes of tests/ligt_scenes.py: base pairs, the system H and its index map, noise-free recovery of the ground truth,
+the eigenvector on noisy scenes, the sign vote, bit reproducibility, the masks, and the Python class.
+
+Bounds: per entry |H_gpu - H_ref| <= 64 eps sum |contribution|, a contribution being every product of magnitudes the
+entry is a signed sum of (the restatement's abs_sum: H assembled from constraint_abs).  The sum has to reach into B, C
+and D: their cross products cancel where v2 and v3 see the point under a small parallax, the restatement's own H is no
+more accurate than eps times that sum there (two orders of evaluating R32 f3 differ by 840 eps sum |M_a' M_b| on the
+70-view track, by 2.4 eps of this sum), and a wrong block, sign, order or missing term is an error of order 1 against
+either.  The recovery error and the
+sine of the angle to the reference eigenvector <= 8 n eps lambda_max / (lambda_2 - lambda_1) of the reference's spectrum
+(Davis-Kahan with the factor's rounding), plus eigensolver_threshold on the noisy scenes.  The recovery error is the
+largest view error relative to the norm of the whole solution vector, which is what that bound speaks of."""
+import types
+
+import numpy as np
+import pytest
+
+from pytheiasfm_amd import global_pose, sfm
+from tests import ligt_scenes as ls
+
+pytestmark = pytest.mark.gpu
+
+EPS = np.finfo(float).eps
+WANT = ("base_pairs", "system", "system_index")
+_runs = {}
+
+
+def run(name):
+    """One library call per scene, shared by the tests (not to be modified)."""
+    if name not in _runs:
+        s, _ = ls.scene(name)
+        out = np.full((s["num_views"], 3), 7.0)
+        rc, p, est, summ, extra = global_pose.ligt_positions(s["orientations"], s["track_offsets"], s["obs_view"],
+                                                             s["obs_feature"], s["edges"], s["rel"], positions_out=out,
+                                                             want=WANT)
+        assert rc == 0, rc
+        _runs[name] = (p, est, summ, extra)
+    return _runs[name]
+
+
+@pytest.mark.parametrize("name", list(ls.SCENES))
+def test_base_pairs_and_counts(name):
+    s, r = ls.scene(name)
+    _, _, summ, extra = run(name)
+    assert np.array_equal(extra["base_pairs"], r["base_pairs"])
+    used = int((r["base_pairs"][:, 0] >= 0).sum())
+    assert (summ.tracks_used, summ.tracks_skipped) == (used, len(r["base_pairs"]) - used)
+    assert summ.num_views_in_system == r["num_views_in_system"] and summ.num_constraints == r["constraints"]
+
+
+@pytest.mark.parametrize("name", list(ls.SCENES))
+def test_system(name):
+    _, r = ls.scene(name)
+    _, _, _, extra = run(name)
+    H = extra["system"]
+    assert np.array_equal(extra["system_index"], r["index"])
+    assert H.shape == r["H"].shape
+    assert np.array_equal(H, H.T)                       # symmetric to the bit
+    excess = np.abs(H - r["H"]) - 64 * EPS * r["abs_sum"]
+    print(f"{name}: max |H_gpu - H_ref| / (eps sum |contribution|) = "
+          f"{(np.abs(H - r['H']) / (EPS * np.maximum(r['abs_sum'], np.finfo(float).tiny))).max():.2f}")
+    assert np.all(excess <= 0.0)
+
+
+def _fit(scene, positions, estimated, index):
+    held = int(np.nonzero(index == -1)[0][0])
+    d = (scene["positions"] - scene["positions"][held])[estimated]
+    p = positions[estimated]
+    s = float((p * d).sum() / (d * d).sum())
+    return s, float(np.linalg.norm(p - s * d, axis=1).max() / np.linalg.norm(s * d))
+
+
+@pytest.mark.parametrize("name", ls.NOISE_FREE + ("v20_extra", "v70_long", "v20_unused"))
+def test_noise_free_recovery(name):
+    s, r = ls.scene(name)
+    p, est, summ, _ = run(name)
+    scale, err = _fit(s, p, est, r["index"])
+    bound = ls.recovery_bound(r)
+    print(f"{name}: scale {scale:.3e}, relative error {err:.2e}, bound {bound:.2e}, iterations {summ.iterations}, "
+          f"eigenvalue {summ.eigenvalue:.3e}, shift {summ.shift:.3e}")
+    assert summ.converged == 1 and 1 <= summ.iterations <= 1000
+    assert scale > 0.0
+    assert err <= bound
+    held = int(np.nonzero(r["index"] == -1)[0][0])
+    assert np.all(p[held] == 0.0)
+
+
+def _same_vote(summ, r):
+    """The eigenvector's sign before the vote is the solver's own (eigh's there, the iteration's start vector here), so
+    the two totals agree up to that sign; each flips exactly when its total is negative."""
+    assert abs(summ.sign_votes) == abs(r["votes"]) and summ.sign_votes != 0
+    assert summ.flipped == int(summ.sign_votes < 0) and bool(r["flipped"]) == (r["votes"] < 0)
+
+
+def _unit_vector(p, index):
+    x = np.zeros(3 * int(index.max() + 1))
+    for v in np.nonzero(index >= 0)[0]:
+        x[3 * index[v]:3 * index[v] + 3] = p[v]
+    return x
+
+
+@pytest.mark.parametrize("name", ls.NOISY)
+def test_noisy_eigenvector(name):
+    _, r = ls.scene(name)
+    p, _, summ, _ = run(name)
+    x = _unit_vector(p, r["index"])
+    assert abs(np.linalg.norm(x) - 1.0) <= 8 * EPS * np.sqrt(len(x))
+    c = abs(float(x @ r["vector"]))
+    sine = float(np.linalg.norm(x - np.sign(x @ r["vector"]) * r["vector"]))   # = 2 sin(angle / 2) >= sin(angle)
+    bound = ls.recovery_bound(r) + 1e-8
+    print(f"{name}: sine {sine:.2e} (cos {c:.15f}), bound {bound:.2e}, iterations {summ.iterations}, "
+          f"eigenvalue {summ.eigenvalue:.6e} against {r['eigenvalues'][0]:.6e}")
+    assert summ.converged == 1 and summ.iterations <= 1000
+    assert sine <= bound
+    _same_vote(summ, r)
+    assert float(x @ _unit_vector(r["positions"], r["index"])) > 0.0   # after the vote both point the same way
+
+
+def test_sign_vote():
+    s, r = ls.scene("v20")
+    p, _, summ, _ = run("v20")
+    _same_vote(summ, r)
+    assert float((p * r["positions"]).sum()) > 0.0
+    rc, pn, _, sn, _ = global_pose.ligt_positions(s["orientations"], s["track_offsets"], s["obs_view"], s["obs_feature"],
+                                                  s["edges"], -s["rel"])
+    assert rc == 0 and np.array_equal(pn, -p)
+    assert sn.sign_votes == -summ.sign_votes and sn.flipped == 1 - summ.flipped
+    rc, p0, _, s0, _ = global_pose.ligt_positions(s["orientations"], s["track_offsets"], s["obs_view"], s["obs_feature"])
+    assert rc == 0 and s0.sign_votes == 0 and s0.flipped == 0
+    assert np.array_equal(p0, -p if summ.flipped else p)     # no edges: the eigenvector as iterated, no flip
+
+
+def test_bit_reproducible():
+    s, _ = ls.scene("v70_long")
+    p, est, summ, extra = run("v70_long")
+    rc, p2, est2, s2, extra2 = global_pose.ligt_positions(s["orientations"], s["track_offsets"], s["obs_view"],
+                                                          s["obs_feature"], s["edges"], s["rel"],
+                                                          positions_out=np.full((s["num_views"], 3), 7.0), want=WANT)
+    assert rc == 0
+    assert np.array_equal(p, p2) and np.array_equal(est, est2) and np.array_equal(extra["system"], extra2["system"])
+    assert (summ.iterations, summ.eigenvalue, summ.shift) == (s2.iterations, s2.eigenvalue, s2.shift)
+
+
+def test_views_outside_the_system_are_left_alone():
+    _, r = ls.scene("v20_unused")
+    p, est, summ, extra = run("v20_unused")
+    assert list(np.nonzero(~est)[0]) == [20, 21] and np.array_equal(est, r["estimated"])
+    assert np.all(p[20:] == 7.0)                   # as passed in
+    assert np.all(extra["system_index"][20:] == -2) and summ.num_views_in_system == 20
+    assert summ.tracks_skipped == 2
+
+
+def test_python_class_against_the_array_call():
+    s, r = ls.scene("v20")
+    p, est, _, _ = run("v20")
+    nv, nt = s["num_views"], len(s["track_offsets"]) - 1
+    rec = sfm.Reconstruction()
+    rec.cam_ext = np.zeros((nv, 6)); rec.view_estimated = np.ones(nv, dtype=bool)
+    rec.view_group = np.zeros(nv, dtype=np.int32); rec.group_model = np.zeros(1, dtype=np.int32)
+    rec.points = np.zeros((nt, 4)); rec.track_estimated = np.ones(nt, dtype=bool)
+    rec.obs_view = s["obs_view"]; rec.obs_uv = np.zeros((len(s["obs_view"]), 2))
+    rec.obs_track = np.repeat(np.arange(nt, dtype=np.int32), np.diff(s["track_offsets"]))
+    pairs = {(int(a), int(b)): types.SimpleNamespace(position_2=t) for (a, b), t in zip(s["edges"], s["rel"])}
+    orientations = {v: s["orientations"][v] for v in range(nv)}
+    e = sfm.LiGTPositionEstimator(sfm.LiGTPositionEstimatorOptions(), rec, normalized_features=s["obs_feature"])
+    got = e.EstimatePositions(pairs, orientations)
+    assert sorted(got) == list(range(nv))
+    # the dict drops a repeated (a, b) key of the random pairs: the votes may differ, the vector may not
+    q = np.array([got[v] for v in range(nv)])
+    assert np.array_equal(q, p) or np.array_equal(q, -p)
+    assert e.last_summary.converged == 1
