@@ -48,11 +48,6 @@ struct ViewBatch {
   double function_tolerance, gradient_tolerance, parameter_tolerance, max_radius;
 };
 
-struct ViewOut {
-  int success, term, iters, nsucc;
-  double initial_cost, final_cost;
-};
-
 // residual-only cost of the camera `ext` over the wave's observation range
 __device__ double view_cost(const ViewBatch& B, int p, const double* ext, int lane, double* invalid) {
   const int64_t beg = B.offsets[p], end = B.counts ? beg + B.counts[p] : B.offsets[p + 1];
@@ -149,7 +144,7 @@ __device__ bool solve6(const double* H, const double* d, const double* g, double
   return true;
 }
 
-__global__ __launch_bounds__(256) void k_view_lm(ViewBatch B, ViewOut* __restrict__ out) {
+__global__ __launch_bounds__(256) void k_view_lm(ViewBatch B, BatchLmOut* __restrict__ out) {
   const int lane = threadIdx.x & 63;
   const int p = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (p >= B.num) return;
@@ -157,8 +152,8 @@ __global__ __launch_bounds__(256) void k_view_lm(ViewBatch B, ViewOut* __restric
   double x[6];
 #pragma unroll
   for (int q = 0; q < 6; ++q) x[q] = B.cam[(size_t)p * 6 + q];
-  ViewOut R;
-  R.success = 0; R.term = THEIA_TERM_NO_CONVERGENCE; R.iters = 0; R.nsucc = 0; R.initial_cost = 0.0; R.final_cost = 0.0;
+  BatchLmOut R;
+  R.success = 0; R.term = THEIA_TERM_NO_CONVERGENCE; R.iters = 0; R.nsucc = 0; R.c0 = 0.0; R.c1 = 0.0;
   double scale[6] = {1.0, 1.0, 1.0, 1.0, 1.0, 1.0};
   double H[21], g[6], x_cost, invalid;
   // Jacobi scaling from the column norms at the initial point (once per solve)
@@ -184,9 +179,9 @@ __global__ __launch_bounds__(256) void k_view_lm(ViewBatch B, ViewOut* __restric
     }
     if (first) {
       first = false;
-      R.initial_cost = x_cost;
+      R.c0 = x_cost;
       minimum_cost = x_cost;
-      if (invalid > 0.0 || !isfinite(x_cost)) { term = THEIA_TERM_FAILURE; R.final_cost = x_cost; break; }
+      if (invalid > 0.0 || !isfinite(x_cost)) { term = THEIA_TERM_FAILURE; R.c1 = x_cost; break; }
       if (all_const) { term = THEIA_TERM_CONVERGENCE; break; }
     }
     if (iter >= B.max_iterations) { term = THEIA_TERM_NO_CONVERGENCE; break; }
@@ -243,7 +238,7 @@ __global__ __launch_bounds__(256) void k_view_lm(ViewBatch B, ViewOut* __restric
     }
   }
   R.iters = iter; R.term = term; R.success = term != THEIA_TERM_FAILURE;
-  if (term != THEIA_TERM_FAILURE) R.final_cost = minimum_cost;
+  if (term != THEIA_TERM_FAILURE) R.c1 = minimum_cost;
   if (lane == 0) {
     out[p] = R;
 #pragma unroll
@@ -340,12 +335,12 @@ __device__ bool solve_small(const double* H, const double* d, const double* g, d
 }
 
 template <int PD>
-__global__ __launch_bounds__(64) void k_track_lm(TrackBatch B, ViewOut* __restrict__ out) {
+__global__ __launch_bounds__(64) void k_track_lm(TrackBatch B, BatchLmOut* __restrict__ out) {
   constexpr int NT = PD * (PD + 1) / 2;
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= B.num) return;
-  ViewOut R;
-  R.success = 1; R.term = THEIA_TERM_CONVERGENCE; R.iters = 0; R.nsucc = 0; R.initial_cost = 0.0; R.final_cost = 0.0;
+  BatchLmOut R;
+  R.success = 1; R.term = THEIA_TERM_CONVERGENCE; R.iters = 0; R.nsucc = 0; R.c0 = 0.0; R.c1 = 0.0;
   double X[4];
   for (int q = 0; q < 4; ++q) X[q] = B.pts[4 * (size_t)p + q];
   double scale[PD], H[NT], g[PD], x_cost;
@@ -354,7 +349,7 @@ __global__ __launch_bounds__(64) void k_track_lm(TrackBatch B, ViewOut* __restri
   const bool is_const = (B.pt_const && B.pt_const[p]) || B.offsets[p + 1] == B.offsets[p];
   track_linearize<PD>(B, p, X, scale, H, g, &x_cost, &invalid, true);
   if (is_const) {   // nothing to optimise: report the cost of its residual blocks
-    R.initial_cost = R.final_cost = x_cost;
+    R.c0 = R.c1 = x_cost;
     out[p] = R;
     return;
   }
@@ -373,8 +368,8 @@ __global__ __launch_bounds__(64) void k_track_lm(TrackBatch B, ViewOut* __restri
     }
     if (first) {
       first = false;
-      R.initial_cost = x_cost; minimum_cost = x_cost;
-      if (invalid || !isfinite(x_cost)) { term = THEIA_TERM_FAILURE; R.final_cost = x_cost; break; }
+      R.c0 = x_cost; minimum_cost = x_cost;
+      if (invalid || !isfinite(x_cost)) { term = THEIA_TERM_FAILURE; R.c1 = x_cost; break; }
     }
     if (iter >= B.max_iterations) { term = THEIA_TERM_NO_CONVERGENCE; break; }
     if (step_successful && gmax <= B.gradient_tolerance) { term = THEIA_TERM_CONVERGENCE; break; }
@@ -429,7 +424,7 @@ __global__ __launch_bounds__(64) void k_track_lm(TrackBatch B, ViewOut* __restri
     }
   }
   R.iters = iter; R.term = term; R.success = term != THEIA_TERM_FAILURE;
-  if (term != THEIA_TERM_FAILURE) R.final_cost = minimum_cost;
+  if (term != THEIA_TERM_FAILURE) R.c1 = minimum_cost;
   out[p] = R;
   for (int q = 0; q < 4; ++q) B.pts[4 * (size_t)p + q] = X[q];
 }
@@ -649,7 +644,7 @@ __global__ __launch_bounds__(64) void k_track_triangulate(TrackBatch B, const do
 // device-resident variant for callers inside the library (LO-RANSAC)
 int views_batch_device(int num, const int64_t* d_offsets, const int* d_counts, const double* d_uv, const double* d_si, const double* d_X,
                        double* d_cam, const double* d_intr, const int* d_model, const uint8_t* d_mask,
-                       const theia_ba_options* o, void* d_out /* ViewOut[num] */, hipStream_t st) {
+                       const theia_ba_options* o, void* d_out /* BatchLmOut[num] */, hipStream_t st) {
   ViewBatch B;
   B.num = num; B.offsets = d_offsets; B.counts = d_counts; B.uv = reinterpret_cast<const double2*>(d_uv);
   B.si = reinterpret_cast<const double2*>(d_si); B.X = reinterpret_cast<const double4*>(d_X);
@@ -657,13 +652,13 @@ int views_batch_device(int num, const int64_t* d_offsets, const int* d_counts, c
   B.loss_type = o->loss_function_type; B.loss_width = o->robust_loss_width; B.max_iterations = o->max_num_iterations;
   B.function_tolerance = o->function_tolerance; B.gradient_tolerance = o->gradient_tolerance;
   B.parameter_tolerance = o->parameter_tolerance; B.max_radius = o->max_trust_region_radius;
-  k_view_lm<<<(num + 3) / 4, 256, 0, st>>>(B, static_cast<ViewOut*>(d_out));
+  k_view_lm<<<(num + 3) / 4, 256, 0, st>>>(B, static_cast<BatchLmOut*>(d_out));
   return 0;
 }
-size_t views_batch_out_bytes() { return sizeof(ViewOut); }
+size_t views_batch_out_bytes() { return sizeof(BatchLmOut); }
 void views_batch_unpack(const void* host_out, int i, int* success, int* term, int* iters, int* nsucc, double* c0, double* c1) {
-  const ViewOut& r = static_cast<const ViewOut*>(host_out)[i];
-  *success = r.success; *term = r.term; *iters = r.iters; *nsucc = r.nsucc; *c0 = r.initial_cost; *c1 = r.final_cost;
+  const BatchLmOut& r = static_cast<const BatchLmOut*>(host_out)[i];
+  *success = r.success; *term = r.term; *iters = r.iters; *nsucc = r.nsucc; *c0 = r.c0; *c1 = r.c1;
 }
 
 }  // namespace thip
@@ -790,7 +785,7 @@ extern "C" int theia_hip_ba_tracks_batch(const theia_ba_problem* p, const theia_
   if ((rc = d_off.up(off.data(), np + 1)) || (rc = d_uv.up(uv.data(), uv.size())) || (rc = d_oc.up(oc.data(), oc.size())) ||
       (rc = d_cam.up(p->cam_ext, 6 * (size_t)p->num_cameras)) || (rc = d_intr.up(p->intrinsics, THEIA_MAX_INTRINSICS * (size_t)p->num_groups)) ||
       (rc = d_gm.up(p->group_model, p->num_groups)) || (rc = d_cg.up(p->cam_group, p->num_cameras)) ||
-      (rc = d_pts.up(p->points, 4 * (size_t)np)) || (rc = d_out.alloc(sizeof(ViewOut) * (size_t)np)))
+      (rc = d_pts.up(p->points, 4 * (size_t)np)) || (rc = d_out.alloc(sizeof(BatchLmOut) * (size_t)np)))
     return rc;
   if (p->obs_sqrt_info && (rc = d_si.up(si.data(), si.size()))) return rc;
   if (p->point_const && (rc = d_pc.up(p->point_const, np))) return rc;
@@ -803,9 +798,9 @@ extern "C" int theia_hip_ba_tracks_batch(const theia_ba_problem* p, const theia_
   B.function_tolerance = o->function_tolerance; B.gradient_tolerance = o->gradient_tolerance;
   B.parameter_tolerance = o->parameter_tolerance; B.max_radius = o->max_trust_region_radius;
   const double t0 = now_s();
-  if (o->use_homogeneous_point_parametrization) k_track_lm<3><<<(np + 63) / 64, 64>>>(B, reinterpret_cast<ViewOut*>(d_out.p));
-  else k_track_lm<4><<<(np + 63) / 64, 64>>>(B, reinterpret_cast<ViewOut*>(d_out.p));
-  std::vector<char> h_out(sizeof(ViewOut) * (size_t)np);
+  if (o->use_homogeneous_point_parametrization) k_track_lm<3><<<(np + 63) / 64, 64>>>(B, reinterpret_cast<BatchLmOut*>(d_out.p));
+  else k_track_lm<4><<<(np + 63) / 64, 64>>>(B, reinterpret_cast<BatchLmOut*>(d_out.p));
+  std::vector<char> h_out(sizeof(BatchLmOut) * (size_t)np);
   HIP_TRY(hipMemcpy(h_out.data(), d_out.p, h_out.size(), hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(p->points, d_pts.p, sizeof(double) * 4 * (size_t)np, hipMemcpyDeviceToHost));
   const double dt = now_s() - t0;
@@ -881,7 +876,7 @@ extern "C" int theia_hip_estimate_tracks(const theia_ba_problem* p, const double
       (rc = d_cam.up(p->cam_ext, 6 * (size_t)p->num_cameras)) || (rc = d_intr.up(p->intrinsics, THEIA_MAX_INTRINSICS * (size_t)p->num_groups)) ||
       (rc = d_gm.up(p->group_model, p->num_groups)) || (rc = d_cg.up(p->cam_group, p->num_cameras)) ||
       (rc = d_pts.up(p->points, 4 * (size_t)np)) || (rc = d_rays.up(rays.data(), rays.size())) || (rc = d_status.alloc(np)) ||
-      (rc = d_out.alloc(sizeof(ViewOut) * (size_t)np)) || (rc = d_err.alloc(np)) || (rc = d_cos.alloc(np)) || (rc = d_nb.alloc(np)))
+      (rc = d_out.alloc(sizeof(BatchLmOut) * (size_t)np)) || (rc = d_err.alloc(np)) || (rc = d_cos.alloc(np)) || (rc = d_nb.alloc(np)))
     return rc;
   if (p->obs_sqrt_info && (rc = d_si.up(G.si.data(), G.si.size()))) return rc;
   if (p->point_const && (rc = d_pc.up(p->point_const, np))) return rc;
@@ -907,9 +902,9 @@ extern "C" int theia_hip_estimate_tracks(const theia_ba_problem* p, const double
   B.pt_const = d_skip.p;
   std::vector<char> h_out;
   if (eo->bundle_adjustment) {
-    if (o->use_homogeneous_point_parametrization) k_track_lm<3><<<grid, 64>>>(B, reinterpret_cast<ViewOut*>(d_out.p));
-    else k_track_lm<4><<<grid, 64>>>(B, reinterpret_cast<ViewOut*>(d_out.p));
-    h_out.resize(sizeof(ViewOut) * (size_t)np);
+    if (o->use_homogeneous_point_parametrization) k_track_lm<3><<<grid, 64>>>(B, reinterpret_cast<BatchLmOut*>(d_out.p));
+    else k_track_lm<4><<<grid, 64>>>(B, reinterpret_cast<BatchLmOut*>(d_out.p));
+    h_out.resize(sizeof(BatchLmOut) * (size_t)np);
     HIP_TRY(hipMemcpy(h_out.data(), d_out.p, h_out.size(), hipMemcpyDeviceToHost));
   }
   k_track_stats<<<grid, 64>>>(B, d_err.p, d_nb.p, d_cos.p);

@@ -353,7 +353,7 @@ __global__ __launch_bounds__(64 * TPS, THIP_FUSED_WAVES) void k_lin_schur(DevPro
   for (int k = 0; k < 12; ++k) stamps[k] = 0;
   Stamp<STAMPS> sk;
   sk.start();
-  // runs are taken from a queue, longest first (ba_solver.hip), ONE RUN AHEAD: the pop's round trip -- and, behind it in the
+  // runs are taken from a queue, longest first (ba_plan.hip), ONE RUN AHEAD: the pop's round trip -- and, behind it in the
   // in-order memory counter, the drain of the previous run's partial-block stores -- is off the path between two runs
   int pending = 0;
   if (tid == 0) pending = atomicAdd(P.frun_next, 1);

@@ -251,7 +251,7 @@ __device__ __forceinline__ void fusedi_phase_l(const DevProblem& P, const LanePr
 }
 
 // KI = 3 or 4: compact intrinsics rows in use (the widest free mask of the problem's groups); a run's partial blocks are
-// BW x BW = (6 + KI)^2 doubles per target and BW x 3 per camera (ba_solver.hip: build_sum_items_intr reads them so).
+// BW x BW = (6 + KI)^2 doubles per target and BW x 3 per camera (ba_plan.hip: build_sum_items_intr reads them so).
 template <int PD, int TPS, unsigned MODELS, int KI, unsigned KMASK, int LOSSK>
 __global__ __launch_bounds__(64 * TPS, 2) void k_lin_schur_i(DevProblem P, const double* __restrict__ pts,
                                                              const double* __restrict__ radius_p,

@@ -30,6 +30,7 @@
 #include "ba_device.h"
 #include "ba_kernels.h"
 #include "ba_priors.h"
+#include "ba_host_rules.h"
 #include "theia_hip.h"
 #include "device_util.h"
 
@@ -498,36 +499,6 @@ int upload(DevBuf<T>& d, const std::vector<T>& h, hipStream_t st) {
   return 0;
 }
 
-// free parameters of a model under an OptimizeIntrinsicsType mask (GetSubsetFromOptimizeIntrinsicsType of every
-// *_camera_model.cc), the sizes of the eight models, the bounds of bundle_adjuster.cc:406-427: as ba_solver.hip
-unsigned id_free_mask(int model, int opt) {
-  const bool noskew = (model == THEIA_CAM_FOV || model == THEIA_CAM_DIVISION_UNDISTORTION);
-  unsigned m = 0;
-  if (opt & THEIA_INTR_FOCAL_LENGTH) m |= 1u << 0;
-  if (opt & THEIA_INTR_ASPECT_RATIO) m |= 1u << 1;
-  if ((opt & THEIA_INTR_SKEW) && !noskew) m |= 1u << 2;
-  if (opt & THEIA_INTR_PRINCIPAL_POINTS) m |= noskew ? (3u << 2) : (3u << 3);
-  if (opt & THEIA_INTR_RADIAL_DISTORTION) {
-    switch (model) {
-      case THEIA_CAM_PINHOLE: case THEIA_CAM_DOUBLE_SPHERE: case THEIA_CAM_EXTENDED_UNIFIED: case THEIA_CAM_ORTHOGRAPHIC: m |= 3u << 5; break;
-      case THEIA_CAM_PINHOLE_RADIAL_TANGENTIAL: m |= 7u << 5; break;
-      case THEIA_CAM_FISHEYE: m |= 15u << 5; break;
-      case THEIA_CAM_FOV: case THEIA_CAM_DIVISION_UNDISTORTION: m |= 1u << 4; break;
-    }
-  }
-  if ((opt & THEIA_INTR_TANGENTIAL_DISTORTION) && model == THEIA_CAM_PINHOLE_RADIAL_TANGENTIAL) m |= 3u << 8;
-  return m;
-}
-int id_intrinsics_size(int model) {
-  static const int K[8] = {7, 10, 9, 5, 5, 7, 7, 7};
-  return (model >= 0 && model < 8) ? K[model] : 0;
-}
-void id_project_to_bounds_host(int model, double* k) {
-  if (k[0] < 1.0) k[0] = 1.0;
-  if (model == THEIA_CAM_DOUBLE_SPHERE) { k[5] = std::min(1.0, std::max(-1.0, k[5])); k[6] = std::min(1.0, std::max(0.0, k[6])); }
-  if (model == THEIA_CAM_EXTENDED_UNIFIED) { k[5] = std::min(1.0, std::max(0.0, k[5])); k[6] = std::max(0.1, k[6]); }
-}
-
 void trace_push(theia_ba_summary* S, double cost, double g, double step, double radius, int acc) {
   if (!S->trace_cost || S->trace_size >= S->trace_capacity) return;
   const int k = S->trace_size++;
@@ -615,8 +586,8 @@ int IdHandle::create(const theia_ba_problem* p, const theia_ba_options* o) {
   for (int64_t i = 0; i < nobs; ++i) grp_used[p->cam_group[p->obs_cam[i]]] = 1;
   ngv = 0;
   for (int g = 0; g < ng; ++g) {
-    grp_k[g] = id_intrinsics_size(p->group_model[g]);
-    const unsigned fm = id_free_mask(p->group_model[g], o->intrinsics_to_optimize);
+    grp_k[g] = intrinsics_size(p->group_model[g]);
+    const unsigned fm = intrinsics_free_mask(p->group_model[g], o->intrinsics_to_optimize);
     if ((p->group_const && p->group_const[g]) || fm == 0 || !grp_used[g]) continue;
     grp_red[g] = ngv++; grp_free[g] = fm;
   }
@@ -639,18 +610,7 @@ int IdHandle::create(const theia_ba_problem* p, const theia_ba_options* o) {
   // camera priors of the views in the problem (AddViewPriors)
   std::vector<int> prior_cam, prior_kind;
   std::vector<double> prior_vec, prior_info;
-  if (p->cam_prior_mask && o->prior_mask) {
-    const double* vecs[3] = {p->cam_position_prior, p->cam_gravity_prior, p->cam_orientation_prior};
-    const double* infos[3] = {p->cam_position_prior_sqrt_info, p->cam_gravity_prior_sqrt_info, p->cam_orientation_prior_sqrt_info};
-    for (int c = 0; c < nc; ++c)
-      for (int k = 0; k < 3; ++k) {
-        const int bit = 1 << k;
-        if (!cam_used[c] || !(p->cam_prior_mask[c] & bit) || !(o->prior_mask & bit) || !vecs[k] || !infos[k]) continue;
-        prior_cam.push_back(c); prior_kind.push_back(bit);
-        prior_vec.insert(prior_vec.end(), vecs[k] + 3 * (size_t)c, vecs[k] + 3 * (size_t)c + 3);
-        prior_info.insert(prior_info.end(), infos[k] + 9 * (size_t)c, infos[k] + 9 * (size_t)c + 9);
-      }
-  }
+  collect_cam_priors(p, o->prior_mask, nc, cam_used.data(), prior_cam, prior_kind, prior_vec, prior_info);
   npri = (int)prior_cam.size();
   std::vector<double> si(2 * (size_t)nobs, 1.0);
   if (p->obs_sqrt_info) std::memcpy(si.data(), p->obs_sqrt_info, sizeof(double) * 2 * nobs);
@@ -719,7 +679,7 @@ int IdHandle::upload_parameters(const theia_ba_problem* p) {
   for (int pt = 0; pt < np; ++pt)   // what create() checks: a reset must not smuggle in what a fresh handle would refuse
     if (h_pt_observed[pt] && !(p->point_inverse_depth[pt] > 0.0)) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "track %d: inverse depth must be positive", pt);
   std::vector<double> hintr(p->intrinsics, p->intrinsics + (size_t)THEIA_MAX_INTRINSICS * ng);
-  for (int g = 0; g < ng; ++g) if (grp_red[g] >= 0) id_project_to_bounds_host(h_group_model[g], &hintr[(size_t)g * kKW]);
+  for (int g = 0; g < ng; ++g) if (grp_red[g] >= 0) project_intrinsics_to_bounds(h_group_model[g], &hintr[(size_t)g * kKW]);
   for (int k = 0; k < 2; ++k) {
     if (ng) HIP_TRYR(hipMemcpyAsync(d_intr[k].p, hintr.data(), sizeof(double) * hintr.size(), hipMemcpyHostToDevice, st));
     if (nc) HIP_TRYR(hipMemcpyAsync(d_cam[k].p, p->cam_ext, sizeof(double) * 6 * (size_t)nc, hipMemcpyHostToDevice, st));
@@ -908,7 +868,7 @@ int ba_solve_inverse_depth(const theia_ba_problem* p, const theia_ba_options* o,
   return rc;
 }
 
-// the handle API's view of the object (ba_solver.hip)
+// the handle API's view of the object (created in ba_plan.hip, driven from ba_solver.hip)
 int id_handle_create(const theia_ba_problem* p, const theia_ba_options* o, void** out) {
   IdHandle* h = new (std::nothrow) IdHandle();
   if (!h) return set_error(THEIA_HIP_ERR_OUT_OF_MEMORY, "out of host memory");

@@ -25,7 +25,7 @@
 
 namespace thip {
 
-// Owner of one hipMalloc block, freed with the object.  (ba_solver.hip's PoolBuf and pools.h's DBuf draw from the
+// Owner of one hipMalloc block, freed with the object.  (ba_handle.h's PoolBuf and pools.h's DBuf draw from the
 // library's device cache instead.)
 template <class T>
 struct DevBuf {

@@ -1,8 +1,11 @@
 // host_team.h -- a small persistent team of host threads for the library's host-side loops over independent parts
-// (handle creation in ba_solver.hip; the sample streams and acceptance replays of ransac.hip).
+// (handle creation in ba_plan.hip, through host_parts of ba_handle.h; the sample streams and acceptance replays of ransac.hip),
+// and host_for, the one parallel-for over them.
 #ifndef THEIA_HIP_HOST_TEAM_H_
 #define THEIA_HIP_HOST_TEAM_H_
+#include <algorithm>
 #include <atomic>
+#include <cstdlib>
 #include <condition_variable>
 #include <cstdint>
 #include <functional>
@@ -95,6 +98,27 @@ inline HostTeam& host_team() {
   return *host_team_slot();
 }
 
+// THEIA_HIP_HOST_THREADS caps a region's threads (default min(hardware threads, 32); 1 = serial); read per region: tests switch it
+inline unsigned host_thread_cap() {
+  const char* e = getenv("THEIA_HIP_HOST_THREADS");
+  const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
+  return e ? (unsigned)std::max(1, atoi(e)) : std::min(hw, 32u);
+}
+
+// fn(k) for the parts k = 0 .. nparts-1 on up to `cap` threads, the caller among them (the result must not depend on who runs which
+// part): serial for cap <= 1, else on the team, else -- the team is busy -- on threads of its own that share a counter of parts.
+template <class F>
+void host_for(int nparts, unsigned cap, F&& fn) {
+  if (cap <= 1) { for (int k = 0; k < nparts; ++k) fn(k); return; }
+  const std::function<void(int)> job = [&fn](int k) { fn(k); };
+  if (host_team().run(nparts, cap, job)) return;
+  std::atomic<int> next{0};
+  auto take = [&] { for (int k = next.fetch_add(1, std::memory_order_relaxed); k < nparts; k = next.fetch_add(1, std::memory_order_relaxed)) fn(k); };
+  std::vector<std::thread> th;
+  for (unsigned t = 1; t < cap; ++t) th.emplace_back(take);
+  take();
+  for (auto& x : th) x.join();
+}
 
 }  // namespace thip
 #endif

@@ -35,7 +35,6 @@
 #include "theia_hip.h"
 #include <atomic>
 #include <mutex>
-#include <functional>
 #include <thread>
 
 #include "device_util.h"
@@ -721,11 +720,9 @@ __global__ __launch_bounds__(64) void k_lo_gather(int est, const int* __restrict
   if (lane == 0) ev_count[e] = base;
 }
 
-struct LoOut { int success, term, iters, nsucc; double c0, c1; };   // = ba_batch.hip ViewOut
-
 // refined pose back into the problem's model (written even when RefineModel returns false)
 __global__ void k_lo_finish(int est, int nev, const int* __restrict__ ev_prob, const double* __restrict__ ev_cam,
-                            const double* __restrict__ ev_model, const LoOut* __restrict__ out, double* __restrict__ cur_models,
+                            const double* __restrict__ ev_model, const BatchLmOut* __restrict__ out, double* __restrict__ cur_models,
                             int* __restrict__ ev_success) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= nev) return;
@@ -1386,26 +1383,11 @@ struct CallSync {   // "my work on the shared stream is done"
 };
 
 // Host-side loops over independent problems (sample streams, acceptance replay) on the library's persistent team of host
-// threads (host_team.h: starting and joining 16 threads per loop cost ~0.6 ms, a round has two such loops); a second caller
-// inside the team's region falls back to threads of its own.  THEIA_HIP_HOST_THREADS caps the count (default min(hardware
-// threads, 32); 1 = serial).
+// threads (host_team.h: starting and joining 16 threads per loop cost ~0.6 ms, a round has two such loops), four problems
+// per thread at least.
 template <class F>
 void host_parallel_for(int n, F&& fn) {
-  static const unsigned cap = [] {
-    const char* e = getenv("THEIA_HIP_HOST_THREADS");
-    const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-    return e ? (unsigned)std::max(1, atoi(e)) : std::min(hw, 32u);
-  }();
-  const unsigned nt = std::min<unsigned>(cap, (unsigned)std::max(1, n / 4));
-  if (nt < 2) { for (int i = 0; i < n; ++i) fn(i); return; }
-  const std::function<void(int)> job = [&fn](int i) { fn(i); };
-  if (host_team().run(n, nt, job)) return;
-  std::atomic<int> next{0};
-  std::vector<std::thread> th;
-  th.reserve(nt);
-  for (unsigned t = 0; t < nt; ++t)
-    th.emplace_back([&] { for (int i = next.fetch_add(1); i < n; i = next.fetch_add(1)) fn(i); });
-  for (auto& t : th) t.join();
+  host_for(n, std::min<unsigned>(host_thread_cap(), (unsigned)std::max(1, n / 4)), fn);
 }
 
 int compute_max_iterations(const theia_ransac_params& P, double min_sample_size, double inlier_ratio,
@@ -1788,7 +1770,7 @@ static int ransac_run(const theia_ransac_batch* batch, const theia_ransac_params
       views_batch_device(nev, d_ev_off.p, d_ev_count.p, d_lo_uv.p, nullptr, d_lo_X.p, d_ev_cam.p, d_lo_intr.p, d_lo_model_id.p,
                          nullptr, &lo_opts, d_lo_out.p, st);
     k_lo_finish<<<(nev + 63) / 64, 64, 0, st>>>(est, nev, d_ev_prob.p, d_ev_cam.p, d_ev_model.p,
-                                                reinterpret_cast<const LoOut*>(d_lo_out.p), d_cur_models.p, d_ev_success.p);
+                                                reinterpret_cast<const BatchLmOut*>(d_lo_out.p), d_cur_models.p, d_ev_success.p);
     HIP_TRYR(hipMemcpyAsync(success.data(), d_ev_success.p, sizeof(int) * nev, hipMemcpyDeviceToHost, st));
     HIP_TRYR(mine.wait(st));
     return 0;

@@ -6,12 +6,26 @@
 #include <unistd.h>
 
 #include <atomic>
+#include <cstdarg>
+#include <cstdio>
 #include <cstring>
 
 #include "theia_hip.h"
 #include "theia_hip_internal.h"
 
 namespace thip {
+
+thread_local std::string g_last_error;
+
+int set_error(int code, const char* fmt, ...) {
+  char buf[1024];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof(buf), fmt, ap);
+  va_end(ap);
+  g_last_error = buf;
+  return code;
+}
 
 static std::atomic<int> g_device{-1};
 

@@ -47,11 +47,6 @@ struct TwoViewBatch {
   int cgnr;                 // 1: the CGNR + JACOBI inexact step; 0: exact solve of the normal equations
 };
 
-struct TwoViewOut {   // = ba_batch.hip ViewOut
-  int success, term, iters, nsucc;
-  double initial_cost, final_cost;
-};
-
 // ceres SphereManifold<3>: householder_vector.h + sphere_manifold_functions.h (2.2)
 __device__ void householder3(const double x[3], double v[3], double& beta) {
   const double sigma = x[0] * x[0] + x[1] * x[1];
@@ -339,15 +334,15 @@ __device__ bool solve5(const double* H, const double* d, const double* g, double
   return true;
 }
 
-__global__ __launch_bounds__(256) void k_twoview_lm(TwoViewBatch B, TwoViewOut* __restrict__ out) {
+__global__ __launch_bounds__(256) void k_twoview_lm(TwoViewBatch B, BatchLmOut* __restrict__ out) {
   const int lane = threadIdx.x & 63;
   const int p = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (p >= B.num) return;
   double x[6];
 #pragma unroll
   for (int q = 0; q < 6; ++q) x[q] = B.pose[(size_t)p * 6 + q];
-  TwoViewOut R;
-  R.success = 0; R.term = THEIA_TERM_NO_CONVERGENCE; R.iters = 0; R.nsucc = 0; R.initial_cost = 0.0; R.final_cost = 0.0;
+  BatchLmOut R;
+  R.success = 0; R.term = THEIA_TERM_NO_CONVERGENCE; R.iters = 0; R.nsucc = 0; R.c0 = 0.0; R.c1 = 0.0;
   double scale[5] = {1.0, 1.0, 1.0, 1.0, 1.0};
   double H[15], g[5], x_cost;
   // Jacobi scaling from the column norms at the initial point (once per solve)
@@ -376,9 +371,9 @@ __global__ __launch_bounds__(256) void k_twoview_lm(TwoViewBatch B, TwoViewOut* 
     }
     if (first) {
       first = false;
-      R.initial_cost = x_cost;
+      R.c0 = x_cost;
       minimum_cost = x_cost;
-      if (!isfinite(x_cost)) { term = THEIA_TERM_FAILURE; R.final_cost = x_cost; break; }
+      if (!isfinite(x_cost)) { term = THEIA_TERM_FAILURE; R.c1 = x_cost; break; }
     }
     if (iter >= B.max_iterations) { term = THEIA_TERM_NO_CONVERGENCE; break; }
     if (step_successful && gmax <= B.gradient_tolerance) { term = THEIA_TERM_CONVERGENCE; break; }
@@ -437,7 +432,7 @@ __global__ __launch_bounds__(256) void k_twoview_lm(TwoViewBatch B, TwoViewOut* 
     }
   }
   R.iters = iter; R.term = term; R.success = term != THEIA_TERM_FAILURE;
-  R.final_cost = term != THEIA_TERM_FAILURE ? minimum_cost : x_cost;
+  R.c1 = term != THEIA_TERM_FAILURE ? minimum_cost : x_cost;
   if (lane == 0) {
     out[p] = R;
 #pragma unroll
@@ -573,14 +568,14 @@ __device__ bool solve9(const double* A, const double* d, const double* g, double
   return true;
 }
 
-__global__ __launch_bounds__(256) void k_homography_lm(HomographyBatch B, TwoViewOut* __restrict__ out) {
+__global__ __launch_bounds__(256) void k_homography_lm(HomographyBatch B, BatchLmOut* __restrict__ out) {
   const int lane = threadIdx.x & 63;
   const int p = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (p >= B.num) return;
   double x[9];
   for (int q = 0; q < 9; ++q) x[q] = B.H[(size_t)p * 9 + q];
-  TwoViewOut R;
-  R.success = 0; R.term = THEIA_TERM_NO_CONVERGENCE; R.iters = 0; R.nsucc = 0; R.initial_cost = 0.0; R.final_cost = 0.0;
+  BatchLmOut R;
+  R.success = 0; R.term = THEIA_TERM_NO_CONVERGENCE; R.iters = 0; R.nsucc = 0; R.c0 = 0.0; R.c1 = 0.0;
   double scale[9];
   for (int q = 0; q < 9; ++q) scale[q] = 1.0;
   double A[45], g[9], x_cost;
@@ -601,7 +596,7 @@ __global__ __launch_bounds__(256) void k_homography_lm(HomographyBatch B, TwoVie
     }
     if (first) {
       first = false;
-      R.initial_cost = x_cost;
+      R.c0 = x_cost;
       minimum_cost = x_cost;
       if (!isfinite(x_cost)) { term = THEIA_TERM_FAILURE; break; }
     }
@@ -654,7 +649,7 @@ __global__ __launch_bounds__(256) void k_homography_lm(HomographyBatch B, TwoVie
     }
   }
   R.iters = iter; R.term = term; R.success = term != THEIA_TERM_FAILURE;
-  R.final_cost = term != THEIA_TERM_FAILURE ? minimum_cost : x_cost;
+  R.c1 = term != THEIA_TERM_FAILURE ? minimum_cost : x_cost;
   if (lane == 0) {
     out[p] = R;
     const double h22 = x[8];   // (*homography) /= (*homography)(2, 2): the divisor is the last element in storage order
@@ -801,14 +796,14 @@ __device__ bool solve7(const double* A, const double* d, const double* g, double
   return true;
 }
 
-__global__ __launch_bounds__(256) void k_fundamental_lm(FundBatch B, TwoViewOut* __restrict__ out) {
+__global__ __launch_bounds__(256) void k_fundamental_lm(FundBatch B, BatchLmOut* __restrict__ out) {
   const int lane = threadIdx.x & 63;
   const int p = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (p >= B.num) return;
   double x[9];
   for (int q = 0; q < 9; ++q) x[q] = B.F[(size_t)p * 9 + q];
-  TwoViewOut R;
-  R.success = 0; R.term = THEIA_TERM_NO_CONVERGENCE; R.iters = 0; R.nsucc = 0; R.initial_cost = 0.0; R.final_cost = 0.0;
+  BatchLmOut R;
+  R.success = 0; R.term = THEIA_TERM_NO_CONVERGENCE; R.iters = 0; R.nsucc = 0; R.c0 = 0.0; R.c1 = 0.0;
   double scale[7];
   for (int q = 0; q < 7; ++q) scale[q] = 1.0;
   double A[28], g[7], x_cost;
@@ -833,7 +828,7 @@ __global__ __launch_bounds__(256) void k_fundamental_lm(FundBatch B, TwoViewOut*
     }
     if (first) {
       first = false;
-      R.initial_cost = x_cost;
+      R.c0 = x_cost;
       minimum_cost = x_cost;
       if (!isfinite(x_cost)) { term = THEIA_TERM_FAILURE; break; }
     }
@@ -887,7 +882,7 @@ __global__ __launch_bounds__(256) void k_fundamental_lm(FundBatch B, TwoViewOut*
     }
   }
   R.iters = iter; R.term = term; R.success = term != THEIA_TERM_FAILURE;
-  R.final_cost = term != THEIA_TERM_FAILURE ? minimum_cost : x_cost;
+  R.c1 = term != THEIA_TERM_FAILURE ? minimum_cost : x_cost;
   if (lane == 0) {
     out[p] = R;
     for (int q = 0; q < 9; ++q) B.F[(size_t)p * 9 + q] = x[q];
@@ -899,14 +894,13 @@ __global__ __launch_bounds__(256) void k_fundamental_lm(FundBatch B, TwoViewOut*
 // device-resident variant for callers inside the library (LO-RANSAC); d_out = views_batch_out_bytes() per problem
 int twoview_batch_device(int num, const int64_t* d_offsets, const int* d_counts, const double* d_corr, double* d_pose,
                          const theia_ba_options* o, int cgnr, void* d_out, hipStream_t st) {
-  static_assert(sizeof(TwoViewOut) == 32, "layout shared with ba_batch.hip ViewOut");
   TwoViewBatch B;
   B.num = num; B.offsets = d_offsets; B.counts = d_counts; B.corr = reinterpret_cast<const double4*>(d_corr); B.pose = d_pose;
   B.loss_type = o->loss_function_type; B.loss_width = o->robust_loss_width; B.max_iterations = o->max_num_iterations;
   B.function_tolerance = o->function_tolerance; B.gradient_tolerance = o->gradient_tolerance;
   B.parameter_tolerance = o->parameter_tolerance; B.max_radius = o->max_trust_region_radius;
   B.cgnr = cgnr;
-  k_twoview_lm<<<(num + 3) / 4, 256, 0, st>>>(B, static_cast<TwoViewOut*>(d_out));
+  k_twoview_lm<<<(num + 3) / 4, 256, 0, st>>>(B, static_cast<BatchLmOut*>(d_out));
   return 0;
 }
 
@@ -918,7 +912,7 @@ int fundamental_batch_device(int num, const int64_t* d_offsets, const int* d_cou
   B.max_iterations = o->max_num_iterations;
   B.function_tolerance = o->function_tolerance; B.gradient_tolerance = o->gradient_tolerance;
   B.parameter_tolerance = o->parameter_tolerance; B.max_radius = o->max_trust_region_radius;
-  k_fundamental_lm<<<(num + 3) / 4, 256, 0, st>>>(B, static_cast<TwoViewOut*>(d_out));
+  k_fundamental_lm<<<(num + 3) / 4, 256, 0, st>>>(B, static_cast<BatchLmOut*>(d_out));
   return 0;
 }
 
@@ -930,7 +924,7 @@ int homography_batch_device(int num, const int64_t* d_offsets, const int* d_coun
   B.loss_type = o->loss_function_type; B.loss_width = o->robust_loss_width; B.max_iterations = o->max_num_iterations;
   B.function_tolerance = o->function_tolerance; B.gradient_tolerance = o->gradient_tolerance;
   B.parameter_tolerance = o->parameter_tolerance; B.max_radius = o->max_trust_region_radius;
-  k_homography_lm<<<(num + 3) / 4, 256, 0, st>>>(B, static_cast<TwoViewOut*>(d_out));
+  k_homography_lm<<<(num + 3) / 4, 256, 0, st>>>(B, static_cast<BatchLmOut*>(d_out));
   return 0;
 }
 
@@ -959,19 +953,19 @@ extern "C" int theia_hip_ba_two_views_angular_batch(const theia_ba_two_view_batc
   if (rc) return rc;
   DevBuf<int64_t> d_off; DevBuf<double> d_corr, d_pose; DevBuf<char> d_out;
   if ((rc = d_off.up(b->offsets, num + 1)) || (rc = d_corr.up(b->correspondences, 4 * total)) ||
-      (rc = d_pose.up(b->rotation_position, 6 * (size_t)num)) || (rc = d_out.alloc(sizeof(TwoViewOut) * num)))
+      (rc = d_pose.up(b->rotation_position, 6 * (size_t)num)) || (rc = d_out.alloc(sizeof(BatchLmOut) * num)))
     return rc;
   const double t0 = now_s();
   twoview_batch_device(num, d_off.p, nullptr, d_corr.p, d_pose.p, o, b->linear_solver == THEIA_TWO_VIEW_CGNR, d_out.p, nullptr);
-  std::vector<TwoViewOut> h_out(num);
-  HIP_TRY(hipMemcpy(h_out.data(), d_out.p, sizeof(TwoViewOut) * num, hipMemcpyDeviceToHost));
+  std::vector<BatchLmOut> h_out(num);
+  HIP_TRY(hipMemcpy(h_out.data(), d_out.p, sizeof(BatchLmOut) * num, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(b->rotation_position, d_pose.p, sizeof(double) * 6 * num, hipMemcpyDeviceToHost));
   const double dt = now_s() - t0;
   for (int i = 0; i < num; ++i) {
     theia_ba_summary& S = summaries[i];
     S.trace_size = 0;
     S.success = h_out[i].success; S.termination_type = h_out[i].term; S.num_iterations = h_out[i].iters;
-    S.num_successful_steps = h_out[i].nsucc; S.initial_cost = h_out[i].initial_cost; S.final_cost = h_out[i].final_cost;
+    S.num_successful_steps = h_out[i].nsucc; S.initial_cost = h_out[i].c0; S.final_cost = h_out[i].c1;
     S.setup_time_in_seconds = 0.0; S.solve_time_in_seconds = dt / num;
     S.time_linearize = S.time_solve_reduced = S.time_backsub = S.time_kernel_linearize = 0.0;
     S.num_linearize_launches = 0;
@@ -1002,12 +996,12 @@ extern "C" int theia_hip_optimize_homography_batch(int32_t num_problems, const i
       for (int j = 0; j < 3; ++j) hcm[(size_t)p * 9 + i + 3 * j] = homographies[(size_t)p * 9 + 3 * i + j];
   DevBuf<int64_t> d_off; DevBuf<double> d_corr, d_H; DevBuf<char> d_out;
   if ((rc = d_off.up(offsets, num + 1)) || (rc = d_corr.up(correspondences, 4 * total)) || (rc = d_H.up(hcm.data(), hcm.size())) ||
-      (rc = d_out.alloc(sizeof(TwoViewOut) * num)))
+      (rc = d_out.alloc(sizeof(BatchLmOut) * num)))
     return rc;
   const double t0 = now_s();
   homography_batch_device(num, d_off.p, nullptr, d_corr.p, d_H.p, o, d_out.p, nullptr);
-  std::vector<TwoViewOut> h_out(num);
-  HIP_TRY(hipMemcpy(h_out.data(), d_out.p, sizeof(TwoViewOut) * num, hipMemcpyDeviceToHost));
+  std::vector<BatchLmOut> h_out(num);
+  HIP_TRY(hipMemcpy(h_out.data(), d_out.p, sizeof(BatchLmOut) * num, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(hcm.data(), d_H.p, sizeof(double) * hcm.size(), hipMemcpyDeviceToHost));
   const double dt = now_s() - t0;
   for (int p = 0; p < num; ++p)
@@ -1017,7 +1011,7 @@ extern "C" int theia_hip_optimize_homography_batch(int32_t num_problems, const i
     theia_ba_summary& S = summaries[i];
     S.trace_size = 0;
     S.success = h_out[i].success; S.termination_type = h_out[i].term; S.num_iterations = h_out[i].iters;
-    S.num_successful_steps = h_out[i].nsucc; S.initial_cost = h_out[i].initial_cost; S.final_cost = h_out[i].final_cost;
+    S.num_successful_steps = h_out[i].nsucc; S.initial_cost = h_out[i].c0; S.final_cost = h_out[i].c1;
     S.setup_time_in_seconds = 0.0; S.solve_time_in_seconds = dt / num;
     S.time_linearize = S.time_solve_reduced = S.time_backsub = S.time_kernel_linearize = 0.0;
     S.num_linearize_launches = 0;
@@ -1045,19 +1039,19 @@ extern "C" int theia_hip_optimize_fundamental_matrix_batch(int32_t num_problems,
   if (rc) return rc;
   DevBuf<int64_t> d_off; DevBuf<double> d_corr, d_F; DevBuf<char> d_out;
   if ((rc = d_off.up(offsets, num + 1)) || (rc = d_corr.up(correspondences, 4 * total)) ||
-      (rc = d_F.up(fundamental_matrices, 9 * (size_t)num)) || (rc = d_out.alloc(sizeof(TwoViewOut) * num)))
+      (rc = d_F.up(fundamental_matrices, 9 * (size_t)num)) || (rc = d_out.alloc(sizeof(BatchLmOut) * num)))
     return rc;
   const double t0 = now_s();
   fundamental_batch_device(num, d_off.p, nullptr, d_corr.p, d_F.p, o, d_out.p, nullptr);
-  std::vector<TwoViewOut> h_out(num);
-  HIP_TRY(hipMemcpy(h_out.data(), d_out.p, sizeof(TwoViewOut) * num, hipMemcpyDeviceToHost));
+  std::vector<BatchLmOut> h_out(num);
+  HIP_TRY(hipMemcpy(h_out.data(), d_out.p, sizeof(BatchLmOut) * num, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(fundamental_matrices, d_F.p, sizeof(double) * 9 * num, hipMemcpyDeviceToHost));
   const double dt = now_s() - t0;
   for (int i = 0; i < num; ++i) {
     theia_ba_summary& S = summaries[i];
     S.trace_size = 0;
     S.success = h_out[i].success; S.termination_type = h_out[i].term; S.num_iterations = h_out[i].iters;
-    S.num_successful_steps = h_out[i].nsucc; S.initial_cost = h_out[i].initial_cost; S.final_cost = h_out[i].final_cost;
+    S.num_successful_steps = h_out[i].nsucc; S.initial_cost = h_out[i].c0; S.final_cost = h_out[i].c1;
     S.setup_time_in_seconds = 0.0; S.solve_time_in_seconds = dt / num;
     S.time_linearize = S.time_solve_reduced = S.time_backsub = S.time_kernel_linearize = 0.0;
     S.num_linearize_launches = 0;

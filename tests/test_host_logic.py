@@ -353,7 +353,7 @@ def test_problem_fingerprint_separates_topology_from_parameters():
 
 
 def test_host_thread_team_survives_a_fork():
-    """ba_solver.hip HostTeam: the worker threads of the parent do not exist in a fork child, and the region state
+    """host_team.h HostTeam: the worker threads of the parent do not exist in a fork child, and the region state
     (generation, worker count, active count) must not be inherited either.  The validation pass of create() runs its
     observation scan on the team (THEIA_HIP_HOST_CHUNK_MIN lowers the size at which it does) before any device call, so it
     is reachable without a GPU: the parent runs it, forks, and the child runs it again -- with an out-of-range index in the
