@@ -9,7 +9,7 @@
 namespace thip {
 namespace {
 
-// ---- DLS-PnP hypotheses (estimate_calibrated_absolute_pose.cc:89-97): this stage, then the eigen stage of ransac.hip.
+// ---- DLS-PnP hypotheses (estimate_calibrated_absolute_pose.cc:89-97): this stage, then the eigen stage of ransac.hip (k_dls_b_team; launched by RansacCall::launch_fit_dls, the directly bound DlsPnp by ransac_solvers.hip).
 // k_dls_a: one workgroup of 192 threads per (problem, iteration); uvals holds the four Macaulay terms of every DlsPnp call of a process
 // (iteration it of a problem = call it: the reference never seeds rand(), and one Estimate() is one process here).
 __global__ __launch_bounds__(dlsdev::kThreads, 3) void k_dls_a(int nprob, int B, const int64_t* __restrict__ offsets,

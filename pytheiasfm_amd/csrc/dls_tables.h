@@ -19,6 +19,7 @@
 
 #include <cstdint>
 #include <cstring>
+#include <vector>
 
 #include "dls_layout.h"
 
@@ -156,6 +157,10 @@ struct GlibcRand {
 };
 // the k-th coefficient of the k-th Vector4d::Random() draw, times 100 (dls_pnp.cc:134)
 inline double macaulay_term_from_rand(int32_t r) { return 100.0 * (-1.0 + (2.0 * (double)r) / 2147483647.0); }
+// Macaulay terms of DlsPnp calls [0, ncalls) of a process
+inline void dls_terms(std::vector<double>& u, GlibcRand& gen, size_t ncalls) {
+  while (u.size() < 4 * ncalls) u.push_back(macaulay_term_from_rand(gen.next()));
+}
 
 }  // namespace dls
 }  // namespace thip

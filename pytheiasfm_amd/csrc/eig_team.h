@@ -30,7 +30,7 @@ __device__ __forceinline__ void team_sync() {
 
 // Development (-DTHIP_EIG_STAMPS): s_memtime ticks per phase of eig_team, summed over the teams' lane 0 into g_eig_stamps
 // {orthes, accumulate, hqr2 deflation scans + root branches, shift + start search, chase steps, back-substitution,
-// back-transformation, calls}; read back with theia_hip_debug_eig_stamps (ransac.hip).
+// back-transformation, calls}; read back with theia_hip_debug_eig_stamps (ransac.hip, the translation unit of the eigen-stage kernels).
 #ifdef THIP_EIG_STAMPS
 __device__ unsigned long long g_eig_stamps[8];
 #define EIG_STAMP_DECL unsigned long long st_t = __builtin_amdgcn_s_memtime(), st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}

@@ -1,5 +1,5 @@
 // host_team.h -- a small persistent team of host threads for the library's host-side loops over independent parts
-// (handle creation in ba_plan.hip, through host_parts of ba_handle.h; the sample streams and acceptance replays of ransac.hip),
+// (handle creation in ba_plan.hip, through host_parts of ba_handle.h; the sample streams and acceptance replays of ransac.hip's RansacCall),
 // and host_for, the one parallel-for over them.
 #ifndef THEIA_HIP_HOST_TEAM_H_
 #define THEIA_HIP_HOST_TEAM_H_

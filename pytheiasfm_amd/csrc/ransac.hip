@@ -1,5 +1,5 @@
 // ransac.hip -- many-hypothesis RANSAC on gfx950: K5 (minimal-solver fit) and
-// K6 (score every correspondence under every model) plus the host driver that
+// K6 (score every correspondence under every model) plus the host driver (RansacCall, ransac_run) that
 // replaces SampleConsensusEstimator<E>::Estimate
 //   (src/theia/solvers/sample_consensus_estimator.h:300-415)
 // for Ransac<E> + RandomSampler (ransac.h:57-61, random_sampler.cc:53-72).
@@ -7,7 +7,7 @@
 // Split of work (DESIGN.md "RANSAC"):
 //  host   : the std::mt19937 sample stream (bit-exact restatement, util/random.cc)
 //           for a ROUND of iterations up front; sequential replay of the
-//           accept / adaptive-termination rules in sample order.
+//           accept / adaptive-termination rules in sample order (both in ransac_rng.h).
 //  device : k_fit   -- one thread per hypothesis: minimal solver -> <= 10 models
 //           k_score -- one thread per (hypothesis, model): walks all N
 //                      correspondences (staged in LDS, broadcast reads) in data
@@ -16,6 +16,8 @@
 //  Hypotheses of a round are independent given the pre-generated samples, so a
 //  batch of problems x iterations fills the chip; results are identical to the
 //  sequential loop because acceptance is replayed in order.
+// The streams entry point and theia_hip_rng_* are in ransac_streams.hip, the directly bound minimal solvers in
+// ransac_solvers.hip (their kernels stay here, behind the launch_* functions of ransac_internal.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -40,68 +42,12 @@
 #include "device_util.h"
 #include "host_team.h"
 #include "pools.h"
+#include "ransac_internal.h"
 
 namespace thip {
 namespace {
 
 constexpr int kMaxCap = 18;   // largest EstimateModel output of the thread-per-hypothesis solvers (SQPnP: 18 solutions)
-// models per sample an estimator can return = slot stride of the per-hypothesis arrays
-__host__ __device__ inline int max_models(int est) {
-  if (est == THEIA_EST_RADIAL_HOMOGRAPHY) return 2;
-  if (est == THEIA_EST_SIMILARITY_2D3D) return dlsdev::kMaxSolutions;
-  if (est == THEIA_EST_UNCALIBRATED_ABSOLUTE_POSE) return 10;
-  if (est == THEIA_EST_RIGID_TRANSFORMATION_2D3D) return 8;
-  if (est == THEIA_EST_RADIAL_DIST_UNCALIBRATED_ABSOLUTE_POSE) return 13;
-  if (est >= THEIA_EST_FUNDAMENTAL_MATRIX) return 1;
-  if (est == THEIA_EST_ABSOLUTE_POSE_DLS) return dlsdev::kMaxSolutions;
-  return est == THEIA_EST_ABSOLUTE_POSE_SQPNP ? 18 : (est == THEIA_EST_ABSOLUTE_POSE_KNEIP ? 4 : 10);
-}
-constexpr int kStride = THEIA_RANSAC_MODEL_STRIDE;
-
-__host__ __device__ inline int sample_size(int est) {
-  switch (est) {
-    case THEIA_EST_RELATIVE_POSE: case THEIA_EST_ESSENTIAL_MATRIX: return 5;
-    case THEIA_EST_FUNDAMENTAL_MATRIX: case THEIA_EST_UNCALIBRATED_RELATIVE_POSE: return 8;
-    case THEIA_EST_HOMOGRAPHY: case THEIA_EST_SIMILARITY_2D3D: case THEIA_EST_UNCALIBRATED_ABSOLUTE_POSE:
-    case THEIA_EST_RIGID_TRANSFORMATION_2D3D: case THEIA_EST_RADIAL_DIST_UNCALIBRATED_ABSOLUTE_POSE: return 4;
-    case THEIA_EST_RADIAL_HOMOGRAPHY: return 6;
-    case THEIA_EST_RELATIVE_POSE_KNOWN_ORIENTATION: case THEIA_EST_ABSOLUTE_POSE_KNOWN_ORIENTATION:
-    case THEIA_EST_TRIANGULATION: return 2;
-    default: return 3;
-  }
-}
-// meaningful doubles of a model row (layouts in theia_hip.h)
-inline int model_doubles(int est) {
-  switch (est) {
-    case THEIA_EST_RELATIVE_POSE: return 21;
-    case THEIA_EST_UNCALIBRATED_RELATIVE_POSE: return 23;
-    case THEIA_EST_ABSOLUTE_POSE_KNEIP: case THEIA_EST_ABSOLUTE_POSE_DLS: case THEIA_EST_ABSOLUTE_POSE_SQPNP: return 12;
-    case THEIA_EST_UNCALIBRATED_ABSOLUTE_POSE: return 12;   // projection matrix, row-major 3 x 4
-    case THEIA_EST_RIGID_TRANSFORMATION_2D3D: return 12;    // rotation | translation
-    case THEIA_EST_RADIAL_DIST_UNCALIBRATED_ABSOLUTE_POSE: return 14;   // rotation | translation | focal length | radial distortion
-    case THEIA_EST_DOMINANT_PLANE: return 6;
-    case THEIA_EST_RELATIVE_POSE_KNOWN_ORIENTATION: case THEIA_EST_ABSOLUTE_POSE_KNOWN_ORIENTATION: return 3;
-    case THEIA_EST_TRIANGULATION: return 4;
-    case THEIA_EST_RADIAL_HOMOGRAPHY: return 20;   // H | l1 | l2 | H^-1
-    case THEIA_EST_SIMILARITY_2D3D: return 13;     // rotation | translation | scale
-    default: return 9;   // essential / fundamental matrix, homography
-  }
-}
-constexpr int kTriDatum = 33;   // PointObservation row of THEIA_EST_TRIANGULATION (theia_hip.h)
-constexpr int kSimDatum = 26;   // CameraAndFeatureCorrespondence2D3D row of THEIA_EST_SIMILARITY_2D3D: dir (3) | point (4) | pixel (2) | extrinsics (6) | model | intrinsics (10)
-__host__ __device__ inline int datum_size(int est) {
-  switch (est) {
-    case THEIA_EST_ABSOLUTE_POSE_KNEIP: case THEIA_EST_ABSOLUTE_POSE_DLS: case THEIA_EST_ABSOLUTE_POSE_SQPNP:
-    case THEIA_EST_ABSOLUTE_POSE_KNOWN_ORIENTATION: case THEIA_EST_UNCALIBRATED_ABSOLUTE_POSE:
-    case THEIA_EST_RADIAL_DIST_UNCALIBRATED_ABSOLUTE_POSE: return 5;
-    case THEIA_EST_DOMINANT_PLANE: return 3;
-    case THEIA_EST_TRIANGULATION: return kTriDatum;
-    case THEIA_EST_RADIAL_HOMOGRAPHY: return rsc::kRadHomDatum;
-    case THEIA_EST_SIMILARITY_2D3D: case THEIA_EST_RIGID_TRANSFORMATION_2D3D: return kSimDatum;
-    default: return 4;
-  }
-}
-constexpr int kMaxSample = 8;            // largest minimal sample (8-point fundamental matrix)
 constexpr int kMaxSampleDoubles = 6 * rsc::kRadHomDatum;   // 8 correspondences x 4, two observations with their cameras (66), six radial-distortion correspondences (72)
 static_assert(kMaxSampleDoubles >= 2 * kTriDatum, "sample buffer");
 // the sample buffer of a k_fit instance: 32 doubles for the correspondence estimators (their kernels keep the frame they had)
@@ -1266,122 +1212,7 @@ int p4pf_kernel_ready() {
   return status;
 }
 
-// Macaulay terms of DlsPnp calls [0, ncalls) of a process
-void dls_terms(std::vector<double>& u, dls::GlibcRand& gen, size_t ncalls) {
-  while (u.size() < 4 * ncalls) u.push_back(dls::macaulay_term_from_rand(gen.next()));
-}
-
 // ------------------------------------------------------------------ host side
-// std::mt19937 + libstdc++ uniform_int_distribution<int> (Lemire), i.e. the
-// stream RandomNumberGenerator::RandInt draws (util/random.cc:46-84).
-// mt + idx are libstdc++'s _M_x + _M_p (theia_rng_state); `twists` counts regenerations, so drawn() is the number of words taken
-// since the last seed (the streams driver's round accounting)
-struct Mt19937 {
-  uint32_t mt[624];
-  int idx;
-  uint64_t twists = 0;
-  void seed(uint32_t s) {
-    mt[0] = s;
-    for (int i = 1; i < 624; ++i) mt[i] = 1812433253u * (mt[i - 1] ^ (mt[i - 1] >> 30)) + (uint32_t)i;
-    idx = 624;
-    twists = 0;
-  }
-  void twist() {
-    for (int i = 0; i < 624; ++i) {
-      const uint32_t y = (mt[i] & 0x80000000u) | (mt[(i + 1) % 624] & 0x7fffffffu);
-      mt[i] = mt[(i + 397) % 624] ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
-    }
-    idx = 0;
-    twists++;
-  }
-  uint64_t drawn() const { return twists * 624 + (uint64_t)idx; }
-  void discard(uint64_t words) {   // = std::mt19937::discard: the tempering of the skipped words is never needed
-    while (words > 0) {
-      if (idx >= 624) twist();
-      const uint64_t k = std::min<uint64_t>(words, (uint64_t)(624 - idx));
-      idx += (int)k; words -= k;
-    }
-  }
-  uint32_t next() {
-    if (idx >= 624) twist();
-    uint32_t y = mt[idx++];
-    y ^= y >> 11; y ^= (y << 7) & 0x9d2c5680u; y ^= (y << 15) & 0xefc60000u; y ^= y >> 18;
-    return y;
-  }
-  // libstdc++ std::uniform_real_distribution<double>(lo, hi): generate_canonical<double, 53> = two 32-bit draws (g0 + g1 * 2^32) / 2^64
-  // (nextafter(1, 0) should the quotient round to 1), then * (hi - lo) + lo -- RandomNumberGenerator::RandDouble (util/random.cc:68-72)
-  double rand_double(double lo, double hi) {
-    double sum = 0.0, tmp = 1.0;
-    for (int k = 0; k < 2; ++k) { sum += (double)next() * tmp; tmp *= 4294967296.0; }
-    double ret = sum / tmp;
-    if (ret >= 1.0) ret = std::nextafter(1.0, 0.0);
-    return ret * (hi - lo) + lo;
-  }
-  // libstdc++ std::normal_distribution<double>(mean, std_dev) on a FRESH distribution object, as RandomNumberGenerator::RandGaussian
-  // makes one per call (util/random.cc:87-91): Marsaglia's polar method on two generate_canonical<double, 53> per trial, rejected
-  // until 0 < r2 <= 1; the call returns the pair's y value and the saved x value dies with the object
-  double rand_gaussian(double mean, double std_dev) {
-    double x, y, r2;
-    do {
-      x = 2.0 * rand_double(0.0, 1.0) - 1.0;
-      y = 2.0 * rand_double(0.0, 1.0) - 1.0;
-      r2 = x * x + y * y;
-    } while (r2 > 1.0 || r2 == 0.0);
-    const double mult = std::sqrt(-2.0 * std::log(r2) / r2);
-    return (y * mult) * std_dev + mean;
-  }
-  int rand_int(int lo, int hi) {
-    const uint32_t urange = (uint32_t)hi - (uint32_t)lo;
-    uint32_t ret;
-    if (urange == 0xffffffffu) ret = next();
-    else {
-      const uint32_t range = urange + 1u;
-      uint64_t product = (uint64_t)next() * (uint64_t)range;
-      uint32_t low = (uint32_t)product;
-      if (low < range) {
-        const uint32_t threshold = (uint32_t)(-range) % range;
-        while (low < threshold) { product = (uint64_t)next() * (uint64_t)range; low = (uint32_t)product; }
-      }
-      ret = (uint32_t)(product >> 32);
-    }
-    return (int)(ret + (uint32_t)lo);
-  }
-};
-
-// sample_consensus_estimator.h:252-297
-// The minimal-solver kernels need up to ~12 KB of scratch per lane; the runtime sizes a hardware queue's
-// scratch arena for a full chip of such waves, and two queues asking for it at the same time end in
-// HSA_STATUS_ERROR_OUT_OF_RESOURCES (queue abort).  Every RANSAC kernel of the process therefore goes to ONE stream
-// (= one hardware queue, one arena), whichever host thread enqueues it: calls from a thread pool interleave their
-// launches on it (each call owns its buffers, the stream keeps each call's own order) and wait for their OWN work
-// through an event -- no host-side lock, nobody waits for another caller's synchronisation.
-hipStream_t solver_stream() {
-  static hipStream_t s = [] {
-    hipStream_t x = nullptr;
-    if (hipStreamCreateWithFlags(&x, hipStreamNonBlocking) != hipSuccess) x = nullptr;
-    return x;
-  }();
-  return s;
-}
-// transfers that may run beside the solver stream's kernels (no kernel ever goes here: no scratch arena)
-hipStream_t copy_stream() {
-  static hipStream_t s = [] {
-    hipStream_t x = nullptr;
-    if (hipStreamCreateWithFlags(&x, hipStreamNonBlocking) != hipSuccess) x = nullptr;
-    return x;
-  }();
-  return s;
-}
-struct CallSync {   // "my work on the shared stream is done"
-  hipEvent_t e = nullptr;
-  CallSync() { (void)hipEventCreateWithFlags(&e, hipEventDisableTiming); }
-  ~CallSync() { if (e) (void)hipEventDestroy(e); }
-  hipError_t wait(hipStream_t st) {
-    hipError_t r = hipEventRecord(e, st);
-    return r != hipSuccess ? r : hipEventSynchronize(e);
-  }
-};
-
 // Host-side loops over independent problems (sample streams, acceptance replay) on the library's persistent team of host
 // threads (host_team.h: starting and joining 16 threads per loop cost ~0.6 ms, a round has two such loops), four problems
 // per thread at least.
@@ -1390,244 +1221,105 @@ void host_parallel_for(int n, F&& fn) {
   host_for(n, std::min<unsigned>(host_thread_cap(), (unsigned)std::max(1, n / 4)), fn);
 }
 
-int compute_max_iterations(const theia_ransac_params& P, double min_sample_size, double inlier_ratio,
-                           double log_failure_prob, int total) {
-  if (inlier_ratio == 1.0) return P.min_iterations;
-  const int ninl = (int)(inlier_ratio * total);
-  const double num_samples = P.use_Tdd_test ? min_sample_size + 1 : min_sample_size;
-  double a = 1.0, b = 1.0;
-  for (int i = 0; i < num_samples; ++i) { a *= ninl - i; b *= total - i; }
-  const double prob_all_inliers = a / b;
-  if (prob_all_inliers < std::numeric_limits<double>::epsilon()) return P.max_iterations;
-  if (prob_all_inliers >= 1.0 - std::numeric_limits<double>::epsilon()) return P.min_iterations;
-  const double num_iterations = log_failure_prob / std::log(1.0 - prob_all_inliers);
-  return (int)std::max((double)P.min_iterations, std::min(num_iterations, (double)P.max_iterations));
+double ms_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
+  return std::chrono::duration<double, std::milli>(b - a).count();
 }
 
-// ProsacSampler::Sample (solvers/prosac_sampler.cc:62-128): data sorted by
-// quality; the k-th sample draws m-1 points from the top n-1 and the n-th point
-// (or m from the top n once T'_n < k).  The reference pushes index `n` itself,
-// which is one past the end once n reaches N; that single case is clamped to N-1
-// here (the reference reads out of bounds there).
-void prosac_sample(Mt19937& rng, int N, int m, int kth, int* out) {
-  double t_n = 20000.0;  // ransac_convergence_iterations_
-  int n = m;
-  for (int i = 0; i < m; ++i) t_n *= (double)(n - i) / (N - i);
-  double t_n_prime = 1.0;
-  for (int t = 1; t <= kth; ++t) {
-    if (t > t_n_prime && n < N) {
-      const double t_n_plus1 = (t_n * (n + 1.0)) / (n + 1.0 - m);
-      t_n_prime += std::ceil(t_n_plus1 - t_n);
-      t_n = t_n_plus1;
-      n++;
+// The correspondences on the device.  They come from pageable memory: the copy occupies the calling thread for
+// total * ds * 8 B / ~11 GB/s (6 ms for 1000 pairs x 2000 matches).  It runs on a helper thread while the caller draws the
+// first chunk's sample streams.  Before wait() the caller enqueues only the two hipMemsetAsync of its set-up (the UPnP
+// states, the best models), which touch neither this buffer nor anything that reads it; the pointer is handed out by data()
+// alone, which joins the helper first, so nothing that reads the buffer can be enqueued ahead of the copy.
+class Correspondences {
+  DBuf<double> buf;
+  std::thread th;
+  hipError_t err = hipSuccess;
+  void join() { if (th.joinable()) th.join(); }
+
+ public:
+  ~Correspondences() { join(); }
+  int start(const double* src, size_t count, hipStream_t st) {
+    if (int rc = buf.ensure(count)) return rc;
+    double* dst = buf.p; const size_t bytes = sizeof(double) * count;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    try {
+      th = std::thread([this, src, dst, bytes, st, dev] { (void)hipSetDevice(dev); err = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st); });
+    } catch (...) {   // no thread to be had: the same copy, here
+      err = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st);
     }
+    return 0;
   }
-  auto draw_unique = [&](int count, int hi) {
-    for (int i = 0; i < count; ++i) {
-      int r;
-      bool dup;
-      do {
-        r = rng.rand_int(0, hi);
-        dup = false;
-        for (int q = 0; q < i; ++q) dup |= (out[q] == r);
-      } while (dup);
-      out[i] = r;
-    }
-  };
-  if (t_n_prime < kth) draw_unique(m, n - 1);
-  else { draw_unique(m - 1, n - 2); out[m - 1] = std::min(n, N - 1); }
-}
-
-struct ProblemState {
-  Mt19937 rng;
-  std::vector<int> idx;
-  double best_cost;
-  int max_iterations, it, n;
-  bool done;
-  int best_slot;
-  int best_hyp = -1;          // hypothesis (chunk-local problem * B + iteration) of the best model, if set in this round
-  int best_samples[kMaxSample];
-  int round_iters;
-  int kth;  // PROSAC sample counter
-  int ex_i, ex_j;  // ExhaustiveSampler cursor (exhaustive_sampler.cc:48,61-79)
-  // replay cursor inside the current round and LO-RANSAC state
-  int base_it, rb, rj;
-  bool round_done, best_refined;
-  double pending_ratio;
-  int num_lo;
-  bool p4pfr_first;   // the P4Pfr solver's static generator re-seeds this problem's stream with 42 after its first sample
-  int last_k;         // iterations of the last finished round
-};
-// streams mode only (StreamInit; kept apart so that the seeded path does not initialise it): the generator at the start of
-// the current round (or at the P4Pfr re-seed inside it), the words iteration b of the round had taken since then (cum[b])
-struct StreamRound {
-  Mt19937 anchor;
-  uint64_t anchor_drawn = 0;
-  std::vector<uint64_t> cum;
+  int wait() {
+    join();
+    return err == hipSuccess ? 0 : set_error(THEIA_HIP_ERR_INTERNAL, "upload of the correspondences: %s", hipGetErrorString(err));
+  }
+  const double* data() { join(); return buf.p; }
 };
 
-// theia_hip_ransac_estimate_streams: the problems of one driver call are the head problems of their streams, one per stream
-// (every problem starts where its stream stands).  gen[stream[p]] is the generator problem p starts from; the driver
-// overwrites it with the generator after exactly num_iterations samples.  Per stream the P4Pfr first-call flag and (DLS /
-// gDLS) the rand() stream positioned at the problem's first call.
-struct StreamInit {
-  Mt19937* gen;
-  const int* stream;
-  const uint8_t* p4pfr_first;
-  const dls::GlibcRand* dls_start;   // NULL unless the estimator is DLS / gDLS
+struct FitScoreEvents {   // start of the fit, between fit and score, end of the score
+  hipEvent_t ev0 = nullptr, ev1 = nullptr, evm = nullptr;
+  int create() { HIP_TRYR(hipEventCreate(&ev0)); HIP_TRYR(hipEventCreate(&ev1)); HIP_TRYR(hipEventCreate(&evm)); return 0; }
+  ~FitScoreEvents() { for (hipEvent_t e : {ev0, ev1, evm}) if (e) (void)hipEventDestroy(e); }
 };
 
-}  // namespace
-}  // namespace thip
+// The sample streams of the NEXT chunk's first round are drawn while this chunk's kernels run; their 30 MB go up on
+// the copy stream at once, into the device buffer of their host buffer, and the solver stream waits for the event instead
+// of copying them between two chunks' kernels.
+struct PreUpload {
+  hipEvent_t ev = nullptr; bool pending = false;
+  PreUpload() { (void)hipEventCreateWithFlags(&ev, hipEventDisableTiming); }
+  ~PreUpload() { if (ev) { if (pending) (void)hipEventSynchronize(ev); (void)hipEventDestroy(ev); } }   // (the buffers outlive the copy)
+};
 
-using namespace thip;
+struct LoEvent { int prob, slot, hyp; int samples[8]; };   // hyp: (problem in chunk) * B + iteration of the round, or -1
 
-static int ransac_run(const theia_ransac_batch* batch, const theia_ransac_params* params, theia_ransac_result* result,
-                      const StreamInit* si);
+// one round of one chunk
+struct Round {
+  int c0, cn, B = 0;
+  size_t nh = 0;             // cn * B hypotheses
+  bool samples_up = false;   // the samples went up on the copy stream already
+  std::chrono::steady_clock::time_point tp0, tp1, tp2;
+};
 
-extern "C" {
+// One call of the batch driver: its buffers, what it knows about the estimator, and the stages of a round in the order
+// ransac_run() calls them.
+struct RansacCall {
+  const theia_ransac_batch* const batch;
+  const theia_ransac_params& P;
+  theia_ransac_result* const result;
+  const StreamInit* const si;
+  // development switches, read once per call
+  const bool fit_one_kernel = getenv("THEIA_HIP_FIT_ONE_KERNEL") != nullptr, dls_thread_eig = getenv("THEIA_HIP_DLS_THREAD_EIG") != nullptr,
+             debug = getenv("THEIA_HIP_RANSAC_DEBUG") != nullptr, refit = getenv("THEIA_HIP_RANSAC_REFIT") != nullptr,
+             host_timing = getenv("THEIA_HIP_RANSAC_TIMING") != nullptr;
+  std::chrono::steady_clock::time_point t_entry, t_loop;
 
-void theia_ransac_params_default(theia_ransac_params* p) {
-  // sample_consensus_estimator.h:59-68
-  std::memset(p, 0, sizeof(*p));
-  p->error_thresh = -1;
-  p->failure_probability = 0.01;
-  p->min_inlier_ratio = 0;
-  p->min_iterations = 100;
-  p->max_iterations = std::numeric_limits<int>::max();
-  p->use_mle = 0; p->use_Tdd_test = 0; p->use_lo = 0; p->lo_start_iterations = 50;
-  p->seed = 0;
-}
-
-int theia_hip_ransac_estimate_batch(const theia_ransac_batch* batch, const theia_ransac_params* params,
-                                    theia_ransac_result* result) {
-  return ransac_run(batch, params, result, nullptr);
-}
-
-}  // extern "C"
-
-// the host driver of both entry points: si == NULL is the seeded batch (problem i: RandomNumberGenerator(seed + i))
-static int ransac_run(const theia_ransac_batch* batch, const theia_ransac_params* params, theia_ransac_result* result,
-                      const StreamInit* si) {
-  if (!batch || !params || !result) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "null argument");
-  const theia_ransac_params& P = *params;
-  // SampleConsensusEstimator ctor CHECKs (sample_consensus_estimator.h:217-223)
-  if (!(P.error_thresh > 0)) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "Error threshold must be set to greater than zero");
-  if (!(P.min_inlier_ratio <= 1.0) || !(P.min_inlier_ratio >= 0.0)) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "min_inlier_ratio must be in [0, 1]");
-  if (!(P.failure_probability < 1.0) || !(P.failure_probability > 0.0)) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "failure_probability must be in (0, 1)");
-  if (P.max_iterations < P.min_iterations) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "max_iterations < min_iterations");
-  const int est = batch->estimator;
+  // ---- traits of the estimator and the sampler (check())
+  int est = 0, nprob = 0, m = 0, ds = 0, kMaxModels = 0;
   EstParams ep{0.0, 0.0};
-  if (est == THEIA_EST_UNCALIBRATED_RELATIVE_POSE && !batch->estimator_params)
-    return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "the uncalibrated relative-pose estimator needs estimator_params = {min, max focal length}");
-  if (est == THEIA_EST_UNCALIBRATED_RELATIVE_POSE && batch->estimator_params) {
-    ep.min_focal = batch->estimator_params[0];
-    ep.max_focal = batch->estimator_params[1];
-  }
-  const bool gdls_est = est == THEIA_EST_SIMILARITY_2D3D;
-  const bool dls_est = est == THEIA_EST_ABSOLUTE_POSE_DLS || gdls_est;   // the Macaulay pipeline: stage A -> eigen stage
-  if (est < 0 || est > THEIA_EST_RADIAL_DIST_UNCALIBRATED_ABSOLUTE_POSE) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "unknown estimator id");
-  const bool abs_pose = est == THEIA_EST_ABSOLUTE_POSE_KNEIP || est == THEIA_EST_ABSOLUTE_POSE_SQPNP || (dls_est && !gdls_est);
-  // estimators that keep Estimator::RefineModel's default "return true" (solvers/estimator.h:86-88): LO only counts
-  const bool trivial_refine = est == THEIA_EST_ESSENTIAL_MATRIX || est == THEIA_EST_DOMINANT_PLANE ||
-                              est == THEIA_EST_RELATIVE_POSE_KNOWN_ORIENTATION || est == THEIA_EST_ABSOLUTE_POSE_KNOWN_ORIENTATION ||
-                              est == THEIA_EST_TRIANGULATION || est == THEIA_EST_RADIAL_HOMOGRAPHY || est == THEIA_EST_SIMILARITY_2D3D ||
-                              est == THEIA_EST_UNCALIBRATED_ABSOLUTE_POSE || est == THEIA_EST_RIGID_TRANSFORMATION_2D3D ||
-                              est == THEIA_EST_RADIAL_DIST_UNCALIBRATED_ABSOLUTE_POSE;
-  const bool rel_pose = est == THEIA_EST_RELATIVE_POSE, uncal_pose = est == THEIA_EST_UNCALIBRATED_RELATIVE_POSE;
-  const bool homog = est == THEIA_EST_HOMOGRAPHY, fund = est == THEIA_EST_FUNDAMENTAL_MATRIX;
-  // every estimator's RefineModel is built: BundleAdjustView (absolute pose), BundleAdjustTwoViewsAngular ((un)calibrated
-  // relative pose), OptimizeHomography, OptimizeFundamentalMatrix, and the default "return true" of the rest
-  // exhaustive_sampler.cc:49-51 CHECK
-  if (P.ransac_type == THEIA_RANSAC_EXHAUSTIVE && sample_size(est) != 2)
-    return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "ExhaustiveSampler makes a hard assumption that the number of samples needed is 2.");
-  const bool lmed = P.ransac_type == THEIA_RANSAC_LMED;
-  if (P.ransac_type != THEIA_RANSAC_RANSAC && P.ransac_type != THEIA_RANSAC_PROSAC && !lmed &&
-      P.ransac_type != THEIA_RANSAC_EXHAUSTIVE)
-    return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "unknown ransac_type");
-  const int nprob = batch->num_problems;
-  if (nprob < 0 || (nprob > 0 && (!batch->offsets || !batch->data))) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "bad batch");
-  if (nprob > 0 && (!result->success || !result->models || !result->num_inliers || !result->inlier_mask ||
-                    !result->num_iterations || !result->confidence))
-    return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "null result array");
-  result->hypotheses_evaluated = 0; result->models_scored = 0; result->time_fit_score_seconds = 0.0;
-  result->time_fit_seconds = 0.0; result->time_score_seconds = 0.0;
-  if (nprob == 0) return 0;
-  int rc = ensure_device();
-  if (rc) return rc;
-  if (dls_est && (rc = dls_ensure_tables())) return rc;
-  const bool upnp_est = est == THEIA_EST_RIGID_TRANSFORMATION_2D3D;
-  if (upnp_est && (rc = upnp_ensure_tables())) return rc;
-  // P4Pfr: estimator_params = RadialDistUncalibratedAbsolutePoseMetaData {max focal length, min focal length, max distortion, min
-  // distortion} [, first call of the process (the solver's static generator re-seeds the shared stream with 42)]
-  const bool p4pfr_est = est == THEIA_EST_RADIAL_DIST_UNCALIBRATED_ABSOLUTE_POSE;
+  bool gdls_est = false, dls_est = false, trivial_refine = false, rel_pose = false, uncal_pose = false, homog = false, fund = false,
+       lmed = false, upnp_est = false, p4pfr_est = false, p4pfr_first_call = false;
   double p4pfr_limits[4] = {0.0, 0.0, 0.0, 0.0};
-  bool p4pfr_first_call = false;
-  if (p4pfr_est) {
-    if (!batch->estimator_params)
-      return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "the radial-distortion absolute-pose estimator needs estimator_params = {max focal length, min focal length, max distortion, min distortion, first call (0 / 1)}");
-    for (int k = 0; k < 4; ++k) p4pfr_limits[k] = batch->estimator_params[k];
-    p4pfr_first_call = !si && batch->estimator_params[4] != 0.0;   // (streams: per problem, StreamInit::p4pfr_first)
-    // the reference CHECKs these (four_point_focal_length_radial_distortion.cc:82-90)
-    if (!(p4pfr_limits[1] >= 0.0 && p4pfr_limits[0] >= 0.0 && p4pfr_limits[0] >= p4pfr_limits[1] && p4pfr_limits[2] <= 0.0 && p4pfr_limits[3] <= 0.0 &&
-          p4pfr_limits[2] <= p4pfr_limits[3]))
-      return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "P4Pfr: needs 0 <= min focal length <= max focal length and max distortion <= min distortion <= 0");
-    if (P.ransac_type == THEIA_RANSAC_EXHAUSTIVE) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "the exhaustive sampler draws pairs: sample size 4 does not fit");
-    if ((rc = p4pfr_ensure_tables())) return rc;
-  }
-  const auto t_entry = std::chrono::steady_clock::now();
-  const int m = sample_size(est), ds = datum_size(est);
-  const int64_t total = batch->offsets[nprob];
-  int nmax = 0;
-  std::vector<uint8_t> undersized(nprob, 0);
-  for (int p = 0; p < nprob; ++p) {
-    const int64_t n = batch->offsets[p + 1] - batch->offsets[p];
-    if (n <= 0) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "Cannot perform estimation with 0 data measurements!");
-    // fewer data than the minimal sample: the reference's sampler cannot be initialised for this problem (CHECK).  In a
-    // batch only that problem fails (success = 0, no inliers, zero model); the others run.
-    if (n < m) undersized[p] = 1;
-    if (n > (1 << 30)) return set_error(THEIA_HIP_ERR_UNSUPPORTED, "problem too large");
-    nmax = std::max(nmax, (int)n);
-  }
-  hipStream_t st = solver_stream();
-  PoolStreamScope pool_scope(st);   // blocks this call hands back to the caches are tagged with an event on this stream (pools.h)
-  if (!st) return set_error(THEIA_HIP_ERR_NO_DEVICE, "could not create the solver stream");
-  CallSync mine;
-  hipEvent_t ev0, ev1, evm;
-  HIP_TRYR(hipEventCreate(&ev0)); HIP_TRYR(hipEventCreate(&ev1)); HIP_TRYR(hipEventCreate(&evm));
-  struct EvGuard { hipEvent_t a, b, c; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); (void)hipEventDestroy(c); } } eguard{ev0, ev1, evm};
-  double fit_ms = 0.0, score_ms = 0.0;
+  theia_ba_options lo_opts;
+  double log_failure_prob = 0.0;
 
-  DBuf<double> d_data; DBuf<int64_t> d_off;
-  if ((rc = d_data.ensure((size_t)total * ds)) || (rc = d_off.ensure(nprob + 1))) return rc;
-  // The correspondences come from pageable memory: the copy occupies the calling thread for total * ds * 8 B / ~11 GB/s (6 ms for
-  // 1000 pairs x 2000 matches).  It runs on a helper thread while this one draws the first chunk's sample streams; nothing is
-  // enqueued behind it on the stream before upload.wait() (the first device work of the chunk loop, and every exit path).
-  struct Upload {
-    std::thread th; hipError_t err = hipSuccess;
-    int wait() { if (th.joinable()) th.join(); return err == hipSuccess ? 0 : set_error(THEIA_HIP_ERR_INTERNAL, "upload of the correspondences: %s", hipGetErrorString(err)); }
-    ~Upload() { if (th.joinable()) th.join(); }
-  } upload;
-  {
-    const double* src = batch->data; double* dst = d_data.p; const size_t bytes = sizeof(double) * (size_t)total * ds;
-    const int dev = [] { int d = 0; (void)hipGetDevice(&d); return d; }();
-    upload.th = std::thread([&upload, src, dst, bytes, st, dev] { (void)hipSetDevice(dev); upload.err = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st); });
-  }
+  SolverCall call;   // (ahead of every buffer)
+  hipStream_t st = nullptr, copy_st = nullptr;
+  FitScoreEvents clk;
+  double fit_ms = 0.0, score_ms = 0.0, fit_score_ms = 0.0;
 
-  const double log_failure_prob = std::log(P.failure_probability);
-  // round size: everything at once when the iteration count is fixed/small,
-  // otherwise chunks that the adaptive bound usually ends within
-  int first_round = std::max(128, std::min(P.max_iterations, std::max(P.min_iterations, 512)));
-  first_round = std::min(first_round, 4096);
-  const int next_round = 1024;
-  // problems per chunk: bound the model workspace (3 GiB by default -- 1.5 GiB cost five-point 1.4 % and SQPnP 5 % in per-chunk
-  // synchronisations; THEIA_HIP_RANSAC_WORKSPACE_MB overrides)
-  const int kMaxModels = max_models(est);   // slot stride of this estimator
-  const size_t per_hyp = (size_t)kMaxModels * kStride * sizeof(double);
-  static const size_t ws_bytes = [] { const char* e = getenv("THEIA_HIP_RANSAC_WORKSPACE_MB"); return e && atol(e) > 0 ? (size_t)atol(e) << 20 : (size_t)3 << 30; }();
-  int chunk = (int)std::max<size_t>(1, ws_bytes / (per_hyp * (size_t)first_round));
-  chunk = std::min(chunk, nprob);
+  // ---- sizes (setup())
+  int64_t total = 0;
+  int nmax = 0, first_round = 0, chunk = 0;
+  static constexpr int next_round = 1024;
+  std::vector<uint8_t> undersized;
+  size_t lmed_lds = 0, lds_bytes = 0;
+  int lmed_in_lds = 1;
+  bool use_lds = false;
 
+  // ---- buffers
+  Correspondences corr; DBuf<int64_t> d_off;
   DBuf<int> d_samples2[2], d_counts, d_ninl, d_active, d_best_samples, d_best_slot, d_dense, d_tags;   // d_samples2: by host sample buffer
   DBuf<int> d_hyp_base;   // [problem][iteration] first dense model of the hypothesis (k_fit)
   DBuf<int> d_save;       // {problem, hypothesis, slot} triples of k_save_best
@@ -1643,65 +1335,108 @@ static int ransac_run(const theia_ransac_batch* batch, const theia_ransac_params
                                                              // counts twice: the next chunk's first round is drawn while the GPU works)
   HBuf<double> h_cost;
   HBuf<int> h_hyp_base, h_prefix;   // per hypothesis: first model in its problem's dense order; per problem: first packed score
-  size_t lmed_lds = (size_t)nmax * sizeof(double);
-  int lmed_in_lds = 1;
-  if (lmed) {
-    // the squared residuals of a model stay in LDS for the radix select: 160 KB per workgroup on gfx950, 8 KB kept for the rest;
-    // beyond that (more than 19 456 data in a problem) the passes of the select re-evaluate them (lmed_sq)
-    if (lmed_lds > 152 * 1024) { lmed_lds = 0; lmed_in_lds = 0; }
-    if (lmed_lds > 48 * 1024) {
-      HIP_TRYR(hipFuncSetAttribute((const void*)k_score_lmed, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lmed_lds));
-      HIP_TRYR(hipFuncSetAttribute((const void*)k_inlier_mask_lmed, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lmed_lds));
-      HIP_TRYR(hipFuncSetAttribute((const void*)k_lo_lmed_bound, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lmed_lds));
-    }
-  }
-  const bool use_lds = (size_t)nmax * ds * sizeof(double) <= 96 * 1024;
-  const size_t lds_bytes = use_lds ? (size_t)nmax * ds * sizeof(double) : 0;
-  if (use_lds && lds_bytes > 48 * 1024) {
-    // every instance that can be launched below opts in (the compile-time-estimator instances are kernels of their own)
-    const void* fn = (const void*)k_score<true>;
-    if (est == THEIA_EST_RELATIVE_POSE) fn = (const void*)k_score<true, THEIA_EST_RELATIVE_POSE>;
-    else if (est == THEIA_EST_ESSENTIAL_MATRIX) fn = (const void*)k_score<true, THEIA_EST_ESSENTIAL_MATRIX>;
-    else if (est == THEIA_EST_ABSOLUTE_POSE_KNEIP) fn = (const void*)k_score<true, THEIA_EST_ABSOLUTE_POSE_KNEIP>;
-    else if (est == THEIA_EST_ABSOLUTE_POSE_DLS) fn = (const void*)k_score<true, THEIA_EST_ABSOLUTE_POSE_DLS>;
-    else if (est == THEIA_EST_ABSOLUTE_POSE_SQPNP) fn = (const void*)k_score<true, THEIA_EST_ABSOLUTE_POSE_SQPNP>;
-    HIP_TRYR(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-  }
-
   DBuf<double> d_upnp_state;   // UPnP: the estimator's accumulating cost parameters per problem (upnp_kernels.hip)
-  if (upnp_est) {
-    if ((rc = d_upnp_state.ensure((size_t)nprob * upnp_state_doubles()))) return rc;
-    HIP_TRYR(hipMemsetAsync(d_upnp_state.p, 0, sizeof(double) * (size_t)nprob * upnp_state_doubles(), st));
-  }
-  std::vector<int> best_samples_all((size_t)nprob * kMaxSample, 0), best_slot_all(nprob, -1);
-  std::vector<ProblemState> S(nprob);
-  std::vector<StreamRound> SR(si ? nprob : 0);
-  std::vector<dls::GlibcRand> SD(si && si->dls_start ? nprob : 0);   // streams: every problem's own rand() stream (DLS / gDLS)
-  host_parallel_for(nprob, [&](int p) {   // (the generator's 624-word seeding and the index permutation of every problem: ~1 us each)
-    ProblemState& s = S[p];
-    s.n = (int)(batch->offsets[p + 1] - batch->offsets[p]);
-    if (si) s.rng = si->gen[si->stream[p]];
-    else s.rng.seed(batch->seeds ? batch->seeds[p] : P.seed + (uint32_t)p);
-    s.p4pfr_first = si ? si->p4pfr_first[si->stream[p]] != 0 : p4pfr_first_call;
-    s.last_k = 0;
-    if (si && si->dls_start) SD[p] = si->dls_start[si->stream[p]];
-    s.idx.resize(s.n);
-    for (int i = 0; i < s.n; ++i) s.idx[i] = i;
-    s.best_cost = std::numeric_limits<double>::max();
-    s.max_iterations = P.max_iterations;
-    if (P.min_inlier_ratio > 0)
-      s.max_iterations = std::min(compute_max_iterations(P, m, P.min_inlier_ratio, log_failure_prob, s.n), P.max_iterations);
-    s.it = 0; s.done = s.max_iterations <= 0 || undersized[p]; s.best_slot = -1; s.kth = 1; s.ex_i = 0; s.ex_j = 1;
-    s.base_it = 0; s.rb = 0; s.rj = 0; s.round_done = true; s.best_refined = false; s.pending_ratio = 0.0; s.num_lo = 0;
-    for (int k = 0; k < kMaxSample; ++k) s.best_samples[k] = 0;
-  });
-  double fit_score_ms = 0.0;
-  // ---- LO-RANSAC (absolute / relative pose): batched RefineModel over a list of events
+  std::vector<ProblemState> S;
+  std::vector<StreamRound> SR;
+  std::vector<dls::GlibcRand> SD;   // streams: every problem's own rand() stream (DLS / gDLS)
+  // LO-RANSAC (absolute / relative pose): batched RefineModel over a list of events
   DBuf<int> d_ev_prob, d_ev_samples, d_ev_slot, d_ev_hyp, d_ev_count, d_ev_success, d_lo_model_id;
   DBuf<int64_t> d_ev_off;
   DBuf<double> d_ev_model, d_ev_cam, d_lo_uv, d_lo_X, d_cur_models, d_lo_intr, d_ev_sqt;
   DBuf<char> d_lo_out;
-  theia_ba_options lo_opts;
+
+  // ---- the chunk loop's state
+  int bufi = 0, pre_c0 = -1, pre_B = 0;   // pre_*: the first round of chunk pre_c0 already sits in buffer 1 - bufi
+  bool offsets_up = false;
+  PreUpload pre_up;
+
+  RansacCall(const theia_ransac_batch* b, const theia_ransac_params& p, theia_ransac_result* r, const StreamInit* s)
+      : batch(b), P(p), result(r), si(s) {}
+
+  int check();
+  void set_lo_options();
+  int setup();
+  int gen_round(int c0, int cn, bool first, int buf, int* B_out);
+  int begin_round(Round& r, bool first);
+  int upload_round(Round& r);
+  int launch_fit_dls(const Round& r);
+  int launch_fit(const Round& r);
+  int launch_score(const Round& r);
+  int predraw_next_chunk(const Round& r);
+  int download_scores(Round& r);
+  int run_lo(const std::vector<LoEvent>& evs, int round_B, std::vector<int>& success);
+  int replay(const Round& r);
+  int save_best(const Round& r);
+  int upload_offsets();
+  int finish();
+};
+
+// Argument and estimator checks; the traits.  nprob == 0 afterwards: nothing to do.
+int RansacCall::check() {
+  // SampleConsensusEstimator ctor CHECKs (sample_consensus_estimator.h:217-223)
+  if (!(P.error_thresh > 0)) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "Error threshold must be set to greater than zero");
+  if (!(P.min_inlier_ratio <= 1.0) || !(P.min_inlier_ratio >= 0.0)) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "min_inlier_ratio must be in [0, 1]");
+  if (!(P.failure_probability < 1.0) || !(P.failure_probability > 0.0)) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "failure_probability must be in (0, 1)");
+  if (P.max_iterations < P.min_iterations) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "max_iterations < min_iterations");
+  est = batch->estimator;
+  if (est == THEIA_EST_UNCALIBRATED_RELATIVE_POSE && !batch->estimator_params)
+    return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "the uncalibrated relative-pose estimator needs estimator_params = {min, max focal length}");
+  if (est == THEIA_EST_UNCALIBRATED_RELATIVE_POSE && batch->estimator_params) {
+    ep.min_focal = batch->estimator_params[0];
+    ep.max_focal = batch->estimator_params[1];
+  }
+  gdls_est = est == THEIA_EST_SIMILARITY_2D3D;
+  dls_est = est == THEIA_EST_ABSOLUTE_POSE_DLS || gdls_est;   // the Macaulay pipeline: stage A -> eigen stage
+  if (est < 0 || est > THEIA_EST_RADIAL_DIST_UNCALIBRATED_ABSOLUTE_POSE) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "unknown estimator id");
+  // estimators that keep Estimator::RefineModel's default "return true" (solvers/estimator.h:86-88): LO only counts
+  trivial_refine = est == THEIA_EST_ESSENTIAL_MATRIX || est == THEIA_EST_DOMINANT_PLANE ||
+                   est == THEIA_EST_RELATIVE_POSE_KNOWN_ORIENTATION || est == THEIA_EST_ABSOLUTE_POSE_KNOWN_ORIENTATION ||
+                   est == THEIA_EST_TRIANGULATION || est == THEIA_EST_RADIAL_HOMOGRAPHY || est == THEIA_EST_SIMILARITY_2D3D ||
+                   est == THEIA_EST_UNCALIBRATED_ABSOLUTE_POSE || est == THEIA_EST_RIGID_TRANSFORMATION_2D3D ||
+                   est == THEIA_EST_RADIAL_DIST_UNCALIBRATED_ABSOLUTE_POSE;
+  rel_pose = est == THEIA_EST_RELATIVE_POSE; uncal_pose = est == THEIA_EST_UNCALIBRATED_RELATIVE_POSE;
+  homog = est == THEIA_EST_HOMOGRAPHY; fund = est == THEIA_EST_FUNDAMENTAL_MATRIX;
+  // every estimator's RefineModel is built: BundleAdjustView (absolute pose), BundleAdjustTwoViewsAngular ((un)calibrated
+  // relative pose), OptimizeHomography, OptimizeFundamentalMatrix, and the default "return true" of the rest
+  // exhaustive_sampler.cc:49-51 CHECK
+  if (P.ransac_type == THEIA_RANSAC_EXHAUSTIVE && sample_size(est) != 2)
+    return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "ExhaustiveSampler makes a hard assumption that the number of samples needed is 2.");
+  lmed = P.ransac_type == THEIA_RANSAC_LMED;
+  if (P.ransac_type != THEIA_RANSAC_RANSAC && P.ransac_type != THEIA_RANSAC_PROSAC && !lmed &&
+      P.ransac_type != THEIA_RANSAC_EXHAUSTIVE)
+    return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "unknown ransac_type");
+  nprob = batch->num_problems;
+  if (nprob < 0 || (nprob > 0 && (!batch->offsets || !batch->data))) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "bad batch");
+  int rc = check_result_arrays(nprob, result);
+  if (rc) return rc;
+  reset_counters(result);
+  if (nprob == 0) return 0;
+  if ((rc = call.open())) return rc;
+  st = call.st;
+  if (dls_est && (rc = dls_ensure_tables())) return rc;
+  upnp_est = est == THEIA_EST_RIGID_TRANSFORMATION_2D3D;
+  if (upnp_est && (rc = upnp_ensure_tables())) return rc;
+  // P4Pfr: estimator_params = RadialDistUncalibratedAbsolutePoseMetaData {max focal length, min focal length, max distortion, min
+  // distortion} [, first call of the process (the solver's static generator re-seeds the shared stream with 42)]
+  p4pfr_est = est == THEIA_EST_RADIAL_DIST_UNCALIBRATED_ABSOLUTE_POSE;
+  if (p4pfr_est) {
+    if (!batch->estimator_params)
+      return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "the radial-distortion absolute-pose estimator needs estimator_params = {max focal length, min focal length, max distortion, min distortion, first call (0 / 1)}");
+    for (int k = 0; k < 4; ++k) p4pfr_limits[k] = batch->estimator_params[k];
+    p4pfr_first_call = !si && batch->estimator_params[4] != 0.0;   // (streams: per problem, StreamInit::p4pfr_first)
+    if ((rc = p4pfr_check_limits(p4pfr_limits))) return rc;
+    if (P.ransac_type == THEIA_RANSAC_EXHAUSTIVE) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "the exhaustive sampler draws pairs: sample size 4 does not fit");
+    if ((rc = p4pfr_ensure_tables())) return rc;
+  }
+  t_entry = std::chrono::steady_clock::now();
+  m = sample_size(est); ds = datum_size(est);
+  kMaxModels = max_models(est);   // slot stride of this estimator
+  log_failure_prob = std::log(P.failure_probability);
+  return 0;
+}
+
+// the options of every estimator's RefineModel
+void RansacCall::set_lo_options() {
   theia_ba_options_default(&lo_opts);
   lo_opts.max_num_iterations = 2;                        // estimate_calibrated_absolute_pose.cc:124-129
   lo_opts.use_homogeneous_point_parametrization = 0;
@@ -1716,440 +1451,473 @@ static int ransac_run(const theia_ransac_batch* batch, const theia_ransac_params
   }
   if (fund) { lo_opts.max_num_iterations = 2; lo_opts.loss_function_type = THEIA_LOSS_TRIVIAL; }   // estimate_fundamental_matrix.cc:56-57
   if (uncal_pose) lo_opts.max_num_iterations = 10;      // estimate_uncalibrated_relative_pose.cc:162-165 (HUBER, 1.5 x thresh)
+}
+
+// sizes, the upload of the correspondences, LDS opt-ins, problem states
+int RansacCall::setup() {
+  int rc;
+  total = batch->offsets[nprob];
+  undersized.assign(nprob, 0);
+  for (int p = 0; p < nprob; ++p) {
+    const int64_t n = batch->offsets[p + 1] - batch->offsets[p];
+    if (n <= 0) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "Cannot perform estimation with 0 data measurements!");
+    // fewer data than the minimal sample: the reference's sampler cannot be initialised for this problem (CHECK).  In a
+    // batch only that problem fails (success = 0, no inliers, zero model); the others run.
+    if (n < m) undersized[p] = 1;
+    if (n > (1 << 30)) return set_error(THEIA_HIP_ERR_UNSUPPORTED, "problem too large");
+    nmax = std::max(nmax, (int)n);
+  }
+  if ((rc = clk.create())) return rc;
+  if ((rc = corr.start(batch->data, (size_t)total * ds, st)) || (rc = d_off.ensure(nprob + 1))) return rc;
+
+  // round size: everything at once when the iteration count is fixed/small,
+  // otherwise chunks that the adaptive bound usually ends within
+  first_round = std::max(128, std::min(P.max_iterations, std::max(P.min_iterations, 512)));
+  first_round = std::min(first_round, 4096);
+  // problems per chunk: bound the model workspace (3 GiB by default -- 1.5 GiB cost five-point 1.4 % and SQPnP 5 % in per-chunk
+  // synchronisations; THEIA_HIP_RANSAC_WORKSPACE_MB overrides)
+  const size_t per_hyp = (size_t)kMaxModels * kStride * sizeof(double);
+  static const size_t ws_bytes = [] { const char* e = getenv("THEIA_HIP_RANSAC_WORKSPACE_MB"); return e && atol(e) > 0 ? (size_t)atol(e) << 20 : (size_t)3 << 30; }();
+  chunk = (int)std::max<size_t>(1, ws_bytes / (per_hyp * (size_t)first_round));
+  chunk = std::min(chunk, nprob);
+
+  lmed_lds = (size_t)nmax * sizeof(double);
+  if (lmed) {
+    // the squared residuals of a model stay in LDS for the radix select: 160 KB per workgroup on gfx950, 8 KB kept for the rest;
+    // beyond that (more than 19 456 data in a problem) the passes of the select re-evaluate them (lmed_sq)
+    if (lmed_lds > 152 * 1024) { lmed_lds = 0; lmed_in_lds = 0; }
+    if (lmed_lds > 48 * 1024) {
+      HIP_TRYR(hipFuncSetAttribute((const void*)k_score_lmed, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lmed_lds));
+      HIP_TRYR(hipFuncSetAttribute((const void*)k_inlier_mask_lmed, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lmed_lds));
+      HIP_TRYR(hipFuncSetAttribute((const void*)k_lo_lmed_bound, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lmed_lds));
+    }
+  }
+  use_lds = (size_t)nmax * ds * sizeof(double) <= 96 * 1024;
+  lds_bytes = use_lds ? (size_t)nmax * ds * sizeof(double) : 0;
+  if (use_lds && lds_bytes > 48 * 1024) {
+    // every instance that can be launched below opts in (the compile-time-estimator instances are kernels of their own)
+    const void* fn = (const void*)k_score<true>;
+    if (est == THEIA_EST_RELATIVE_POSE) fn = (const void*)k_score<true, THEIA_EST_RELATIVE_POSE>;
+    else if (est == THEIA_EST_ESSENTIAL_MATRIX) fn = (const void*)k_score<true, THEIA_EST_ESSENTIAL_MATRIX>;
+    else if (est == THEIA_EST_ABSOLUTE_POSE_KNEIP) fn = (const void*)k_score<true, THEIA_EST_ABSOLUTE_POSE_KNEIP>;
+    else if (est == THEIA_EST_ABSOLUTE_POSE_DLS) fn = (const void*)k_score<true, THEIA_EST_ABSOLUTE_POSE_DLS>;
+    else if (est == THEIA_EST_ABSOLUTE_POSE_SQPNP) fn = (const void*)k_score<true, THEIA_EST_ABSOLUTE_POSE_SQPNP>;
+    HIP_TRYR(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+  }
+
+  if (upnp_est) {
+    if ((rc = d_upnp_state.ensure((size_t)nprob * upnp_state_doubles()))) return rc;
+    HIP_TRYR(hipMemsetAsync(d_upnp_state.p, 0, sizeof(double) * (size_t)nprob * upnp_state_doubles(), st));
+  }
+  S.resize(nprob);
+  SR.resize(si ? nprob : 0);
+  SD.resize(si && si->dls_start ? nprob : 0);
+  host_parallel_for(nprob, [&](int p) {   // (the generator's 624-word seeding and the index permutation of every problem: ~1 us each)
+    ProblemState& s = S[p];
+    if (si) s.rng = si->gen[si->stream[p]];
+    else s.rng.seed(batch->seeds ? batch->seeds[p] : P.seed + (uint32_t)p);
+    s.p4pfr_first = si ? si->p4pfr_first[si->stream[p]] != 0 : p4pfr_first_call;
+    s.last_k = 0;
+    if (si && si->dls_start) SD[p] = si->dls_start[si->stream[p]];
+    problem_init(s, (int)(batch->offsets[p + 1] - batch->offsets[p]), m, P, log_failure_prob, undersized[p] != 0);
+  });
   if (P.use_lo && (rc = d_cur_models.ensure((size_t)nprob * kStride))) return rc;
   if ((rc = d_best_models.ensure((size_t)nprob * kStride))) return rc;
   HIP_TRYR(hipMemsetAsync(d_best_models.p, 0, sizeof(double) * nprob * kStride, st));
-  struct LoEvent { int prob, slot, hyp; int samples[8]; };   // hyp: (problem in chunk) * B + iteration of the round, or -1
-  int lo_round_B = 0;
-  // refines every event's model on its inliers; writes the refined pose to d_cur_models[prob]
-  auto run_lo = [&](const std::vector<LoEvent>& evs, std::vector<int>& success) -> int {
-    const int nev = (int)evs.size();
-    success.assign(nev, 0);
-    if (nev == 0) return 0;
-    std::vector<int> hp(nev), hs((size_t)nev * kMaxSample), hsl(nev), hmod(nev, THEIA_CAM_PINHOLE), hhyp(nev);
-    std::vector<int64_t> hoff(nev + 1, 0);
-    std::vector<double> hintr((size_t)nev * THEIA_MAX_INTRINSICS, 0.0);
-    for (int e = 0; e < nev; ++e) {
-      hp[e] = evs[e].prob; hsl[e] = evs[e].slot; hhyp[e] = evs[e].hyp;
-      for (int k = 0; k < kMaxSample; ++k) hs[(size_t)e * kMaxSample + k] = evs[e].samples[k];
-      hoff[e + 1] = hoff[e] + S[evs[e].prob].n;          // capacity: every datum could be an inlier
-      hintr[(size_t)e * THEIA_MAX_INTRINSICS] = 1.0; hintr[(size_t)e * THEIA_MAX_INTRINSICS + 1] = 1.0;   // Camera(): f = 1, aspect 1
+  copy_st = copy_stream();
+  t_loop = std::chrono::steady_clock::now();
+  return 0;
+}
+
+// one round of a chunk on the host, into host buffer `buf`: iterations per problem and the sample streams
+// (gen_round_problem); problems are independent (own generator, own slice): host threads share them
+int RansacCall::gen_round(int c0, int cn, bool first, int buf, int* B_out) {
+  HBuf<int>& act = h_active2[buf]; HBuf<int>& smp = h_samples2[buf]; HBuf<double>& rotb = h_rot2[buf];
+  int B = 0;
+  if (!act.assign(cn, 0)) return set_error(THEIA_HIP_ERR_OUT_OF_MEMORY, "hipHostMalloc failed");
+  for (int q = 0; q < cn; ++q) {
+    ProblemState& s = S[c0 + q];
+    s.round_iters = 0;
+    if (s.done) continue;
+    const int cap = first ? first_round : next_round;
+    s.round_iters = std::min(cap, s.max_iterations - s.it);
+    act[q] = s.round_iters;
+    B = std::max(B, s.round_iters);
+  }
+  *B_out = B;
+  if (B == 0) return 0;
+  if (!smp.resize((size_t)cn * B * m)) return set_error(THEIA_HIP_ERR_OUT_OF_MEMORY, "hipHostMalloc failed");
+  if (p4pfr_est && !rotb.resize((size_t)cn * B * 9)) return set_error(THEIA_HIP_ERR_OUT_OF_MEMORY, "hipHostMalloc failed");
+  host_parallel_for(cn, [&](int q) {
+    ProblemState& s = S[c0 + q];
+    double* rot = p4pfr_est ? rotb.data() + (size_t)q * B * 9 : nullptr;   // the three draws of a hypothesis land in its matrix' slot
+    gen_round_problem(s, si ? &SR[c0 + q] : nullptr, P.ransac_type, m, B, p4pfr_est, smp.data() + (size_t)q * B * m, rot, 9);
+    for (int b = 0; p4pfr_est && b < s.round_iters; ++b) {
+      const double v[3] = {rot[(size_t)b * 9], rot[(size_t)b * 9 + 1], rot[(size_t)b * 9 + 2]};
+      p4pfr_rotation_from_draws(v, rot + (size_t)b * 9);
     }
-    int rc2;
-    if ((rc2 = d_ev_prob.ensure(nev)) || (rc2 = d_ev_samples.ensure((size_t)nev * kMaxSample)) || (rc2 = d_ev_slot.ensure(nev)) ||
-        (rc2 = d_ev_count.ensure(nev)) || (rc2 = d_ev_success.ensure(nev)) || (rc2 = d_ev_off.ensure(nev + 1)) ||
-        (rc2 = d_ev_model.ensure((size_t)nev * kStride)) || (rc2 = d_ev_cam.ensure((size_t)nev * 9)) ||
-        (rc2 = d_lo_uv.ensure((size_t)hoff[nev] * 2)) || (rc2 = d_lo_X.ensure((size_t)hoff[nev] * 4)) ||
-        (rc2 = d_lo_intr.ensure(hintr.size())) || (rc2 = d_lo_model_id.ensure(nev)) ||
-        (rc2 = d_lo_out.ensure(views_batch_out_bytes() * nev)))
-      return rc2;
-    HIP_TRYR(hipMemcpyAsync(d_ev_prob.p, hp.data(), sizeof(int) * nev, hipMemcpyHostToDevice, st));
-    HIP_TRYR(hipMemcpyAsync(d_ev_samples.p, hs.data(), sizeof(int) * nev * kMaxSample, hipMemcpyHostToDevice, st));
-    HIP_TRYR(hipMemcpyAsync(d_ev_slot.p, hsl.data(), sizeof(int) * nev, hipMemcpyHostToDevice, st));
-    if ((rc2 = d_ev_hyp.ensure(nev))) return rc2;
-    HIP_TRYR(hipMemcpyAsync(d_ev_hyp.p, hhyp.data(), sizeof(int) * nev, hipMemcpyHostToDevice, st));
-    HIP_TRYR(hipMemcpyAsync(d_ev_off.p, hoff.data(), sizeof(int64_t) * (nev + 1), hipMemcpyHostToDevice, st));
-    HIP_TRYR(hipMemcpyAsync(d_lo_intr.p, hintr.data(), sizeof(double) * hintr.size(), hipMemcpyHostToDevice, st));
-    HIP_TRYR(hipMemcpyAsync(d_lo_model_id.p, hmod.data(), sizeof(int) * nev, hipMemcpyHostToDevice, st));
-    k_lo_prepare<<<(nev + 63) / 64, 64, 0, st>>>(est, nev, d_ev_prob.p, d_ev_samples.p, d_ev_slot.p, d_ev_hyp.p, lo_round_B,
-                                                 d_models.p, d_hyp_base.p, d_off.p, d_data.p,
-                                                 d_cur_models.p, d_ev_model.p, d_ev_cam.p, ep);
-    if (lmed) {
-      if ((rc2 = d_ev_sqt.ensure(nev))) return rc2;
-      k_lo_lmed_bound<<<nev, 256, lmed_lds, st>>>(est, d_ev_prob.p, d_off.p, d_data.p, d_ev_model.p, d_ev_sqt.p, lmed_in_lds);
-    }
-    k_lo_gather<<<nev, 64, 0, st>>>(est, d_ev_prob.p, d_off.p, d_data.p, d_ev_model.p, P.error_thresh, lmed ? d_ev_sqt.p : nullptr, d_ev_off.p, d_ev_count.p,
-                                    reinterpret_cast<double2*>(d_lo_uv.p), reinterpret_cast<double4*>(d_lo_X.p));
-    if (fund)
-      fundamental_batch_device(nev, d_ev_off.p, d_ev_count.p, d_lo_X.p, d_ev_cam.p, &lo_opts, d_lo_out.p, st);
-    else if (homog)
-      homography_batch_device(nev, d_ev_off.p, d_ev_count.p, d_lo_X.p, d_ev_cam.p, &lo_opts, d_lo_out.p, st);
-    else if (rel_pose || uncal_pose)   // the relative-pose RefineModel asks for CGNR, the uncalibrated one keeps the direct default
-      twoview_batch_device(nev, d_ev_off.p, d_ev_count.p, d_lo_X.p, d_ev_cam.p, &lo_opts, rel_pose ? 1 : 0, d_lo_out.p, st);
-    else
-      views_batch_device(nev, d_ev_off.p, d_ev_count.p, d_lo_uv.p, nullptr, d_lo_X.p, d_ev_cam.p, d_lo_intr.p, d_lo_model_id.p,
-                         nullptr, &lo_opts, d_lo_out.p, st);
-    k_lo_finish<<<(nev + 63) / 64, 64, 0, st>>>(est, nev, d_ev_prob.p, d_ev_cam.p, d_ev_model.p,
-                                                reinterpret_cast<const BatchLmOut*>(d_lo_out.p), d_cur_models.p, d_ev_success.p);
-    HIP_TRYR(hipMemcpyAsync(success.data(), d_ev_success.p, sizeof(int) * nev, hipMemcpyDeviceToHost, st));
-    HIP_TRYR(mine.wait(st));
-    return 0;
-  };
-  const bool host_timing = getenv("THEIA_HIP_RANSAC_TIMING") != nullptr;
-  // one round of a chunk on the host: iterations per problem and the sample stream (RandomSampler::Sample with its
-  // persistent permutation, PROSAC, EXHAUSTIVE); problems are independent (own generator, own slice): host threads share them
-  auto gen_round = [&](int c0, int cn, bool first, HBuf<int>& act, HBuf<int>& smp, HBuf<double>& rotb, int* B_out) -> int {
-    int B = 0;
-    if (!act.assign(cn, 0)) return set_error(THEIA_HIP_ERR_OUT_OF_MEMORY, "hipHostMalloc failed");
+  });
+  return 0;
+}
+
+// the round's samples: the ones drawn ahead for this chunk, or drawn now
+int RansacCall::begin_round(Round& r, bool first) {
+  r.tp0 = std::chrono::steady_clock::now();
+  if (first && pre_c0 == r.c0) { bufi ^= 1; r.B = pre_B; pre_c0 = -1; r.samples_up = pre_up.pending; }
+  else if (int rc = gen_round(r.c0, r.cn, first, bufi, &r.B)) return rc;
+  r.nh = (size_t)r.cn * r.B;
+  r.tp1 = std::chrono::steady_clock::now();
+  return 0;
+}
+
+int RansacCall::upload_offsets() {
+  if (int rc = corr.wait()) return rc;
+  HIP_TRYR(hipMemcpyAsync(d_off.p, batch->offsets, sizeof(int64_t) * (nprob + 1), hipMemcpyHostToDevice, st));
+  offsets_up = true;
+  return 0;
+}
+
+// the round's device buffers, samples and active counts; starts the fit's clock
+int RansacCall::upload_round(Round& r) {
+  int rc;
+  const size_t nh = r.nh;
+  const int cn = r.cn;
+  DBuf<int>& d_samples = d_samples2[bufi];
+  if ((rc = d_samples.ensure(nh * m)) || (rc = d_counts.ensure(nh)) || (rc = d_models.ensure(nh * kMaxModels * kStride)) ||
+      (rc = d_cost.ensure(nh * kMaxModels)) || (rc = d_ninl.ensure(nh * kMaxModels)) || (rc = d_active.ensure(cn)) ||
+      (rc = d_dense.ensure(cn)) || (rc = d_tags.ensure(nh * kMaxModels)) || (rc = d_hyp_base.ensure(nh)))
+    return rc;
+  if (!offsets_up && (rc = upload_offsets())) return rc;
+  HIP_TRYR(hipMemsetAsync(d_dense.p, 0, sizeof(int) * cn, st));
+  if (r.samples_up) { HIP_TRYR(hipStreamWaitEvent(st, pre_up.ev, 0)); pre_up.pending = false; }
+  else HIP_TRYR(hipMemcpyAsync(d_samples.p, h_samples2[bufi].data(), sizeof(int) * nh * m, hipMemcpyHostToDevice, st));
+  HIP_TRYR(hipMemcpyAsync(d_active.p, h_active2[bufi].data(), sizeof(int) * cn, hipMemcpyHostToDevice, st));
+  HIP_TRYR(hipEventRecord(clk.ev0, st));
+  return 0;
+}
+
+// DLS / gDLS: the Macaulay terms of the round's calls, stage A (dls_kernels.hip), eigen stage
+int RansacCall::launch_fit_dls(const Round& r) {
+  int rc;
+  const int c0 = r.c0, cn = r.cn, B = r.B;
+  const size_t nh = r.nh;
+  const int* d_samples = d_samples2[bufi].p;
+  const double* d_data = corr.data();
+  h_iter_base.assign(cn, 0);
+  size_t had = h_dls_u.size();
+  if (si) {   // streams: every problem's calls continue its own rand() stream -- this round's terms, problem after problem
+    h_dls_u.clear(); had = (size_t)-1;
     for (int q = 0; q < cn; ++q) {
       ProblemState& s = S[c0 + q];
-      s.round_iters = 0;
-      if (s.done) continue;
-      const int cap = first ? first_round : next_round;
-      s.round_iters = std::min(cap, s.max_iterations - s.it);
-      act[q] = s.round_iters;
-      B = std::max(B, s.round_iters);
+      h_iter_base[q] = (int)(h_dls_u.size() / 4);
+      for (int k = 0; k < 4 * s.round_iters; ++k) h_dls_u.push_back(dls::macaulay_term_from_rand(SD[c0 + q].next()));
     }
-    *B_out = B;
-    if (B == 0) return 0;
-    if (!smp.resize((size_t)cn * B * m)) return set_error(THEIA_HIP_ERR_OUT_OF_MEMORY, "hipHostMalloc failed");
-    if (p4pfr_est && !rotb.resize((size_t)cn * B * 9)) return set_error(THEIA_HIP_ERR_OUT_OF_MEMORY, "hipHostMalloc failed");
-    host_parallel_for(cn, [&](int q) {
-      ProblemState& s = S[c0 + q];
-      int* out = smp.data() + (size_t)q * B * m;
-      StreamRound* sr = si ? &SR[c0 + q] : nullptr;
-      if (sr && s.round_iters > 0) { sr->anchor = s.rng; sr->anchor_drawn = s.rng.drawn(); sr->cum.resize(s.round_iters); }
-      // P4Pfr takes three RandDouble(-0.5, 0.5) from the SAME generator after every sample (every RandomNumberGenerator object
-      // shares one std::mt19937, util/random.cc:46-66); the solver's static RandomNumberGenerator(42) re-seeds that generator the
-      // first time it runs in a process (four_point_focal_length_radial_distortion.cc:134-138)
-      auto p4pfr_draws = [&](int b) {
-        if (!p4pfr_est) return;
-        if (s.p4pfr_first && s.it + b == 0) {
-          s.rng.seed(42);
-          if (sr) { sr->anchor = s.rng; sr->anchor_drawn = s.rng.drawn(); }   // (a problem ends after >= 1 iteration: past this point)
-        }
-        double v[3];
-        for (int k = 0; k < 3; ++k) v[k] = s.rng.rand_double(-0.5, 0.5);
-        p4pfr_rotation_from_draws(v, rotb.data() + ((size_t)q * B + b) * 9);
-      };
-      for (int b = 0; b < s.round_iters; ++b) {
-        if (P.ransac_type == THEIA_RANSAC_PROSAC) { prosac_sample(s.rng, s.n, m, s.kth++, out + (size_t)b * m); p4pfr_draws(b); }
-        else if (P.ransac_type == THEIA_RANSAC_EXHAUSTIVE) {   // all pairs (i, j > i), wrapping around
-          out[(size_t)b * 2] = s.ex_i; out[(size_t)b * 2 + 1] = s.ex_j;
-          if (++s.ex_j >= s.n) {
-            if (++s.ex_i >= s.n - 1) s.ex_i = 0;
-            s.ex_j = s.ex_i + 1;
-          }
-        } else {
-          for (int i = 0; i < m; ++i) {
-            std::swap(s.idx[i], s.idx[s.rng.rand_int(i, s.n - 1)]);
-            out[(size_t)b * m + i] = s.idx[i];
-          }
-          p4pfr_draws(b);
-        }
-        if (sr) sr->cum[b] = s.rng.drawn() - sr->anchor_drawn;
-      }
-      for (size_t e = (size_t)s.round_iters * m; e < (size_t)B * m; ++e) out[e] = 0;   // iterations beyond this problem's round
-    });
-    return 0;
-  };
-  int bufi = 0, pre_c0 = -1, pre_B = 0;   // pre_*: the first round of chunk pre_c0 already sits in buffer 1 - bufi
-  bool offsets_up = false;
-  // The sample streams of the NEXT chunk's first round are drawn while this chunk's kernels run (pre_*); their 30 MB go up on
-  // the copy stream at once, into the device buffer of their host buffer, and the solver stream waits for the event instead
-  // of copying them between two chunks' kernels.
-  hipStream_t copy_st = copy_stream();
-  struct PreUpload {
-    hipEvent_t ev = nullptr; bool pending = false;
-    PreUpload() { (void)hipEventCreateWithFlags(&ev, hipEventDisableTiming); }
-    ~PreUpload() { if (ev) { if (pending) (void)hipEventSynchronize(ev); (void)hipEventDestroy(ev); } }   // (the buffers outlive the copy)
-  } pre_up;
-  const auto t_loop = std::chrono::steady_clock::now();
-  for (int c0 = 0; c0 < nprob; c0 += chunk) {
-    const int cn = std::min(chunk, nprob - c0);
-    bool first = true;
-    while (true) {
-      int B = 0;
-      const auto tp0 = std::chrono::steady_clock::now();
-      bool samples_up = false;
-      if (first && pre_c0 == c0) { bufi ^= 1; B = pre_B; pre_c0 = -1; samples_up = pre_up.pending; }
-      else if ((rc = gen_round(c0, cn, first, h_active2[bufi], h_samples2[bufi], h_rot2[bufi], &B))) return rc;
-      HBuf<int>& h_active = h_active2[bufi];
-      HBuf<int>& h_samples = h_samples2[bufi];
-      DBuf<int>& d_samples = d_samples2[bufi];
-      if (B == 0) break;
-      first = false;
-      const auto tp1 = std::chrono::steady_clock::now();
-      const size_t nh = (size_t)cn * B;
-      if ((rc = d_samples.ensure(nh * m)) || (rc = d_counts.ensure(nh)) || (rc = d_models.ensure(nh * kMaxModels * kStride)) ||
-          (rc = d_cost.ensure(nh * kMaxModels)) || (rc = d_ninl.ensure(nh * kMaxModels)) || (rc = d_active.ensure(cn)) ||
-          (rc = d_dense.ensure(cn)) || (rc = d_tags.ensure(nh * kMaxModels)) || (rc = d_hyp_base.ensure(nh)))
-        return rc;
-      if (!offsets_up) {
-        if ((rc = upload.wait())) return rc;
-        HIP_TRYR(hipMemcpyAsync(d_off.p, batch->offsets, sizeof(int64_t) * (nprob + 1), hipMemcpyHostToDevice, st));
-        offsets_up = true;
-      }
-      HIP_TRYR(hipMemsetAsync(d_dense.p, 0, sizeof(int) * cn, st));
-      if (samples_up) { HIP_TRYR(hipStreamWaitEvent(st, pre_up.ev, 0)); pre_up.pending = false; }
-      else HIP_TRYR(hipMemcpyAsync(d_samples.p, h_samples.data(), sizeof(int) * nh * m, hipMemcpyHostToDevice, st));
-      HIP_TRYR(hipMemcpyAsync(d_active.p, h_active.data(), sizeof(int) * cn, hipMemcpyHostToDevice, st));
-      HIP_TRYR(hipEventRecord(ev0, st));
-      if (dls_est) {
-        h_iter_base.assign(cn, 0);
-        size_t had = h_dls_u.size();
-        if (si) {   // streams: every problem's calls continue its own rand() stream -- this round's terms, problem after problem
-          h_dls_u.clear(); had = (size_t)-1;
-          for (int q = 0; q < cn; ++q) {
-            ProblemState& s = S[c0 + q];
-            h_iter_base[q] = (int)(h_dls_u.size() / 4);
-            for (int k = 0; k < 4 * s.round_iters; ++k) h_dls_u.push_back(dls::macaulay_term_from_rand(SD[c0 + q].next()));
-          }
-        } else {
-          int calls = 0;
-          for (int q = 0; q < cn; ++q) { h_iter_base[q] = S[c0 + q].it; calls = std::max(calls, S[c0 + q].it + S[c0 + q].round_iters); }
-          dls_terms(h_dls_u, dls_gen, (size_t)calls);
-        }
-        if ((rc = d_dls_action.ensure(nh * 729)) || (rc = d_dls_tfac.ensure(nh * 36)) || (rc = d_dls_ok.ensure(nh)) ||
-            (rc = d_iter_base.ensure(cn)))
-          return rc;
-        if (h_dls_u.size() != had || d_dls_u.cap < h_dls_u.size()) {
-          if ((rc = d_dls_u.ensure(std::max<size_t>(h_dls_u.size(), 4 * 4096)))) return rc;
-          HIP_TRYR(hipMemcpyAsync(d_dls_u.p, h_dls_u.data(), sizeof(double) * h_dls_u.size(), hipMemcpyHostToDevice, st));
-        }
-        HIP_TRYR(hipMemcpyAsync(d_iter_base.p, h_iter_base.data(), sizeof(int) * cn, hipMemcpyHostToDevice, st));
-        HIP_TRYR(hipEventRecord(ev0, st));   // (re-recorded: the uploads above are not part of the fit time)
-        if (gdls_est) {
-          launch_dls_stage_a(true, kSimDatum, cn, B, d_off.p + c0, d_data.p, d_samples.p, d_active.p, d_iter_base.p, d_dls_u.p,
-                             d_dls_action.p, d_dls_tfac.p, d_dls_ok.p, st);
-          k_gdls_b_team<<<(unsigned)((nh + kDlsTeamsPerWave - 1) / kDlsTeamsPerWave), 64, 0, st>>>(
-              nh, B, d_off.p + c0, d_data.p, d_samples.p, d_active.p, d_dls_action.p, d_dls_tfac.p, d_dls_ok.p, d_models.p,
-              d_counts.p, d_dense.p, d_tags.p, d_hyp_base.p);
-        } else {
-        launch_dls_stage_a(false, 5, cn, B, d_off.p + c0, d_data.p, d_samples.p, d_active.p, d_iter_base.p, d_dls_u.p,
-                           d_dls_action.p, d_dls_tfac.p, d_dls_ok.p, st);
-        if (getenv("THEIA_HIP_DLS_THREAD_EIG"))
-          k_dls_b<<<dim3((B + 63) / 64, cn), 64, 0, st>>>(cn, B, d_off.p + c0, d_data.p, d_samples.p, d_active.p, d_dls_action.p,
-                                                          d_dls_tfac.p, d_dls_ok.p, d_models.p, d_counts.p, d_dense.p, d_tags.p,
-                                                          d_hyp_base.p);
-        else
-          k_dls_b_team<<<(unsigned)((nh + kDlsTeamsPerWave - 1) / kDlsTeamsPerWave), 64, 0, st>>>(
-              nh, B, d_off.p + c0, d_data.p, d_samples.p, d_active.p, d_dls_action.p, d_dls_tfac.p, d_dls_ok.p, d_models.p,
-              d_counts.p, d_dense.p, d_tags.p, d_hyp_base.p);
-        }
-      } else if ((est == THEIA_EST_RELATIVE_POSE || est == THEIA_EST_ESSENTIAL_MATRIX) && !getenv("THEIA_HIP_FIT_ONE_KERNEL")) {
-        if ((rc = d_fp_ws.ensure(nh * kFpWs)) || (rc = d_fp_sol.ensure(nh * 40)) || (rc = d_fp_ok.ensure(nh)) || (rc = d_fp_mask.ensure(nh)))
-          return rc;
-        dim3 grid((B + 63) / 64, cn);
-        k_fit5_a_team<<<(unsigned)((nh + 3) / 4), 64, 0, st>>>(cn, B, d_off.p + c0, d_data.p, d_samples.p, d_active.p, d_fp_ws.p, d_fp_ok.p);
-        k_fit5_b<false><<<(unsigned)((nh + kFpTeamsPerWave - 1) / kFpTeamsPerWave), 64, 0, st>>>(nh, d_fp_ok.p, d_fp_ws.p, d_fp_sol.p, d_fp_mask.p);
-        // (one LANE per root on teams of 16 -- a lane carries one model instead of ten -- measured 8 % slower on the leg: two or
-        // three of a hypothesis' ten roots are real, so most lanes of such a team idle)
-        if (est == THEIA_EST_RELATIVE_POSE)
-          k_fit5_c<THEIA_EST_RELATIVE_POSE><<<grid, 64, 0, st>>>(cn, B, d_off.p + c0, d_data.p, d_samples.p, d_active.p, d_fp_ws.p, d_fp_sol.p,
-                                                                d_fp_mask.p, d_models.p, d_counts.p, d_dense.p, d_tags.p, d_hyp_base.p);
-        else
-          k_fit5_c<THEIA_EST_ESSENTIAL_MATRIX><<<grid, 64, 0, st>>>(cn, B, d_off.p + c0, d_data.p, d_samples.p, d_active.p, d_fp_ws.p, d_fp_sol.p,
-                                                                   d_fp_mask.p, d_models.p, d_counts.p, d_dense.p, d_tags.p, d_hyp_base.p);
-      } else if (p4pfr_est) {
-        if ((rc = d_fp_ws.ensure(nh * (size_t)p4pfr_workspace_doubles())) || (rc = d_rot.ensure(nh * 9))) return rc;
-        HIP_TRYR(hipMemcpyAsync(d_rot.p, h_rot2[bufi].data(), sizeof(double) * nh * 9, hipMemcpyHostToDevice, st));
-        HIP_TRYR(hipEventRecord(ev0, st));   // (re-recorded: the upload above is not part of the fit time)
-        launch_p4pfr_fit(cn, B, d_off.p + c0, d_data.p, d_samples.p, d_active.p, d_rot.p, p4pfr_limits, d_fp_ws.p, d_models.p, d_counts.p, d_dense.p,
-                         d_tags.p, d_hyp_base.p, st);
-      } else if (upnp_est) {
-        if ((rc = d_fp_ws.ensure(nh * (size_t)upnp_workspace_doubles()))) return rc;
-        launch_upnp_fit(cn, B, d_off.p + c0, d_data.p, d_samples.p, d_active.p, d_upnp_state.p + (size_t)c0 * upnp_state_doubles(), d_fp_ws.p,
-                        d_models.p, d_counts.p, d_dense.p, d_tags.p, d_hyp_base.p, st);
-      } else if (est == THEIA_EST_UNCALIBRATED_ABSOLUTE_POSE) {
-        if ((rc = d_fp_ws.ensure(nh * kFpWs)) || (rc = d_fp_sol.ensure(nh * 50)) || (rc = d_fp_ok.ensure(nh)) || (rc = d_fp_mask.ensure(nh)))
-          return rc;
-        if ((rc = p4pf_kernel_ready())) return rc;
-        dim3 grid((B + 63) / 64, cn);
-        k_p4pf_a<<<(unsigned)nh, p4pfdev::kThreads, p4pfdev::kLdsBytes, st>>>(cn, B, d_off.p + c0, d_data.p, d_samples.p, d_active.p, d_fp_ws.p, d_fp_ok.p);
-        k_fit5_b<true><<<(unsigned)((nh + kFpTeamsPerWave - 1) / kFpTeamsPerWave), 64, 0, st>>>(nh, d_fp_ok.p, d_fp_ws.p, d_fp_sol.p, d_fp_mask.p);
-        k_p4pf_c<<<grid, 64, 0, st>>>(cn, B, d_active.p, d_fp_ws.p, d_fp_sol.p, d_fp_mask.p, d_models.p, d_counts.p, d_dense.p, d_tags.p, d_hyp_base.p);
-      } else if (est == THEIA_EST_HOMOGRAPHY && !getenv("THEIA_HIP_FIT_ONE_KERNEL")) {
-        if ((rc = d_fp_ws.ensure(nh * kHomWs))) return rc;
-        dim3 grid((B + 63) / 64, cn);
-        k_hom_a<<<grid, 64, 0, st>>>(cn, B, d_off.p + c0, d_data.p, d_samples.p, d_active.p, d_fp_ws.p);
-        k_hom_b<<<(unsigned)((nh + kSqTeamsPerWave - 1) / kSqTeamsPerWave), 64, 0, st>>>(nh, B, d_active.p, d_fp_ws.p);
-        k_hom_c<<<grid, 64, 0, st>>>(cn, B, d_active.p, d_fp_ws.p, d_models.p, d_counts.p, d_dense.p, d_tags.p, d_hyp_base.p);
-      } else if (est == THEIA_EST_ABSOLUTE_POSE_SQPNP && !getenv("THEIA_HIP_FIT_ONE_KERNEL")) {
-        if ((rc = d_fp_ws.ensure(nh * kSqWs)) || (rc = d_fp_ok.ensure(nh))) return rc;
-        dim3 grid((B + 63) / 64, cn);
-        k_sqp_a<<<grid, 64, 0, st>>>(cn, B, d_off.p + c0, d_data.p, d_samples.p, d_active.p, d_fp_ws.p, d_fp_ok.p);
-        k_sqp_b<<<(unsigned)((nh + kSqTeamsPerWave - 1) / kSqTeamsPerWave), 64, 0, st>>>(nh, d_fp_ok.p, d_fp_ws.p);
-        k_sqp_c<<<grid, 64, 0, st>>>(cn, B, d_active.p, d_fp_ok.p, d_fp_ws.p, d_models.p, d_counts.p, d_dense.p, d_tags.p, d_hyp_base.p);
-      } else {
-        dim3 grid((B + 63) / 64, cn);
-#define THIP_FIT(E) k_fit<E><<<grid, 64, 0, st>>>(est, cn, B, d_off.p + c0, d_data.p, d_samples.p, d_active.p, d_models.p, d_counts.p, d_dense.p, d_tags.p, d_hyp_base.p, ep)
-        switch (est) {
-          case THEIA_EST_RELATIVE_POSE: THIP_FIT(THEIA_EST_RELATIVE_POSE); break;
-          case THEIA_EST_ESSENTIAL_MATRIX: THIP_FIT(THEIA_EST_ESSENTIAL_MATRIX); break;
-          case THEIA_EST_ABSOLUTE_POSE_KNEIP: THIP_FIT(THEIA_EST_ABSOLUTE_POSE_KNEIP); break;
-          case THEIA_EST_ABSOLUTE_POSE_SQPNP: THIP_FIT(THEIA_EST_ABSOLUTE_POSE_SQPNP); break;
-          case THEIA_EST_FUNDAMENTAL_MATRIX: THIP_FIT(THEIA_EST_FUNDAMENTAL_MATRIX); break;
-          case THEIA_EST_HOMOGRAPHY: THIP_FIT(THEIA_EST_HOMOGRAPHY); break;
-          case THEIA_EST_DOMINANT_PLANE: THIP_FIT(THEIA_EST_DOMINANT_PLANE); break;
-          case THEIA_EST_RELATIVE_POSE_KNOWN_ORIENTATION: THIP_FIT(THEIA_EST_RELATIVE_POSE_KNOWN_ORIENTATION); break;
-          case THEIA_EST_UNCALIBRATED_RELATIVE_POSE: THIP_FIT(THEIA_EST_UNCALIBRATED_RELATIVE_POSE); break;
-          case THEIA_EST_TRIANGULATION: THIP_FIT(THEIA_EST_TRIANGULATION); break;
-          case THEIA_EST_RADIAL_HOMOGRAPHY: THIP_FIT(THEIA_EST_RADIAL_HOMOGRAPHY); break;
-          default: THIP_FIT(THEIA_EST_ABSOLUTE_POSE_KNOWN_ORIENTATION); break;
-        }
+  } else {
+    int calls = 0;
+    for (int q = 0; q < cn; ++q) { h_iter_base[q] = S[c0 + q].it; calls = std::max(calls, S[c0 + q].it + S[c0 + q].round_iters); }
+    dls::dls_terms(h_dls_u, dls_gen, (size_t)calls);
+  }
+  if ((rc = d_dls_action.ensure(nh * 729)) || (rc = d_dls_tfac.ensure(nh * 36)) || (rc = d_dls_ok.ensure(nh)) ||
+      (rc = d_iter_base.ensure(cn)))
+    return rc;
+  if (h_dls_u.size() != had || d_dls_u.cap < h_dls_u.size()) {
+    if ((rc = d_dls_u.ensure(std::max<size_t>(h_dls_u.size(), 4 * 4096)))) return rc;
+    HIP_TRYR(hipMemcpyAsync(d_dls_u.p, h_dls_u.data(), sizeof(double) * h_dls_u.size(), hipMemcpyHostToDevice, st));
+  }
+  HIP_TRYR(hipMemcpyAsync(d_iter_base.p, h_iter_base.data(), sizeof(int) * cn, hipMemcpyHostToDevice, st));
+  HIP_TRYR(hipEventRecord(clk.ev0, st));   // (re-recorded: the uploads above are not part of the fit time)
+  launch_dls_stage_a(gdls_est, gdls_est ? kSimDatum : 5, cn, B, d_off.p + c0, d_data, d_samples, d_active.p, d_iter_base.p, d_dls_u.p,
+                     d_dls_action.p, d_dls_tfac.p, d_dls_ok.p, st);
+  const unsigned team_grid = (unsigned)((nh + kDlsTeamsPerWave - 1) / kDlsTeamsPerWave);
+  if (gdls_est)
+    k_gdls_b_team<<<team_grid, 64, 0, st>>>(nh, B, d_off.p + c0, d_data, d_samples, d_active.p, d_dls_action.p, d_dls_tfac.p, d_dls_ok.p,
+                                            d_models.p, d_counts.p, d_dense.p, d_tags.p, d_hyp_base.p);
+  else if (dls_thread_eig)
+    k_dls_b<<<dim3((B + 63) / 64, cn), 64, 0, st>>>(cn, B, d_off.p + c0, d_data, d_samples, d_active.p, d_dls_action.p, d_dls_tfac.p,
+                                                    d_dls_ok.p, d_models.p, d_counts.p, d_dense.p, d_tags.p, d_hyp_base.p);
+  else
+    k_dls_b_team<<<team_grid, 64, 0, st>>>(nh, B, d_off.p + c0, d_data, d_samples, d_active.p, d_dls_action.p, d_dls_tfac.p, d_dls_ok.p,
+                                           d_models.p, d_counts.p, d_dense.p, d_tags.p, d_hyp_base.p);
+  return 0;
+}
+
+// the minimal solver of the estimator on every hypothesis of the round; ends the fit's clock
+int RansacCall::launch_fit(const Round& r) {
+  int rc;
+  const int c0 = r.c0, cn = r.cn, B = r.B;
+  const size_t nh = r.nh;
+  const int* d_samples = d_samples2[bufi].p;
+  const double* d_data = corr.data();
+  const int64_t* off = d_off.p + c0;
+  const dim3 grid((B + 63) / 64, cn);
+  if (dls_est) {
+    if ((rc = launch_fit_dls(r))) return rc;
+  } else if ((est == THEIA_EST_RELATIVE_POSE || est == THEIA_EST_ESSENTIAL_MATRIX) && !fit_one_kernel) {
+    if ((rc = d_fp_ws.ensure(nh * kFpWs)) || (rc = d_fp_sol.ensure(nh * 40)) || (rc = d_fp_ok.ensure(nh)) || (rc = d_fp_mask.ensure(nh)))
+      return rc;
+    k_fit5_a_team<<<(unsigned)((nh + 3) / 4), 64, 0, st>>>(cn, B, off, d_data, d_samples, d_active.p, d_fp_ws.p, d_fp_ok.p);
+    k_fit5_b<false><<<(unsigned)((nh + kFpTeamsPerWave - 1) / kFpTeamsPerWave), 64, 0, st>>>(nh, d_fp_ok.p, d_fp_ws.p, d_fp_sol.p, d_fp_mask.p);
+    // (one LANE per root on teams of 16 -- a lane carries one model instead of ten -- measured 8 % slower on the leg: two or
+    // three of a hypothesis' ten roots are real, so most lanes of such a team idle)
+    if (est == THEIA_EST_RELATIVE_POSE)
+      k_fit5_c<THEIA_EST_RELATIVE_POSE><<<grid, 64, 0, st>>>(cn, B, off, d_data, d_samples, d_active.p, d_fp_ws.p, d_fp_sol.p,
+                                                            d_fp_mask.p, d_models.p, d_counts.p, d_dense.p, d_tags.p, d_hyp_base.p);
+    else
+      k_fit5_c<THEIA_EST_ESSENTIAL_MATRIX><<<grid, 64, 0, st>>>(cn, B, off, d_data, d_samples, d_active.p, d_fp_ws.p, d_fp_sol.p,
+                                                               d_fp_mask.p, d_models.p, d_counts.p, d_dense.p, d_tags.p, d_hyp_base.p);
+  } else if (p4pfr_est) {
+    if ((rc = d_fp_ws.ensure(nh * (size_t)p4pfr_workspace_doubles())) || (rc = d_rot.ensure(nh * 9))) return rc;
+    HIP_TRYR(hipMemcpyAsync(d_rot.p, h_rot2[bufi].data(), sizeof(double) * nh * 9, hipMemcpyHostToDevice, st));
+    HIP_TRYR(hipEventRecord(clk.ev0, st));   // (re-recorded: the upload above is not part of the fit time)
+    launch_p4pfr_fit(cn, B, off, d_data, d_samples, d_active.p, d_rot.p, p4pfr_limits, d_fp_ws.p, d_models.p, d_counts.p, d_dense.p,
+                     d_tags.p, d_hyp_base.p, st);
+  } else if (upnp_est) {
+    if ((rc = d_fp_ws.ensure(nh * (size_t)upnp_workspace_doubles()))) return rc;
+    launch_upnp_fit(cn, B, off, d_data, d_samples, d_active.p, d_upnp_state.p + (size_t)c0 * upnp_state_doubles(), d_fp_ws.p,
+                    d_models.p, d_counts.p, d_dense.p, d_tags.p, d_hyp_base.p, st);
+  } else if (est == THEIA_EST_UNCALIBRATED_ABSOLUTE_POSE) {
+    if ((rc = d_fp_ws.ensure(nh * kFpWs)) || (rc = d_fp_sol.ensure(nh * 50)) || (rc = d_fp_ok.ensure(nh)) || (rc = d_fp_mask.ensure(nh)))
+      return rc;
+    if ((rc = launch_p4pf_fit(cn, B, off, d_data, d_samples, d_active.p, d_fp_ws.p, d_fp_sol.p, d_fp_ok.p, d_fp_mask.p, d_models.p,
+                              d_counts.p, d_dense.p, d_tags.p, d_hyp_base.p, st)))
+      return rc;
+  } else if (est == THEIA_EST_HOMOGRAPHY && !fit_one_kernel) {
+    if ((rc = d_fp_ws.ensure(nh * kHomWs))) return rc;
+    k_hom_a<<<grid, 64, 0, st>>>(cn, B, off, d_data, d_samples, d_active.p, d_fp_ws.p);
+    k_hom_b<<<(unsigned)((nh + kSqTeamsPerWave - 1) / kSqTeamsPerWave), 64, 0, st>>>(nh, B, d_active.p, d_fp_ws.p);
+    k_hom_c<<<grid, 64, 0, st>>>(cn, B, d_active.p, d_fp_ws.p, d_models.p, d_counts.p, d_dense.p, d_tags.p, d_hyp_base.p);
+  } else if (est == THEIA_EST_ABSOLUTE_POSE_SQPNP && !fit_one_kernel) {
+    if ((rc = d_fp_ws.ensure(nh * kSqWs)) || (rc = d_fp_ok.ensure(nh))) return rc;
+    k_sqp_a<<<grid, 64, 0, st>>>(cn, B, off, d_data, d_samples, d_active.p, d_fp_ws.p, d_fp_ok.p);
+    k_sqp_b<<<(unsigned)((nh + kSqTeamsPerWave - 1) / kSqTeamsPerWave), 64, 0, st>>>(nh, d_fp_ok.p, d_fp_ws.p);
+    k_sqp_c<<<grid, 64, 0, st>>>(cn, B, d_active.p, d_fp_ok.p, d_fp_ws.p, d_models.p, d_counts.p, d_dense.p, d_tags.p, d_hyp_base.p);
+  } else {
+#define THIP_FIT(E) k_fit<E><<<grid, 64, 0, st>>>(est, cn, B, off, d_data, d_samples, d_active.p, d_models.p, d_counts.p, d_dense.p, d_tags.p, d_hyp_base.p, ep)
+    switch (est) {
+      case THEIA_EST_RELATIVE_POSE: THIP_FIT(THEIA_EST_RELATIVE_POSE); break;
+      case THEIA_EST_ESSENTIAL_MATRIX: THIP_FIT(THEIA_EST_ESSENTIAL_MATRIX); break;
+      case THEIA_EST_ABSOLUTE_POSE_KNEIP: THIP_FIT(THEIA_EST_ABSOLUTE_POSE_KNEIP); break;
+      case THEIA_EST_ABSOLUTE_POSE_SQPNP: THIP_FIT(THEIA_EST_ABSOLUTE_POSE_SQPNP); break;
+      case THEIA_EST_FUNDAMENTAL_MATRIX: THIP_FIT(THEIA_EST_FUNDAMENTAL_MATRIX); break;
+      case THEIA_EST_HOMOGRAPHY: THIP_FIT(THEIA_EST_HOMOGRAPHY); break;
+      case THEIA_EST_DOMINANT_PLANE: THIP_FIT(THEIA_EST_DOMINANT_PLANE); break;
+      case THEIA_EST_RELATIVE_POSE_KNOWN_ORIENTATION: THIP_FIT(THEIA_EST_RELATIVE_POSE_KNOWN_ORIENTATION); break;
+      case THEIA_EST_UNCALIBRATED_RELATIVE_POSE: THIP_FIT(THEIA_EST_UNCALIBRATED_RELATIVE_POSE); break;
+      case THEIA_EST_TRIANGULATION: THIP_FIT(THEIA_EST_TRIANGULATION); break;
+      case THEIA_EST_RADIAL_HOMOGRAPHY: THIP_FIT(THEIA_EST_RADIAL_HOMOGRAPHY); break;
+      default: THIP_FIT(THEIA_EST_ABSOLUTE_POSE_KNOWN_ORIENTATION); break;
+    }
 #undef THIP_FIT
-      }
-      HIP_TRYR(hipEventRecord(evm, st));
-      if (lmed) {
-        dim3 grid(B * kMaxModels, cn);
-        k_score_lmed<<<grid, 256, lmed_lds, st>>>(est, cn, B, d_off.p + c0, d_data.p, d_models.p, d_dense.p, d_tags.p, d_cost.p, d_ninl.p, lmed_in_lds);
-      } else {
-#define THIP_SCORE(L, E, BYTES) k_score<L, E><<<dim3((B * kMaxModels + score_threads(E) - 1) / score_threads(E), cn), score_threads(E), BYTES, st>>>(est, cn, B, d_off.p + c0, d_data.p, d_models.p, d_dense.p, d_tags.p, P.error_thresh, P.use_mle, d_cost.p, d_ninl.p)
-        if (use_lds) {
-          if (est == THEIA_EST_RELATIVE_POSE) THIP_SCORE(true, THEIA_EST_RELATIVE_POSE, lds_bytes);
-          else if (est == THEIA_EST_ESSENTIAL_MATRIX) THIP_SCORE(true, THEIA_EST_ESSENTIAL_MATRIX, lds_bytes);
-          else if (est == THEIA_EST_ABSOLUTE_POSE_KNEIP) THIP_SCORE(true, THEIA_EST_ABSOLUTE_POSE_KNEIP, lds_bytes);
-          else if (est == THEIA_EST_ABSOLUTE_POSE_DLS) THIP_SCORE(true, THEIA_EST_ABSOLUTE_POSE_DLS, lds_bytes);
-          else if (est == THEIA_EST_ABSOLUTE_POSE_SQPNP) THIP_SCORE(true, THEIA_EST_ABSOLUTE_POSE_SQPNP, lds_bytes);
-          else THIP_SCORE(true, -1, lds_bytes);
-        } else {
-          if (est == THEIA_EST_RELATIVE_POSE) THIP_SCORE(false, THEIA_EST_RELATIVE_POSE, 0);
-          else if (est == THEIA_EST_ABSOLUTE_POSE_SQPNP) THIP_SCORE(false, THEIA_EST_ABSOLUTE_POSE_SQPNP, 0);
-          else THIP_SCORE(false, -1, 0);
-        }
+  }
+  HIP_TRYR(hipEventRecord(clk.evm, st));
+  return 0;
+}
+
+// every correspondence of a problem under every model of its hypotheses; ends the score's clock
+int RansacCall::launch_score(const Round& r) {
+  const int c0 = r.c0, cn = r.cn, B = r.B;
+  const double* d_data = corr.data();
+  if (lmed) {
+    dim3 grid(B * kMaxModels, cn);
+    k_score_lmed<<<grid, 256, lmed_lds, st>>>(est, cn, B, d_off.p + c0, d_data, d_models.p, d_dense.p, d_tags.p, d_cost.p, d_ninl.p, lmed_in_lds);
+  } else {
+#define THIP_SCORE(L, E, BYTES) k_score<L, E><<<dim3((B * kMaxModels + score_threads(E) - 1) / score_threads(E), cn), score_threads(E), BYTES, st>>>(est, cn, B, d_off.p + c0, d_data, d_models.p, d_dense.p, d_tags.p, P.error_thresh, P.use_mle, d_cost.p, d_ninl.p)
+    if (use_lds) {
+      if (est == THEIA_EST_RELATIVE_POSE) THIP_SCORE(true, THEIA_EST_RELATIVE_POSE, lds_bytes);
+      else if (est == THEIA_EST_ESSENTIAL_MATRIX) THIP_SCORE(true, THEIA_EST_ESSENTIAL_MATRIX, lds_bytes);
+      else if (est == THEIA_EST_ABSOLUTE_POSE_KNEIP) THIP_SCORE(true, THEIA_EST_ABSOLUTE_POSE_KNEIP, lds_bytes);
+      else if (est == THEIA_EST_ABSOLUTE_POSE_DLS) THIP_SCORE(true, THEIA_EST_ABSOLUTE_POSE_DLS, lds_bytes);
+      else if (est == THEIA_EST_ABSOLUTE_POSE_SQPNP) THIP_SCORE(true, THEIA_EST_ABSOLUTE_POSE_SQPNP, lds_bytes);
+      else THIP_SCORE(true, -1, lds_bytes);
+    } else {
+      if (est == THEIA_EST_RELATIVE_POSE) THIP_SCORE(false, THEIA_EST_RELATIVE_POSE, 0);
+      else if (est == THEIA_EST_ABSOLUTE_POSE_SQPNP) THIP_SCORE(false, THEIA_EST_ABSOLUTE_POSE_SQPNP, 0);
+      else THIP_SCORE(false, -1, 0);
+    }
 #undef THIP_SCORE
+  }
+  HIP_TRYR(hipEventRecord(clk.ev1, st));
+  return 0;
+}
+
+// while the GPU fits and scores this round: the first round of the next chunk (its problems are not touched before)
+int RansacCall::predraw_next_chunk(const Round& r) {
+  if (!(pre_c0 < 0 && r.c0 + chunk < nprob)) return 0;
+  int rc;
+  const int nc0 = r.c0 + chunk, ncn = std::min(chunk, nprob - nc0), nb = 1 - bufi;
+  if ((rc = gen_round(nc0, ncn, true, nb, &pre_B))) return rc;
+  pre_c0 = nc0;
+  const size_t pnh = (size_t)ncn * pre_B;
+  if (pre_B > 0 && copy_st && pre_up.ev && !pre_up.pending) {
+    if ((rc = d_samples2[nb].ensure(pnh * m))) return rc;
+    HIP_TRYR(hipMemcpyAsync(d_samples2[nb].p, h_samples2[nb].data(), sizeof(int) * pnh * m, hipMemcpyHostToDevice, copy_st));
+    HIP_TRYR(hipEventRecord(pre_up.ev, copy_st));
+    pre_up.pending = true;
+  }
+  return 0;
+}
+
+// model counts down, then the scores packed: only the models that exist travel (all max_models slots of every hypothesis
+// were 100 - 270 MB a round)
+int RansacCall::download_scores(Round& r) {
+  int rc;
+  const int cn = r.cn, B = r.B;
+  const size_t nh = r.nh;
+  if (!h_counts.resize(nh) || !h_hyp_base.resize(nh) || !h_prefix.resize((size_t)cn + 1))
+    return set_error(THEIA_HIP_ERR_OUT_OF_MEMORY, "hipHostMalloc failed");
+  HIP_TRYR(hipMemcpyAsync(h_counts.data(), d_counts.p, sizeof(int) * nh, hipMemcpyDeviceToHost, st));
+  HIP_TRYR(hipMemcpyAsync(h_hyp_base.data(), d_hyp_base.p, sizeof(int) * nh, hipMemcpyDeviceToHost, st));
+  HIP_TRYR(hipMemcpyAsync(h_prefix.data() + 1, d_dense.p, sizeof(int) * cn, hipMemcpyDeviceToHost, st));
+  HIP_TRYR(hipGetLastError());
+  if ((rc = predraw_next_chunk(r))) return rc;
+  HIP_TRYR(call.wait());
+  h_prefix.data()[0] = 0;
+  int most = 0;
+  for (int q = 0; q < cn; ++q) { most = std::max(most, h_prefix.data()[q + 1]); h_prefix.data()[q + 1] += h_prefix.data()[q]; }
+  const size_t total_models = (size_t)h_prefix.data()[cn];
+  if (!h_cost.resize(std::max<size_t>(1, total_models)) || !h_ninl.resize(std::max<size_t>(1, total_models)))
+    return set_error(THEIA_HIP_ERR_OUT_OF_MEMORY, "hipHostMalloc failed");
+  if (total_models > 0) {
+    if ((rc = d_prefix.ensure((size_t)cn + 1)) || (rc = d_pcost.ensure(total_models)) || (rc = d_pninl.ensure(total_models))) return rc;
+    HIP_TRYR(hipMemcpyAsync(d_prefix.p, h_prefix.data(), sizeof(int) * ((size_t)cn + 1), hipMemcpyHostToDevice, st));
+    k_pack_scores<<<dim3((unsigned)std::min(64, (most + 255) / 256), cn), 256, 0, st>>>(B, kMaxModels, d_dense.p, d_prefix.p, d_cost.p, d_ninl.p,
+                                                                                    d_pcost.p, d_pninl.p);
+    HIP_TRYR(hipMemcpyAsync(h_cost.data(), d_pcost.p, sizeof(double) * total_models, hipMemcpyDeviceToHost, st));
+    HIP_TRYR(hipMemcpyAsync(h_ninl.data(), d_pninl.p, sizeof(int) * total_models, hipMemcpyDeviceToHost, st));
+    HIP_TRYR(hipGetLastError());
+    HIP_TRYR(call.wait());
+  }
+  r.tp2 = std::chrono::steady_clock::now();
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, clk.ev0, clk.ev1) == hipSuccess) fit_score_ms += ms;
+  if (hipEventElapsedTime(&ms, clk.ev0, clk.evm) == hipSuccess) fit_ms += ms;
+  if (hipEventElapsedTime(&ms, clk.evm, clk.ev1) == hipSuccess) score_ms += ms;
+  return 0;
+}
+
+// refines every event's model on its inliers; writes the refined pose to d_cur_models[prob]
+int RansacCall::run_lo(const std::vector<LoEvent>& evs, int round_B, std::vector<int>& success) {
+  const int nev = (int)evs.size();
+  success.assign(nev, 0);
+  if (nev == 0) return 0;
+  const double* d_data = corr.data();
+  std::vector<int> hp(nev), hs((size_t)nev * kMaxSample), hsl(nev), hmod(nev, THEIA_CAM_PINHOLE), hhyp(nev);
+  std::vector<int64_t> hoff(nev + 1, 0);
+  std::vector<double> hintr((size_t)nev * THEIA_MAX_INTRINSICS, 0.0);
+  for (int e = 0; e < nev; ++e) {
+    hp[e] = evs[e].prob; hsl[e] = evs[e].slot; hhyp[e] = evs[e].hyp;
+    for (int k = 0; k < kMaxSample; ++k) hs[(size_t)e * kMaxSample + k] = evs[e].samples[k];
+    hoff[e + 1] = hoff[e] + S[evs[e].prob].n;          // capacity: every datum could be an inlier
+    hintr[(size_t)e * THEIA_MAX_INTRINSICS] = 1.0; hintr[(size_t)e * THEIA_MAX_INTRINSICS + 1] = 1.0;   // Camera(): f = 1, aspect 1
+  }
+  int rc2;
+  if ((rc2 = d_ev_prob.ensure(nev)) || (rc2 = d_ev_samples.ensure((size_t)nev * kMaxSample)) || (rc2 = d_ev_slot.ensure(nev)) ||
+      (rc2 = d_ev_count.ensure(nev)) || (rc2 = d_ev_success.ensure(nev)) || (rc2 = d_ev_off.ensure(nev + 1)) ||
+      (rc2 = d_ev_model.ensure((size_t)nev * kStride)) || (rc2 = d_ev_cam.ensure((size_t)nev * 9)) ||
+      (rc2 = d_lo_uv.ensure((size_t)hoff[nev] * 2)) || (rc2 = d_lo_X.ensure((size_t)hoff[nev] * 4)) ||
+      (rc2 = d_lo_intr.ensure(hintr.size())) || (rc2 = d_lo_model_id.ensure(nev)) ||
+      (rc2 = d_lo_out.ensure(views_batch_out_bytes() * nev)))
+    return rc2;
+  HIP_TRYR(hipMemcpyAsync(d_ev_prob.p, hp.data(), sizeof(int) * nev, hipMemcpyHostToDevice, st));
+  HIP_TRYR(hipMemcpyAsync(d_ev_samples.p, hs.data(), sizeof(int) * nev * kMaxSample, hipMemcpyHostToDevice, st));
+  HIP_TRYR(hipMemcpyAsync(d_ev_slot.p, hsl.data(), sizeof(int) * nev, hipMemcpyHostToDevice, st));
+  if ((rc2 = d_ev_hyp.ensure(nev))) return rc2;
+  HIP_TRYR(hipMemcpyAsync(d_ev_hyp.p, hhyp.data(), sizeof(int) * nev, hipMemcpyHostToDevice, st));
+  HIP_TRYR(hipMemcpyAsync(d_ev_off.p, hoff.data(), sizeof(int64_t) * (nev + 1), hipMemcpyHostToDevice, st));
+  HIP_TRYR(hipMemcpyAsync(d_lo_intr.p, hintr.data(), sizeof(double) * hintr.size(), hipMemcpyHostToDevice, st));
+  HIP_TRYR(hipMemcpyAsync(d_lo_model_id.p, hmod.data(), sizeof(int) * nev, hipMemcpyHostToDevice, st));
+  k_lo_prepare<<<(nev + 63) / 64, 64, 0, st>>>(est, nev, d_ev_prob.p, d_ev_samples.p, d_ev_slot.p, d_ev_hyp.p, round_B,
+                                               d_models.p, d_hyp_base.p, d_off.p, d_data,
+                                               d_cur_models.p, d_ev_model.p, d_ev_cam.p, ep);
+  if (lmed) {
+    if ((rc2 = d_ev_sqt.ensure(nev))) return rc2;
+    k_lo_lmed_bound<<<nev, 256, lmed_lds, st>>>(est, d_ev_prob.p, d_off.p, d_data, d_ev_model.p, d_ev_sqt.p, lmed_in_lds);
+  }
+  k_lo_gather<<<nev, 64, 0, st>>>(est, d_ev_prob.p, d_off.p, d_data, d_ev_model.p, P.error_thresh, lmed ? d_ev_sqt.p : nullptr, d_ev_off.p, d_ev_count.p,
+                                  reinterpret_cast<double2*>(d_lo_uv.p), reinterpret_cast<double4*>(d_lo_X.p));
+  if (fund)
+    fundamental_batch_device(nev, d_ev_off.p, d_ev_count.p, d_lo_X.p, d_ev_cam.p, &lo_opts, d_lo_out.p, st);
+  else if (homog)
+    homography_batch_device(nev, d_ev_off.p, d_ev_count.p, d_lo_X.p, d_ev_cam.p, &lo_opts, d_lo_out.p, st);
+  else if (rel_pose || uncal_pose)   // the relative-pose RefineModel asks for CGNR, the uncalibrated one keeps the direct default
+    twoview_batch_device(nev, d_ev_off.p, d_ev_count.p, d_lo_X.p, d_ev_cam.p, &lo_opts, rel_pose ? 1 : 0, d_lo_out.p, st);
+  else
+    views_batch_device(nev, d_ev_off.p, d_ev_count.p, d_lo_uv.p, nullptr, d_lo_X.p, d_ev_cam.p, d_lo_intr.p, d_lo_model_id.p,
+                       nullptr, &lo_opts, d_lo_out.p, st);
+  k_lo_finish<<<(nev + 63) / 64, 64, 0, st>>>(est, nev, d_ev_prob.p, d_ev_cam.p, d_ev_model.p,
+                                              reinterpret_cast<const BatchLmOut*>(d_lo_out.p), d_cur_models.p, d_ev_success.p);
+  HIP_TRYR(hipMemcpyAsync(success.data(), d_ev_success.p, sizeof(int) * nev, hipMemcpyDeviceToHost, st));
+  HIP_TRYR(call.wait());
+  return 0;
+}
+
+// Sequential replay of the acceptance rules (replay_problem).  With use_lo a problem pauses at each RefineModel event; the
+// events of all problems are refined as one batch, then every replay resumes where it stopped.
+int RansacCall::replay(const Round& r) {
+  const int c0 = r.c0, cn = r.cn;
+  for (int q = 0; q < cn; ++q) replay_begin_round(S[c0 + q]);
+  const RoundScores sc{r.B, h_counts.data(), h_hyp_base.data(), h_prefix.data(), h_cost.data(), h_ninl.data(), h_samples2[bufi].data()};
+  std::vector<LoEvent> events;
+  std::vector<int> ev_ok;
+  std::atomic<long long> n_hyp{0}, n_scored{0};
+  while (true) {
+    events.clear();
+    // without LO nothing is shared between the problems' replays (the counters are atomics): host threads
+    auto replay_one = [&](int q) {
+      ProblemState& s = S[c0 + q];
+      ReplaySink sink;
+      replay_problem(s, q, m, sc, P, log_failure_prob, trivial_refine, sink);
+      if (sink.paused) {
+        LoEvent ev; ev.prob = c0 + q; ev.slot = sink.lo_slot; ev.hyp = sink.lo_hyp;
+        for (int i = 0; i < kMaxSample; ++i) ev.samples[i] = s.best_samples[i];
+        events.push_back(ev);
       }
-      HIP_TRYR(hipEventRecord(ev1, st));
-      if (!h_counts.resize(nh) || !h_hyp_base.resize(nh) || !h_prefix.resize((size_t)cn + 1))
-        return set_error(THEIA_HIP_ERR_OUT_OF_MEMORY, "hipHostMalloc failed");
-      HIP_TRYR(hipMemcpyAsync(h_counts.data(), d_counts.p, sizeof(int) * nh, hipMemcpyDeviceToHost, st));
-      HIP_TRYR(hipMemcpyAsync(h_hyp_base.data(), d_hyp_base.p, sizeof(int) * nh, hipMemcpyDeviceToHost, st));
-      HIP_TRYR(hipMemcpyAsync(h_prefix.data() + 1, d_dense.p, sizeof(int) * cn, hipMemcpyDeviceToHost, st));
-      HIP_TRYR(hipGetLastError());
-      // while the GPU fits and scores this round: the first round of the next chunk (its problems are not touched before)
-      if (pre_c0 < 0 && c0 + chunk < nprob) {
-        const int nc0 = c0 + chunk;
-        if ((rc = gen_round(nc0, std::min(chunk, nprob - nc0), true, h_active2[1 - bufi], h_samples2[1 - bufi], h_rot2[1 - bufi], &pre_B))) return rc;
-        pre_c0 = nc0;
-        const size_t pnh = (size_t)std::min(chunk, nprob - nc0) * pre_B;
-        if (pre_B > 0 && copy_st && pre_up.ev && !pre_up.pending) {
-          if ((rc = d_samples2[1 - bufi].ensure(pnh * m))) return rc;
-          HIP_TRYR(hipMemcpyAsync(d_samples2[1 - bufi].p, h_samples2[1 - bufi].data(), sizeof(int) * pnh * m, hipMemcpyHostToDevice, copy_st));
-          HIP_TRYR(hipEventRecord(pre_up.ev, copy_st));
-          pre_up.pending = true;
-        }
-      }
-      HIP_TRYR(mine.wait(st));
-      {   // the scores, packed: only the models that exist travel (all max_models slots of every hypothesis were 100 - 270 MB a round)
-        h_prefix.data()[0] = 0;
-        int most = 0;
-        for (int q = 0; q < cn; ++q) { most = std::max(most, h_prefix.data()[q + 1]); h_prefix.data()[q + 1] += h_prefix.data()[q]; }
-        const size_t total_models = (size_t)h_prefix.data()[cn];
-        if (!h_cost.resize(std::max<size_t>(1, total_models)) || !h_ninl.resize(std::max<size_t>(1, total_models)))
-          return set_error(THEIA_HIP_ERR_OUT_OF_MEMORY, "hipHostMalloc failed");
-        if (total_models > 0) {
-          if ((rc = d_prefix.ensure((size_t)cn + 1)) || (rc = d_pcost.ensure(total_models)) || (rc = d_pninl.ensure(total_models))) return rc;
-          HIP_TRYR(hipMemcpyAsync(d_prefix.p, h_prefix.data(), sizeof(int) * ((size_t)cn + 1), hipMemcpyHostToDevice, st));
-          k_pack_scores<<<dim3((unsigned)std::min(64, (most + 255) / 256), cn), 256, 0, st>>>(B, kMaxModels, d_dense.p, d_prefix.p, d_cost.p, d_ninl.p,
-                                                                                          d_pcost.p, d_pninl.p);
-          HIP_TRYR(hipMemcpyAsync(h_cost.data(), d_pcost.p, sizeof(double) * total_models, hipMemcpyDeviceToHost, st));
-          HIP_TRYR(hipMemcpyAsync(h_ninl.data(), d_pninl.p, sizeof(int) * total_models, hipMemcpyDeviceToHost, st));
-          HIP_TRYR(hipGetLastError());
-          HIP_TRYR(mine.wait(st));
-        }
-      }
-      const auto tp2 = std::chrono::steady_clock::now();
-      { float ms = 0.f; if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) fit_score_ms += ms;
-        if (hipEventElapsedTime(&ms, ev0, evm) == hipSuccess) fit_ms += ms;
-        if (hipEventElapsedTime(&ms, evm, ev1) == hipSuccess) score_ms += ms; }
-      // sequential replay of the acceptance rules (sample_consensus_estimator.h:330-394).  With
-      // use_lo a problem pauses at each RefineModel event; the events of all problems are refined
-      // as one batch, then every replay resumes where it stopped.
-      for (int q = 0; q < cn; ++q) {
-        ProblemState& s = S[c0 + q];
-        s.base_it = s.it; s.rb = 0; s.rj = 0; s.round_done = s.done; s.best_hyp = -1;
-      }
-      lo_round_B = B;
-      std::vector<LoEvent> events;
-      std::vector<int> ev_q, ev_ok;
-      std::atomic<long long> n_hyp{0}, n_scored{0};
-      while (true) {
-        events.clear(); ev_q.clear();
-        // without LO nothing is shared between the problems' replays (the counters are atomics): host threads
-        auto replay_one = [&](int q) {
-          ProblemState& s = S[c0 + q];
-          if (s.round_done) return;
-          long long my_hyp = 0, my_scored = 0;
-          bool paused = false;
-          // (a hypothesis interrupted by an LO event is finished even if max_iterations dropped meanwhile)
-          while (!paused && s.rb < s.round_iters && (s.rj > 0 || s.base_it + s.rb < s.max_iterations)) {
-            const size_t hyp = (size_t)q * B + s.rb;
-            const int nm = h_counts[hyp];
-            if (s.rj == 0) my_hyp++;
-            while (s.rj < nm) {
-              const int j = s.rj++;
-              const size_t at = (size_t)h_prefix.data()[q] + (size_t)h_hyp_base[hyp] + (size_t)j;
-              const double cost = h_cost[at];
-              const int ninl = h_ninl[at];
-              my_scored++;
-              const double inlier_ratio = (double)ninl / (double)s.n;
-              if (cost < s.best_cost) {
-                s.best_cost = cost;
-                s.best_slot = j;
-                s.best_hyp = (int)hyp;
-                s.best_refined = false;
-                for (int i = 0; i < m; ++i) s.best_samples[i] = h_samples[hyp * m + i];
-                if (inlier_ratio < m / (double)s.n) continue;
-                if (P.use_lo && trivial_refine && s.base_it + s.rb >= P.lo_start_iterations) {
-                  s.num_lo++;   // RefineModel = "return true": nothing changes but the counter
-                } else if (P.use_lo && s.base_it + s.rb >= P.lo_start_iterations) {   // :373-381
-                  LoEvent ev; ev.prob = c0 + q; ev.slot = j; ev.hyp = (int)hyp;
-                  for (int i = 0; i < kMaxSample; ++i) ev.samples[i] = s.best_samples[i];
-                  events.push_back(ev); ev_q.push_back(q);
-                  s.pending_ratio = inlier_ratio;
-                  paused = true;
-                  break;
-                }
-                s.max_iterations = std::min(compute_max_iterations(P, m, inlier_ratio, log_failure_prob, s.n), s.max_iterations);
-              }
-            }
-            if (!paused) { s.rb++; s.rj = 0; }
-          }
-          if (!paused) {
-            s.round_done = true;
-            s.it = s.base_it + s.rb;
-            s.last_k = s.rb;
-            if (s.it >= s.max_iterations) s.done = true;
-          }
-          n_hyp += my_hyp; n_scored += my_scored;
-        };
-        if (P.use_lo) { for (int q = 0; q < cn; ++q) replay_one(q); }   // LO events are collected in problem order
-        else host_parallel_for(cn, replay_one);
-        if (events.empty()) break;
-        if ((rc = run_lo(events, ev_ok))) return rc;
-        for (size_t e = 0; e < events.size(); ++e) {
-          ProblemState& s = S[events[e].prob];
-          s.best_refined = true;                       // RefineModel overwrites the pose even when it fails
-          if (getenv("THEIA_HIP_RANSAC_DEBUG"))
-            std::fprintf(stderr, "[hip] prob %d it %d slot %d ratio %.17g lo %d\n", events[e].prob, s.base_it + s.rb, events[e].slot, s.pending_ratio, ev_ok[e]);
-          if (!ev_ok[e]) continue;                     // "continue": no max_iterations update
-          s.num_lo++;
-          s.max_iterations = std::min(compute_max_iterations(P, m, s.pending_ratio, log_failure_prob, s.n), s.max_iterations);
-        }
-      }
-      if (host_timing) {
-        const auto tp3 = std::chrono::steady_clock::now();
-        auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-        std::fprintf(stderr, "[theia_hip ransac] chunk %d+%d round B=%d: samples %.1f ms, upload + kernels + download %.1f ms, replay %.1f ms\n",
-                     c0, cn, B, ms(tp0, tp1), ms(tp1, tp2), ms(tp2, tp3));
-      }
-      {   // best models found in this round -> d_best_models
-        std::vector<int> sp, sh, ss;
-        for (int q = 0; q < cn; ++q) {
-          const ProblemState& s = S[c0 + q];
-          if (s.best_hyp >= 0) { sp.push_back(c0 + q); sh.push_back(s.best_hyp); ss.push_back(s.best_slot); }
-        }
-        if (!sp.empty()) {
-          const int ns = (int)sp.size();
-          if ((rc = d_save.ensure((size_t)3 * ns))) return rc;
-          HIP_TRYR(hipMemcpyAsync(d_save.p, sp.data(), sizeof(int) * ns, hipMemcpyHostToDevice, st));
-          HIP_TRYR(hipMemcpyAsync(d_save.p + ns, sh.data(), sizeof(int) * ns, hipMemcpyHostToDevice, st));
-          HIP_TRYR(hipMemcpyAsync(d_save.p + 2 * ns, ss.data(), sizeof(int) * ns, hipMemcpyHostToDevice, st));
-          k_save_best<<<(ns * kStride + 255) / 256, 256, 0, st>>>(est, ns, d_save.p, d_save.p + ns, d_save.p + 2 * ns, B, d_models.p,
-                                                                  d_hyp_base.p, d_best_models.p);
-          HIP_TRYR(mine.wait(st));   // the host vectors above are the sources of asynchronous uploads
-        }
-      }
-      result->hypotheses_evaluated += n_hyp.load(); result->models_scored += n_scored.load();
+      n_hyp += sink.hypotheses; n_scored += sink.models_scored;
+    };
+    if (P.use_lo) { for (int q = 0; q < cn; ++q) replay_one(q); }   // LO events are collected in problem order
+    else host_parallel_for(cn, replay_one);
+    if (events.empty()) break;
+    if (int rc = run_lo(events, r.B, ev_ok)) return rc;
+    for (size_t e = 0; e < events.size(); ++e) {
+      ProblemState& s = S[events[e].prob];
+      if (debug)
+        std::fprintf(stderr, "[hip] prob %d it %d slot %d ratio %.17g lo %d\n", events[e].prob, s.base_it + s.rb, events[e].slot, s.pending_ratio, ev_ok[e]);
+      replay_lo_result(s, m, ev_ok[e] != 0, P, log_failure_prob);
     }
   }
-  const auto t_final = std::chrono::steady_clock::now();
-  if (!offsets_up) {   // (no round ran at all)
-    if ((rc = upload.wait())) return rc;
-    HIP_TRYR(hipMemcpyAsync(d_off.p, batch->offsets, sizeof(int64_t) * (nprob + 1), hipMemcpyHostToDevice, st));
+  if (host_timing)
+    std::fprintf(stderr, "[theia_hip ransac] chunk %d+%d round B=%d: samples %.1f ms, upload + kernels + download %.1f ms, replay %.1f ms\n",
+                 c0, cn, r.B, ms_between(r.tp0, r.tp1), ms_between(r.tp1, r.tp2), ms_between(r.tp2, std::chrono::steady_clock::now()));
+  result->hypotheses_evaluated += n_hyp.load(); result->models_scored += n_scored.load();
+  return 0;
+}
+
+// best models found in this round -> d_best_models
+int RansacCall::save_best(const Round& r) {
+  std::vector<int> sp, sh, ss;
+  for (int q = 0; q < r.cn; ++q) {
+    const ProblemState& s = S[r.c0 + q];
+    if (s.best_hyp >= 0) { sp.push_back(r.c0 + q); sh.push_back(s.best_hyp); ss.push_back(s.best_slot); }
   }
-  // final models + inlier masks
+  if (sp.empty()) return 0;
+  const int ns = (int)sp.size();
+  if (int rc = d_save.ensure((size_t)3 * ns)) return rc;
+  HIP_TRYR(hipMemcpyAsync(d_save.p, sp.data(), sizeof(int) * ns, hipMemcpyHostToDevice, st));
+  HIP_TRYR(hipMemcpyAsync(d_save.p + ns, sh.data(), sizeof(int) * ns, hipMemcpyHostToDevice, st));
+  HIP_TRYR(hipMemcpyAsync(d_save.p + 2 * ns, ss.data(), sizeof(int) * ns, hipMemcpyHostToDevice, st));
+  k_save_best<<<(ns * kStride + 255) / 256, 256, 0, st>>>(est, ns, d_save.p, d_save.p + ns, d_save.p + 2 * ns, r.B, d_models.p,
+                                                          d_hyp_base.p, d_best_models.p);
+  HIP_TRYR(call.wait());   // the host vectors above are the sources of asynchronous uploads
+  return 0;
+}
+
+// final models, inlier masks, the last LO pass, results, stream states
+int RansacCall::finish() {
+  int rc;
+  const auto t_final = std::chrono::steady_clock::now();
+  if (!offsets_up && (rc = upload_offsets())) return rc;   // (no round ran at all)
+  const double* d_data = corr.data();
+  std::vector<int> best_samples_all((size_t)nprob * kMaxSample, 0), best_slot_all(nprob, -1);
   for (int p = 0; p < nprob; ++p) {
     best_slot_all[p] = S[p].best_slot;
     for (int k = 0; k < kMaxSample; ++k) best_samples_all[(size_t)p * kMaxSample + k] = S[p].best_samples[k];
@@ -2161,8 +1929,8 @@ static int ransac_run(const theia_ransac_batch* batch, const theia_ransac_params
   HIP_TRYR(hipMemcpyAsync(d_best_slot.p, best_slot_all.data(), sizeof(int) * nprob, hipMemcpyHostToDevice, st));
   // d_best_models already holds every problem's best model (k_save_best); THEIA_HIP_RANSAC_REFIT=1 recomputes them from the
   // best samples instead (the same bits: the solver is deterministic)
-  if (getenv("THEIA_HIP_RANSAC_REFIT") && !dls_est)
-    k_refit<<<(nprob + 63) / 64, 64, 0, st>>>(est, nprob, d_off.p, d_data.p, d_best_samples.p, d_best_slot.p, d_best_models.p, ep);
+  if (refit && !dls_est)
+    k_refit<<<(nprob + 63) / 64, 64, 0, st>>>(est, nprob, d_off.p, d_data, d_best_samples.p, d_best_slot.p, d_best_models.p, ep);
   std::vector<int> use_cur;   // source of an asynchronous upload: lives until the final synchronisation
   if (P.use_lo && !trivial_refine) {   // the best model of a problem may be the refined pose of its last LO event
     use_cur.resize(nprob);
@@ -2172,10 +1940,10 @@ static int ransac_run(const theia_ransac_batch* batch, const theia_ransac_params
     k_select_models<<<(nprob + 63) / 64, 64, 0, st>>>(nprob, d_ev_slot.p, d_cur_models.p, d_best_models.p);
   }
   if (lmed) {
-    k_inlier_mask_lmed<<<nprob, 256, lmed_lds, st>>>(est, nprob, d_off.p, d_data.p, d_best_models.p, d_mask.p, lmed_in_lds);
+    k_inlier_mask_lmed<<<nprob, 256, lmed_lds, st>>>(est, nprob, d_off.p, d_data, d_best_models.p, d_mask.p, lmed_in_lds);
   } else {
     dim3 grid((nmax + 255) / 256, nprob);
-    k_inlier_mask<<<grid, 256, 0, st>>>(est, nprob, d_off.p, d_data.p, d_best_models.p, P.error_thresh, d_mask.p);
+    k_inlier_mask<<<grid, 256, 0, st>>>(est, nprob, d_off.p, d_data, d_best_models.p, P.error_thresh, d_mask.p);
   }
   if (P.use_lo && trivial_refine) {   // :401-406 with RefineModel = "return true": the counter only
     for (int p = 0; p < nprob; ++p) S[p].num_lo++;   // "++summary->num_lo_iterations" is unconditional
@@ -2185,21 +1953,18 @@ static int ransac_run(const theia_ransac_batch* batch, const theia_ransac_params
     for (int p = 0; p < nprob; ++p)
       if (S[p].best_slot >= 0) { LoEvent ev; ev.prob = p; ev.slot = -1; ev.hyp = -1; for (int k = 0; k < kMaxSample; ++k) ev.samples[k] = 0; evs.push_back(ev); }
     std::vector<int> ok;
-    if ((rc = run_lo(evs, ok))) return rc;
+    if ((rc = run_lo(evs, 0, ok))) return rc;
     for (int p = 0; p < nprob; ++p) S[p].num_lo++;   // unconditional in the reference, also when no model was found
     HIP_TRYR(hipMemcpyAsync(d_best_models.p, d_cur_models.p, sizeof(double) * nprob * kStride, hipMemcpyDeviceToDevice, st));
   }
   HIP_TRYR(hipGetLastError());
-  HIP_TRYR(mine.wait(st));
+  HIP_TRYR(call.wait());
   // caller-owned (pageable) destinations: blocking copies after the stream has drained
   HIP_TRYR(hipMemcpy(result->models, d_best_models.p, sizeof(double) * nprob * kStride, hipMemcpyDeviceToHost));
   HIP_TRYR(hipMemcpy(result->inlier_mask, d_mask.p, (size_t)total, hipMemcpyDeviceToHost));
-  {   // the slots of a model row past the estimator's layout (theia_hip.h) are padding: handed back as zeros
-    const int used = model_doubles(est);
-    for (int p = 0; p < nprob; ++p)
-      for (int k = used; k < kStride; ++k) result->models[(size_t)p * kStride + k] = 0.0;
-  }
+  const int used = model_doubles(est);   // the slots of a model row past the estimator's layout (theia_hip.h) are padding: handed back as zeros
   for (int p = 0; p < nprob; ++p) {
+    for (int k = used; k < kStride; ++k) result->models[(size_t)p * kStride + k] = 0.0;
     const ProblemState& s = S[p];
     int cnt = 0;
     for (int64_t i = batch->offsets[p]; i < batch->offsets[p + 1]; ++i) cnt += result->inlier_mask[i];
@@ -2225,428 +1990,103 @@ static int ransac_run(const theia_ransac_batch* batch, const theia_ransac_params
       g.discard(s.last_k > 0 ? SR[p].cum[s.last_k - 1] : 0);
     });
   }
-  if (host_timing) {
-    auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-    std::fprintf(stderr, "[theia_hip ransac] call: set-up %.1f ms, rounds %.1f ms, best models + inlier masks + results %.1f ms\n", ms(t_entry, t_loop),
-                 ms(t_loop, t_final), ms(t_final, std::chrono::steady_clock::now()));
-  }
+  if (host_timing)
+    std::fprintf(stderr, "[theia_hip ransac] call: set-up %.1f ms, rounds %.1f ms, best models + inlier masks + results %.1f ms\n",
+                 ms_between(t_entry, t_loop), ms_between(t_loop, t_final), ms_between(t_final, std::chrono::steady_clock::now()));
   return 0;
 }
 
-static bool rng_state_ok(const theia_rng_state* st) { return st && st->pos >= 0 && st->pos <= 624; }
-static void rng_load(Mt19937& g, const theia_rng_state& st) {
-  std::memcpy(g.mt, st.mt, sizeof(g.mt)); g.idx = st.pos; g.twists = 0;
+}  // namespace
+
+hipStream_t solver_stream() {
+  static hipStream_t s = [] {
+    hipStream_t x = nullptr;
+    if (hipStreamCreateWithFlags(&x, hipStreamNonBlocking) != hipSuccess) x = nullptr;
+    return x;
+  }();
+  return s;
 }
-static void rng_store(theia_rng_state& st, const Mt19937& g) { std::memcpy(st.mt, g.mt, sizeof(g.mt)); st.pos = g.idx; }
+hipStream_t copy_stream() {
+  static hipStream_t s = [] {
+    hipStream_t x = nullptr;
+    if (hipStreamCreateWithFlags(&x, hipStreamNonBlocking) != hipSuccess) x = nullptr;
+    return x;
+  }();
+  return s;
+}
+
+int p4pf_workspace_doubles() { return kFpWs; }
+int launch_p4pf_fit(int nprob, int B, const int64_t* offsets, const double* data, const int* samples, const int* active_iters,
+                    double* ws, double* sol, int* ok, int* mask, double* models, int* counts, int* dense_count, int* tags,
+                    int* hyp_base, hipStream_t st) {
+  if (int rc = p4pf_kernel_ready()) return rc;
+  const size_t nh = (size_t)nprob * B;
+  k_p4pf_a<<<(unsigned)nh, p4pfdev::kThreads, p4pfdev::kLdsBytes, st>>>(nprob, B, offsets, data, samples, active_iters, ws, ok);
+  k_fit5_b<true><<<(unsigned)((nh + kFpTeamsPerWave - 1) / kFpTeamsPerWave), 64, 0, st>>>(nh, ok, ws, sol, mask);
+  k_p4pf_c<<<dim3((B + 63) / 64, nprob), 64, 0, st>>>(nprob, B, active_iters, ws, sol, mask, models, counts, dense_count, tags, hyp_base);
+  return 0;
+}
+void launch_five_point(int num, const double* corr, double* E, int* nsol, hipStream_t st) {
+  k_five_point<<<(num + 63) / 64, 64, 0, st>>>(num, corr, E, nsol);
+}
+void launch_p3p(int num, const double* corr, double* R, double* t, int* nsol, hipStream_t st) {
+  k_p3p<<<(num + 63) / 64, 64, 0, st>>>(num, corr, R, t, nsol);
+}
+void launch_sqpnp(int num, const int64_t* offsets, const double* feat, const double* world, double* quat, double* trans, int* nsol,
+                  hipStream_t st) {
+  k_sqpnp<<<(num + 63) / 64, 64, 0, st>>>(num, offsets, feat, world, quat, trans, nsol);
+}
+void launch_dls_solve_b(int num, const int64_t* offsets, const double* world, const double* action, const double* tfac, const int* ok,
+                        double* quat, double* trans, int* nsol, hipStream_t st) {
+  k_dls_solve_b<<<(num + 63) / 64, 64, 0, st>>>(num, offsets, world, action, tfac, ok, quat, trans, nsol);
+}
+
+// The chunk / round loop.  Every enqueue, event record and wait of a round happens inside the stage that is named for it,
+// in the order of the calls below.
+int ransac_run(const theia_ransac_batch* batch, const theia_ransac_params* params, theia_ransac_result* result,
+               const StreamInit* si) {
+  if (!batch || !params || !result) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  RansacCall c(batch, *params, result, si);
+  int rc = c.check();
+  if (rc || c.nprob == 0) return rc;
+  c.set_lo_options();
+  if ((rc = c.setup())) return rc;
+  for (int c0 = 0; c0 < c.nprob; c0 += c.chunk) {
+    const int cn = std::min(c.chunk, c.nprob - c0);
+    for (bool first = true;; first = false) {
+      Round r{c0, cn};
+      if ((rc = c.begin_round(r, first))) return rc;
+      if (r.B == 0) break;
+      if ((rc = c.upload_round(r)) || (rc = c.launch_fit(r)) || (rc = c.launch_score(r)) || (rc = c.download_scores(r)) ||
+          (rc = c.replay(r)) || (rc = c.save_best(r)))
+        return rc;
+    }
+  }
+  return c.finish();
+}
+
+}  // namespace thip
+
+using namespace thip;
 
 extern "C" {
 
-// Every problem of one stream is an Estimate() call that starts where the previous one of its stream stopped, so the k-th
-// problems of all streams ("wave" k) are independent of each other and run as one call of the batch driver; wave k + 1
-// starts from the states wave k handed back.  A wave's problems are contiguous in the batch when the streams are
-// interleaved (or one problem each); otherwise their data are gathered.
-int theia_hip_ransac_estimate_streams(const theia_ransac_batch* batch, const theia_ransac_params* params,
-                                      const theia_ransac_streams* streams, theia_ransac_result* result) {
-  if (!batch || !params || !streams || !result) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "null argument");
-  if (batch->seeds) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "the streams entry point draws from the caller's generators: batch->seeds must be NULL");
-  const int nprob = batch->num_problems, ns = streams->num_streams;
-  if (nprob < 0 || (nprob > 0 && (!batch->offsets || !batch->data))) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "bad batch");
-  if (ns < 1 || !streams->states) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "streams: num_streams >= 1 and a states array are needed");
-  for (int k = 0; k < ns; ++k) {
-    if (!rng_state_ok(&streams->states[k])) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "stream %d: pos outside [0, 624]", k);
-    if (streams->states[k].dls_calls < 0) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "stream %d: dls_calls < 0", k);
-  }
-  if (nprob > 0 && (!result->success || !result->models || !result->num_inliers || !result->inlier_mask ||
-                    !result->num_iterations || !result->confidence))
-    return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "null result array");
-  std::vector<int> sid(nprob, 0), rank(nprob, 0), count(ns, 0);
-  for (int p = 0; p < nprob; ++p) {
-    const int k = streams->stream_of_problem ? streams->stream_of_problem[p] : 0;
-    if (k < 0 || k >= ns) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "problem %d: stream id %d outside [0, %d)", p, k, ns);
-    if (batch->offsets[p + 1] - batch->offsets[p] <= 0) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "Cannot perform estimation with 0 data measurements!");
-    sid[p] = k; rank[p] = count[k]++;
-  }
-  const int est = batch->estimator;
-  const bool dls_est = est == THEIA_EST_ABSOLUTE_POSE_DLS || est == THEIA_EST_SIMILARITY_2D3D;
-  const bool p4pfr_est = est == THEIA_EST_RADIAL_DIST_UNCALIBRATED_ABSOLUTE_POSE;
-  double p4pfr_params[5] = {0.0, 0.0, 0.0, 0.0, 0.0};   // the four limits; the first-call flag comes from the streams
-  if (p4pfr_est && batch->estimator_params) std::memcpy(p4pfr_params, batch->estimator_params, sizeof(double) * 4);
-  theia_ransac_batch sub = *batch;
-  if (p4pfr_est && batch->estimator_params) sub.estimator_params = p4pfr_params;
-  if (nprob == 0) { sub.num_problems = 0; return ransac_run(&sub, params, result, nullptr); }   // (the parameter checks)
-  const int ds = (est >= 0 && est <= THEIA_EST_RADIAL_DIST_UNCALIBRATED_ABSOLUTE_POSE) ? datum_size(est) : 1;
-
-  // the streams, worked on in copies: the caller's states change only when every wave succeeded
-  std::vector<Mt19937> gen(ns);
-  std::vector<uint8_t> first(ns);   // the P4Pfr solver's static generator has not run on this stream yet
-  std::vector<int64_t> dls_calls(ns);
-  std::vector<dls::GlibcRand> dls_gen(dls_est ? ns : 0);
-  for (int k = 0; k < ns; ++k) {
-    rng_load(gen[k], streams->states[k]);
-    first[k] = streams->states[k].p4pfr_static_seeded == 0;
-    dls_calls[k] = streams->states[k].dls_calls;
-    if (dls_est)
-      for (int64_t i = 0; i < 4 * dls_calls[k]; ++i) (void)dls_gen[k].next();
-  }
-  const int nwaves = *std::max_element(count.begin(), count.end());
-  std::vector<std::vector<int>> waves(nwaves);
-  for (int p = 0; p < nprob; ++p) waves[rank[p]].push_back(p);
-
-  result->hypotheses_evaluated = 0; result->models_scored = 0; result->time_fit_score_seconds = 0.0;
-  result->time_fit_seconds = 0.0; result->time_score_seconds = 0.0;
-  constexpr int kS = THEIA_RANSAC_MODEL_STRIDE;
-  std::vector<int64_t> off;
-  std::vector<double> gathered;
-  std::vector<int> wsid;
-  std::vector<int32_t> r_succ, r_ninl, r_nit, r_nlo;
-  std::vector<double> r_models, r_conf;
-  std::vector<uint8_t> r_mask;
-  for (const std::vector<int>& W : waves) {
-    const int nw = (int)W.size(), p0 = W[0];
-    bool contiguous = true;
-    for (int i = 1; i < nw; ++i) contiguous &= W[i] == p0 + i;
-    off.assign(nw + 1, 0);
-    for (int i = 0; i < nw; ++i) off[i + 1] = off[i] + (batch->offsets[W[i] + 1] - batch->offsets[W[i]]);
-    const double* data = batch->data + (size_t)batch->offsets[p0] * ds;
-    theia_ransac_result r{};
-    if (contiguous) {   // the wave's slice of the batch: data and results in place
-      r.success = result->success + p0; r.models = result->models + (size_t)p0 * kS; r.num_inliers = result->num_inliers + p0;
-      r.inlier_mask = result->inlier_mask + batch->offsets[p0]; r.num_iterations = result->num_iterations + p0;
-      r.confidence = result->confidence + p0; r.num_lo_iterations = result->num_lo_iterations ? result->num_lo_iterations + p0 : nullptr;
-    } else {
-      gathered.resize((size_t)off[nw] * ds);
-      for (int i = 0; i < nw; ++i)
-        std::memcpy(gathered.data() + (size_t)off[i] * ds, batch->data + (size_t)batch->offsets[W[i]] * ds, sizeof(double) * (size_t)(off[i + 1] - off[i]) * ds);
-      data = gathered.data();
-      r_succ.assign(nw, 0); r_ninl.assign(nw, 0); r_nit.assign(nw, 0); r_nlo.assign(nw, 0);
-      r_models.assign((size_t)nw * kS, 0.0); r_conf.assign(nw, 0.0); r_mask.assign((size_t)off[nw], 0);
-      r.success = r_succ.data(); r.models = r_models.data(); r.num_inliers = r_ninl.data(); r.inlier_mask = r_mask.data();
-      r.num_iterations = r_nit.data(); r.confidence = r_conf.data(); r.num_lo_iterations = r_nlo.data();
-    }
-    wsid.resize(nw);
-    for (int i = 0; i < nw; ++i) wsid[i] = sid[W[i]];
-    sub.num_problems = nw; sub.offsets = off.data(); sub.data = data; sub.seeds = nullptr;
-    const StreamInit si{gen.data(), wsid.data(), first.data(), dls_est ? dls_gen.data() : nullptr};
-    const int rc = ransac_run(&sub, params, &r, &si);   // (advances gen[] of the wave's streams)
-    if (rc) return rc;
-    if (!contiguous) {
-      for (int i = 0; i < nw; ++i) {
-        const int p = W[i];
-        result->success[p] = r_succ[i]; result->num_inliers[p] = r_ninl[i]; result->num_iterations[p] = r_nit[i];
-        result->confidence[p] = r_conf[i];
-        if (result->num_lo_iterations) result->num_lo_iterations[p] = r_nlo[i];
-        std::memcpy(result->models + (size_t)p * kS, r_models.data() + (size_t)i * kS, sizeof(double) * kS);
-        std::memcpy(result->inlier_mask + batch->offsets[p], r_mask.data() + off[i], (size_t)(off[i + 1] - off[i]));
-      }
-    }
-    for (int i = 0; i < nw; ++i) {
-      const int k = wsid[i], nit = r.num_iterations[i];
-      if (nit > 0) {   // (an undersized problem leaves its stream as it was)
-        if (p4pfr_est) first[k] = 0;
-        if (dls_est) {
-          dls_calls[k] += nit;
-          for (int64_t j = 0; j < 4 * (int64_t)nit; ++j) (void)dls_gen[k].next();
-        }
-      }
-    }
-    result->hypotheses_evaluated += r.hypotheses_evaluated; result->models_scored += r.models_scored;
-    result->time_fit_score_seconds += r.time_fit_score_seconds;
-    result->time_fit_seconds += r.time_fit_seconds; result->time_score_seconds += r.time_score_seconds;
-  }
-  for (int k = 0; k < ns; ++k) {
-    theia_rng_state& st = streams->states[k];
-    rng_store(st, gen[k]);
-    if (p4pfr_est) st.p4pfr_static_seeded = !first[k];
-    st.dls_calls = dls_calls[k];
-  }
-  return 0;
+void theia_ransac_params_default(theia_ransac_params* p) {
+  // sample_consensus_estimator.h:59-68
+  std::memset(p, 0, sizeof(*p));
+  p->error_thresh = -1;
+  p->failure_probability = 0.01;
+  p->min_inlier_ratio = 0;
+  p->min_iterations = 100;
+  p->max_iterations = std::numeric_limits<int>::max();
+  p->use_mle = 0; p->use_lo = 0; p->use_Tdd_test = 0; p->lo_start_iterations = 50;
+  p->seed = 0;
 }
 
-int theia_hip_rng_seed(theia_rng_state* state, uint32_t seed) {
-  if (!state) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "null state");
-  Mt19937 g;
-  g.seed(seed);
-  rng_store(*state, g);
-  return 0;
+int theia_hip_ransac_estimate_batch(const theia_ransac_batch* batch, const theia_ransac_params* params,
+                                    theia_ransac_result* result) {
+  return ransac_run(batch, params, result, nullptr);
 }
-
-int theia_hip_rng_rand_int(theia_rng_state* state, int32_t lo, int32_t hi, int32_t n, int32_t* out) {
-  if (!rng_state_ok(state)) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "null state or pos outside [0, 624]");
-  if (n < 0 || (n > 0 && !out) || lo > hi) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "bad argument");
-  Mt19937 g;
-  rng_load(g, *state);
-  for (int32_t i = 0; i < n; ++i) out[i] = g.rand_int(lo, hi);
-  rng_store(*state, g);
-  return 0;
-}
-
-int theia_hip_rng_rand_double(theia_rng_state* state, double lo, double hi, int32_t n, double* out) {
-  if (!rng_state_ok(state)) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "null state or pos outside [0, 624]");
-  if (n < 0 || (n > 0 && !out) || !(lo <= hi)) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "bad argument");
-  Mt19937 g;
-  rng_load(g, *state);
-  for (int32_t i = 0; i < n; ++i) out[i] = g.rand_double(lo, hi);
-  rng_store(*state, g);
-  return 0;
-}
-
-int theia_hip_rng_rand_gaussian(theia_rng_state* state, double mean, double std_dev, int32_t n, double* out) {
-  if (!rng_state_ok(state)) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "null state or pos outside [0, 624]");
-  if (n < 0 || (n > 0 && !out)) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "bad argument");
-  Mt19937 g;
-  rng_load(g, *state);
-  for (int32_t i = 0; i < n; ++i) out[i] = g.rand_gaussian(mean, std_dev);
-  rng_store(*state, g);
-  return 0;
-}
-
-int theia_hip_rng_discard(theia_rng_state* state, uint64_t words) {
-  if (!rng_state_ok(state)) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "null state or pos outside [0, 624]");
-  Mt19937 g;
-  rng_load(g, *state);
-  g.discard(words);
-  rng_store(*state, g);
-  return 0;
-}
-
-int theia_hip_five_point_relative_pose(int32_t num, const double* corr, double* essential_matrices, int32_t* num_solutions) {
-  if (num < 0 || (num > 0 && (!corr || !essential_matrices || !num_solutions))) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "bad argument");
-  if (num == 0) return 0;
-  int rc = ensure_device();
-  if (rc) return rc;
-  hipStream_t st = solver_stream();
-  PoolStreamScope pool_scope(st);   // blocks this call hands back to the caches are tagged with an event on this stream (pools.h)
-  if (!st) return set_error(THEIA_HIP_ERR_NO_DEVICE, "could not create the solver stream");
-  CallSync mine;
-  DBuf<double> dc, de; DBuf<int> dn;
-  if ((rc = dc.ensure((size_t)num * 20)) || (rc = de.ensure((size_t)num * 90)) || (rc = dn.ensure(num))) return rc;
-  HIP_TRYR(hipMemcpyAsync(dc.p, corr, sizeof(double) * num * 20, hipMemcpyHostToDevice, st));
-  k_five_point<<<(num + 63) / 64, 64, 0, st>>>(num, dc.p, de.p, dn.p);
-  HIP_TRYR(hipMemcpyAsync(essential_matrices, de.p, sizeof(double) * num * 90, hipMemcpyDeviceToHost, st));
-  HIP_TRYR(hipMemcpyAsync(num_solutions, dn.p, sizeof(int) * num, hipMemcpyDeviceToHost, st));
-  HIP_TRYR(hipGetLastError());
-  HIP_TRYR(mine.wait(st));
-  return 0;
-}
-
-int theia_hip_four_point_pose_and_focal_length(int32_t num, const double* corr2d3d, double* projection_matrices, int32_t* num_solutions) {
-  if (num < 0 || (num > 0 && (!corr2d3d || !projection_matrices || !num_solutions))) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "bad argument");
-  if (num == 0) return 0;
-  int rc = ensure_device();
-  if (rc || (rc = p4pf_kernel_ready())) return rc;
-  hipStream_t st = solver_stream();
-  PoolStreamScope pool_scope(st);   // blocks this call hands back to the caches are tagged with an event on this stream (pools.h)
-  if (!st) return set_error(THEIA_HIP_ERR_NO_DEVICE, "could not create the solver stream");
-  CallSync mine;
-  // one problem of four data per call row, one hypothesis each with the identity sample: the RANSAC stages as they are
-  DBuf<double> dc, dws, dsol, dmod; DBuf<int> dn, dok, dmask, dsamp, dact, ddense, dtags, dbase; DBuf<int64_t> doff;
-  const size_t n = (size_t)num;
-  if ((rc = dc.ensure(n * 20)) || (rc = dws.ensure(n * kFpWs)) || (rc = dsol.ensure(n * 50)) || (rc = dmod.ensure(n * 10 * kStride)) ||
-      (rc = dn.ensure(n)) || (rc = dok.ensure(n)) || (rc = dmask.ensure(n)) || (rc = dsamp.ensure(n * 4)) || (rc = dact.ensure(n)) ||
-      (rc = ddense.ensure(n)) || (rc = dtags.ensure(n * 10)) || (rc = dbase.ensure(n)) || (rc = doff.ensure(n + 1)))
-    return rc;
-  std::vector<int64_t> off(n + 1);
-  std::vector<int> samp(n * 4), act(n, 1);
-  for (size_t i = 0; i <= n; ++i) off[i] = (int64_t)(4 * i);
-  for (size_t i = 0; i < n * 4; ++i) samp[i] = (int)(i % 4);
-  HIP_TRYR(hipMemcpyAsync(dc.p, corr2d3d, sizeof(double) * n * 20, hipMemcpyHostToDevice, st));
-  HIP_TRYR(hipMemcpyAsync(doff.p, off.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, st));
-  HIP_TRYR(hipMemcpyAsync(dsamp.p, samp.data(), sizeof(int) * n * 4, hipMemcpyHostToDevice, st));
-  HIP_TRYR(hipMemcpyAsync(dact.p, act.data(), sizeof(int) * n, hipMemcpyHostToDevice, st));
-  HIP_TRYR(hipMemsetAsync(ddense.p, 0, sizeof(int) * n, st));
-  HIP_TRYR(hipMemsetAsync(dmod.p, 0, sizeof(double) * n * 10 * kStride, st));
-  k_p4pf_a<<<(unsigned)n, p4pfdev::kThreads, p4pfdev::kLdsBytes, st>>>(num, 1, doff.p, dc.p, dsamp.p, dact.p, dws.p, dok.p);
-  k_fit5_b<true><<<(unsigned)((n + kFpTeamsPerWave - 1) / kFpTeamsPerWave), 64, 0, st>>>(n, dok.p, dws.p, dsol.p, dmask.p);
-  k_p4pf_c<<<dim3(1, num), 64, 0, st>>>(num, 1, dact.p, dws.p, dsol.p, dmask.p, dmod.p, dn.p, ddense.p, dtags.p, dbase.p);
-  std::vector<double> hm(n * 10 * kStride);
-  HIP_TRYR(hipMemcpyAsync(hm.data(), dmod.p, sizeof(double) * hm.size(), hipMemcpyDeviceToHost, st));
-  HIP_TRYR(hipMemcpyAsync(num_solutions, dn.p, sizeof(int) * n, hipMemcpyDeviceToHost, st));
-  HIP_TRYR(hipGetLastError());
-  HIP_TRYR(mine.wait(st));
-  for (size_t i = 0; i < n; ++i)
-    for (int j = 0; j < 10; ++j)
-      for (int k = 0; k < 12; ++k) projection_matrices[(i * 10 + j) * 12 + k] = j < num_solutions[i] ? hm[(i * 10 + j) * kStride + k] : 0.0;
-  return 0;
-}
-
-// n draws of RandomNumberGenerator(seed).RandInt(lo, hi) (util/random.cc:46-84: std::mt19937 + uniform_int_distribution<int>), for
-// host code that has to follow the reference's generator outside the sampler (the random candidates of the guided matcher)
-int theia_hip_randint_stream(uint32_t seed, int32_t n, int32_t lo, int32_t hi, int32_t* out) {
-  if (n < 0 || hi < lo || (n > 0 && !out)) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "bad argument");
-  Mt19937 g;
-  g.seed(seed);
-  for (int i = 0; i < n; ++i) out[i] = g.rand_int(lo, hi);
-  return 0;
-}
-
-int theia_hip_four_point_focal_length_radial_distortion(int32_t num, const double* corr2d3d, const double* limits, const double* rotation_draws,
-                                                        double* models, int32_t* num_solutions) {
-  // (the six-argument form of rounds 1 - 4 keeps its symbol and its ABI; the solver's pre-filter count is the _ex form's)
-  return theia_hip_four_point_focal_length_radial_distortion_ex(num, corr2d3d, limits, rotation_draws, models, num_solutions, nullptr);
-}
-
-int theia_hip_four_point_focal_length_radial_distortion_ex(int32_t num, const double* corr2d3d, const double* limits, const double* rotation_draws,
-                                                           double* models, int32_t* num_solutions, int32_t* num_solver_solutions) {
-  if (num < 0 || !limits || (num > 0 && (!corr2d3d || !models || !num_solutions))) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "bad argument");
-  if (!(limits[1] >= 0.0 && limits[0] >= 0.0 && limits[0] >= limits[1] && limits[2] <= 0.0 && limits[3] <= 0.0 && limits[2] <= limits[3]))
-    return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "P4Pfr: needs 0 <= min focal length <= max focal length and max distortion <= min distortion <= 0");
-  if (num == 0) return 0;
-  int rc = ensure_device();
-  if (rc || (rc = p4pfr_ensure_tables())) return rc;
-  hipStream_t st = solver_stream();
-  PoolStreamScope pool_scope(st);   // blocks this call hands back to the caches are tagged with an event on this stream (pools.h)
-  if (!st) return set_error(THEIA_HIP_ERR_NO_DEVICE, "could not create the solver stream");
-  CallSync mine;
-  // one problem of four data per call row, one hypothesis each with the identity sample: the RANSAC stages as they are
-  constexpr int kMm = 13, kMd = 14;
-  DBuf<double> dc, dws, dmod, drot; DBuf<int> dn, dsamp, dact, ddense, dtags, dbase, dsolver; DBuf<int64_t> doff;
-  const size_t n = (size_t)num;
-  if ((rc = dsolver.ensure(n))) return rc;
-  if ((rc = dc.ensure(n * 20)) || (rc = dws.ensure(n * (size_t)p4pfr_workspace_doubles())) || (rc = dmod.ensure(n * kMm * kStride)) || (rc = drot.ensure(n * 9)) ||
-      (rc = dn.ensure(n)) || (rc = dsamp.ensure(n * 4)) || (rc = dact.ensure(n)) || (rc = ddense.ensure(n)) || (rc = dtags.ensure(n * kMm)) ||
-      (rc = dbase.ensure(n)) || (rc = doff.ensure(n + 1)))
-    return rc;
-  std::vector<int64_t> off(n + 1);
-  std::vector<int> samp(n * 4), act(n, 1);
-  std::vector<double> rot(n * 9);
-  for (size_t i = 0; i <= n; ++i) off[i] = (int64_t)(4 * i);
-  for (size_t i = 0; i < n * 4; ++i) samp[i] = (int)(i % 4);
-  Mt19937 g;
-  g.seed(42);   // rotation_draws == NULL: the calls of a fresh process, in order (the solver's static RandomNumberGenerator(42))
-  for (size_t i = 0; i < n; ++i) {
-    double v[3];
-    for (int k = 0; k < 3; ++k) v[k] = rotation_draws ? rotation_draws[3 * i + k] : g.rand_double(-0.5, 0.5);
-    p4pfr_rotation_from_draws(v, rot.data() + 9 * i);
-  }
-  HIP_TRYR(hipMemcpyAsync(dc.p, corr2d3d, sizeof(double) * n * 20, hipMemcpyHostToDevice, st));
-  HIP_TRYR(hipMemcpyAsync(doff.p, off.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, st));
-  HIP_TRYR(hipMemcpyAsync(dsamp.p, samp.data(), sizeof(int) * n * 4, hipMemcpyHostToDevice, st));
-  HIP_TRYR(hipMemcpyAsync(dact.p, act.data(), sizeof(int) * n, hipMemcpyHostToDevice, st));
-  HIP_TRYR(hipMemcpyAsync(drot.p, rot.data(), sizeof(double) * n * 9, hipMemcpyHostToDevice, st));
-  HIP_TRYR(hipMemsetAsync(ddense.p, 0, sizeof(int) * n, st));
-  HIP_TRYR(hipMemsetAsync(dmod.p, 0, sizeof(double) * n * kMm * kStride, st));
-  launch_p4pfr_fit(num, 1, doff.p, dc.p, dsamp.p, dact.p, drot.p, limits, dws.p, dmod.p, dn.p, ddense.p, dtags.p, dbase.p, st, dsolver.p);
-  if (num_solver_solutions) HIP_TRYR(hipMemcpyAsync(num_solver_solutions, dsolver.p, sizeof(int) * n, hipMemcpyDeviceToHost, st));
-  std::vector<double> hm(n * kMm * kStride);
-  HIP_TRYR(hipMemcpyAsync(hm.data(), dmod.p, sizeof(double) * hm.size(), hipMemcpyDeviceToHost, st));
-  HIP_TRYR(hipMemcpyAsync(num_solutions, dn.p, sizeof(int) * n, hipMemcpyDeviceToHost, st));
-  HIP_TRYR(hipGetLastError());
-  HIP_TRYR(mine.wait(st));
-  for (size_t i = 0; i < n; ++i)
-    for (int j = 0; j < kMm; ++j)
-      for (int k = 0; k < kMd; ++k) models[(i * kMm + j) * kMd + k] = j < num_solutions[i] ? hm[(i * kMm + j) * kStride + k] : 0.0;
-  return 0;
-}
-
-int theia_hip_pose_from_three_points(int32_t num, const double* corr2d3d, double* rotations, double* translations, int32_t* num_solutions) {
-  if (num < 0 || (num > 0 && (!corr2d3d || !rotations || !translations || !num_solutions))) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "bad argument");
-  if (num == 0) return 0;
-  int rc = ensure_device();
-  if (rc) return rc;
-  hipStream_t st = solver_stream();
-  PoolStreamScope pool_scope(st);   // blocks this call hands back to the caches are tagged with an event on this stream (pools.h)
-  if (!st) return set_error(THEIA_HIP_ERR_NO_DEVICE, "could not create the solver stream");
-  CallSync mine;
-  DBuf<double> dc, dr, dt; DBuf<int> dn;
-  if ((rc = dc.ensure((size_t)num * 15)) || (rc = dr.ensure((size_t)num * 36)) || (rc = dt.ensure((size_t)num * 12)) || (rc = dn.ensure(num))) return rc;
-  HIP_TRYR(hipMemcpyAsync(dc.p, corr2d3d, sizeof(double) * num * 15, hipMemcpyHostToDevice, st));
-  k_p3p<<<(num + 63) / 64, 64, 0, st>>>(num, dc.p, dr.p, dt.p, dn.p);
-  HIP_TRYR(hipMemcpyAsync(rotations, dr.p, sizeof(double) * num * 36, hipMemcpyDeviceToHost, st));
-  HIP_TRYR(hipMemcpyAsync(translations, dt.p, sizeof(double) * num * 12, hipMemcpyDeviceToHost, st));
-  HIP_TRYR(hipMemcpyAsync(num_solutions, dn.p, sizeof(int) * num, hipMemcpyDeviceToHost, st));
-  HIP_TRYR(hipGetLastError());
-  HIP_TRYR(mine.wait(st));
-  return 0;
-}
-
-int theia_hip_sqpnp(int32_t num, const int64_t* offsets, const double* features, const double* world_points,
-                    double* quaternions, double* translations, int32_t* num_solutions) {
-  if (num < 0 || (num > 0 && (!offsets || !features || !world_points || !quaternions || !translations || !num_solutions)))
-    return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "bad argument");
-  if (num == 0) return 0;
-  int rc = thip::ensure_device();
-  if (rc) return rc;
-  hipStream_t st = solver_stream();
-  PoolStreamScope pool_scope(st);   // blocks this call hands back to the caches are tagged with an event on this stream (pools.h)
-  if (!st) return set_error(THEIA_HIP_ERR_NO_DEVICE, "could not create the solver stream");
-  CallSync mine;
-  for (int i = 0; i < num; ++i)
-    if (offsets[i + 1] < offsets[i]) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "offsets must be non-decreasing");
-  const int64_t total = offsets[num] - offsets[0];
-  if (offsets[0] != 0) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "offsets[0] must be 0");
-  DBuf<double> df, dw, dq, dt; DBuf<int> dn; DBuf<int64_t> dof;
-  if ((rc = df.ensure((size_t)std::max<int64_t>(1, total) * 2)) || (rc = dw.ensure((size_t)std::max<int64_t>(1, total) * 3)) ||
-      (rc = dq.ensure((size_t)num * 72)) || (rc = dt.ensure((size_t)num * 54)) || (rc = dn.ensure(num)) || (rc = dof.ensure(num + 1)))
-    return rc;
-  if (total) {
-    HIP_TRYR(hipMemcpyAsync(df.p, features, sizeof(double) * total * 2, hipMemcpyHostToDevice, st));
-    HIP_TRYR(hipMemcpyAsync(dw.p, world_points, sizeof(double) * total * 3, hipMemcpyHostToDevice, st));
-  }
-  HIP_TRYR(hipMemcpyAsync(dof.p, offsets, sizeof(int64_t) * (num + 1), hipMemcpyHostToDevice, st));
-  k_sqpnp<<<(num + 63) / 64, 64, 0, st>>>(num, dof.p, df.p, dw.p, dq.p, dt.p, dn.p);
-  HIP_TRYR(hipMemcpyAsync(quaternions, dq.p, sizeof(double) * num * 72, hipMemcpyDeviceToHost, st));
-  HIP_TRYR(hipMemcpyAsync(translations, dt.p, sizeof(double) * num * 54, hipMemcpyDeviceToHost, st));
-  HIP_TRYR(hipMemcpyAsync(num_solutions, dn.p, sizeof(int) * num, hipMemcpyDeviceToHost, st));
-  HIP_TRYR(hipGetLastError());
-  HIP_TRYR(mine.wait(st));
-  return 0;
-}
-
-void theia_hip_dls_macaulay_terms(int64_t first_call, int64_t num_calls, double* out) {
-  if (first_call < 0 || num_calls <= 0 || !out) return;
-  std::vector<double> u; dls::GlibcRand gen;
-  dls_terms(u, gen, (size_t)(first_call + num_calls));
-  std::memcpy(out, u.data() + 4 * first_call, sizeof(double) * 4 * num_calls);
-}
-
-int theia_hip_dls_pnp(int32_t num, const int64_t* offsets, const double* features, const double* world_points,
-                      const int64_t* call_index, double* quaternions, double* translations, int32_t* num_solutions) {
-  if (num < 0 || (num > 0 && (!offsets || !features || !world_points || !quaternions || !translations || !num_solutions)))
-    return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "bad argument");
-  if (num == 0) return 0;
-  int rc = thip::ensure_device();
-  if (rc || (rc = dls_ensure_tables())) return rc;
-  hipStream_t st = solver_stream();
-  PoolStreamScope pool_scope(st);   // blocks this call hands back to the caches are tagged with an event on this stream (pools.h)
-  if (!st) return set_error(THEIA_HIP_ERR_NO_DEVICE, "could not create the solver stream");
-  CallSync mine;
-  if (offsets[0] != 0) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "offsets[0] must be 0");
-  int64_t max_call = num - 1;
-  for (int i = 0; i < num; ++i) {
-    if (offsets[i + 1] < offsets[i]) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "offsets must be non-decreasing");
-    if (call_index) {
-      if (call_index[i] < 0 || call_index[i] > (1 << 26)) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "call_index out of range");
-      max_call = std::max(max_call, call_index[i]);
-    }
-  }
-  const int64_t total = offsets[num];
-  std::vector<double> uall, u((size_t)num * 4); dls::GlibcRand gen;
-  dls_terms(uall, gen, (size_t)max_call + 1);
-  for (int i = 0; i < num; ++i) std::memcpy(&u[(size_t)4 * i], &uall[(size_t)4 * (call_index ? call_index[i] : i)], 4 * sizeof(double));
-  constexpr int NS = dlsdev::kMaxSolutions;
-  DBuf<double> df, dw, dq, dt, du, da, dtf; DBuf<int> dn, dok; DBuf<int64_t> dof;
-  if ((rc = df.ensure((size_t)std::max<int64_t>(1, total) * 2)) || (rc = dw.ensure((size_t)std::max<int64_t>(1, total) * 3)) ||
-      (rc = dq.ensure((size_t)num * 4 * NS)) || (rc = dt.ensure((size_t)num * 3 * NS)) || (rc = dn.ensure(num)) || (rc = dof.ensure(num + 1)) ||
-      (rc = du.ensure((size_t)num * 4)) || (rc = da.ensure((size_t)num * 729)) || (rc = dtf.ensure((size_t)num * 27)) || (rc = dok.ensure(num)))
-    return rc;
-  if (total) {
-    HIP_TRYR(hipMemcpyAsync(df.p, features, sizeof(double) * total * 2, hipMemcpyHostToDevice, st));
-    HIP_TRYR(hipMemcpyAsync(dw.p, world_points, sizeof(double) * total * 3, hipMemcpyHostToDevice, st));
-  }
-  HIP_TRYR(hipMemcpyAsync(dof.p, offsets, sizeof(int64_t) * (num + 1), hipMemcpyHostToDevice, st));
-  HIP_TRYR(hipMemcpyAsync(du.p, u.data(), sizeof(double) * num * 4, hipMemcpyHostToDevice, st));
-  launch_dls_solve_a(num, dof.p, df.p, dw.p, du.p, da.p, dtf.p, dok.p, st);
-  k_dls_solve_b<<<(num + 63) / 64, 64, 0, st>>>(num, dof.p, dw.p, da.p, dtf.p, dok.p, dq.p, dt.p, dn.p);
-  HIP_TRYR(hipGetLastError());
-  HIP_TRYR(hipMemcpyAsync(quaternions, dq.p, sizeof(double) * num * 4 * NS, hipMemcpyDeviceToHost, st));
-  HIP_TRYR(hipMemcpyAsync(translations, dt.p, sizeof(double) * num * 3 * NS, hipMemcpyDeviceToHost, st));
-  HIP_TRYR(hipMemcpyAsync(num_solutions, dn.p, sizeof(int) * num, hipMemcpyDeviceToHost, st));
-  HIP_TRYR(hipGetLastError());
-  HIP_TRYR(mine.wait(st));
-  return 0;
-}
-
-void theia_hip_release_scratch(void) { dev_pool().release(); host_pool().release(); }
 
 }  // extern "C"
 

@@ -12,7 +12,7 @@ int ensure_device();  // lazily selects device 0 unless theia_hip_init chose one
 #include <cstdint>
 #include "theia_hip.h"
 namespace thip {
-// result record of the batched LM solvers (ba_batch.hip, twoview_lm.hip; read by ransac.hip): c0 = initial, c1 = final cost
+// result record of the batched LM solvers (ba_batch.hip, twoview_lm.hip; read by ransac.hip's RansacCall::run_lo): c0 = initial, c1 = final cost
 struct BatchLmOut { int success, term, iters, nsucc; double c0, c1; };
 // ba_batch.hip: batched single-view LM on device-resident data (one wave per problem);
 // problem p covers [offsets[p], offsets[p+1]) or, with counts, [offsets[p], offsets[p] + counts[p]).
