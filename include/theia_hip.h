@@ -523,6 +523,48 @@ int theia_hip_robust_rotation_averaging(int32_t num_views, double* orientations,
                                         const int32_t* edges, const double* relative_rotations,
                                         const theia_rotation_options* options, theia_rotation_summary* summary);
 
+/* LinearRotationEstimator::EstimateRotations (global_pose_estimation/linear_rotation_estimator.cc:76-204, Martinec &
+ * Pajdla; the LINEAR global rotation estimator of the global pipeline, global_reconstruction_estimator.cc:349-353):
+ * orientations from the pairs' relative rotations alone, without an initial guess (csrc/linear_rotations.hip).  Per pair
+ * e = (i, j) with R_e = AngleAxisToRotationMatrix(relative_rotations[e]), R_j = R_e R_i, the symmetric 3n x 3n matrix M
+ * over the n views that have an edge gets +I on the diagonal blocks (i, i) and (j, j), -R_e' at block (i, j) and -R_e at
+ * block (j, i) (:90-150); repeated pairs add up.  The eigenvectors of its three smallest eigenvalues, X [3n][3], hold
+ * X_i = R_i Q / sqrt(n) for one common orthogonal Q, and view i's orientation is ProjectToRotationMatrix(X_i)
+ * (sfm/pose/util.cc:117-129: U V' of the Jacobi SVD, negated when its determinant is negative) as angle-axis (:170-201).
+ * Where the reference runs Spectra's shift-invert Lanczos (3 of 6 vectors, shift 0, 1000 iterations, 1e-4) over a sparse
+ * Cholesky of M, this runs a block inverse iteration over one dense Cholesky of M + mu I, mu = 3n eps max diag M (the three
+ * eigenvalues are rounding errors of either sign on noise-free input; the shift moves no eigenvector): from a fixed
+ * pseudo-random start block, Y = (M + mu I)^-1 X, Q = Y orthonormalised (modified Gram-Schmidt, two passes), until
+ * |Q - X (X' Q)|_F <= subspace_convergence_threshold.  The result is defined up to Q: the reference fixes no view and
+ * neither does this; Q differs from the reference's and is the same in every run (no floating-point atomics, every sum
+ * in a fixed order: two runs are bit-identical).
+ * edges [num_edges][2] = (i, j); orientations_out [num_views][3] angle-axis and estimated_out [num_views]: a view with an
+ * edge gets its orientation and 1; a view without one gets 0 and its orientations_out row is left untouched (the
+ * reference gives it no entry).
+ * THEIA_HIP_ERR_INVALID_ARGUMENT (checked before the device is touched; outputs untouched, summary zeroed): no edge (the
+ * reference's CHECK_GT, :158); an edge naming a view out of range; an edge from a view to itself (the reference would
+ * write -R into a diagonal block); the views that have edges do not form one connected graph (the reference does not
+ * check: the null space then has three dimensions per component and its result is meaningless);
+ * max_num_iterations <= 0; a threshold that is not positive and finite.
+ * THEIA_HIP_ERR_INTERNAL: a pivot of the factorisation was not positive (outputs untouched, summary holds the shift), or
+ * the iteration did not converge within max_num_iterations (outputs hold the state reached).
+ * THEIA_HIP_ERR_OUT_OF_MEMORY: the dense (3n + 1)^2 array of doubles does not fit on the device. */
+typedef struct theia_linear_rotation_options {
+  int32_t max_num_iterations;      /* 1000, the reference's Spectra limit */
+  int32_t reserved;
+  double subspace_convergence_threshold;   /* 1e-10 */
+} theia_linear_rotation_options;
+typedef struct theia_linear_rotation_summary {
+  int32_t iterations, num_views_in_system;
+  double eigenvalues[3];           /* ascending, shift subtracted: 1 / theta - mu for the eigenvalues theta of X' Y */
+  double subspace_change;          /* |Q - X (X' Q)|_F of the last step */
+  double shift;                    /* mu */
+  double setup_ms, factor_ms, iterate_ms;   /* set-up = checks, plan, uploads, assembly, start block */
+} theia_linear_rotation_summary;
+int theia_hip_linear_rotations(int32_t num_views, int32_t num_edges, const int32_t* edges,
+                               const double* relative_rotations, const theia_linear_rotation_options* options /*NULL = defaults*/,
+                               double* orientations_out, uint8_t* estimated_out, theia_linear_rotation_summary* summary);
+
 /* LeastUnsquaredDeviationPositionEstimator::EstimatePositions (global_pose_estimation/
  * least_unsquared_deviation_position_estimator.cc:75-213; pybind sfm.cc:1196-1204, 1707-1726, the default
  * LEAST_UNSQUARED_DEVIATION position stage of the global pipeline): per pair e = (i, j) the rows c_j - c_i - s_e d_e with

@@ -24,8 +24,8 @@
 //                 land on the (v1, v3) blocks and are summed within the track first -- three items per track, and three
 //                 per constraint (C'C, B'C, C'D)
 //   k_blocks      one thread per non-empty block: adds its items in order, writes the lower triangle
-//   k_shift       mu = kShiftMultiple n eps max diag H on the diagonal (H's smallest eigenvalue is a rounding error of
-//                 either sign on noise-free data; the shift moves no eigenvector)
+//   k_shift       mu = kShiftMultiple n eps max diag H on the diagonal and x = b = 1 / sqrt(n) (spectral_shift.h: H's
+//                 smallest eigenvalue is a rounding error of either sign on noise-free data; the shift moves no eigenvector)
 //   dense_cholesky_factor once, then per inverse iteration dense_cholesky_solve_factored and k_iterate: normalise,
 //                 |x_new - s x_old|_2 with s = sign(x_new . x_old), and the stop flag on the device (the pattern of
 //                 lud_positions.hip: the host reads the flag once per chunk of iterations)
@@ -37,6 +37,7 @@
 #include "ransac_device.h"
 #include "ba_kernels.h"
 #include "wave_reduce.h"
+#include "spectral_shift.h"
 #include "device_util.h"
 
 #include <algorithm>
@@ -266,29 +267,6 @@ __global__ __launch_bounds__(kThreads) void k_full_system(int n, int lda, const 
   if (k >= (size_t)n * n) return;
   const int r = (int)(k / n), c = (int)(k % n);
   full[k] = r >= c ? H[(size_t)r * lda + c] : H[(size_t)c * lda + r];
-}
-
-// One workgroup: max diag H, then mu = multiple n eps max diag H on the diagonal; x = b = 1 / sqrt(n).
-__global__ __launch_bounds__(kThreads) void k_shift(int n, int lda, double* __restrict__ H, double multiple,
-                                                    double* __restrict__ x, double* __restrict__ b,
-                                                    LigtState* __restrict__ st) {
-  __shared__ double red[kThreads];
-  double m = 0.0;
-  for (int k = threadIdx.x; k < n; k += kThreads) m = fmax(m, H[(size_t)k * lda + k]);
-  red[threadIdx.x] = m;
-  __syncthreads();
-  for (int s = kThreads / 2; s > 0; s >>= 1) {
-    if (threadIdx.x < s) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + s]);
-    __syncthreads();
-  }
-  const double max_diag = red[0];
-  const double mu = ((multiple * (double)n) * DBL_EPSILON) * max_diag;
-  const double x0 = 1.0 / sqrt((double)n);
-  for (int k = threadIdx.x; k < n; k += kThreads) {
-    H[(size_t)k * lda + k] += mu;
-    x[k] = x0; b[k] = x0;
-  }
-  if (threadIdx.x == 0) { st->shift = mu; st->max_diag = max_diag; }
 }
 
 // One workgroup, after y = (H + mu I)^-1 x: x_new = y / |y|, the step |x_new - s x|_2 with s = sign(x_new . x), the
@@ -531,7 +509,7 @@ extern "C" int theia_hip_ligt_positions(int32_t num_views, const double* orienta
                                                               d_items.p, lda, d_H.p);
   if (system_out)
     k_full_system<<<grid_of((size_t)n3 * n3, kThreads), kThreads, 0, st>>>(n3, lda, d_H.p, d_full.p);
-  k_shift<<<1, kThreads, 0, st>>>(n3, lda, d_H.p, kShiftMultiple, d_x.p, d_b.p, d_st.p);
+  k_shift<kThreads><<<1, kThreads, 0, st>>>(n3, lda, d_H.p, kShiftMultiple, d_x.p, d_b.p, &d_st.p->shift, &d_st.p->max_diag);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(st));
   sm.assemble_ms = ms_since(t_assemble);

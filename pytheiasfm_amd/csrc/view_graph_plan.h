@@ -1,6 +1,8 @@
-// view_graph_plan.h -- what the global-pose stages (rotation_averaging.hip, lud_positions.hip) derive from a view graph on
-// the host before they touch the device: which views are free, and the two CSR lists their kernels assemble the
-// Laplacian-shaped system from without atomics.  Host code only.
+// view_graph_plan.h -- what the global-pose stages (rotation_averaging.hip, lud_positions.hip, linear_rotations.hip) derive
+// from a view graph on the host before they touch the device: which views are free, and the two CSR lists their kernels
+// assemble the Laplacian-shaped system from without atomics.  Host code only.  The first two fix a view per connected
+// component (build_view_graph_plan); the third fixes none and leaves out the views without edges (it checks its graph
+// itself, with view_graph_components, and calls fill_view_graph_lists).
 //
 // The lists, as the kernels read them:
 //   inc[inc_off[t] .. inc_off[t + 1])            the edges incident to free view t, in edge order;
@@ -33,30 +35,8 @@ inline int find_root(std::vector<int>& parent, int v) {
   return v;
 }
 
-// Checks the edges and builds the plan.  fixed: [n] flags or null; no view flagged: view 0 is fixed.  `word` names a
-// fixed view in the error text ("fixed" for rotations, "held" for positions).  THEIA_HIP_ERR_INVALID_ARGUMENT: an edge
-// names a view out of range; a connected component has no fixed view (the system would be singular).
-inline int build_view_graph_plan(int n, const uint8_t* fixed, int E, const int32_t* edges, const char* word,
-                                 ViewGraphPlan* plan) {
-  for (int e = 0; e < E; ++e)
-    if (edges[2 * e] < 0 || edges[2 * e] >= n || edges[2 * e + 1] < 0 || edges[2 * e + 1] >= n)
-      return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "edge %d names a view out of range", e);
-
-  std::vector<uint8_t> fix(n, 0);
-  bool any = false;
-  for (int v = 0; v < n && fixed; ++v) { fix[v] = fixed[v] ? 1 : 0; any = any || fix[v]; }
-  if (!any) fix[0] = 1;
-  std::vector<int> parent(n);
-  std::iota(parent.begin(), parent.end(), 0);
-  for (int e = 0; e < E; ++e) {
-    const int a = find_root(parent, edges[2 * e]), b = find_root(parent, edges[2 * e + 1]);
-    if (a != b) parent[std::max(a, b)] = std::min(a, b);
-  }
-  std::vector<uint8_t> anchored(n, 0);
-  for (int v = 0; v < n; ++v) if (fix[v]) anchored[find_root(parent, v)] = 1;
-  for (int v = 0; v < n; ++v)
-    if (!anchored[find_root(parent, v)])
-      return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "view %d lies in a connected component without a %s view", v, word);
+// The lists of the free views, those with fix[v] == 0, indexed compactly in view order.  The edges are in range.
+inline void fill_view_graph_lists(int n, const std::vector<uint8_t>& fix, int E, const int32_t* edges, ViewGraphPlan* plan) {
   std::vector<int>& idx = plan->idx;
   idx.assign(n, -1);
   plan->free_view.clear();
@@ -100,6 +80,43 @@ inline int build_view_graph_plan(int n, const uint8_t* fixed, int E, const int32
   }
   plan->pair_off.push_back((int)pe.size());
   plan->P = (int)plan->pair_rc.size();
+}
+
+// Checks that every edge names views in range (THEIA_HIP_ERR_INVALID_ARGUMENT otherwise) and gives every view the root of
+// its connected component, the component's smallest view.
+inline int view_graph_components(int n, int E, const int32_t* edges, std::vector<int>* root) {
+  for (int e = 0; e < E; ++e)
+    if (edges[2 * e] < 0 || edges[2 * e] >= n || edges[2 * e + 1] < 0 || edges[2 * e + 1] >= n)
+      return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "edge %d names a view out of range", e);
+  std::vector<int>& parent = *root;
+  parent.resize(n);
+  std::iota(parent.begin(), parent.end(), 0);
+  for (int e = 0; e < E; ++e) {
+    const int a = find_root(parent, edges[2 * e]), b = find_root(parent, edges[2 * e + 1]);
+    if (a != b) parent[std::max(a, b)] = std::min(a, b);
+  }
+  for (int v = 0; v < n; ++v) parent[v] = find_root(parent, v);
+  return 0;
+}
+
+// Checks the edges and builds the plan.  fixed: [n] flags or null; no view flagged: view 0 is fixed.  `word` names a
+// fixed view in the error text ("fixed" for rotations, "held" for positions).  THEIA_HIP_ERR_INVALID_ARGUMENT: an edge
+// names a view out of range; a connected component has no fixed view (the system would be singular).
+inline int build_view_graph_plan(int n, const uint8_t* fixed, int E, const int32_t* edges, const char* word,
+                                 ViewGraphPlan* plan) {
+  std::vector<int> root;
+  if (int rc = view_graph_components(n, E, edges, &root)) return rc;
+
+  std::vector<uint8_t> fix(n, 0);
+  bool any = false;
+  for (int v = 0; v < n && fixed; ++v) { fix[v] = fixed[v] ? 1 : 0; any = any || fix[v]; }
+  if (!any) fix[0] = 1;
+  std::vector<uint8_t> anchored(n, 0);
+  for (int v = 0; v < n; ++v) if (fix[v]) anchored[root[v]] = 1;
+  for (int v = 0; v < n; ++v)
+    if (!anchored[root[v]])
+      return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "view %d lies in a connected component without a %s view", v, word);
+  fill_view_graph_lists(n, fix, E, edges, plan);
   return 0;
 }
 

@@ -105,7 +105,7 @@ __device__ __forceinline__ double wave_max_abs(double v) {
 }
 
 // Sum of v over a workgroup of THREADS (a power of two) in a fixed tree order -- halving strides over red[THREADS] in LDS;
-// the result is valid in thread 0.  The global-pose stages' tests restate this order on the host and compare bits.
+// the result is returned in every thread.  The global-pose stages' tests restate this order on the host and compare bits.
 template <int THREADS>
 __device__ __forceinline__ double block_sum(double v, double* red) {
   const int tid = threadIdx.x;

@@ -5,7 +5,10 @@ global_pose_estimation/least_unsquared_deviation_position_estimator.{h,cc}).
 
 The solve runs on the device through theia_hip_robust_rotation_averaging (csrc/rotation_averaging.hip).  The object
 keeps the reference's state across calls: constraints accumulate over EstimateRotations / AddRelativeRotationConstraint
-calls on one object, and the view fixed by default on the first call stays fixed on later ones.  The positions run
+calls on one object, and the view fixed by default on the first call stays fixed on later ones.  The estimator that
+needs no initial guess, pytheia.sfm.LinearRotationEstimator (sfm.cc:1789-1795 ->
+global_pose_estimation/linear_rotation_estimator.{h,cc}), runs through theia_hip_linear_rotations
+(csrc/linear_rotations.hip).  The positions run
 through theia_hip_lud_positions (csrc/lud_positions.hip), or, from the tracks' features and without the pairs' relative
 translations, through theia_hip_ligt_positions (pytheia.sfm.LiGTPositionEstimator, sfm.cc:1728-1747 ->
 global_pose_estimation/LiGT_position_estimator.{h,cc}; csrc/ligt_positions.hip).
@@ -118,6 +121,82 @@ class RobustRotationEstimator:
         self.last_success = rc == 0
         self.last_summary = s
         return {v: out[k].copy() for k, v in enumerate(ids)}
+
+
+class LinearRotationEstimatorOptions:
+    """The two stopping rules of the block inverse iteration (the reference's class has no options: it hands Spectra 1000
+    iterations and a tolerance of 1e-4, linear_rotation_estimator.cc:178)."""
+
+    def __init__(self):
+        self.max_num_iterations = 1000
+        self.subspace_convergence_threshold = 1e-10
+
+    def to_c(self):
+        o = capi.LinearRotationOptions()
+        o.max_num_iterations = int(self.max_num_iterations)
+        o.subspace_convergence_threshold = float(self.subspace_convergence_threshold)
+        return o
+
+
+def linear_rotations(num_views, edges, relative_rotations, options=None, orientations_out=None):
+    """theia_hip_linear_rotations on arrays: edges [E][2] view indices, relative_rotations [E][3] = TwoViewInfo::rotation_2.
+    Returns (return code, orientations [num_views][3], estimated [num_views] bool, LinearRotationSummary); a view without
+    an edge keeps its orientations_out row (zeros without orientations_out); on a refusal nothing is written.  The
+    orientations are defined up to one common rotation on the right."""
+    o = (options or LinearRotationEstimatorOptions()).to_c()
+    n = int(num_views)
+    e, r = _pair_arrays(edges, relative_rotations, "relative rotation")
+    out = np.zeros((max(n, 0), 3)) if orientations_out is None else orientations_out
+    if out.shape != (n, 3) or out.dtype != np.float64 or not out.flags["C_CONTIGUOUS"]:
+        raise ValueError("orientations_out must be a C-contiguous float64 [num_views][3] array")
+    est = np.zeros(max(n, 0), dtype=np.uint8)
+    s = capi.LinearRotationSummary()
+    rc = capi.lib().theia_hip_linear_rotations(n, e.shape[0], capi.ptr(e, C.c_int32), capi.ptr(r, C.c_double), C.byref(o),
+                                               capi.ptr(out, C.c_double), capi.ptr(est, C.c_uint8), C.byref(s))
+    return rc, out, est.astype(bool), s
+
+
+class LinearRotationEstimator:
+    """LinearRotationEstimator() with AddRelativeRotationConstraint(view_id_pair, relative_rotation) and
+    EstimateRotations(view_pairs, orientations=None) -> dict (sfm.cc:1789-1795 -> linear_rotation_estimator.{h,cc}).
+
+    The views are indexed in the order the constraints first name them (InsertIfNotPresent, :97-98), and the constraints
+    accumulate over the calls on one object (constraint_entries_ is a member).  A view id already in `orientations` keeps
+    the value passed in (the reference's emplace does not overwrite, :200); the dict returned holds those entries and
+    every view of the constraints.  pyTheia's binding returns only the bool, and its dict argument is a copy the caller
+    never sees: this mirror returns the dict, as RobustRotationEstimator's binding does, and keeps the bool in
+    last_success."""
+
+    def __init__(self):
+        self._constraints = []      # [((id1, id2), aa)] in the order they were added
+        self.last_summary = None
+        self.last_success = None
+
+    def AddRelativeRotationConstraint(self, view_id_pair, relative_rotation):
+        self._constraints.append(((int(view_id_pair[0]), int(view_id_pair[1])),
+                                  np.asarray(relative_rotation, dtype=np.float64).reshape(3).copy()))
+
+    def EstimateRotations(self, view_pairs, orientations=None):
+        for pair, info in view_pairs.items():
+            self.AddRelativeRotationConstraint(pair, info.rotation_2)
+        if not self._constraints:   # CHECK_GT(constraint_entries_.size(), 0)
+            raise capi.TheiaHipError(capi.THEIA_HIP_ERR_INVALID_ARGUMENT, "no relative rotation constraints")
+        ids = {}
+        for (a, b), _ in self._constraints:
+            ids.setdefault(a, len(ids))
+            ids.setdefault(b, len(ids))
+        edges = np.array([(ids[a], ids[b]) for (a, b), _ in self._constraints], dtype=np.int32)
+        rel = np.array([r for _, r in self._constraints], dtype=np.float64)
+        rc, out, _, s = linear_rotations(len(ids), edges, rel)
+        if rc not in (0, capi.THEIA_HIP_ERR_INTERNAL):
+            capi.check(rc)
+        self.last_success = rc == 0
+        self.last_summary = s
+        result = {} if orientations is None else {int(v): np.asarray(r, dtype=np.float64).reshape(3).copy()
+                                                  for v, r in orientations.items()}
+        for v, k in ids.items():
+            result.setdefault(v, out[k].copy())
+        return result
 
 
 class GlobalPositionEstimatorType(enum.IntEnum):  # reconstruction_estimator_options.h:80-85 (pybind sfm.cc:1196-1204)

@@ -21,7 +21,8 @@ from . import _capi as capi
 from . import ba as _ba
 from .synth import angle_axis_to_matrix
 from .global_pose import (GlobalRotationEstimatorType, RobustRotationEstimator,  # noqa: F401  (pyTheia's names)
-                          RobustRotationEstimatorOptions, GlobalPositionEstimatorType,
+                          RobustRotationEstimatorOptions, LinearRotationEstimator,
+                          LinearRotationEstimatorOptions, GlobalPositionEstimatorType,
                           LeastUnsquaredDeviationPositionEstimator, LeastUnsquaredDeviationPositionEstimatorOptions,
                           LiGTPositionEstimator, LiGTPositionEstimatorOptions,
                           FilterViewPairsFromOrientation, FilterViewPairsFromRelativeTranslation,
