@@ -653,6 +653,93 @@ int theia_hip_ligt_positions(
     double* system_out /*optional*/, int32_t* system_index_out /*optional [num_views]*/,
     theia_ligt_summary* summary);
 
+/* LinearPositionEstimator::EstimatePositions (global_pose_estimation/linear_position_estimator.cc:151-473, options
+ * linear_position_estimator.h; compute_triplet_baseline_ratios.cc:52-157; math/graph/triplet_extractor.h;
+ * triangulation.cc:130-157, 236-250; the LINEAR_TRIPLET position stage of the global pipeline; Jiang, Cui, Tan, ICCV 2013):
+ * positions from the global orientations, the view pairs' relative poses and the tracks' normalised features
+ * (csrc/linear_positions.hip).
+ *  1. Every triangle (a < b < c) of the view pairs (triplet_extractor.h FindTriplets).
+ *  2. Per triangle and per track seen by all three views the unit rays f = (x, y, 1) / |.|; each of the pairs (a, b),
+ *     (a, c), (b, c) is triangulated in its first view's frame from the origins 0 and position_2 and the directions f_first
+ *     and R_2' f_second (compute_triplet_baseline_ratios.cc:52-88): the rays must satisfy d0 . d1 < cos(2 deg)
+ *     (triangulation.cc:236-250), TriangulateMidpoint solves sum (I - d d') p = sum (I - d d') o by LLT (:130-157), the depths
+ *     are |p| and |p - position_2|.  baseline = (1, median(depth1_12 / depth1_13), median(depth2_12 / depth2_23)) (:92-157).
+ *  3. Per view the number of triangles it is in; the views indexed in the order a, b, c over the triangles, the first held at
+ *     the origin (index -1) (linear_position_estimator.cc:222-243); w = 1 / sqrt(min of the three counts) (:374-380).
+ *  4. Per triangle t01 = -R_a' p2(a, b), t02 = -R_a' p2(a, c), t12 = -R_b' p2(b, c), r012 = FromTwoVectors(t12, -t01),
+ *     r201 = FromTwoVectors(t01, t02), r120 = FromTwoVectors(-t02, -t12) (:335-364), s012 = b0 / b2, s201 = b1 / b0,
+ *     s120 = b2 / b1, the three constraint rows of :396-422, and H += Ci' Cj on the views' 3 x 3 blocks without the held
+ *     view's rows and columns (:87-134).
+ *  5. The positions are the unit eigenvector of H's smallest eigenvalue (the reference: Spectra shift-invert, :189-196).
+ *     Here: one dense Cholesky of H + mu I, mu = n eps max diag H (the shift moves no eigenvector; on noise-free data the
+ *     eigenvalue is a rounding error of either sign), then inverse iteration from x = 1 / sqrt(n) until
+ *     |x_new - sign(x_new . x) x|_2 <= eigensolver_threshold or max_power_iterations.
+ *  6. The sign is voted by the view pairs (:435-473): +1 when (R_first (c_second - c_first) / |.|) . position_2 > 0, else
+ *     -1, over the pairs whose two views are in the system; a negative total flips every position.
+ * orientations [num_views][3] angle-axis (world -> camera); edges [num_edges][2] with first < second, each pair at most
+ * once; relative_rotations / relative_translations [num_edges][3] = TwoViewInfo::rotation_2 / position_2; the tracks as
+ * theia_hip_ligt_positions takes them.
+ * Where the reference depends on the order of its hash containers or threads, or is undefined, the rule here is:
+ *  - Order: the triangles are in lexicographic (a, b, c) order, and "in order" below means this order.
+ *  - A track is skipped for a triangle when any of its three pairs fails the angle test, a midpoint solve meets a
+ *    non-positive pivot, or either ratio is not finite and positive.
+ *  - The median of k valid ratios is the element of rank k / 2 (integer division, 0-based, ascending: nth_element at
+ *    size / 2); the two medians are independent.
+ *  - A triangle with k = 0 is dropped before the components are formed (the reference divides by its zero baseline);
+ *    components, counts, view indexing and weights are taken over the surviving triangles only.
+ *  - Two triangles are connected when they share an edge; the largest component is used, ties go to the one holding the
+ *    lexicographically first triangle (the reference sorts by size only).
+ *  - The held view is a of the first used triangle.
+ *  - FromTwoVectors is Eigen's arithmetic: both normalised, c = v0 . v1, axis v0 x v1, s = sqrt(2 (1 + c)), the quaternion
+ *    (s / 2, axis / s) and its matrix.  Where c < -1 + 1e-12 Eigen takes an SVD; here the result is the rotation by pi,
+ *    2 u u' - I, about u = normalize(v0 x e_k), k the first component of v0 of the smallest magnitude (three cameras on a
+ *    line give t12 parallel to t01).
+ *  - Every entry of H is summed in triangle order by one owner, within a triangle the three constraint rows in the
+ *    reference's order.  No floating-point atomics anywhere: two runs are bit-identical.
+ * positions_out [num_views][3] and estimated_out [num_views]: a view of the system gets its position (the held view zeros)
+ * and 1; a view outside it gets 0 and its positions_out row is left untouched.  Optional outputs: triplets_out
+ * [triplet_capacity][3], triplet_state_out [triplet_capacity] (0 used, 1 no ratios, 2 other component), baselines_out
+ * [triplet_capacity][3] (zeros for state 1): the first triplet_capacity triangles, summary->num_triplets is the total;
+ * system_out [3 (m - 1)]^2 row-major, H before the shift, both triangles (m = summary->num_views_in_system; size it for
+ * num_views); system_index_out [num_views]: the view's block in H, -1 held, -2 not in the system.
+ * THEIA_HIP_ERR_INVALID_ARGUMENT (nothing written; checked before the device is touched): a view index out of range, an
+ * edge with first >= second, a duplicate edge, decreasing track_offsets, a track naming a view twice,
+ * max_power_iterations <= 0, a non-positive or non-finite eigensolver_threshold, fewer than 3 edges; the same code,
+ * outputs untouched, after the stage that finds it when the graph has no triangle or no triangle has ratios.
+ * THEIA_HIP_ERR_OUT_OF_MEMORY: the triangle list (24 bytes per triangle, at most INT32_MAX / 3 triangles), the ratio
+ * scratch (one triangle with more than 2^24 possible common tracks) or the dense (3 (m - 1) + 1)^2 array of doubles
+ * (twice with system_out) do not fit.  THEIA_HIP_ERR_INTERNAL: the factorisation failed even with the shift (outputs
+ * untouched, summary holds the shift). */
+typedef struct theia_linear_triplet_options {   /* LinearPositionEstimator::Options (linear_position_estimator.h) */
+  int32_t max_power_iterations, reserved;   /* 1000; the reference declares both and reads neither */
+  double eigensolver_threshold;             /* 1e-8 */
+} theia_linear_triplet_options;
+typedef struct theia_linear_triplet_summary {
+  int32_t num_triplets;                  /* triangles found */
+  int32_t triplets_without_ratios;       /* state 1 */
+  int32_t triplets_in_other_components;  /* state 2 */
+  int32_t triplets_used;                 /* state 0 */
+  int32_t num_views_in_system;   /* m: the held view and the 3 (m - 1) unknowns' views */
+  int32_t iterations, converged; /* converged: the step test passed within max_power_iterations */
+  int32_t sign_votes, flipped;   /* the total of the +1 / -1 votes; 1 = every position was negated */
+  int32_t reserved;
+  double eigenvalue;             /* the last iterate's Rayleigh quotient minus the shift */
+  double shift;                  /* mu */
+  double setup_ms, triplets_ms, ratios_ms, assemble_ms, factor_ms, eig_ms;   /* set-up = checks, lists, uploads */
+} theia_linear_triplet_summary;
+int theia_hip_linear_triplet_positions(
+    int32_t num_views, const double* orientations /*[num_views][3] angle-axis, world -> camera*/,
+    int32_t num_edges, const int32_t* edges /*[num_edges][2], first < second*/,
+    const double* relative_rotations /*[num_edges][3]*/, const double* relative_translations /*[num_edges][3]*/,
+    int32_t num_tracks, const int32_t* track_offsets /*[num_tracks+1]*/,
+    const int32_t* obs_view /*[num_obs]*/, const double* obs_feature /*[num_obs][2], normalised*/,
+    const theia_linear_triplet_options* options /*NULL = defaults*/,
+    double* positions_out /*[num_views][3]*/, uint8_t* estimated_out /*[num_views]*/,
+    int32_t triplet_capacity, int32_t* triplets_out /*optional [triplet_capacity][3]*/,
+    uint8_t* triplet_state_out /*optional [triplet_capacity]*/, double* baselines_out /*optional [triplet_capacity][3]*/,
+    double* system_out /*optional*/, int32_t* system_index_out /*optional [num_views]*/,
+    theia_linear_triplet_summary* summary);
+
 /* FilterViewPairsFromRelativeTranslation (sfm/filter_view_pairs_from_relative_translation.cc:264-312, step 6 of the global
  * pipeline, sfm/global_reconstruction_estimator.cc:126-138; options: filter_view_pairs_from_relative_translation.h:48-66):
  * Wilson & Snavely's 1DSfM outlier test on the device (csrc/view_pair_filters.hip).  The translations are rotated into the

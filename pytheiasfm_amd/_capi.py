@@ -207,6 +207,24 @@ class LigtSummary(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class LinearTripletOptions(C.Structure):
+    """theia_linear_triplet_options."""
+    _fields_ = [("max_power_iterations", C.c_int32), ("reserved", C.c_int32), ("eigensolver_threshold", C.c_double)]
+
+
+class LinearTripletSummary(C.Structure):
+    """theia_linear_triplet_summary."""
+    _fields_ = [("num_triplets", C.c_int32), ("triplets_without_ratios", C.c_int32),
+                ("triplets_in_other_components", C.c_int32), ("triplets_used", C.c_int32),
+                ("num_views_in_system", C.c_int32), ("iterations", C.c_int32), ("converged", C.c_int32),
+                ("sign_votes", C.c_int32), ("flipped", C.c_int32), ("reserved", C.c_int32), ("eigenvalue", C.c_double),
+                ("shift", C.c_double), ("setup_ms", C.c_double), ("triplets_ms", C.c_double), ("ratios_ms", C.c_double),
+                ("assemble_ms", C.c_double), ("factor_ms", C.c_double), ("eig_ms", C.c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 # theia_hip.h THEIA_MFAS_LDS_MAX_VIEWS: up to this many views the 1DSfM ordering keeps its per-view state in LDS
 MFAS_LDS_MAX_VIEWS = 5632
 
@@ -242,7 +260,7 @@ EXPORTED_SYMBOLS = [
     "theia_hip_ba_reset_parameters", "theia_hip_estimate_tracks", "theia_hip_ba_set_shard", "theia_hip_ba_snapshot_parameters", "theia_hip_ba_restore_parameters", "theia_hip_ba_set_options", "theia_hip_ba_run", "theia_hip_ba_download",
     "theia_hip_ba_destroy", "theia_hip_ba_covariance", "theia_hip_ba_evaluate", "theia_hip_ba_evaluate_ex", "theia_hip_ba_reduced_system",
     "theia_hip_ba_set_allreduce", "theia_hip_ba_set_inner_global", "theia_hip_ba_plan_info", "theia_hip_rccl_unique_id", "theia_hip_rccl_comm_create",
-    "theia_hip_optimize_relative_position_batch", "theia_hip_rccl_comm_destroy", "theia_hip_rccl_comm_count", "theia_hip_ba_set_rccl", "theia_hip_dense_spd_solve", "theia_hip_dense_spd_solve_multi", "theia_hip_tile_sparse_spd_solve", "theia_hip_tile_sparse_spd_solve_sharded", "theia_hip_robust_rotation_averaging", "theia_hip_linear_rotations", "theia_hip_lud_positions", "theia_hip_ligt_positions", "theia_hip_filter_view_pairs_from_relative_translation", "theia_hip_translation_filter_last_stats", "theia_hip_filter_view_pairs_from_orientation", "theia_ransac_params_default",
+    "theia_hip_optimize_relative_position_batch", "theia_hip_rccl_comm_destroy", "theia_hip_rccl_comm_count", "theia_hip_ba_set_rccl", "theia_hip_dense_spd_solve", "theia_hip_dense_spd_solve_multi", "theia_hip_tile_sparse_spd_solve", "theia_hip_tile_sparse_spd_solve_sharded", "theia_hip_robust_rotation_averaging", "theia_hip_linear_rotations", "theia_hip_lud_positions", "theia_hip_ligt_positions", "theia_hip_linear_triplet_positions", "theia_hip_filter_view_pairs_from_relative_translation", "theia_hip_translation_filter_last_stats", "theia_hip_filter_view_pairs_from_orientation", "theia_ransac_params_default",
     "theia_hip_ransac_estimate_batch", "theia_hip_five_point_relative_pose",
     "theia_hip_pose_from_three_points", "theia_hip_sqpnp", "theia_hip_dls_pnp", "theia_hip_dls_macaulay_terms", "theia_hip_four_point_pose_and_focal_length", "theia_hip_four_point_focal_length_radial_distortion", "theia_hip_four_point_focal_length_radial_distortion_ex", "theia_hip_release_scratch", "theia_hip_guided_knn", "theia_hip_randint_stream", "theia_hip_selftest_wave_primitives",
     "theia_hip_selftest_eig_team", "theia_hip_selftest_svd9_team", "theia_hip_selftest_five_point_pre_team",
@@ -302,6 +320,10 @@ def lib():
     L.theia_hip_ligt_positions.argtypes = [C.c_int32, c_double_p, C.c_int32, c_int32_p, c_int32_p, c_double_p, C.c_int32,
                                            c_int32_p, c_double_p, C.POINTER(LigtOptions), c_double_p, c_uint8_p,
                                            c_int32_p, c_double_p, c_int32_p, C.POINTER(LigtSummary)]
+    L.theia_hip_linear_triplet_positions.argtypes = [
+        C.c_int32, c_double_p, C.c_int32, c_int32_p, c_double_p, c_double_p, C.c_int32, c_int32_p, c_int32_p, c_double_p,
+        C.POINTER(LinearTripletOptions), c_double_p, c_uint8_p, C.c_int32, c_int32_p, c_uint8_p, c_double_p, c_double_p,
+        c_int32_p, C.POINTER(LinearTripletSummary)]
     L.theia_hip_filter_view_pairs_from_relative_translation.argtypes = [
         C.c_int32, C.c_int32, c_int32_p, c_double_p, c_double_p, C.POINTER(TranslationFilterOptions), C.POINTER(RngState),
         c_double_p, c_uint8_p, c_double_p, c_int32_p, c_double_p, c_double_p]

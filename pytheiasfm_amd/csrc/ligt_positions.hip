@@ -23,7 +23,8 @@
 //   k_items       one thread per used track: B, C, D of every constraint in registers; B'B, B'D and D'D of a track all
 //                 land on the (v1, v3) blocks and are summed within the track first -- three items per track, and three
 //                 per constraint (C'C, B'C, C'D)
-//   k_blocks      one thread per non-empty block: adds its items in order, writes the lower triangle
+//   k_blocks      one thread per non-empty block: adds its items in order, writes the lower triangle (this, k_iterate and
+//                 k_sign_vote: smallest_eigenvector.h, shared with linear_positions.hip)
 //   k_shift       mu = kShiftMultiple n eps max diag H on the diagonal and x = b = 1 / sqrt(n) (spectral_shift.h: H's
 //                 smallest eigenvalue is a rounding error of either sign on noise-free data; the shift moves no eigenvector)
 //   dense_cholesky_factor once, then per inverse iteration dense_cholesky_solve_factored and k_iterate: normalise,
@@ -38,6 +39,7 @@
 #include "ba_kernels.h"
 #include "wave_reduce.h"
 #include "spectral_shift.h"
+#include "smallest_eigenvector.h"
 #include "device_util.h"
 
 #include <algorithm>
@@ -55,20 +57,6 @@ constexpr int kChunk = 4;                        // inverse iterations enqueued 
 // mu = kShiftMultiple * n * eps * max diag H (DESIGN.md 3.6f has the rule and the scenes it was chosen on)
 constexpr double kShiftMultiple = 1.0;
 
-struct LigtState {
-  int done, converged, iterations, pad;
-  double diff, eigenvalue, shift, max_diag;
-};
-
-__global__ __launch_bounds__(kThreads) void k_rotations(int n, const double* __restrict__ aa, double* __restrict__ R) {
-  const int v = blockIdx.x * kThreads + threadIdx.x;
-  if (v >= n) return;
-  double r[9];
-  rsc::angle_axis_to_rot(aa + 3 * (size_t)v, r);
-#pragma unroll
-  for (int k = 0; k < 9; ++k) R[9 * (size_t)v + k] = r[k];
-}
-
 __global__ __launch_bounds__(kThreads) void k_rays(int num_obs, const int* __restrict__ obs_view,
                                                    const double* __restrict__ feat, const double* __restrict__ R,
                                                    double* __restrict__ ray) {
@@ -78,12 +66,6 @@ __global__ __launch_bounds__(kThreads) void k_rays(int num_obs, const int* __res
   const double x = feat[2 * (size_t)o], y = feat[2 * (size_t)o + 1];
 #pragma unroll
   for (int c = 0; c < 3; ++c) ray[3 * (size_t)o + c] = (r[c] * x + r[3 + c] * y) + r[6 + c];
-}
-
-__device__ __forceinline__ void cross3(const double* a, const double* b, double* c) {
-  c[0] = a[1] * b[2] - a[2] * b[1];
-  c[1] = a[2] * b[0] - a[0] * b[2];
-  c[2] = a[0] * b[1] - a[1] * b[0];
 }
 
 // first pair index of row i among the pairs (i, j > i) of L observations
@@ -143,19 +125,6 @@ __global__ __launch_bounds__(kThreads) void k_base_pairs(int num_tracks, const i
       base[t] = make_int2((int)i, (int)(i + 1 + (p - pair_row_start(i, L))));
     }
   }
-}
-
-// out = X' Y (3 x 3, row-major)
-__device__ __forceinline__ void atb(const double* X, const double* Y, double* out) {
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) out[3 * r + c] = (X[r] * Y[c] + X[3 + r] * Y[3 + c]) + X[6 + r] * Y[6 + c];
-}
-
-__device__ __forceinline__ void store9(double* __restrict__ dst, const double* v) {
-#pragma unroll
-  for (int k = 0; k < 9; ++k) dst[k] = v[k];
 }
 
 // One thread per used track.  Items of track t from item_base[t]: [0] sum B'B, [1] sum B'D, [2] sum D'D, then per
@@ -231,112 +200,6 @@ __global__ __launch_bounds__(kThreads) void k_items(int num_tracks, const int* _
   store9(head, S11); store9(head + 9, S13); store9(head + 18, S33);
 }
 
-// One thread per non-empty block of H's lower triangle: its items in (track, observation) order.  seg_item = item
-// index * 2 + (1: the item is added transposed).  A diagonal block writes its own lower triangle only.
-__global__ __launch_bounds__(kThreads) void k_blocks(int num_blocks, const int2* __restrict__ block_rc,
-                                                     const long long* __restrict__ seg_off, const int* __restrict__ seg_item,
-                                                     const double* __restrict__ items, int lda, double* __restrict__ H) {
-  const int b = blockIdx.x * kThreads + threadIdx.x;
-  if (b >= num_blocks) return;
-  double acc[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (long long k = seg_off[b]; k < seg_off[b + 1]; ++k) {
-    const int it = seg_item[k];
-    const double* v = items + 9 * (size_t)(it >> 1);
-    if (it & 1) {
-#pragma unroll
-      for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) acc[3 * r + c] += v[3 * c + r];
-    } else {
-#pragma unroll
-      for (int q = 0; q < 9; ++q) acc[q] += v[q];
-    }
-  }
-  const int2 rc = block_rc[b];
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-      if (rc.x != rc.y || c <= r) H[(size_t)(3 * rc.x + r) * lda + 3 * rc.y + c] = acc[3 * r + c];
-}
-
-// system_out: both triangles of the n x n system from the lower triangle (before the shift)
-__global__ __launch_bounds__(kThreads) void k_full_system(int n, int lda, const double* __restrict__ H,
-                                                          double* __restrict__ full) {
-  const size_t k = (size_t)blockIdx.x * kThreads + threadIdx.x;
-  if (k >= (size_t)n * n) return;
-  const int r = (int)(k / n), c = (int)(k % n);
-  full[k] = r >= c ? H[(size_t)r * lda + c] : H[(size_t)c * lda + r];
-}
-
-// One workgroup, after y = (H + mu I)^-1 x: x_new = y / |y|, the step |x_new - s x|_2 with s = sign(x_new . x), the
-// Rayleigh quotient of y as the eigenvalue estimate, the iteration count and the stop flag.  b = x_new for the next solve.
-__global__ __launch_bounds__(kThreads) void k_iterate(int n, const double* __restrict__ y, double* __restrict__ x,
-                                                      double* __restrict__ b, double threshold,
-                                                      LigtState* __restrict__ st) {
-  __shared__ double red[kThreads];
-  if (st->done) return;
-  double yy = 0.0, yx = 0.0;
-  for (int k = threadIdx.x; k < n; k += kThreads) { yy += y[k] * y[k]; yx += y[k] * x[k]; }
-  const double syy = block_sum<kThreads>(yy, red), syx = block_sum<kThreads>(yx, red);
-  __shared__ double bc[2];
-  if (threadIdx.x == 0) { bc[0] = sqrt(syy); bc[1] = syx; }
-  __syncthreads();
-  const double norm = bc[0], dot = bc[1];
-  if (!(norm > 0.0) || !isfinite(norm)) {   // a breakdown of the solve: stop, not converged, x stays
-    if (threadIdx.x == 0) { st->iterations += 1; st->done = 1; st->converged = 0; st->diff = norm; }
-    return;
-  }
-  const double s = dot < 0.0 ? -1.0 : 1.0;
-  double dd = 0.0;
-  for (int k = threadIdx.x; k < n; k += kThreads) {
-    const double xn = y[k] / norm, d = xn - s * x[k];
-    dd += d * d;
-    x[k] = xn; b[k] = xn;
-  }
-  const double sdd = block_sum<kThreads>(dd, red);
-  if (threadIdx.x == 0) {
-    const double diff = sqrt(sdd);
-    st->iterations += 1;
-    st->diff = diff;
-    st->eigenvalue = dot / syy - st->shift;
-    if (diff <= threshold) { st->done = 1; st->converged = 1; }
-  }
-}
-
-// VectorsAreSameDirection (:130-139) per view pair whose two views are in the system: +1 when
-// (R_first (c_second - c_first) / |.|) . position_2 > 0, else -1.  idx: -1 held (the origin), -2 not in the system.
-__global__ __launch_bounds__(kThreads) void k_sign_vote(int E, const int2* __restrict__ edges, const int* __restrict__ idx,
-                                                        const double* __restrict__ x, const double* __restrict__ R,
-                                                        const double* __restrict__ rel, int* __restrict__ votes) {
-  __shared__ int red[kThreads];
-  const int e = blockIdx.x * kThreads + threadIdx.x;
-  int vote = 0;
-  if (e < E) {
-    const int2 ij = edges[e];
-    const int a = idx[ij.x], c = idx[ij.y];
-    if (a != -2 && c != -2) {
-      double d[3];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) d[k] = (c >= 0 ? x[3 * (size_t)c + k] : 0.0) - (a >= 0 ? x[3 * (size_t)a + k] : 0.0);
-      const double nrm = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
-      if (nrm > 0.0) { d[0] /= nrm; d[1] /= nrm; d[2] /= nrm; }
-      const double* r = R + 9 * (size_t)ij.x;
-      double dot = 0.0;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) dot += ((r[3 * k] * d[0] + r[3 * k + 1] * d[1]) + r[3 * k + 2] * d[2]) * rel[3 * (size_t)e + k];
-      vote = dot > 0.0 ? 1 : -1;
-    }
-  }
-  red[threadIdx.x] = vote;
-  __syncthreads();
-  for (int s = kThreads / 2; s > 0; s >>= 1) {
-    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0 && red[0] != 0) atomicAdd(votes, red[0]);
-}
-
 }  // namespace
 }  // namespace thip
 
@@ -397,7 +260,7 @@ extern "C" int theia_hip_ligt_positions(int32_t num_views, const double* orienta
     return rc;
 
   // ---- set-up: rotations, rays, base pairs, plan
-  k_rotations<<<grid_of(n, kThreads), kThreads, 0, st>>>(n, d_aa.p, d_R.p);
+  k_rotations<kThreads><<<grid_of(n, kThreads), kThreads, 0, st>>>(n, d_aa.p, d_R.p);
   k_rays<<<grid_of(num_obs, kThreads), kThreads, 0, st>>>(num_obs, d_obs_view.p, d_feat.p, d_R.p, d_ray.p);
   k_base_pairs<<<grid_of(T, kTracksPerBlock), kThreads, 0, st>>>(T, d_off.p, d_ray.p, d_base.p);
   HIP_TRY(hipGetLastError());
@@ -443,11 +306,9 @@ extern "C" int theia_hip_ligt_positions(int32_t num_views, const double* orienta
     return rc;
 
   // the segment list: per block (row >= col, free views) of the lower triangle its items, by a stable counting sort
-  const size_t tri = (size_t)mf * (mf + 1) / 2;
-  std::vector<long long> seg_start(tri + 1, 0);
-  auto block_of = [](int a, int b) { return a >= b ? (size_t)a * (a + 1) / 2 + b : (size_t)b * (b + 1) / 2 + a; };
   // an item (va, vb) holds X' Y with X on va and Y on vb: it lands on block (idx va, idx vb), transposed when that lies above
-  auto visit = [&](auto&& emit) {
+  BlockSegments seg;
+  build_block_segments(mf, [&](auto&& emit) {
     for (int t = 0; t < T; ++t) {
       if (item_base[t] < 0) continue;
       const int o0 = track_offsets[t], L = track_offsets[t + 1] - o0;
@@ -463,30 +324,17 @@ extern "C" int theia_hip_ligt_positions(int32_t num_views, const double* orienta
         it += 3;
       }
     }
-  };
-  visit([&](int a, int b, long long) { if (a >= 0 && b >= 0) seg_start[block_of(a, b) + 1] += 1; });
-  for (size_t k = 0; k < tri; ++k) seg_start[k + 1] += seg_start[k];
-  std::vector<int> seg_item((size_t)std::max<long long>(1, seg_start[tri]));
-  {
-    std::vector<long long> fill(seg_start.begin(), seg_start.end() - 1);
-    visit([&](int a, int b, long long it) {
-      if (a >= 0 && b >= 0) seg_item[(size_t)fill[block_of(a, b)]++] = (int)(2 * it + (a < b ? 1 : 0));
-    });
-  }
-  std::vector<int2> block_rc;
-  std::vector<long long> seg_off(1, 0);
-  for (int a = 0; a < mf; ++a)
-    for (int b = 0; b <= a; ++b) {
-      const size_t k = block_of(a, b);
-      if (seg_start[k + 1] > seg_start[k]) { block_rc.push_back(make_int2(a, b)); seg_off.push_back(seg_start[k + 1]); }
-    }
+  }, &seg);
+  const std::vector<int2>& block_rc = seg.block_rc;
+  const std::vector<long long>& seg_off = seg.seg_off;
+  const std::vector<int>& seg_item = seg.seg_item;
   const int num_blocks = (int)block_rc.size();
 
   DevBuf<double> d_items, d_x, d_b, d_y, d_T, d_rel;
   DevBuf<long long> d_item_base, d_seg_off;
   DevBuf<int> d_seg_item, d_idx, d_votes;
   DevBuf<int2> d_block_rc, d_edges;
-  DevBuf<LigtState> d_st;
+  DevBuf<InverseIterationState> d_st;
   if ((rc = d_items.alloc(9 * (size_t)num_items)) ||
       (rc = d_item_base.up(item_base.data(), T)) || (rc = d_seg_off.up(seg_off.data(), seg_off.size())) ||
       (rc = d_seg_item.up(seg_item.data(), seg_item.size())) || (rc = d_block_rc.up(block_rc.data(), block_rc.size())) ||
@@ -497,7 +345,7 @@ extern "C" int theia_hip_ligt_positions(int32_t num_views, const double* orienta
   HIP_TRY(hipMemsetAsync(d_H.p, 0, sizeof(double) * dense, st));
   HIP_TRY(hipMemsetAsync(d_flag.p, 0, sizeof(double), st));
   HIP_TRY(hipMemsetAsync(d_votes.p, 0, sizeof(int), st));
-  HIP_TRY(hipMemsetAsync(d_st.p, 0, sizeof(LigtState), st));
+  HIP_TRY(hipMemsetAsync(d_st.p, 0, sizeof(InverseIterationState), st));
   HIP_TRY(hipStreamSynchronize(st));
   sm.setup_ms = ms_since(t_start);
 
@@ -505,10 +353,10 @@ extern "C" int theia_hip_ligt_positions(int32_t num_views, const double* orienta
   const auto t_assemble = std::chrono::steady_clock::now();
   k_items<<<grid_of(T, kThreads), kThreads, 0, st>>>(T, d_off.p, d_obs_view.p, d_feat.p, d_R.p, d_ray.p, d_base.p,
                                                     d_item_base.p, d_items.p);
-  k_blocks<<<grid_of(num_blocks, kThreads), kThreads, 0, st>>>(num_blocks, d_block_rc.p, d_seg_off.p, d_seg_item.p,
+  k_blocks<kThreads><<<grid_of(num_blocks, kThreads), kThreads, 0, st>>>(num_blocks, d_block_rc.p, d_seg_off.p, d_seg_item.p,
                                                               d_items.p, lda, d_H.p);
   if (system_out)
-    k_full_system<<<grid_of((size_t)n3 * n3, kThreads), kThreads, 0, st>>>(n3, lda, d_H.p, d_full.p);
+    k_full_system<kThreads><<<grid_of((size_t)n3 * n3, kThreads), kThreads, 0, st>>>(n3, lda, d_H.p, d_full.p);
   k_shift<kThreads><<<1, kThreads, 0, st>>>(n3, lda, d_H.p, kShiftMultiple, d_x.p, d_b.p, &d_st.p->shift, &d_st.p->max_diag);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(st));
@@ -521,9 +369,9 @@ extern "C" int theia_hip_ligt_positions(int32_t num_views, const double* orienta
   double flag = 0.0;
   HIP_TRY(hipMemcpy(&flag, d_flag.p, sizeof(double), hipMemcpyDeviceToHost));
   sm.factor_ms = ms_since(t_factor);
-  LigtState hs{};
+  InverseIterationState hs{};
   if (flag != 0.0) {
-    HIP_TRY(hipMemcpy(&hs, d_st.p, sizeof(LigtState), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&hs, d_st.p, sizeof(InverseIterationState), hipMemcpyDeviceToHost));
     sm.shift = hs.shift;
     *summary = sm;
     return set_error(THEIA_HIP_ERR_INTERNAL, "the Cholesky factorisation of H + mu I failed (mu = %g)", hs.shift);
@@ -536,16 +384,16 @@ extern "C" int theia_hip_ligt_positions(int32_t num_views, const double* orienta
     const int chunk = std::min(kChunk, o.max_power_iterations - enqueued);
     for (int c = 0; c < chunk; ++c) {
       dense_cholesky_solve_factored(n3, d_H.p, lda, d_work.p, 1, d_b.p, n3, d_T.p, d_y.p, n3, st, done);
-      k_iterate<<<1, kThreads, 0, st>>>(n3, d_y.p, d_x.p, d_b.p, o.eigensolver_threshold, d_st.p);
+      k_iterate<kThreads><<<1, kThreads, 0, st>>>(n3, d_y.p, d_x.p, d_b.p, o.eigensolver_threshold, d_st.p);
     }
     enqueued += chunk;
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(&hs, d_st.p, sizeof(LigtState), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&hs, d_st.p, sizeof(InverseIterationState), hipMemcpyDeviceToHost));
     if (hs.done) break;
   }
   // ---- sign vote and scatter
   if (E > 0) {
-    k_sign_vote<<<grid_of(E, kThreads), kThreads, 0, st>>>(E, d_edges.p, d_idx.p, d_x.p, d_R.p, d_rel.p, d_votes.p);
+    k_sign_vote<kThreads><<<grid_of(E, kThreads), kThreads, 0, st>>>(E, d_edges.p, d_idx.p, d_x.p, d_R.p, d_rel.p, d_votes.p);
     HIP_TRY(hipGetLastError());
   }
   std::vector<double> x(n3);

@@ -1,5 +1,5 @@
-// spectral_shift.h -- the diagonal shift of the two stages that take eigenvectors of the smallest eigenvalues by inverse
-// iteration over one dense Cholesky (ligt_positions.hip, linear_rotations.hip).  On noise-free input those eigenvalues
+// spectral_shift.h -- the diagonal shift of the stages that take eigenvectors of the smallest eigenvalues by inverse
+// iteration over one dense Cholesky (ligt_positions.hip, linear_positions.hip, linear_rotations.hip).  On noise-free input those eigenvalues
 // are rounding errors of either sign, so the matrix itself may have no Cholesky factor; H + mu I with
 //   mu = multiple n eps max diag H
 // has one, and the shift moves no eigenvector (DESIGN.md 3.6f has the rule and the scenes it was chosen on).

@@ -11,7 +11,9 @@ global_pose_estimation/linear_rotation_estimator.{h,cc}), runs through theia_hip
 (csrc/linear_rotations.hip).  The positions run
 through theia_hip_lud_positions (csrc/lud_positions.hip), or, from the tracks' features and without the pairs' relative
 translations, through theia_hip_ligt_positions (pytheia.sfm.LiGTPositionEstimator, sfm.cc:1728-1747 ->
-global_pose_estimation/LiGT_position_estimator.{h,cc}; csrc/ligt_positions.hip).
+global_pose_estimation/LiGT_position_estimator.{h,cc}; csrc/ligt_positions.hip), or, from the pairs' relative poses and
+the features together, through theia_hip_linear_triplet_positions (pytheia.sfm.LinearPositionEstimator ->
+global_pose_estimation/linear_position_estimator.{h,cc}; csrc/linear_positions.hip).
 
 Between them sit the two view-graph filters (sfm/filter_view_pairs_from_orientation.{h,cc} after the rotations,
 sfm/filter_view_pairs_from_relative_translation.{h,cc}, the 1DSfM test, before the positions): csrc/view_pair_filters.hip
@@ -381,18 +383,13 @@ def _pinhole_normalized(intrinsics, uv):
     return np.column_stack([ux, uy])
 
 
-class LiGTPositionEstimator:
-    """LiGTPositionEstimator(options, reconstruction) with EstimatePositions(view_pairs, orientations) -> dict, as
-    pyTheia binds it.  reconstruction: the array-backed sfm.Reconstruction (obs_view, obs_track and obs_uv are read; ids
-    are dense indices); view_pairs: {(id1, id2): TwoViewInfo}, whose position_2 only votes on the sign; orientations:
-    {view_id: angle-axis}.
-
-    The tracks are taken in increasing id and a track's observations in the order the reconstruction lists them
-    (DESIGN.md 3.6f: the reference walks hash containers).  normalized_features [N][2]: the observations'
-    hnormalized(PixelToNormalizedCoordinates(pixel)); without it the pixels of pinhole groups are un-projected here and any
-    other model raises, as ransac.Camera.pixel_to_normalized does.  An observation of a view without an orientation
-    raises (the reference's orientations_.at() throws).  The dict holds the views of the system: those of the tracks
-    that were used."""
+class _TrackPositionEstimator:
+    """What the position estimators that read the tracks share (LiGTPositionEstimator, LinearPositionEstimator): the
+    reconstruction's observations as the array calls take them.  The tracks are taken in increasing id and a track's
+    observations in the order the reconstruction lists them (the reference walks hash containers).
+    normalized_features [N][2]: the observations' hnormalized(PixelToNormalizedCoordinates(pixel)); without it the pixels
+    of pinhole groups are un-projected here and any other model raises, as ransac.Camera.pixel_to_normalized does.  An
+    observation of a view without an orientation raises (the reference's lookups throw or die)."""
 
     def __init__(self, options, reconstruction, normalized_features=None):
         if not options.num_threads > 0:   # CHECK_GT(options.num_threads, 0)
@@ -416,7 +413,9 @@ class LiGTPositionEstimator:
         return _pinhole_normalized(np.asarray(r.group_intrinsics, dtype=np.float64)[groups],
                                    np.asarray(r.obs_uv, dtype=np.float64).reshape(-1, 2))
 
-    def EstimatePositions(self, view_pairs, orientations):
+    def _track_arrays(self, orientations):
+        """(views: the ids with an orientation, sorted; pos: id -> index; orientations [n][3]; track_offsets; obs_view as
+        indices; obs_feature), the last three in track order."""
         r = self.reconstruction
         ov = np.asarray(r.obs_view, dtype=np.int64)
         ot = np.asarray(r.obs_track, dtype=np.int64)
@@ -431,11 +430,133 @@ class LiGTPositionEstimator:
         order = np.argsort(ot, kind="stable")   # tracks in increasing id, observations in the reconstruction's order
         ntracks = r.NumTracks()
         offsets = np.concatenate([[0], np.cumsum(np.bincount(ot, minlength=ntracks))]).astype(np.int32)
+        aa = np.array([np.asarray(orientations[v], dtype=np.float64).reshape(3) for v in views]).reshape(-1, 3)
+        return views, pos, aa, offsets, lut[ov[order]], feats[order]
+
+
+class LiGTPositionEstimator(_TrackPositionEstimator):
+    """LiGTPositionEstimator(options, reconstruction) with EstimatePositions(view_pairs, orientations) -> dict, as
+    pyTheia binds it.  reconstruction: the array-backed sfm.Reconstruction (obs_view, obs_track and obs_uv are read; ids
+    are dense indices); view_pairs: {(id1, id2): TwoViewInfo}, whose position_2 only votes on the sign; orientations:
+    {view_id: angle-axis}.
+
+    The tracks are taken in increasing id and a track's observations in the order the reconstruction lists them
+    (DESIGN.md 3.6f: the reference walks hash containers).  normalized_features [N][2]: the observations'
+    hnormalized(PixelToNormalizedCoordinates(pixel)); without it the pixels of pinhole groups are un-projected here and any
+    other model raises, as ransac.Camera.pixel_to_normalized does.  An observation of a view without an orientation
+    raises (the reference's orientations_.at() throws).  The dict holds the views of the system: those of the tracks
+    that were used."""
+
+    def EstimatePositions(self, view_pairs, orientations):
+        views, pos, aa, offsets, ov, feats = self._track_arrays(orientations)
         keys = [k for k in view_pairs if int(k[0]) in pos and int(k[1]) in pos]
         edges = np.array([(pos[int(a)], pos[int(b)]) for a, b in keys], dtype=np.int32).reshape(-1, 2)
         rel = np.array([np.asarray(view_pairs[k].position_2, dtype=np.float64).reshape(3) for k in keys]).reshape(-1, 3)
-        aa = np.array([np.asarray(orientations[v], dtype=np.float64).reshape(3) for v in views]).reshape(-1, 3)
-        rc, p, est, s, _ = ligt_positions(aa, offsets, lut[ov[order]], feats[order], edges, rel, self.options)
+        rc, p, est, s, _ = ligt_positions(aa, offsets, ov, feats, edges, rel, self.options)
+        capi.check(rc)
+        self.last_summary = s
+        return {v: p[k].copy() for k, v in enumerate(views) if est[k]}
+
+
+class LinearPositionEstimatorOptions:  # linear_position_estimator.h
+    def __init__(self):
+        self.num_threads = 1              # held and ignored (checked > 0): the triangles are wavefronts of the launches
+        self.max_power_iterations = 1000  # the reference declares these two and reads neither; here they stop the
+        self.eigensolver_threshold = 1e-8  # inverse iteration
+
+    def to_c(self):
+        o = capi.LinearTripletOptions()
+        o.max_power_iterations = int(self.max_power_iterations)
+        o.eigensolver_threshold = float(self.eigensolver_threshold)
+        return o
+
+
+LINEAR_TRIPLET_OUTPUTS = ("triplets", "triplet_state", "baselines", "system", "system_index")
+
+
+def linear_triplet_positions(orientations, edges, relative_rotations, relative_translations, track_offsets, obs_view,
+                             obs_feature, options=None, positions_out=None, want=(), triplet_capacity=None):
+    """theia_hip_linear_triplet_positions on arrays: orientations [n][3] angle-axis, edges [E][2] view indices with first <
+    second, relative_rotations / relative_translations [E][3] (TwoViewInfo::rotation_2 / position_2), track t =
+    observations track_offsets[t] .. track_offsets[t + 1] - 1 of obs_view [N] / obs_feature [N][2] (normalised).  want:
+    names of the optional outputs to fetch, out of LINEAR_TRIPLET_OUTPUTS; the three per-triangle ones hold the first
+    triplet_capacity triangles (default: room for every triangle the view pairs could form, E (n - 2) / 3 at most, capped
+    at 2^20).  Returns (return code, positions [n][3], estimated [n] bool, LinearTripletSummary, dict of the outputs asked
+    for); a view outside the system keeps its positions_out row (zeros without positions_out); on a refusal nothing is
+    written and the dict is empty."""
+    o = (options or LinearPositionEstimatorOptions()).to_c()
+    aa = np.ascontiguousarray(np.asarray(orientations, dtype=np.float64).reshape(-1, 3))
+    e, rr = _pair_arrays(edges, relative_rotations, "relative rotation")
+    _, rt = _pair_arrays(edges, relative_translations, "relative translation")
+    off = np.ascontiguousarray(np.asarray(track_offsets, dtype=np.int32).reshape(-1))
+    ov = np.ascontiguousarray(np.asarray(obs_view, dtype=np.int32).reshape(-1))
+    of = np.ascontiguousarray(np.asarray(obs_feature, dtype=np.float64).reshape(-1, 2))
+    if off.shape[0] < 1:
+        raise ValueError("track_offsets needs num_tracks + 1 entries")
+    if ov.shape[0] != of.shape[0] or (off.shape[0] > 1 and int(off.max()) > ov.shape[0]):
+        raise ValueError("one view and one feature per observation, and offsets within them")
+    unknown = set(want) - set(LINEAR_TRIPLET_OUTPUTS)
+    if unknown:
+        raise ValueError(f"unknown outputs {sorted(unknown)}")
+    n, E, T = aa.shape[0], e.shape[0], off.shape[0] - 1
+    out = np.zeros((n, 3)) if positions_out is None else positions_out
+    if out.shape != (n, 3) or out.dtype != np.float64 or not out.flags["C_CONTIGUOUS"]:
+        raise ValueError("positions_out must be a C-contiguous float64 [n][3] array")
+    est = np.zeros(n, dtype=np.uint8)
+    per_triangle = {"triplets", "triplet_state", "baselines"} & set(want)
+    cap = 0
+    if per_triangle:
+        cap = min(E * max(0, n - 2) // 3, 1 << 20) if triplet_capacity is None else int(triplet_capacity)
+    bufs = {}
+    if "triplets" in want:
+        bufs["triplets"] = np.full((cap, 3), -1, dtype=np.int32)
+    if "triplet_state" in want:
+        bufs["triplet_state"] = np.full(cap, 255, dtype=np.uint8)
+    if "baselines" in want:
+        bufs["baselines"] = np.zeros((cap, 3))
+    if "system" in want:   # sized for every view in the system; cut to [3 (m - 1)]^2 below
+        bufs["system"] = np.zeros(max(1, 3 * (n - 1)) ** 2)
+    if "system_index" in want:
+        bufs["system_index"] = np.full(n, -2, dtype=np.int32)
+    s = capi.LinearTripletSummary()
+    rc = capi.lib().theia_hip_linear_triplet_positions(
+        n, capi.ptr(aa, C.c_double), E, capi.ptr(e, C.c_int32), capi.ptr(rr, C.c_double), capi.ptr(rt, C.c_double),
+        T, capi.ptr(off, C.c_int32), capi.ptr(ov, C.c_int32), capi.ptr(of, C.c_double), C.byref(o),
+        capi.ptr(out, C.c_double), capi.ptr(est, C.c_uint8), cap, capi.ptr(bufs.get("triplets"), C.c_int32),
+        capi.ptr(bufs.get("triplet_state"), C.c_uint8), capi.ptr(bufs.get("baselines"), C.c_double),
+        capi.ptr(bufs.get("system"), C.c_double), capi.ptr(bufs.get("system_index"), C.c_int32), C.byref(s))
+    if rc == 0:
+        if "system" in bufs:
+            k = 3 * (s.num_views_in_system - 1)
+            bufs["system"] = bufs["system"][:k * k].reshape(k, k).copy()
+        head = min(cap, s.num_triplets)
+        for name in per_triangle:
+            bufs[name] = bufs[name][:head].copy()
+    return rc, out, est.astype(bool), s, (bufs if rc == 0 else {})
+
+
+class LinearPositionEstimator(_TrackPositionEstimator):
+    """LinearPositionEstimator(options, reconstruction) with EstimatePositions(view_pairs, orientations) -> dict, as
+    pyTheia binds it.  reconstruction: the array-backed sfm.Reconstruction (obs_view, obs_track and obs_uv are read; ids
+    are dense indices); view_pairs: {(id1, id2): TwoViewInfo} keyed id1 < id2, whose rotation_2 and position_2 are read;
+    orientations: {view_id: angle-axis}.  Tracks, ids and un-projection as LiGTPositionEstimator takes them.  A pair or
+    an observation naming a view without an orientation raises (the reference's FindOrDie).  The dict holds the views of
+    the system: those of the largest component of triangles."""
+
+    def EstimatePositions(self, view_pairs, orientations):
+        views, pos, aa, offsets, ov, feats = self._track_arrays(orientations)
+        for a, b in view_pairs:
+            for v in (a, b):
+                if int(v) not in pos:
+                    raise capi.TheiaHipError(capi.THEIA_HIP_ERR_INVALID_ARGUMENT,
+                                             f"view pair ({a}, {b}) names view {v}, which has no orientation")
+            if not int(a) < int(b):
+                raise capi.TheiaHipError(capi.THEIA_HIP_ERR_INVALID_ARGUMENT, f"view pair ({a}, {b}) is not keyed id1 < id2")
+        keys = list(view_pairs)
+        edges = np.array([(pos[int(a)], pos[int(b)]) for a, b in keys], dtype=np.int32).reshape(-1, 2)
+        rot = np.array([np.asarray(view_pairs[k].rotation_2, dtype=np.float64).reshape(3) for k in keys]).reshape(-1, 3)
+        rel = np.array([np.asarray(view_pairs[k].position_2, dtype=np.float64).reshape(3) for k in keys]).reshape(-1, 3)
+        rc, p, est, s, _ = linear_triplet_positions(aa, edges, rot, rel, offsets, ov, feats, self.options)
         capi.check(rc)
         self.last_summary = s
         return {v: p[k].copy() for k, v in enumerate(views) if est[k]}

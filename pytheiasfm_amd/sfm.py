@@ -25,6 +25,7 @@ from .global_pose import (GlobalRotationEstimatorType, RobustRotationEstimator, 
                           LinearRotationEstimatorOptions, GlobalPositionEstimatorType,
                           LeastUnsquaredDeviationPositionEstimator, LeastUnsquaredDeviationPositionEstimatorOptions,
                           LiGTPositionEstimator, LiGTPositionEstimatorOptions,
+                          LinearPositionEstimator, LinearPositionEstimatorOptions,
                           FilterViewPairsFromOrientation, FilterViewPairsFromRelativeTranslation,
                           FilterViewPairsFromRelativeTranslationOptions)
 

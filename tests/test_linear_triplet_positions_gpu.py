@@ -1,0 +1,207 @@
+"""GPU: theia_hip_linear_triplet_positions (csrc/linear_positions.hip) against the numpy restatement
+(tests/linear_triplet_ref.py) on the scenes of tests/linear_triplet_scenes.py.
+
+Bounds (DESIGN.md 3.6h has the derivations):
+  baselines  an order statistic moves by no more than the largest perturbation of its elements, so per triangle and
+             median the bound is the largest per-track bound of its valid tracks.  A ratio of two midpoint depths: a
+             midpoint p solves A p = b with A's eigenvalues 2, 1 + c, 1 - c (c = d0 . d1), entries of A within [-2, 2]
+             and of b within |position_2|, so |dp| <= 2 / (1 - c^2) (|position_2| + 2 |p|) per unit rounding, a depth
+             has the relative error |dp| / depth and a ratio the sum of its two depths'; 64 eps per unit covers both
+             sides' roundings (linear_triplet_ref.RATIO_EPS).
+  system     |H_gpu - H_ref| <= sum over the triangles of (64 eps + 2 (b1 + b2)) |contribution|, entry by entry: the
+             magnitudes are H assembled from the operands' magnitudes, and the s ratios of a triangle carry its two
+             medians' relative bounds b1, b2 (s120 = b2 / b1 both), a product of two constraint blocks twice that.
+  recovery   Davis-Kahan with the factorisation's 8 n eps lambda_max and the system bound's norm over the gap.
+  noisy      against eigh of the device's own system: threshold / (1 - rho), rho = lambda_1 / lambda_2 the contraction
+             of a step (|x_k - x_(k-1)| >= (1 - rho) e_(k-1) >= (1 - rho) e_k), plus the factorisation's term.
+The iteration count is within one of the restatement's on every scene (two roundings of one system can stop one step
+apart); the other integers of the summary are the restatement's exactly, the vote up to the sign of the iterate, which
+the test derives from the restated positions (the iteration starts at 1 / sqrt(n))."""
+import types
+
+import numpy as np
+import pytest
+
+from pytheiasfm_amd import global_pose, sfm
+from tests import linear_triplet_ref as ref
+from tests import linear_triplet_scenes as ls
+
+pytestmark = pytest.mark.gpu
+
+EPS = np.finfo(float).eps
+WANT = global_pose.LINEAR_TRIPLET_OUTPUTS
+_runs = {}
+
+
+def call(s, **kw):
+    return global_pose.linear_triplet_positions(s["orientations"], s["edges"], s["rot"], s["rel"], s["track_offsets"],
+                                                s["obs_view"], s["obs_feature"], **kw)
+
+
+def run(name):
+    """One library call per scene, shared by the tests (not to be modified)."""
+    if name not in _runs:
+        s, _ = ls.scene(name)
+        rc, p, est, summ, extra = call(s, positions_out=np.full((s["num_views"], 3), 7.0), want=WANT)
+        assert rc == 0, rc
+        _runs[name] = (p, est, summ, extra)
+    return _runs[name]
+
+
+@pytest.mark.parametrize("name", list(ls.SCENES))
+def test_triangles_states_and_counts(name):
+    s, r = ls.scene(name)
+    p, est, summ, extra = run(name)
+    assert np.array_equal(extra["triplets"], r["triplets"])
+    assert np.array_equal(extra["triplet_state"], r["state"])
+    assert np.array_equal(extra["system_index"], r["index"])
+    assert np.array_equal(est, r["estimated"])
+    st = np.bincount(r["state"], minlength=3)
+    assert (summ.num_triplets, summ.triplets_used, summ.triplets_without_ratios, summ.triplets_in_other_components) == \
+        (len(r["state"]), st[0], st[1], st[2])
+    assert summ.num_views_in_system == r["num_views_in_system"]
+    assert summ.converged == 1
+    it, _, _ = ref.inverse_iteration(r["H"])
+    assert abs(summ.iterations - it) <= 1
+    # the vote: the restatement's total up to the sign of eigh's vector; the iterate's side is that of its component sum
+    assert abs(summ.sign_votes) == abs(r["votes"]) and summ.sign_votes != 0
+    assert summ.flipped == int(summ.sign_votes < 0)
+    x = r["positions"][r["index"] >= 0].ravel()
+    side = x.sum() / np.linalg.norm(x)
+    if abs(side) > 0.1:
+        assert summ.flipped == int(side < 0.0)
+    assert float((p[est] * r["positions"][est]).sum()) > 0.0
+
+
+@pytest.mark.parametrize("name", list(ls.SCENES))
+def test_baselines(name):
+    _, r = ls.scene(name)
+    _, _, _, extra = run(name)
+    b = extra["baselines"]
+    none = r["state"] == 1
+    assert np.all(b[none] == 0.0) and np.all(b[~none, 0] == 1.0)
+    rel = np.abs(b[~none, 1:] - r["baselines"][~none, 1:]) / r["baselines"][~none, 1:]
+    bound = r["baseline_bound"][~none]
+    print(f"{name}: max relative baseline difference {rel.max():.2e} ({(rel / EPS).max():.1f} eps), "
+          f"largest share of its bound {(rel / bound).max():.2e}")
+    assert np.all(rel <= bound)
+
+
+@pytest.mark.parametrize("name", list(ls.SCENES))
+def test_system(name):
+    _, r = ls.scene(name)
+    _, _, _, extra = run(name)
+    H = extra["system"]
+    assert H.shape == r["H"].shape
+    assert np.array_equal(H, H.T)                       # symmetric to the bit
+    diff = np.abs(H - r["H"])
+    print(f"{name}: max |H_gpu - H_ref| / (eps sum |contribution|) = "
+          f"{(diff / (EPS * np.maximum(r['abs_sum'], np.finfo(float).tiny))).max():.2f}, "
+          f"largest share of its bound {(diff / np.maximum(r['h_bound'], np.finfo(float).tiny)).max():.2e}")
+    assert np.all(diff <= r["h_bound"])
+
+
+@pytest.mark.parametrize("name", ls.NOISE_FREE)
+def test_noise_free_recovery(name):
+    s, r = ls.scene(name)
+    p, est, summ, _ = run(name)
+    scale, err = ls.fit(s, p, est, r["index"])
+    bound = ls.recovery_bound(r)
+    print(f"{name}: scale {scale:.3e}, relative error {err:.2e}, bound {bound:.2e}, iterations {summ.iterations}, "
+          f"eigenvalue {summ.eigenvalue:.3e}, shift {summ.shift:.3e}")
+    assert summ.converged == 1 and 1 <= summ.iterations <= 1000
+    assert scale > 0.0
+    assert err <= bound
+    held = int(np.nonzero(r["index"] == -1)[0][0])
+    assert np.all(p[held] == 0.0) and est[held]
+
+
+def _unit_vector(p, index):
+    x = np.zeros(3 * int(index.max() + 1))
+    for v in np.nonzero(index >= 0)[0]:
+        x[3 * index[v]:3 * index[v] + 3] = p[v]
+    return x
+
+
+@pytest.mark.parametrize("name", ls.NOISY)
+def test_noisy_eigenvector(name):
+    _, r = ls.scene(name)
+    p, _, summ, extra = run(name)
+    x = _unit_vector(p, r["index"])
+    assert abs(np.linalg.norm(x) - 1.0) <= 8 * EPS * np.sqrt(len(x))
+    w, V = np.linalg.eigh(extra["system"])
+    v = V[:, 0]
+    sine = float(np.linalg.norm(x - np.sign(x @ v) * v))   # = 2 sin(angle / 2) >= sin(angle)
+    rho = w[0] / w[1]
+    bound = 1e-8 / (1.0 - rho) + 8.0 * len(w) * EPS * w[-1] / (w[1] - w[0])
+    it, _, conv = ref.inverse_iteration(r["H"])
+    print(f"{name}: sine {sine:.2e}, bound {bound:.2e}, rho {rho:.2e}, iterations {summ.iterations} against {it}, "
+          f"eigenvalue {summ.eigenvalue:.6e} against {w[0]:.6e}")
+    assert conv and summ.converged == 1 and abs(summ.iterations - it) <= 1
+    assert sine <= bound
+    assert abs(summ.eigenvalue - w[0]) <= 1e-8 * w[1] + 64 * len(w) * EPS * w[-1]
+
+
+def test_flip():
+    p, est, summ, extra = run("v12_flip")
+    p0, est0, summ0, extra0 = run("v12_strip")
+    assert summ.flipped == 1 and summ0.flipped == 0
+    assert summ.sign_votes == -summ0.sign_votes and summ.sign_votes < 0
+    assert np.array_equal(extra["system"], extra0["system"])     # position_2 -> -position_2 changes no bit of H
+    assert np.array_equal(p, -p0) and np.array_equal(est, est0)
+
+
+def test_triplet_capacity_smaller_than_the_count():
+    s, r = ls.scene("v10_gate")
+    _, _, summ, extra = run("v10_gate")
+    rc, p, est, s5, x5 = call(s, want=WANT, triplet_capacity=5)
+    assert rc == 0 and s5.num_triplets == summ.num_triplets == 120
+    assert x5["triplets"].shape == (5, 3) and np.array_equal(x5["triplets"], extra["triplets"][:5])
+    assert np.array_equal(x5["triplet_state"], extra["triplet_state"][:5])
+    assert np.array_equal(x5["baselines"], extra["baselines"][:5])
+    rc, p0, _, s0, x0 = call(s, want=("triplets",), triplet_capacity=0)
+    assert rc == 0 and x0["triplets"].shape == (0, 3) and s0.num_triplets == 120
+    assert np.array_equal(p0, p)
+
+
+@pytest.mark.parametrize("name", ["v12_sparse", "v70_hub"])
+def test_bit_reproducible(name):
+    s, _ = ls.scene(name)
+    p, est, summ, extra = run(name)
+    rc, p2, est2, s2, extra2 = call(s, positions_out=np.full((s["num_views"], 3), 7.0), want=WANT)
+    assert rc == 0
+    assert p.tobytes() == p2.tobytes() and np.array_equal(est, est2)
+    for key in WANT:
+        assert extra[key].tobytes() == extra2[key].tobytes(), key
+    ints = [k for k, v in summ.as_dict().items() if isinstance(v, int)]
+    assert [getattr(summ, k) for k in ints] == [getattr(s2, k) for k in ints]
+    assert (summ.eigenvalue, summ.shift) == (s2.eigenvalue, s2.shift)
+
+
+def test_views_outside_the_system_are_left_alone():
+    _, r = ls.scene("v14_two_components")
+    p, est, summ, extra = run("v14_two_components")
+    assert list(np.nonzero(~est)[0]) == list(range(8, 14))
+    assert np.all(p[8:] == 7.0)                    # as passed in
+    assert np.all(extra["system_index"][8:] == -2) and summ.num_views_in_system == 8
+    assert summ.triplets_in_other_components == 21
+
+
+def test_python_class_against_the_array_call():
+    s, r = ls.scene("v4_full")
+    p, est, _, _ = run("v4_full")
+    nv, nt = s["num_views"], len(s["track_offsets"]) - 1
+    rec = sfm.Reconstruction()
+    rec.cam_ext = np.zeros((nv, 6)); rec.view_estimated = np.ones(nv, dtype=bool)
+    rec.view_group = np.zeros(nv, dtype=np.int32); rec.group_model = np.zeros(1, dtype=np.int32)
+    rec.points = np.zeros((nt, 4)); rec.track_estimated = np.ones(nt, dtype=bool)
+    rec.obs_view = s["obs_view"]; rec.obs_uv = np.zeros((len(s["obs_view"]), 2))
+    rec.obs_track = np.repeat(np.arange(nt, dtype=np.int32), np.diff(s["track_offsets"]))
+    pairs = {(int(a), int(b)): types.SimpleNamespace(rotation_2=w, position_2=t)
+             for (a, b), w, t in zip(s["edges"], s["rot"], s["rel"])}
+    orientations = {v: s["orientations"][v] for v in range(nv)}
+    e = sfm.LinearPositionEstimator(sfm.LinearPositionEstimatorOptions(), rec, normalized_features=s["obs_feature"])
+    got = e.EstimatePositions(pairs, orientations)
+    assert sorted(got) == list(range(nv))
+    assert np.array_equal(np.array([got[v] for v in range(nv)]), p)
+    assert e.last_summary.converged == 1 and e.last_summary.num_triplets == 4
