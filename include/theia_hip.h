@@ -565,6 +565,62 @@ int theia_hip_linear_rotations(int32_t num_views, int32_t num_edges, const int32
                                const double* relative_rotations, const theia_linear_rotation_options* options /*NULL = defaults*/,
                                double* orientations_out, uint8_t* estimated_out, theia_linear_rotation_summary* summary);
 
+/* NonlinearRotationEstimator::EstimateRotations (global_pose_estimation/nonlinear_rotation_estimator.cc:49-98 with
+ * pairwise_rotation_error.h:65-96; pybind sfm.cc:1782-1787; the NONLINEAR global rotation estimator of the global
+ * pipeline): Ceres' Levenberg-Marquardt solve over one PairwiseRotationError block per pair, weight 1, under
+ * SoftLOneLoss(robust_loss_width), restated on the device in FP64 (csrc/nonlinear_rotations.hip).  Per
+ * pair e = (i, j) the residual is the angle-axis vector of R(w_j) R(w_i)' R(rel_e)' (ceres::AngleAxisToRotationMatrix,
+ * ceres::RotationMatrixToAngleAxis, small-angle branches included); the Jacobians are closed forms of the branch taken.
+ * The solver is ceres::Solver::Options at its defaults with max_num_iterations = 200 (:90-92): TrustRegionMinimizer +
+ * LevenbergMarquardtStrategy of Ceres 2.2 on the dense normal equations of order 3m, m = the views that take part.
+ * orientations [num_views][3] angle-axis, in/out; fixed [num_views] non-zero = held constant (no columns, not in |x|,
+ * bits unchanged), or NULL: no view is held, the reference's problem -- the gauge (a common rotation on the right) is
+ * then free, only the LM diagonal makes the system definite, and a factorisation that meets a pivot that is not positive
+ * is an invalid step, not an error.  A view without an edge is not in the problem and is left untouched; a pair between
+ * two held views is not in the problem either.  edges [num_edges][2] = (i, j) with relative_rotations [num_edges][3] =
+ * TwoViewInfo::rotation_2, R_j ~ R_ij R_i; repeated and reversed pairs add up.
+ * trace_out (optional) [trace_capacity][5]: (cost, gradient max norm, step norm, radius, accepted) per row, row 0 the
+ * start, then one row per iteration, in theia_ba_summary's convention; summary->trace_size rows are written.
+ * Returns 0 whatever the termination, as the reference returns true: after THEIA_ROTATION_TERM_FAILURE (five invalid
+ * steps in a row) the orientations are as passed in, after the cap they hold the last accepted iterate.
+ * THEIA_HIP_ERR_INVALID_ARGUMENT (checked before the device is touched; orientations untouched, summary zeroed): no edge;
+ * an edge naming a view out of range; an edge from a view to itself (Ceres refuses a residual block that names one
+ * parameter block twice); max_num_iterations < 0; a width or a maximum radius that is not positive and finite; a
+ * tolerance that is negative or not finite (zero switches a rule off, as in Ceres).
+ * THEIA_HIP_ERR_OUT_OF_MEMORY: the dense (3m + 1)^2 array of doubles does not fit on the device. */
+enum {
+  THEIA_ROTATION_TERM_NONE = 0,                 /* nothing to solve: every view of every edge is held */
+  THEIA_ROTATION_TERM_GRADIENT_TOLERANCE = 1,
+  THEIA_ROTATION_TERM_FUNCTION_TOLERANCE = 2,
+  THEIA_ROTATION_TERM_PARAMETER_TOLERANCE = 3,
+  THEIA_ROTATION_TERM_MAX_ITERATIONS = 4,
+  THEIA_ROTATION_TERM_FAILURE = 5,
+  THEIA_ROTATION_TERM_MIN_RADIUS = 6            /* the radius fell to 1e-32 */
+};
+typedef struct theia_nonlinear_rotation_options {
+  int32_t max_num_iterations;      /* 200 */
+  int32_t reserved;
+  double robust_loss_width;        /* 0.1 */
+  double function_tolerance;       /* 1e-6 */
+  double gradient_tolerance;       /* 1e-10 */
+  double parameter_tolerance;      /* 1e-8 */
+  double max_trust_region_radius;  /* 1e16, Ceres' default (the BA's options carry 1e12) */
+} theia_nonlinear_rotation_options;
+typedef struct theia_nonlinear_rotation_summary {
+  int32_t iterations;              /* passes of the loop; a pass that ends on the parameter or function tolerance is in none of the three counts below */
+  int32_t num_successful_steps, num_unsuccessful_steps, num_invalid_steps;
+  int32_t termination;             /* THEIA_ROTATION_TERM_* */
+  int32_t num_views_in_problem;    /* m */
+  int32_t trace_size, reserved;
+  double initial_cost, final_cost, final_radius, final_gradient_max_norm, seconds;
+} theia_nonlinear_rotation_summary;
+int theia_hip_nonlinear_rotations(int32_t num_views, double* orientations /* [n][3], in/out */,
+                                  const uint8_t* fixed /* [n] or NULL */, int32_t num_edges, const int32_t* edges,
+                                  const double* relative_rotations,
+                                  const theia_nonlinear_rotation_options* options /*NULL = defaults*/,
+                                  theia_nonlinear_rotation_summary* summary, double* trace_out /* optional */,
+                                  int32_t trace_capacity);
+
 /* LeastUnsquaredDeviationPositionEstimator::EstimatePositions (global_pose_estimation/
  * least_unsquared_deviation_position_estimator.cc:75-213; pybind sfm.cc:1196-1204, 1707-1726, the default
  * LEAST_UNSQUARED_DEVIATION position stage of the global pipeline): per pair e = (i, j) the rows c_j - c_i - s_e d_e with

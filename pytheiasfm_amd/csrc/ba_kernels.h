@@ -257,9 +257,10 @@ void dense_cholesky_solve(int n, double* A, int lda, double* b, double* work, do
 // work = dense_cholesky_workspace(n) doubles and keeps the 64 x 64 block inverses for the solves below.
 // dense_cholesky_back_substitute: X = L^-T Y for k vectors (Y [k][ldy] is overwritten).
 // dense_cholesky_solve_factored: X = A^-1 B for k vectors (B [k][ldb] overwritten; T: [k][n] scratch).
-// skip (device int, optional): every launch of the two returns at once while *skip is non-zero (lud_positions.hip's
-// device-side stopping test); the arithmetic is the same with or without it.
-void dense_cholesky_factor(int n, int k, double* A, int lda, double* work, double* fail_flag, hipStream_t st);
+// skip (device int, optional): every launch of the three returns at once while *skip is non-zero (lud_positions.hip's
+// and nonlinear_rotations.hip's device-side stopping tests); the arithmetic is the same with or without it.
+void dense_cholesky_factor(int n, int k, double* A, int lda, double* work, double* fail_flag, hipStream_t st,
+                           const int* skip = nullptr);
 void dense_cholesky_back_substitute(int n, const double* A, int lda, const double* work, int k, double* Y, int ldy,
                                     double* X, int ldx, hipStream_t st, const int* skip = nullptr);
 void dense_cholesky_solve_factored(int n, const double* A, int lda, const double* work, int k, double* B, int ldb,

@@ -22,6 +22,9 @@ for f in $SRCS; do
     # ba_inner.hip: the same switch -- sinking the stores of two branches into one store through a pointer phi kept observe_rot()'s
     # residual pair in scratch (24 B per lane, written and read per observation)
     case "$f" in ba_inner.hip) CONTRACT="off -mllvm -simplifycfg-sink-common=false" ;; esac
+    # nonlinear_rotations.hip: the same -- the three largest-diagonal branches of the matrix logarithm write different
+    # quaternion entries; sunk into one store they kept the whole edge evaluation in scratch (576 B per lane)
+    case "$f" in nonlinear_rotations.hip) CONTRACT="off -mllvm -simplifycfg-sink-common=false" ;; esac
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=$CONTRACT -munsafe-fp-atomics \
       -I../../include -I. ${THIP_EXTRA_DEFS:-} -c "$f" -o "$o" &
     PIDS="$PIDS $!"

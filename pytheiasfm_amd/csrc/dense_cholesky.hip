@@ -29,16 +29,19 @@ namespace {
 using namespace chol;
 
 __global__ __launch_bounds__(256) void k_potrf(double* __restrict__ A, int lda, int k0, int nb,
-                                               double* __restrict__ Linv, double* __restrict__ fail_flag) {
+                                               double* __restrict__ Linv, double* __restrict__ fail_flag,
+                                               const int* __restrict__ skip) {
+  if (skip && *skip) return;   // workgroup-uniform, before any barrier
   potrf64_wg(A, lda, k0, nb, Linv, fail_flag);
 }
 
 // A21 <- A21 * L11^-T for rows [k0 + nb, nrows): X[r][j] = sum_i P[r][i] Z[j][i].
 // 128 rows per workgroup; wave w owns rows [32w, 32w + 32).
 __global__ __launch_bounds__(256) void k_trsm(double* __restrict__ A, int lda, int nrows, int k0, int nb,
-                                              const double* __restrict__ Linv) {
+                                              const double* __restrict__ Linv, const int* __restrict__ skip) {
   __shared__ double P[128][LDP];
   __shared__ double Z[NB][LDP];
+  if (skip && *skip) return;
   const int tid = threadIdx.x;
   const int r0 = k0 + nb + blockIdx.x * 128;
   for (int t = tid; t < NB * NB; t += 256) Z[t / NB][t % NB] = Linv[t];
@@ -82,10 +85,11 @@ __global__ __launch_bounds__(256) void k_trsm(double* __restrict__ A, int lda, i
 // 16x16 MFMA accumulators.  C[i][j] -= sum_k P[i][k] * P[j][k], k < nb.
 //   v_mfma_f64_16x16x4_f64: A[i=l&15][k=l>>4], B[k=l>>4][j=l&15],
 //   C/D: col = l&15, row = (l>>4) + 4*reg   (f64 layout, see CDNA guide sec.3)
-__global__ __launch_bounds__(256) void k_syrk(double* __restrict__ A, int lda, int nrows, int k0, int nb) {
+__global__ __launch_bounds__(256) void k_syrk(double* __restrict__ A, int lda, int nrows, int k0, int nb,
+                                              const int* __restrict__ skip) {
   const int base = k0 + nb;  // first trailing row/col
   const int ti = blockIdx.y, tj = blockIdx.x;
-  if (tj > ti) return;  // lower tiles only
+  if (tj > ti || (skip && *skip)) return;  // lower tiles only
   const int r0 = base + ti * 64, c0 = base + tj * 64;
   __shared__ double Pr[64][LDP];  // rows of the panel for this tile's rows
   __shared__ double Pc[64][LDP];  // rows of the panel for this tile's cols
@@ -246,7 +250,8 @@ size_t dense_cholesky_workspace(int n) {
   return (size_t)std::max(1, nblk) * NB * NB + (size_t)n + 8;
 }
 
-void dense_cholesky_factor(int n, int k, double* A, int lda, double* work, double* fail_flag, hipStream_t st) {
+void dense_cholesky_factor(int n, int k, double* A, int lda, double* work, double* fail_flag, hipStream_t st,
+                           const int* skip) {
   if (n <= 0) return;
   const int nrows = n + k;  // rows n .. n+k-1 = right-hand sides, forward-substituted in place
   const int nblk = (n + NB - 1) / NB;
@@ -256,12 +261,12 @@ void dense_cholesky_factor(int n, int k, double* A, int lda, double* work, doubl
     const int nb = (n - k0 < NB) ? (n - k0) : NB;
     const int below = nrows - (k0 + nb);
     double* Zk = Linv + (size_t)kb * NB * NB;
-    k_potrf<<<1, 256, 0, st>>>(A, lda, k0, nb, Zk, fail_flag);
+    k_potrf<<<1, 256, 0, st>>>(A, lda, k0, nb, Zk, fail_flag, skip);
     if (below > 0) {
-      k_trsm<<<(below + 127) / 128, 256, 0, st>>>(A, lda, nrows, k0, nb, Zk);
+      k_trsm<<<(below + 127) / 128, 256, 0, st>>>(A, lda, nrows, k0, nb, Zk, skip);
       const int tiles = (below + 63) / 64;
       dim3 grid(tiles, tiles);
-      k_syrk<<<grid, 256, 0, st>>>(A, lda, nrows, k0, nb);
+      k_syrk<<<grid, 256, 0, st>>>(A, lda, nrows, k0, nb, skip);
     }
   }
 }
@@ -292,7 +297,7 @@ void dense_cholesky_solve_factored(int n, const double* A, int lda, const double
 void dense_cholesky_solve(int n, double* A, int lda, double* b, double* work, double* fail_flag, hipStream_t st) {
   if (n <= 0) return;
   // row n = right-hand side (b must alias A + n*lda): the factorisation leaves y = L^-1 b there
-  dense_cholesky_factor(n, 1, A, lda, work, fail_flag, st);
+  dense_cholesky_factor(n, 1, A, lda, work, fail_flag, st, nullptr);
   const int nblk = (n + NB - 1) / NB;
   double* Linv = work;
   double* x = work + (size_t)nblk * NB * NB;

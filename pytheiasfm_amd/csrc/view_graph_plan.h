@@ -1,8 +1,9 @@
-// view_graph_plan.h -- what the global-pose stages (rotation_averaging.hip, lud_positions.hip, linear_rotations.hip) derive
-// from a view graph on the host before they touch the device: which views are free, and the two CSR lists their kernels
-// assemble the Laplacian-shaped system from without atomics.  Host code only.  The first two fix a view per connected
-// component (build_view_graph_plan); the third fixes none and leaves out the views without edges (it checks its graph
-// itself, with view_graph_components, and calls fill_view_graph_lists).
+// view_graph_plan.h -- what the global-pose stages (rotation_averaging.hip, lud_positions.hip, linear_rotations.hip,
+// nonlinear_rotations.hip) derive from a view graph on the host before they touch the device: which views are free, and
+// the two CSR lists their kernels assemble the Laplacian-shaped system from without atomics.  Host code only.  The first
+// two fix a view per connected component (build_view_graph_plan); the third fixes none and leaves out the views without
+// edges (it checks its graph itself, with view_graph_components, and calls fill_view_graph_lists), and so does the
+// fourth, which also leaves out the views its caller holds.
 //
 // The lists, as the kernels read them:
 //   inc[inc_off[t] .. inc_off[t + 1])            the edges incident to free view t, in edge order;

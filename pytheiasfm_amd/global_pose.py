@@ -8,7 +8,10 @@ keeps the reference's state across calls: constraints accumulate over EstimateRo
 calls on one object, and the view fixed by default on the first call stays fixed on later ones.  The estimator that
 needs no initial guess, pytheia.sfm.LinearRotationEstimator (sfm.cc:1789-1795 ->
 global_pose_estimation/linear_rotation_estimator.{h,cc}), runs through theia_hip_linear_rotations
-(csrc/linear_rotations.hip).  The positions run
+(csrc/linear_rotations.hip); the Ceres refinement of given orientations, pytheia.sfm.NonlinearRotationEstimator
+(sfm.cc:1782-1787 -> global_pose_estimation/nonlinear_rotation_estimator.{h,cc}), through theia_hip_nonlinear_rotations
+(csrc/nonlinear_rotations.hip); both pipelines seed it with OrientationsFromMaximumSpanningTree
+(view_graph/orientations_from_maximum_spanning_tree.cc), host code here as there.  The positions run
 through theia_hip_lud_positions (csrc/lud_positions.hip), or, from the tracks' features and without the pairs' relative
 translations, through theia_hip_ligt_positions (pytheia.sfm.LiGTPositionEstimator, sfm.cc:1728-1747 ->
 global_pose_estimation/LiGT_position_estimator.{h,cc}; csrc/ligt_positions.hip), or, from the pairs' relative poses and
@@ -27,9 +30,12 @@ import math
 import numpy as np
 
 from . import _capi as capi
+from .synth import angle_axis_to_matrix
 
 
 class GlobalRotationEstimatorType(enum.IntEnum):  # reconstruction_estimator_options.h:64-70
+    # on the device: ROBUST_L1L2 (RobustRotationEstimator), NONLINEAR (NonlinearRotationEstimator), LINEAR
+    # (LinearRotationEstimator); LAGRANGE_DUAL and HYBRID need an SDP solver and have no counterpart here
     ROBUST_L1L2 = 0
     NONLINEAR = 1
     LINEAR = 2
@@ -199,6 +205,194 @@ class LinearRotationEstimator:
         for v, k in ids.items():
             result.setdefault(v, out[k].copy())
         return result
+
+
+class NonlinearRotationEstimatorOptions:
+    """ceres::Solver::Options as NonlinearRotationEstimator leaves them (nonlinear_rotation_estimator.cc:90-92), and the
+    loss width of its constructor.  The reference's class exposes only the width; the rest is here so that every
+    stopping rule can be reached."""
+
+    def __init__(self):
+        self.robust_loss_width = 0.1
+        self.max_num_iterations = 200
+        self.function_tolerance = 1e-6
+        self.gradient_tolerance = 1e-10
+        self.parameter_tolerance = 1e-8
+        self.max_trust_region_radius = 1e16
+
+    def to_c(self):
+        o = capi.NonlinearRotationOptions()
+        o.max_num_iterations = int(self.max_num_iterations)
+        o.robust_loss_width = float(self.robust_loss_width)
+        o.function_tolerance = float(self.function_tolerance)
+        o.gradient_tolerance = float(self.gradient_tolerance)
+        o.parameter_tolerance = float(self.parameter_tolerance)
+        o.max_trust_region_radius = float(self.max_trust_region_radius)
+        return o
+
+
+def nonlinear_rotations(orientations, edges, relative_rotations, fixed=None, options=None, want_trace=False):
+    """theia_hip_nonlinear_rotations on arrays: orientations [n][3] angle-axis (not modified), edges [E][2] view indices,
+    relative_rotations [E][3] = TwoViewInfo::rotation_2, fixed: [n] booleans or None (no view held, the reference's
+    problem).  Returns (return code, new orientations [n][3], NonlinearRotationSummary) and, with want_trace, the trace
+    [rows][5] = (cost, gradient max norm, step norm, radius, accepted) as a fourth entry.  The orientations are the input
+    on a refusal and after a FAILURE termination, the last accepted iterate otherwise."""
+    o = (options or NonlinearRotationEstimatorOptions()).to_c()
+    aa = np.array(orientations, dtype=np.float64).reshape(-1, 3)
+    e, r = _pair_arrays(edges, relative_rotations, "relative rotation")
+    f = None if fixed is None else np.ascontiguousarray(np.asarray(fixed, dtype=bool).astype(np.uint8))
+    if f is not None and f.shape != (aa.shape[0],):
+        raise ValueError("fixed must have one entry per view")
+    rows = max(0, int(o.max_num_iterations)) + 1 if want_trace else 0
+    trace = np.zeros((rows, 5)) if want_trace else None
+    s = capi.NonlinearRotationSummary()
+    rc = capi.lib().theia_hip_nonlinear_rotations(aa.shape[0], capi.ptr(aa, C.c_double), capi.ptr(f, C.c_uint8), e.shape[0],
+                                                  capi.ptr(e, C.c_int32), capi.ptr(r, C.c_double), C.byref(o), C.byref(s),
+                                                  capi.ptr(trace, C.c_double), rows)
+    if want_trace:
+        return rc, aa, s, trace[:s.trace_size].copy()
+    return rc, aa, s
+
+
+class NonlinearRotationEstimator:
+    """NonlinearRotationEstimator(robust_loss_width=0.1) with EstimateRotations(view_pairs, orientations) -> dict
+    (sfm.cc:1782-1787 -> nonlinear_rotation_estimator.{h,cc}), in RobustRotationEstimator's conventions: the input dict
+    is not modified and the dict comes back whatever the outcome, the reference's bool is in last_success.
+
+    Every pair whose two views both have an orientation adds one residual; a pair that lacks one is skipped silently
+    (:76-80).  With no orientation, no pair, or no pair left (Ceres then has nothing to solve), last_success is False
+    for the first two as in the reference (:53-62) and for the third as well, and the input comes back.  No view is held
+    (DESIGN.md 3.6i on the gauge).  The constraints do not accumulate: the reference's class keeps no state."""
+
+    def __init__(self, robust_loss_width=0.1):
+        self.options = NonlinearRotationEstimatorOptions()
+        self.options.robust_loss_width = float(robust_loss_width)
+        self.last_summary = None
+        self.last_success = None
+
+    def EstimateRotations(self, view_pairs, orientations):
+        result = {int(v): np.asarray(r, dtype=np.float64).reshape(3).copy() for v, r in orientations.items()}
+        ids = list(result)
+        pos = {v: k for k, v in enumerate(ids)}
+        kept = [((int(a), int(b)), info) for (a, b), info in view_pairs.items() if int(a) in pos and int(b) in pos]
+        self.last_summary = capi.NonlinearRotationSummary()
+        if not ids or not kept:
+            self.last_success = False
+            return result
+        edges = np.array([(pos[a], pos[b]) for (a, b), _ in kept], dtype=np.int32)
+        rel = np.array([np.asarray(info.rotation_2, dtype=np.float64).reshape(3) for _, info in kept])
+        aa = np.array([result[v] for v in ids])
+        rc, out, s = nonlinear_rotations(aa, edges, rel, None, self.options)
+        capi.check(rc)
+        self.last_success = True
+        self.last_summary = s
+        return {v: out[k].copy() for k, v in enumerate(ids)}
+
+
+def OrientationsFromMaximumSpanningTree(view_pairs):
+    """OrientationsFromMaximumSpanningTree (view_graph/orientations_from_maximum_spanning_tree.cc:109-180) on the
+    {(id1, id2): TwoViewInfo} dict that stands in for the ViewGraph: the largest connected component, its maximum
+    spanning tree on num_verified_matches, the root at the zero vector, and every other view of the component chained
+    along the tree: R_rel R_source when source id < neighbour id, R_rel' R_source otherwise (:74-77; a pair is stored
+    under (smaller id, larger id) in the ViewGraph, and so it is read here whichever way the key names it -- a key
+    (larger, smaller) is taken as that pair).  Host code, as in the reference.  Returns {view id: angle-axis}; a view
+    outside the component gets no entry; an empty dict gives an empty dict.
+
+    Where the reference follows hash order, two rules make the result a function of the graph alone:
+      * the root is the smallest view id of the component (the reference: the first view of its unordered_set of tree
+        edges); among components of equal size the one holding the smallest view id is taken;
+      * the tree is Kruskal's over the pairs sorted by (-num_verified_matches, smaller id, larger id): among equal
+        weights the pair with the smaller ids wins, whatever the order of the dict.
+    Another root changes the result by a common rotation on the right, another tree among equal weights by the tree.
+    The order in which the reference's heap visits the tree does not matter: a view's orientation is the product along
+    its tree path."""
+    pairs = {}
+    for (a, b), info in view_pairs.items():
+        a, b = int(a), int(b)
+        if a != b:
+            pairs[(min(a, b), max(a, b))] = info
+    if not pairs:
+        return {}
+    parent = {}
+
+    def find(v):
+        while parent[v] != v:
+            parent[v] = parent[parent[v]]
+            v = parent[v]
+        return v
+
+    for a, b in pairs:
+        parent.setdefault(a, a)
+        parent.setdefault(b, b)
+    for a, b in pairs:
+        ra, rb = find(a), find(b)
+        if ra != rb:
+            parent[max(ra, rb)] = min(ra, rb)       # a component's representative is its smallest view id
+    members = {}
+    for v in parent:
+        members.setdefault(find(v), []).append(v)
+    root = min(members, key=lambda c: (-len(members[c]), c))
+    component = set(members[root])
+    # Kruskal, maximum weight first
+    tree = {v: v for v in component}
+
+    def find_t(v):
+        while tree[v] != v:
+            tree[v] = tree[tree[v]]
+            v = tree[v]
+        return v
+
+    neighbours = {v: [] for v in component}
+    for (a, b) in sorted((p for p in pairs if p[0] in component),
+                         key=lambda p: (-int(pairs[p].num_verified_matches), p[0], p[1])):
+        ra, rb = find_t(a), find_t(b)
+        if ra != rb:
+            tree[ra] = rb
+            neighbours[a].append(b)
+            neighbours[b].append(a)
+    out = {root: np.zeros(3)}
+    R = {root: np.eye(3)}
+    stack = [root]
+    while stack:
+        src = stack.pop()
+        for nb in neighbours[src]:
+            if nb in R:
+                continue
+            Rrel = angle_axis_to_matrix(np.asarray(pairs[(min(src, nb), max(src, nb))].rotation_2, dtype=np.float64).reshape(3))
+            R[nb] = (Rrel if src < nb else Rrel.T) @ R[src]
+            out[nb] = _matrix_to_angle_axis(R[nb])
+            stack.append(nb)
+    return out
+
+
+def _matrix_to_angle_axis(R):
+    """ceres::RotationMatrixToAngleAxis (through the quaternion, as Ceres 2.2)."""
+    tr = R[0, 0] + R[1, 1] + R[2, 2]
+    q = np.zeros(4)
+    if tr >= 0.0:
+        t = math.sqrt(tr + 1.0)
+        q[0] = 0.5 * t
+        t = 0.5 / t
+        q[1], q[2], q[3] = (R[2, 1] - R[1, 2]) * t, (R[0, 2] - R[2, 0]) * t, (R[1, 0] - R[0, 1]) * t
+    else:
+        i = 0
+        if R[1, 1] > R[0, 0]:
+            i = 1
+        if R[2, 2] > R[i, i]:
+            i = 2
+        j, k = (i + 1) % 3, (i + 2) % 3
+        t = math.sqrt(R[i, i] - R[j, j] - R[k, k] + 1.0)
+        q[i + 1] = 0.5 * t
+        t = 0.5 / t
+        q[0] = (R[k, j] - R[j, k]) * t
+        q[j + 1] = (R[j, i] + R[i, j]) * t
+        q[k + 1] = (R[k, i] + R[i, k]) * t
+    s2 = float(q[1:] @ q[1:])
+    if s2 > 0.0:
+        st = math.sqrt(s2)
+        two_theta = 2.0 * (math.atan2(-st, -q[0]) if q[0] < 0.0 else math.atan2(st, q[0]))
+        return q[1:] * (two_theta / st)
+    return q[1:] * 2.0
 
 
 class GlobalPositionEstimatorType(enum.IntEnum):  # reconstruction_estimator_options.h:80-85 (pybind sfm.cc:1196-1204)

@@ -22,7 +22,9 @@ from . import ba as _ba
 from .synth import angle_axis_to_matrix
 from .global_pose import (GlobalRotationEstimatorType, RobustRotationEstimator,  # noqa: F401  (pyTheia's names)
                           RobustRotationEstimatorOptions, LinearRotationEstimator,
-                          LinearRotationEstimatorOptions, GlobalPositionEstimatorType,
+                          LinearRotationEstimatorOptions, NonlinearRotationEstimator,
+                          NonlinearRotationEstimatorOptions, OrientationsFromMaximumSpanningTree,
+                          GlobalPositionEstimatorType,
                           LeastUnsquaredDeviationPositionEstimator, LeastUnsquaredDeviationPositionEstimatorOptions,
                           LiGTPositionEstimator, LiGTPositionEstimatorOptions,
                           LinearPositionEstimator, LinearPositionEstimatorOptions,
