@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "dense_cholesky.h"
+
 namespace thip {
 
 // One workgroup of the fused linearise + Schur kernel (ba_fused.hip): consecutive wave tiles whose tracks see at
@@ -247,24 +249,7 @@ void launch_long_backsub(const DevProblem& P, const double* cam, const double* p
                          double* cand_pts, const double* yc, const double* Vinv, double* scratch, double* scalB,
                          hipStream_t st);
 
-// dense SPD solve  A x = b  (lower triangle of row-major A, leading dim lda;
-// A is overwritten by its Cholesky factor, b by x).  fail_flag (device) is
-// incremented if a pivot is not positive.
-size_t dense_cholesky_workspace(int n);  // doubles
-void dense_cholesky_solve(int n, double* A, int lda, double* b, double* work, double* fail_flag, hipStream_t st);
-// The same kernels factored once and solved many times (rotation_averaging.hip).  dense_cholesky_factor: rows
-// n .. n+k-1 of A (k >= 1) hold k right-hand sides and come out forward-substituted (y = L^-1 b); lda >= n + k;
-// work = dense_cholesky_workspace(n) doubles and keeps the 64 x 64 block inverses for the solves below.
-// dense_cholesky_back_substitute: X = L^-T Y for k vectors (Y [k][ldy] is overwritten).
-// dense_cholesky_solve_factored: X = A^-1 B for k vectors (B [k][ldb] overwritten; T: [k][n] scratch).
-// skip (device int, optional): every launch of the three returns at once while *skip is non-zero (lud_positions.hip's
-// and nonlinear_rotations.hip's device-side stopping tests); the arithmetic is the same with or without it.
-void dense_cholesky_factor(int n, int k, double* A, int lda, double* work, double* fail_flag, hipStream_t st,
-                           const int* skip = nullptr);
-void dense_cholesky_back_substitute(int n, const double* A, int lda, const double* work, int k, double* Y, int ldy,
-                                    double* X, int ldx, hipStream_t st, const int* skip = nullptr);
-void dense_cholesky_solve_factored(int n, const double* A, int lda, const double* work, int k, double* B, int ldb,
-                                   double* T, double* X, int ldx, hipStream_t st, const int* skip = nullptr);
+// the dense SPD solve (dense_cholesky.hip): dense_cholesky.h
 
 // Tile-sparse, nested-dissection ordered, level-scheduled variant of the same
 // solve (sparse_cholesky.hip).  adj = symmetric nt x nt (nt = ceil(n/64)) tile

@@ -311,3 +311,28 @@ void dense_cholesky_solve(int n, double* A, int lda, double* b, double* work, do
 }
 
 }  // namespace thip
+
+using namespace thip;
+
+// Introspection for the parity tests: factor A once, then solve the k right-hand sides against the factor
+// (dense_cholesky_solve_factored: the forward and backward kernels of the ADMM solves).
+extern "C" int theia_hip_dense_spd_solve_multi(int32_t n, const double* A, int32_t k, const double* B, double* X) {
+  if (n < 0 || k < 1 || (n > 0 && (!A || !B || !X))) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "bad argument");
+  if (n == 0) return 0;
+  int rc = thip::ensure_device();
+  if (rc) return rc;
+  DenseSpd S;   // row n: the factorisation's right-hand-side row (zero, unused)
+  DevBuf<double> dB, dT, dX;
+  if ((rc = S.alloc(n, 1)) || (rc = dB.up(B, (size_t)k * n)) || (rc = dT.alloc((size_t)k * n)) || (rc = dX.alloc((size_t)k * n)))
+    return rc;
+  if ((rc = S.clear(nullptr, true))) return rc;
+  HIP_TRY(hipMemcpy2D(S.A(), sizeof(double) * S.lda, A, sizeof(double) * n, sizeof(double) * n, n, hipMemcpyHostToDevice));
+  S.factor(1, nullptr);
+  S.solve_factored(k, dB.p, dT.p, dX.p, nullptr);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(X, dX.p, sizeof(double) * (size_t)k * n, hipMemcpyDeviceToHost));
+  bool failed = false;
+  if ((rc = S.failed(&failed))) return rc;
+  if (failed) return set_error(THEIA_HIP_ERR_INTERNAL, "matrix is not positive definite");
+  return 0;
+}

@@ -61,4 +61,21 @@ inline double ms_since(std::chrono::steady_clock::time_point t0) {
 // workgroups of `threads` that cover n items, at least one
 inline int grid_of(size_t n, int threads) { return (int)std::max<size_t>(1, (n + threads - 1) / threads); }
 
+// The loop of a stage whose stopping test runs on the device: every kernel of an iteration returns at once while the
+// device state's `done` is set, so the host enqueues `chunk` iterations at a time and reads the state once per chunk.
+// enqueue(): one iteration's launches; returns 0 or an error code.  Starts nothing when hs->done is already set; reads
+// the state back after every chunk; returns a HIP error as HIP_TRY would.
+template <class State, class Enqueue>
+int run_until_done(int max_iterations, int chunk, const State* d_state, State* hs, Enqueue&& enqueue) {
+  for (int enqueued = 0; !hs->done && enqueued < max_iterations;) {
+    const int now = std::min(chunk, max_iterations - enqueued);
+    for (int c = 0; c < now; ++c)
+      if (int rc = enqueue()) return rc;
+    enqueued += now;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(hs, d_state, sizeof(State), hipMemcpyDeviceToHost));
+  }
+  return 0;
+}
+
 }  // namespace thip

@@ -35,12 +35,7 @@
 //
 // Determinism: no floating-point atomics.  Every entry of H is a sum in (track, observation) order by one owner, every
 // norm a fixed tree (block_sum), the votes are integers.  Two runs on one input are bit-identical.
-#include "ransac_device.h"
-#include "ba_kernels.h"
-#include "wave_reduce.h"
-#include "spectral_shift.h"
 #include "smallest_eigenvector.h"
-#include "device_util.h"
 
 #include <algorithm>
 #include <chrono>
@@ -53,7 +48,6 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kTracksPerBlock = kThreads / 64;   // k_base_pairs: one wavefront per track
-constexpr int kChunk = 4;                        // inverse iterations enqueued between two reads of the `done` flag
 // mu = kShiftMultiple * n * eps * max diag H (DESIGN.md 3.6f has the rule and the scenes it was chosen on)
 constexpr double kShiftMultiple = 1.0;
 
@@ -292,18 +286,13 @@ extern "C" int theia_hip_ligt_positions(int32_t num_views, const double* orienta
   }
   if (sm.tracks_used == 0) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "no track has a pair of positive theta^2: no track used");
   if (num_items >= (1LL << 30)) return set_error(THEIA_HIP_ERR_OUT_OF_MEMORY, "%lld 3 x 3 items: too many constraints", num_items);
-  const int mf = m - 1, n3 = 3 * mf;   // free views
+  const int mf = m - 1;   // free views
   sm.num_views_in_system = m;
   sm.num_constraints = (int32_t)std::min<long long>(num_constraints, INT32_MAX);
   if (mf < 1) return set_error(THEIA_HIP_ERR_INTERNAL, "a used track with one view");
 
-  // the dense system first: when it does not fit, that is the answer, before the host builds lists of its size
-  const int lda = n3 + 1;   // row n3: the factorisation's right-hand-side row (zero, unused)
-  const size_t dense = (size_t)(n3 + 1) * lda;
-  DevBuf<double> d_H, d_work, d_flag, d_full;
-  if ((rc = d_H.alloc(dense)) || (rc = d_work.alloc(dense_cholesky_workspace(n3))) || (rc = d_flag.alloc(1)) ||
-      (system_out && (rc = d_full.alloc((size_t)n3 * n3))))
-    return rc;
+  SmallestEigenvector ev;
+  if ((rc = ev.alloc(mf, system_out != nullptr))) return rc;
 
   // the segment list: per block (row >= col, free views) of the lower triangle its items, by a stable counting sort
   // an item (va, vb) holds X' Y with X on va and Y on vb: it lands on block (idx va, idx vb), transposed when that lies above
@@ -325,27 +314,14 @@ extern "C" int theia_hip_ligt_positions(int32_t num_views, const double* orienta
       }
     }
   }, &seg);
-  const std::vector<int2>& block_rc = seg.block_rc;
-  const std::vector<long long>& seg_off = seg.seg_off;
-  const std::vector<int>& seg_item = seg.seg_item;
-  const int num_blocks = (int)block_rc.size();
 
-  DevBuf<double> d_items, d_x, d_b, d_y, d_T, d_rel;
-  DevBuf<long long> d_item_base, d_seg_off;
-  DevBuf<int> d_seg_item, d_idx, d_votes;
-  DevBuf<int2> d_block_rc, d_edges;
-  DevBuf<InverseIterationState> d_st;
-  if ((rc = d_items.alloc(9 * (size_t)num_items)) ||
-      (rc = d_item_base.up(item_base.data(), T)) || (rc = d_seg_off.up(seg_off.data(), seg_off.size())) ||
-      (rc = d_seg_item.up(seg_item.data(), seg_item.size())) || (rc = d_block_rc.up(block_rc.data(), block_rc.size())) ||
-      (rc = d_idx.up(idx.data(), n)) || (rc = d_votes.alloc(1)) || (rc = d_edges.up(edges, E)) ||
-      (rc = d_rel.up(relative_translations, 3 * (size_t)E)) || (rc = d_x.alloc(n3)) || (rc = d_b.alloc(n3)) ||
-      (rc = d_y.alloc(n3)) || (rc = d_T.alloc(n3)) || (rc = d_st.alloc(1)))
+  DevBuf<double> d_items, d_rel;
+  DevBuf<long long> d_item_base;
+  DevBuf<int> d_idx;
+  DevBuf<int2> d_edges;
+  if ((rc = d_items.alloc(9 * (size_t)num_items)) || (rc = d_item_base.up(item_base.data(), T)) || (rc = d_idx.up(idx.data(), n)) ||
+      (rc = d_edges.up(edges, E)) || (rc = d_rel.up(relative_translations, 3 * (size_t)E)) || (rc = ev.upload(seg, st)))
     return rc;
-  HIP_TRY(hipMemsetAsync(d_H.p, 0, sizeof(double) * dense, st));
-  HIP_TRY(hipMemsetAsync(d_flag.p, 0, sizeof(double), st));
-  HIP_TRY(hipMemsetAsync(d_votes.p, 0, sizeof(int), st));
-  HIP_TRY(hipMemsetAsync(d_st.p, 0, sizeof(InverseIterationState), st));
   HIP_TRY(hipStreamSynchronize(st));
   sm.setup_ms = ms_since(t_start);
 
@@ -353,75 +329,20 @@ extern "C" int theia_hip_ligt_positions(int32_t num_views, const double* orienta
   const auto t_assemble = std::chrono::steady_clock::now();
   k_items<<<grid_of(T, kThreads), kThreads, 0, st>>>(T, d_off.p, d_obs_view.p, d_feat.p, d_R.p, d_ray.p, d_base.p,
                                                     d_item_base.p, d_items.p);
-  k_blocks<kThreads><<<grid_of(num_blocks, kThreads), kThreads, 0, st>>>(num_blocks, d_block_rc.p, d_seg_off.p, d_seg_item.p,
-                                                              d_items.p, lda, d_H.p);
-  if (system_out)
-    k_full_system<kThreads><<<grid_of((size_t)n3 * n3, kThreads), kThreads, 0, st>>>(n3, lda, d_H.p, d_full.p);
-  k_shift<kThreads><<<1, kThreads, 0, st>>>(n3, lda, d_H.p, kShiftMultiple, d_x.p, d_b.p, &d_st.p->shift, &d_st.p->max_diag);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(st));
+  if ((rc = ev.assemble(d_items.p, kShiftMultiple, st))) return rc;
   sm.assemble_ms = ms_since(t_assemble);
 
-  // ---- factor H + mu I once
-  const auto t_factor = std::chrono::steady_clock::now();
-  dense_cholesky_factor(n3, 1, d_H.p, lda, d_work.p, d_flag.p, st);
-  HIP_TRY(hipGetLastError());
-  double flag = 0.0;
-  HIP_TRY(hipMemcpy(&flag, d_flag.p, sizeof(double), hipMemcpyDeviceToHost));
-  sm.factor_ms = ms_since(t_factor);
-  InverseIterationState hs{};
-  if (flag != 0.0) {
-    HIP_TRY(hipMemcpy(&hs, d_st.p, sizeof(InverseIterationState), hipMemcpyDeviceToHost));
-    sm.shift = hs.shift;
-    *summary = sm;
-    return set_error(THEIA_HIP_ERR_INTERNAL, "the Cholesky factorisation of H + mu I failed (mu = %g)", hs.shift);
-  }
+  if ((rc = ev.factor(st, &sm, summary))) return rc;
 
-  // ---- inverse iteration from x = 1 / sqrt(n)
+  // ---- inverse iteration, sign vote (FlipSignOfPositionsIfNecessary needs view pairs), scatter
   const auto t_eig = std::chrono::steady_clock::now();
-  const int* done = &d_st.p->done;
-  for (int enqueued = 0; enqueued < o.max_power_iterations;) {
-    const int chunk = std::min(kChunk, o.max_power_iterations - enqueued);
-    for (int c = 0; c < chunk; ++c) {
-      dense_cholesky_solve_factored(n3, d_H.p, lda, d_work.p, 1, d_b.p, n3, d_T.p, d_y.p, n3, st, done);
-      k_iterate<kThreads><<<1, kThreads, 0, st>>>(n3, d_y.p, d_x.p, d_b.p, o.eigensolver_threshold, d_st.p);
-    }
-    enqueued += chunk;
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(&hs, d_st.p, sizeof(InverseIterationState), hipMemcpyDeviceToHost));
-    if (hs.done) break;
-  }
-  // ---- sign vote and scatter
-  if (E > 0) {
-    k_sign_vote<kThreads><<<grid_of(E, kThreads), kThreads, 0, st>>>(E, d_edges.p, d_idx.p, d_x.p, d_R.p, d_rel.p, d_votes.p);
-    HIP_TRY(hipGetLastError());
-  }
-  std::vector<double> x(n3);
-  int votes = 0;
-  HIP_TRY(hipMemcpy(x.data(), d_x.p, sizeof(double) * (size_t)n3, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(&votes, d_votes.p, sizeof(int), hipMemcpyDeviceToHost));
-  std::vector<double> full;
-  if (system_out) {
-    full.resize((size_t)n3 * n3);
-    HIP_TRY(hipMemcpy(full.data(), d_full.p, sizeof(double) * full.size(), hipMemcpyDeviceToHost));
-  }
+  if ((rc = ev.iterate(o.max_power_iterations, o.eigensolver_threshold, st)) ||
+      (E > 0 && (rc = ev.vote(E, d_edges.p, d_idx.p, d_R.p, d_rel.p, st))) || (rc = ev.fetch()))
+    return rc;
   sm.eig_ms = ms_since(t_eig);
-  sm.iterations = hs.iterations;
-  sm.converged = hs.converged;
-  sm.eigenvalue = hs.eigenvalue;
-  sm.shift = hs.shift;
-  sm.sign_votes = votes;
-  sm.flipped = votes < 0;
-  const double sign = votes < 0 ? -1.0 : 1.0;
-  for (int v = 0; v < n; ++v) {
-    estimated_out[v] = idx[v] != -2;
-    if (idx[v] == -2) continue;
-    for (int c = 0; c < 3; ++c) positions_out[3 * (size_t)v + c] = idx[v] >= 0 ? sign * x[3 * (size_t)idx[v] + c] : 0.0;
-  }
+  ev.scatter(n, idx, positions_out, estimated_out, system_out, system_index_out, &sm);
   if (base_pairs_out)
     for (int t = 0; t < T; ++t) { base_pairs_out[2 * (size_t)t] = base[t].x; base_pairs_out[2 * (size_t)t + 1] = base[t].y; }
-  if (system_out) std::copy(full.begin(), full.end(), system_out);
-  if (system_index_out) std::copy(idx.begin(), idx.end(), system_index_out);
   *summary = sm;
   return 0;
 }

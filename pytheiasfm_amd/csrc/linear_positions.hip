@@ -34,13 +34,8 @@
 //
 // Determinism: no floating-point atomics.  The ratios are compacted in track order, a selection is exact, every entry of
 // H is a sum in triangle order by one owner.  Two runs on one input are bit-identical.
-#include "ransac_device.h"
-#include "ba_kernels.h"
-#include "wave_reduce.h"
-#include "spectral_shift.h"
 #include "smallest_eigenvector.h"
 #include "view_graph_plan.h"
-#include "device_util.h"
 
 #include <algorithm>
 #include <chrono>
@@ -55,7 +50,6 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
-constexpr int kChunk = 4;                        // inverse iterations enqueued between two reads of the `done` flag
 constexpr double kShiftMultiple = 1.0;           // mu = kShiftMultiple * n * eps * max diag H, as in 3.6f
 // ratio scratch: two doubles per slot, a slot per possible common track of a triangle of the chunk: 256 MiB at most
 constexpr long long kScratchSlots = 1LL << 24;
@@ -631,17 +625,12 @@ extern "C" int theia_hip_linear_triplet_positions(
     const int* v = &tri[3 * (size_t)used[u]];
     weight[u] = 1.0 / std::sqrt((double)std::min({cnt[v[0]], cnt[v[1]], cnt[v[2]]}));
   }
-  const int mf = m - 1, n3 = 3 * mf;   // free views
+  const int mf = m - 1;   // free views
   sm.num_views_in_system = m;
   if (6LL * U >= (1LL << 30)) return set_error(THEIA_HIP_ERR_OUT_OF_MEMORY, "%d used triangles: too many 3 x 3 items", U);
 
-  // the dense system first: when it does not fit, that is the answer, before the host builds lists of its size
-  const int lda = n3 + 1;   // row n3: the factorisation's right-hand-side row (zero, unused)
-  const size_t dense = (size_t)(n3 + 1) * lda;
-  DevBuf<double> d_H, d_work, d_flag, d_full;
-  if ((rc = d_H.alloc(dense)) || (rc = d_work.alloc(dense_cholesky_workspace(n3))) || (rc = d_flag.alloc(1)) ||
-      (system_out && (rc = d_full.alloc((size_t)n3 * n3))))
-    return rc;
+  SmallestEigenvector ev;
+  if ((rc = ev.alloc(mf, system_out != nullptr))) return rc;
 
   BlockSegments seg;
   build_block_segments(mf, [&](auto&& emit) {
@@ -652,97 +641,35 @@ extern "C" int theia_hip_linear_triplet_positions(
         for (int j = i; j < 3; ++j) emit(idx[v[i]], idx[v[j]], it++);
     }
   }, &seg);
-  const int num_blocks = (int)seg.block_rc.size();
 
-  DevBuf<double> d_items, d_weight, d_x, d_b, d_y, d_T;
-  DevBuf<long long> d_seg_off;
-  DevBuf<int> d_seg_item, d_idx, d_votes, d_used;
-  DevBuf<int2> d_block_rc;
-  DevBuf<InverseIterationState> d_st;
+  DevBuf<double> d_items, d_weight;
+  DevBuf<int> d_idx, d_used;
   if ((rc = d_items.alloc(54 * (size_t)U)) || (rc = d_weight.up(weight.data(), U)) || (rc = d_used.up(used.data(), U)) ||
-      (rc = d_seg_off.up(seg.seg_off.data(), seg.seg_off.size())) || (rc = d_seg_item.up(seg.seg_item.data(), seg.seg_item.size())) ||
-      (rc = d_block_rc.up(seg.block_rc.data(), seg.block_rc.size())) || (rc = d_idx.up(idx.data(), n)) ||
-      (rc = d_votes.alloc(1)) || (rc = d_x.alloc(n3)) || (rc = d_b.alloc(n3)) || (rc = d_y.alloc(n3)) ||
-      (rc = d_T.alloc(n3)) || (rc = d_st.alloc(1)))
+      (rc = d_idx.up(idx.data(), n)) || (rc = ev.upload(seg, st)))
     return rc;
-  HIP_TRY(hipMemsetAsync(d_H.p, 0, sizeof(double) * dense, st));
-  HIP_TRY(hipMemsetAsync(d_flag.p, 0, sizeof(double), st));
-  HIP_TRY(hipMemsetAsync(d_votes.p, 0, sizeof(int), st));
-  HIP_TRY(hipMemsetAsync(d_st.p, 0, sizeof(InverseIterationState), st));
   k_triplet_items<<<grid_of(U, kThreads), kThreads, 0, st>>>(U, d_used.p, d_weight.p, d_tri.p, d_tri_edge.p, d_base.p, d_R.p,
                                                             d_rel.p, d_items.p);
-  k_blocks<kThreads><<<grid_of(num_blocks, kThreads), kThreads, 0, st>>>(num_blocks, d_block_rc.p, d_seg_off.p, d_seg_item.p,
-                                                                        d_items.p, lda, d_H.p);
-  if (system_out)
-    k_full_system<kThreads><<<grid_of((size_t)n3 * n3, kThreads), kThreads, 0, st>>>(n3, lda, d_H.p, d_full.p);
-  k_shift<kThreads><<<1, kThreads, 0, st>>>(n3, lda, d_H.p, kShiftMultiple, d_x.p, d_b.p, &d_st.p->shift, &d_st.p->max_diag);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(st));
+  if ((rc = ev.assemble(d_items.p, kShiftMultiple, st))) return rc;
   sm.assemble_ms = ms_since(t_assemble);
 
-  // ---- factor H + mu I once
-  const auto t_factor = std::chrono::steady_clock::now();
-  dense_cholesky_factor(n3, 1, d_H.p, lda, d_work.p, d_flag.p, st);
-  HIP_TRY(hipGetLastError());
-  double flag = 0.0;
-  HIP_TRY(hipMemcpy(&flag, d_flag.p, sizeof(double), hipMemcpyDeviceToHost));
-  sm.factor_ms = ms_since(t_factor);
-  InverseIterationState hs{};
-  if (flag != 0.0) {
-    HIP_TRY(hipMemcpy(&hs, d_st.p, sizeof(InverseIterationState), hipMemcpyDeviceToHost));
-    sm.shift = hs.shift;
-    *summary = sm;
-    return set_error(THEIA_HIP_ERR_INTERNAL, "the Cholesky factorisation of H + mu I failed (mu = %g)", hs.shift);
-  }
+  if ((rc = ev.factor(st, &sm, summary))) return rc;
 
-  // ---- inverse iteration from x = 1 / sqrt(n)
+  // ---- inverse iteration, sign vote, scatter
   const auto t_eig = std::chrono::steady_clock::now();
-  const int* done = &d_st.p->done;
-  for (int enqueued = 0; enqueued < o.max_power_iterations;) {
-    const int chunk = std::min(kChunk, o.max_power_iterations - enqueued);
-    for (int c = 0; c < chunk; ++c) {
-      dense_cholesky_solve_factored(n3, d_H.p, lda, d_work.p, 1, d_b.p, n3, d_T.p, d_y.p, n3, st, done);
-      k_iterate<kThreads><<<1, kThreads, 0, st>>>(n3, d_y.p, d_x.p, d_b.p, o.eigensolver_threshold, d_st.p);
-    }
-    enqueued += chunk;
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(&hs, d_st.p, sizeof(InverseIterationState), hipMemcpyDeviceToHost));
-    if (hs.done) break;
-  }
-  // ---- sign vote and scatter
-  k_sign_vote<kThreads><<<grid_of(E, kThreads), kThreads, 0, st>>>(E, d_edges.p, d_idx.p, d_x.p, d_R.p, d_rel.p, d_votes.p);
-  HIP_TRY(hipGetLastError());
-  std::vector<double> x(n3), full, base;
-  int votes = 0;
-  HIP_TRY(hipMemcpy(x.data(), d_x.p, sizeof(double) * (size_t)n3, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(&votes, d_votes.p, sizeof(int), hipMemcpyDeviceToHost));
-  if (system_out) {
-    full.resize((size_t)n3 * n3);
-    HIP_TRY(hipMemcpy(full.data(), d_full.p, sizeof(double) * full.size(), hipMemcpyDeviceToHost));
-  }
+  if ((rc = ev.iterate(o.max_power_iterations, o.eigensolver_threshold, st)) ||
+      (rc = ev.vote(E, d_edges.p, d_idx.p, d_R.p, d_rel.p, st)) || (rc = ev.fetch()))
+    return rc;
+  std::vector<double> base;
   const int head = std::min(Tn, triplet_capacity);
   if (baselines_out && head > 0) {
     base.resize(3 * (size_t)head);
     HIP_TRY(hipMemcpy(base.data(), d_base.p, sizeof(double) * base.size(), hipMemcpyDeviceToHost));
   }
   sm.eig_ms = ms_since(t_eig);
-  sm.iterations = hs.iterations;
-  sm.converged = hs.converged;
-  sm.eigenvalue = hs.eigenvalue;
-  sm.shift = hs.shift;
-  sm.sign_votes = votes;
-  sm.flipped = votes < 0;
-  const double sign = votes < 0 ? -1.0 : 1.0;
-  for (int v = 0; v < n; ++v) {
-    estimated_out[v] = idx[v] != -2;
-    if (idx[v] == -2) continue;
-    for (int c = 0; c < 3; ++c) positions_out[3 * (size_t)v + c] = idx[v] >= 0 ? sign * x[3 * (size_t)idx[v] + c] : 0.0;
-  }
+  ev.scatter(n, idx, positions_out, estimated_out, system_out, system_index_out, &sm);
   if (triplets_out) std::copy(tri.begin(), tri.begin() + 3 * (size_t)head, triplets_out);
   if (triplet_state_out) std::copy(state.begin(), state.begin() + head, triplet_state_out);
   if (baselines_out) std::copy(base.begin(), base.end(), baselines_out);
-  if (system_out) std::copy(full.begin(), full.end(), system_out);
-  if (system_index_out) std::copy(idx.begin(), idx.end(), system_index_out);
   *summary = sm;
   return 0;
 }

@@ -31,11 +31,9 @@
 // Determinism: no floating-point atomics.  Every entry of M is a sum in edge order by one owner, every dot product and norm
 // a fixed tree (block_sum).  Two runs on one input are bit-identical.
 #include "ransac_device.h"
-#include "ba_kernels.h"
-#include "wave_reduce.h"
+#include "dense_cholesky.h"
 #include "spectral_shift.h"
-#include "device_util.h"
-#include "view_graph_plan.h"
+#include "view_graph_device.h"
 
 #include <algorithm>
 #include <chrono>
@@ -65,25 +63,22 @@ __global__ __launch_bounds__(kThreads) void k_rel_matrices(int E, const double* 
 
 // The lower triangle of M into the zeroed array.  Thread t < m: view t's diagonal, its degree.  Thread t = m + p: pair
 // p = (a, b), a > b: block (a, b) = -sum over the pair's edges of R_e (the edge runs b -> a) or R_e' (a -> b).
-// inc_off, pair_off, pair_edge, pair_rc: view_graph_plan.h; idx: view -> index in the system.
-__global__ __launch_bounds__(kThreads) void k_lin_assemble(int m, int P, int lda, const int* __restrict__ inc_off,
-                                                           const int* __restrict__ pair_off, const int* __restrict__ pair_edge,
-                                                           const int2* __restrict__ pair_rc, const int2* __restrict__ edges,
-                                                           const int* __restrict__ idx, const double* __restrict__ R,
+// vg: view_graph_device.h; vg.idx: view -> index in the system.
+__global__ __launch_bounds__(kThreads) void k_lin_assemble(ViewGraphLists vg, int lda, const double* __restrict__ R,
                                                            double* __restrict__ M) {
-  const int t = blockIdx.x * kThreads + threadIdx.x;
+  const int t = blockIdx.x * kThreads + threadIdx.x, m = vg.m;
   if (t < m) {
-    const double degree = (double)(inc_off[t + 1] - inc_off[t]);
+    const double degree = (double)(vg.inc_off[t + 1] - vg.inc_off[t]);
 #pragma unroll
     for (int r = 0; r < 3; ++r) M[(size_t)(3 * t + r) * lda + 3 * t + r] = degree;
-  } else if (t < m + P) {
+  } else if (t < m + vg.P) {
     const int p = t - m;
-    const int2 rc = pair_rc[p];
+    const int2 rc = vg.pair_rc[p];
     double acc[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int k = pair_off[p]; k < pair_off[p + 1]; ++k) {
-      const int e = pair_edge[k];
+    for (int k = vg.pair_off[p]; k < vg.pair_off[p + 1]; ++k) {
+      const int e = vg.pair_edge[k];
       const double* v = R + 9 * (size_t)e;
-      if (idx[edges[e].y] == rc.x) {
+      if (vg.idx[vg.edges[e].y] == rc.x) {
 #pragma unroll
         for (int q = 0; q < 9; ++q) acc[q] += v[q];
       } else {
@@ -268,7 +263,7 @@ extern "C" int theia_hip_linear_rotations(int32_t num_views, int32_t num_edges, 
       return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "the view graph is not connected: no path from view %d to view %d", edges[0], v);
   ViewGraphPlan g;
   fill_view_graph_lists(n, no_edge, E, edges, &g);
-  const int m = g.m, P = g.P;
+  const int m = g.m;
   if ((long long)m * 3 + 1 > INT32_MAX / 2) return set_error(THEIA_HIP_ERR_OUT_OF_MEMORY, "%d views: the dense system does not fit", m);
   const int n3 = 3 * m;
 
@@ -277,30 +272,23 @@ extern "C" int theia_hip_linear_rotations(int32_t num_views, int32_t num_edges, 
   theia_linear_rotation_summary sm{};
   sm.num_views_in_system = m;
   hipStream_t st = nullptr;
-  const int lda = n3 + 1;   // row n3: the factorisation's right-hand-side row (zero, unused)
-  const size_t dense = (size_t)(n3 + 1) * lda;
-  DevBuf<double> d_M, d_work, d_flag, d_rel, d_R, d_x, d_b, d_y, d_T, d_aa;
-  DevBuf<int> d_idx, d_inc_off, d_pair_off, d_pair_edge;
-  DevBuf<int2> d_edges, d_pair_rc;
+  DenseSpd M;   // row n3: the factorisation's right-hand-side row (zero, unused)
+  DeviceViewGraph dg;
+  DevBuf<double> d_rel, d_R, d_x, d_b, d_y, d_T, d_aa;
   DevBuf<LinearState> d_st;
   // the dense system first: when it does not fit, that is the answer
-  if ((rc = d_M.alloc(dense)) || (rc = d_work.alloc(dense_cholesky_workspace(n3))) || (rc = d_flag.alloc(1)) ||
-      (rc = d_rel.up(relative_rotations, 3 * (size_t)E)) || (rc = d_R.alloc(9 * (size_t)E)) || (rc = d_edges.up(edges, E)) ||
-      (rc = d_idx.up(g.idx.data(), n)) || (rc = d_inc_off.up(g.inc_off.data(), (size_t)m + 1)) ||
-      (rc = d_pair_off.up(g.pair_off.data(), g.pair_off.size())) || (rc = d_pair_edge.up(g.pair_edge.data(), g.pair_edge.size())) ||
-      (rc = d_pair_rc.up(g.pair_rc.data(), g.pair_rc.size())) || (rc = d_x.alloc(3 * (size_t)n3)) ||
-      (rc = d_b.alloc(3 * (size_t)n3)) || (rc = d_y.alloc(3 * (size_t)n3)) || (rc = d_T.alloc(3 * (size_t)n3)) ||
-      (rc = d_aa.alloc(3 * (size_t)m)) || (rc = d_st.alloc(1)))
+  if ((rc = M.alloc(n3, 1)) || (rc = d_rel.up(relative_rotations, 3 * (size_t)E)) || (rc = d_R.alloc(9 * (size_t)E)) ||
+      (rc = dg.up(g, edges, E, n)) || (rc = d_x.alloc(3 * (size_t)n3)) || (rc = d_b.alloc(3 * (size_t)n3)) ||
+      (rc = d_y.alloc(3 * (size_t)n3)) || (rc = d_T.alloc(3 * (size_t)n3)) || (rc = d_aa.alloc(3 * (size_t)m)) ||
+      (rc = d_st.alloc(1)))
     return rc;
 
   // ---- set-up: R_e, M, the shift, the start block
-  HIP_TRY(hipMemsetAsync(d_M.p, 0, sizeof(double) * dense, st));
-  HIP_TRY(hipMemsetAsync(d_flag.p, 0, sizeof(double), st));
+  if ((rc = M.clear(st, true))) return rc;
   HIP_TRY(hipMemsetAsync(d_st.p, 0, sizeof(LinearState), st));
   k_rel_matrices<<<grid_of(E, kThreads), kThreads, 0, st>>>(E, d_rel.p, d_R.p);
-  k_lin_assemble<<<grid_of((size_t)m + P, kThreads), kThreads, 0, st>>>(m, P, lda, d_inc_off.p, d_pair_off.p, d_pair_edge.p,
-                                                                       d_pair_rc.p, d_edges.p, d_idx.p, d_R.p, d_M.p);
-  k_shift<kThreads><<<1, kThreads, 0, st>>>(n3, lda, d_M.p, 1.0, nullptr, nullptr, &d_st.p->shift, &d_st.p->max_diag);
+  k_lin_assemble<<<grid_of((size_t)m + g.P, kThreads), kThreads, 0, st>>>(dg.lists, M.lda, d_R.p, M.A());
+  k_shift<kThreads><<<1, kThreads, 0, st>>>(n3, M.lda, M.A(), 1.0, nullptr, nullptr, &d_st.p->shift, &d_st.p->max_diag);
   k_start_block<<<1, kThreads, 0, st>>>(n3, d_x.p, d_b.p);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(st));
@@ -308,15 +296,14 @@ extern "C" int theia_hip_linear_rotations(int32_t num_views, int32_t num_edges, 
 
   // ---- factor M + mu I once
   const auto t_factor = std::chrono::steady_clock::now();
-  dense_cholesky_factor(n3, 1, d_M.p, lda, d_work.p, d_flag.p, st);
-  HIP_TRY(hipGetLastError());
-  double flag = 0.0;
+  M.factor(1, st);
+  bool failed = false;
   LinearState hs{};
-  HIP_TRY(hipMemcpy(&flag, d_flag.p, sizeof(double), hipMemcpyDeviceToHost));
+  if ((rc = M.failed(&failed))) return rc;
   HIP_TRY(hipMemcpy(&hs, d_st.p, sizeof(LinearState), hipMemcpyDeviceToHost));
   sm.factor_ms = ms_since(t_factor);
   sm.shift = hs.shift;
-  if (flag != 0.0) {   // nothing to project: the outputs stay as passed in
+  if (failed) {   // nothing to project: the outputs stay as passed in
     *summary = sm;
     return set_error(THEIA_HIP_ERR_INTERNAL, "the Cholesky factorisation of M + mu I failed (mu = %g)", hs.shift);
   }
@@ -324,17 +311,12 @@ extern "C" int theia_hip_linear_rotations(int32_t num_views, int32_t num_edges, 
   // ---- block inverse iteration, then the projection of whatever it reached
   const auto t_iterate = std::chrono::steady_clock::now();
   const int* done = &d_st.p->done;
-  for (int enqueued = 0; enqueued < o.max_num_iterations;) {
-    const int chunk = std::min(kChunk, o.max_num_iterations - enqueued);
-    for (int c = 0; c < chunk; ++c) {
-      dense_cholesky_solve_factored(n3, d_M.p, lda, d_work.p, 3, d_b.p, n3, d_T.p, d_y.p, n3, st, done);
-      k_subspace_step<<<1, kThreads, 0, st>>>(n3, d_y.p, d_x.p, d_b.p, o.subspace_convergence_threshold, d_st.p);
-    }
-    enqueued += chunk;
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(&hs, d_st.p, sizeof(LinearState), hipMemcpyDeviceToHost));
-    if (hs.done) break;
-  }
+  rc = run_until_done(o.max_num_iterations, kChunk, d_st.p, &hs, [&]() {
+    M.solve_factored(3, d_b.p, d_T.p, d_y.p, st, done);
+    k_subspace_step<<<1, kThreads, 0, st>>>(n3, d_y.p, d_x.p, d_b.p, o.subspace_convergence_threshold, d_st.p);
+    return 0;
+  });
+  if (rc) return rc;
   k_project_so3<<<grid_of(m, kThreads), kThreads, 0, st>>>(m, n3, d_x.p, d_aa.p);
   HIP_TRY(hipGetLastError());
   std::vector<double> aa(3 * (size_t)m);

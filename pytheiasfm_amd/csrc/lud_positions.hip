@@ -23,10 +23,8 @@
 // lanes and added by the butterfly; every norm is a per-block sum followed by one workgroup summing the blocks in order.
 // Two runs on one input are bit-identical.
 #include "ransac_device.h"
-#include "ba_kernels.h"
-#include "wave_reduce.h"
-#include "device_util.h"
-#include "view_graph_plan.h"
+#include "dense_cholesky.h"
+#include "view_graph_device.h"
 
 #include <algorithm>
 #include <chrono>
@@ -37,7 +35,7 @@ namespace thip {
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kViewsPerBlock = kThreads / 64;   // k_rhs, k_view: one wavefront per free view
+static_assert(kThreads == 64 * kViewsPerBlock, "k_rhs, k_view: one wavefront per free view");
 constexpr int kChunk = 32;   // ADMM iterations enqueued between two reads of the `done` flag
 
 // Device-side state of the stopping test.
@@ -70,17 +68,14 @@ __device__ __forceinline__ double m_entry(const double* d, double De, int r, int
 // The lower triangle of S into the zeroed array (row-major, leading dimension lda):
 //   thread t < m       : free view t -- its 3 x 3 diagonal block, sum of M_e over its incident edges
 //   thread t = m + p   : pair p = (a > b) -- block (a, b) = -sum of M_e over the pair's edges
-// inc, pair_edge, pair_rc: view_graph_plan.h.
-__global__ __launch_bounds__(kThreads) void k_assemble(int m, int P, int lda, const int* __restrict__ inc_off,
-                                                       const int* __restrict__ inc, const int* __restrict__ pair_off,
-                                                       const int* __restrict__ pair_edge, const int2* __restrict__ pair_rc,
-                                                       const double* __restrict__ d, const double* __restrict__ D,
-                                                       double* __restrict__ S) {
-  const int t = blockIdx.x * kThreads + threadIdx.x;
+// vg: view_graph_device.h.
+__global__ __launch_bounds__(kThreads) void k_assemble(ViewGraphLists vg, int lda, const double* __restrict__ d,
+                                                       const double* __restrict__ D, double* __restrict__ S) {
+  const int t = blockIdx.x * kThreads + threadIdx.x, m = vg.m;
   double acc[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   if (t < m) {
-    for (int k = inc_off[t]; k < inc_off[t + 1]; ++k) {
-      const int e = inc[k] >> 1;
+    for (int k = vg.inc_off[t]; k < vg.inc_off[t + 1]; ++k) {
+      const int e = vg.inc[k] >> 1;
       const double de[3] = {d[3 * (size_t)e], d[3 * (size_t)e + 1], d[3 * (size_t)e + 2]};
       const double De = D[e];
 #pragma unroll
@@ -92,10 +87,10 @@ __global__ __launch_bounds__(kThreads) void k_assemble(int m, int P, int lda, co
     for (int r = 0; r < 3; ++r)
 #pragma unroll
       for (int c = 0; c <= r; ++c) S[(size_t)(3 * t + r) * lda + 3 * t + c] = acc[3 * r + c];
-  } else if (t < m + P) {
+  } else if (t < m + vg.P) {
     const int p = t - m;
-    for (int k = pair_off[p]; k < pair_off[p + 1]; ++k) {
-      const int e = pair_edge[k];
+    for (int k = vg.pair_off[p]; k < vg.pair_off[p + 1]; ++k) {
+      const int e = vg.pair_edge[k];
       const double de[3] = {d[3 * (size_t)e], d[3 * (size_t)e + 1], d[3 * (size_t)e + 2]};
       const double De = D[e];
 #pragma unroll
@@ -103,7 +98,7 @@ __global__ __launch_bounds__(kThreads) void k_assemble(int m, int P, int lda, co
 #pragma unroll
         for (int c = 0; c < 3; ++c) acc[3 * r + c] += m_entry(de, De, r, c);
     }
-    const int2 rc = pair_rc[p];
+    const int2 rc = vg.pair_rc[p];
 #pragma unroll
     for (int r = 0; r < 3; ++r)
 #pragma unroll
@@ -121,24 +116,21 @@ __device__ __forceinline__ double edge_w(const double* __restrict__ z, const dou
 }
 
 // Reduced right-hand side of the x-update (:145): g_v = sum over incident edges of -/+ (w_e + d_e g_s,e / D_e), view-major.
-// One wavefront per free view (kViewsPerBlock per workgroup): lane l takes the view's incident edges l, l + 64, .. in
-// order, then the butterfly sums the lanes in a fixed order.
-__global__ __launch_bounds__(kThreads) void k_rhs(int m, const int* __restrict__ inc_off, const int* __restrict__ inc,
-                                                  const double* __restrict__ d, const double* __restrict__ D,
+// One wavefront per free view (for_each_incident_edge), then the butterfly sums the lanes in a fixed order.
+__global__ __launch_bounds__(kThreads) void k_rhs(ViewGraphLists vg, const double* __restrict__ d, const double* __restrict__ D,
                                                   const double* __restrict__ z, const double* __restrict__ u,
                                                   double* __restrict__ g, const LudState* __restrict__ st) {
   if (st->done) return;
   const int v = blockIdx.x * kViewsPerBlock + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (v >= m) return;   // wave-uniform
+  if (v >= vg.m) return;   // wave-uniform
   double g0 = 0.0, g1 = 0.0, g2 = 0.0;
-  for (int k = inc_off[v] + lane; k < inc_off[v + 1]; k += 64) {
-    const int e = inc[k] >> 1;
+  for_each_incident_edge(vg, v, lane, [&](int e, bool plus) {
     const double de[3] = {d[3 * (size_t)e], d[3 * (size_t)e + 1], d[3 * (size_t)e + 2]};
     double w[4];
     const double f = edge_w(z, u, 4 * (size_t)e, de, w) / D[e];
     const double h0 = w[0] + de[0] * f, h1 = w[1] + de[1] * f, h2 = w[2] + de[2] * f;
-    if (inc[k] & 1) { g0 += h0; g1 += h1; g2 += h2; } else { g0 -= h0; g1 -= h1; g2 -= h2; }
-  }
+    if (plus) { g0 += h0; g1 += h1; g2 += h2; } else { g0 -= h0; g1 -= h1; g2 -= h2; }
+  });
   g0 = wave_sum_butterfly(g0); g1 = wave_sum_butterfly(g1); g2 = wave_sum_butterfly(g2);
   if (lane == 0) { g[3 * (size_t)v] = g0; g[3 * (size_t)v + 1] = g1; g[3 * (size_t)v + 2] = g2; }
 }
@@ -180,7 +172,7 @@ __global__ __launch_bounds__(kThreads) void k_edge(int E, const int2* __restrict
       const double bq = q == 3 ? 1.0 : 0.0, zq = z[e4 + q], uq = u[e4 + q];
       const double ax_hat = alpha * ax[q] + (1.0 - alpha) * (zq + bq);
       const double v = (ax_hat - bq) + uq;
-      const double zn = q == 3 ? fmax(v, 0.0) : fmax(0.0, v - kappa) - fmax(0.0, -v - kappa);
+      const double zn = q == 3 ? fmax(v, 0.0) : soft_threshold(v, kappa);
       un[q] = uq + ((ax_hat - zn) - bq);
       dzn[q] = zn - zq;
       z[e4 + q] = zn;
@@ -203,25 +195,24 @@ __global__ __launch_bounds__(kThreads) void k_edge(int E, const int2* __restrict
 
 // The position rows of |rho A'(z - z_old)|^2 and |rho A'u|^2 (:157, :162), one wavefront per free view as in k_rhs;
 // part[block][2] = the sums of the workgroup's views in view order.
-__global__ __launch_bounds__(kThreads) void k_view(int m, const int* __restrict__ inc_off, const int* __restrict__ inc,
-                                                   const double* __restrict__ dz, const double* __restrict__ u, double rho,
-                                                   double* __restrict__ part, const LudState* __restrict__ st) {
+__global__ __launch_bounds__(kThreads) void k_view(ViewGraphLists vg, const double* __restrict__ dz,
+                                                   const double* __restrict__ u, double rho, double* __restrict__ part,
+                                                   const LudState* __restrict__ st) {
   __shared__ double red[2][kViewsPerBlock];
   if (st->done) return;
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int v = blockIdx.x * kViewsPerBlock + wv;
   double ss = 0.0, tt = 0.0;
-  if (v < m) {   // wave-uniform
+  if (v < vg.m) {   // wave-uniform
     double s[3] = {0.0, 0.0, 0.0}, t[3] = {0.0, 0.0, 0.0};
-    for (int k = inc_off[v] + lane; k < inc_off[v + 1]; k += 64) {
-      const size_t e4 = 4 * (size_t)(inc[k] >> 1);
-      const bool plus = inc[k] & 1;
+    for_each_incident_edge(vg, v, lane, [&](int e, bool plus) {
+      const size_t e4 = 4 * (size_t)e;
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
         s[c] += plus ? dz[e4 + c] : -dz[e4 + c];
         t[c] += plus ? u[e4 + c] : -u[e4 + c];
       }
-    }
+    });
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const double sc = rho * wave_sum_butterfly(s[c]), tc = rho * wave_sum_butterfly(t[c]);
@@ -246,16 +237,8 @@ __global__ __launch_bounds__(kThreads) void k_test(const double* __restrict__ pa
   __shared__ double red[kThreads];
   if (st->done) return;
   double sum[7];
-  for (int c = 0; c < 5; ++c) {
-    double s = 0.0;
-    for (int b = threadIdx.x; b < nbE; b += kThreads) s += part_e[5 * (size_t)b + c];
-    sum[c] = block_sum<kThreads>(s, red);
-  }
-  for (int c = 0; c < 2; ++c) {
-    double s = 0.0;
-    for (int b = threadIdx.x; b < nbV; b += kThreads) s += part_v[2 * (size_t)b + c];
-    sum[5 + c] = block_sum<kThreads>(s, red);
-  }
+  for (int c = 0; c < 5; ++c) sum[c] = block_sum_column<kThreads>(part_e, nbE, 5, c, red);
+  for (int c = 0; c < 2; ++c) sum[5 + c] = block_sum_column<kThreads>(part_v, nbV, 2, c, red);
   if (threadIdx.x == 0) {
     const double r_norm = sqrt(sum[0]);
     const double s_norm = sqrt(sum[5] + sum[3]);
@@ -289,52 +272,44 @@ extern "C" int theia_hip_lud_positions(int32_t num_views, const double* orientat
   ViewGraphPlan g;
   int rc = build_view_graph_plan(n, fixed, E, edges, "held", &g);
   if (rc) return rc;
-  const int m = g.m, P = g.P;
-  const int n3 = 3 * m;
+  const int m = g.m, n3 = 3 * m;
 
   if ((rc = thip::ensure_device())) return rc;
-  const int lda = n3 + 1;   // row n3: the factorisation's right-hand-side row (zero, unused)
   const int nbE = grid_of(E, kThreads), nbV = std::max(1, (m + kViewsPerBlock - 1) / kViewsPerBlock);
-  DevBuf<double> d_aa, d_rel, d_d, d_D, d_S, d_work, d_flag, d_z, d_u, d_dz, d_g, d_T, d_x, d_pe, d_pv;
-  DevBuf<int2> d_edges, d_pair_rc;
-  DevBuf<int> d_idx, d_inc_off, d_inc, d_pair_off, d_pair_edge;
+  DenseSpd S;   // row n3: the factorisation's right-hand-side row (zero, unused)
+  DeviceViewGraph dg;
+  DevBuf<double> d_aa, d_rel, d_d, d_D, d_z, d_u, d_dz, d_g, d_T, d_x, d_pe, d_pv;
   DevBuf<LudState> d_st;
-  const size_t dense = (size_t)(n3 + 1) * lda;
-  if ((rc = d_S.alloc(dense)) || (rc = d_work.alloc(dense_cholesky_workspace(n3))) || (rc = d_flag.alloc(1)) ||
-      (rc = d_aa.up(orientations, 3 * (size_t)n)) || (rc = d_rel.up(relative_translations, 3 * (size_t)E)) ||
-      (rc = d_edges.up(edges, E)) || (rc = d_idx.up(g.idx.data(), n)) || (rc = d_inc_off.up(g.inc_off.data(), m + 1)) ||
-      (rc = d_inc.up(g.inc.data(), g.inc.size())) || (rc = d_pair_off.up(g.pair_off.data(), g.pair_off.size())) ||
-      (rc = d_pair_edge.up(g.pair_edge.data(), g.pair_edge.size())) || (rc = d_pair_rc.up(g.pair_rc.data(), g.pair_rc.size())) ||
+  if ((rc = S.alloc(n3, 1)) || (rc = d_aa.up(orientations, 3 * (size_t)n)) ||
+      (rc = d_rel.up(relative_translations, 3 * (size_t)E)) || (rc = dg.up(g, edges, E, n)) ||
       (rc = d_d.alloc(3 * (size_t)E)) || (rc = d_D.alloc(E)) || (rc = d_z.alloc(4 * (size_t)E)) ||
       (rc = d_u.alloc(4 * (size_t)E)) || (rc = d_dz.alloc(4 * (size_t)E)) || (rc = d_g.alloc(n3)) ||
       (rc = d_T.alloc(n3)) || (rc = d_x.alloc(n3)) || (rc = d_pe.alloc(5 * (size_t)nbE)) ||
       (rc = d_pv.alloc(2 * (size_t)nbV)) || (rc = d_st.alloc(1)))
     return rc;
+  const ViewGraphLists& vg = dg.lists;
   theia_lud_summary sm{};
   hipStream_t st = nullptr;
 
   // ---- setup: d_e, D_e, S (ConstrainedL1Solver's constructor, :49-91, in Schur form)
-  HIP_TRY(hipMemsetAsync(d_S.p, 0, sizeof(double) * dense, st));
-  HIP_TRY(hipMemsetAsync(d_flag.p, 0, sizeof(double), st));
+  if ((rc = S.clear(st, true))) return rc;
   HIP_TRY(hipMemsetAsync(d_x.p, 0, sizeof(double) * std::max(1, n3), st));
   HIP_TRY(hipMemsetAsync(d_z.p, 0, sizeof(double) * 4 * (size_t)E, st));
   HIP_TRY(hipMemsetAsync(d_u.p, 0, sizeof(double) * 4 * (size_t)E, st));
   HIP_TRY(hipMemsetAsync(d_st.p, 0, sizeof(LudState), st));
-  k_setup<<<nbE, kThreads, 0, st>>>(E, d_edges.p, d_aa.p, d_rel.p, d_d.p, d_D.p);
-  k_assemble<<<grid_of(m + P, kThreads), kThreads, 0, st>>>(m, P, lda, d_inc_off.p, d_inc.p, d_pair_off.p, d_pair_edge.p,
-                                                           d_pair_rc.p, d_d.p, d_D.p, d_S.p);
+  k_setup<<<nbE, kThreads, 0, st>>>(E, vg.edges, d_aa.p, d_rel.p, d_d.p, d_D.p);
+  k_assemble<<<grid_of(m + g.P, kThreads), kThreads, 0, st>>>(vg, S.lda, d_d.p, d_D.p, S.A());
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(st));
   sm.setup_ms = ms_since(t_start);
 
   // ---- factor S once
   const auto t_factor = std::chrono::steady_clock::now();
-  dense_cholesky_factor(n3, 1, d_S.p, lda, d_work.p, d_flag.p, st);
-  HIP_TRY(hipGetLastError());
-  double flag = 0.0;
-  HIP_TRY(hipMemcpy(&flag, d_flag.p, sizeof(double), hipMemcpyDeviceToHost));
+  S.factor(1, st);
+  bool failed = false;
+  if ((rc = S.failed(&failed))) return rc;
   sm.factor_ms = ms_since(t_factor);
-  if (flag != 0.0) {
+  if (failed) {
     *summary = sm;
     return set_error(THEIA_HIP_ERR_INTERNAL, "the Cholesky factorisation of the reduced system failed");
   }
@@ -347,22 +322,17 @@ extern "C" int theia_hip_lud_positions(int32_t num_views, const double* orientat
   const double kappa = 1.0 / o->rho;
   const int* done = &d_st.p->done;
   LudState hs{};
-  for (int enqueued = 0; enqueued < o->max_num_iterations;) {
-    const int chunk = std::min(kChunk, o->max_num_iterations - enqueued);
-    for (int c = 0; c < chunk; ++c) {
-      k_rhs<<<nbV, kThreads, 0, st>>>(m, d_inc_off.p, d_inc.p, d_d.p, d_D.p, d_z.p, d_u.p, d_g.p, d_st.p);
-      dense_cholesky_solve_factored(n3, d_S.p, lda, d_work.p, 1, d_g.p, n3, d_T.p, d_x.p, n3, st, done);
-      k_edge<<<nbE, kThreads, 0, st>>>(E, d_edges.p, d_idx.p, d_d.p, d_D.p, d_x.p, d_z.p, d_u.p, d_dz.p, o->alpha, kappa,
-                                       o->rho, d_pe.p, d_st.p);
-      k_view<<<nbV, kThreads, 0, st>>>(m, d_inc_off.p, d_inc.p, d_dz.p, d_u.p, o->rho, d_pv.p, d_st.p);
-      k_test<<<1, kThreads, 0, st>>>(d_pe.p, nbE, d_pv.p, nbV, rhs_norm, primal_abs_eps, dual_abs_eps,
-                                     o->relative_tolerance, d_st.p);
-    }
-    enqueued += chunk;
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(&hs, d_st.p, sizeof(LudState), hipMemcpyDeviceToHost));
-    if (hs.done) break;
-  }
+  rc = run_until_done(o->max_num_iterations, kChunk, d_st.p, &hs, [&]() {
+    k_rhs<<<nbV, kThreads, 0, st>>>(vg, d_d.p, d_D.p, d_z.p, d_u.p, d_g.p, d_st.p);
+    S.solve_factored(1, d_g.p, d_T.p, d_x.p, st, done);
+    k_edge<<<nbE, kThreads, 0, st>>>(E, vg.edges, vg.idx, d_d.p, d_D.p, d_x.p, d_z.p, d_u.p, d_dz.p, o->alpha, kappa, o->rho,
+                                     d_pe.p, d_st.p);
+    k_view<<<nbV, kThreads, 0, st>>>(vg, d_dz.p, d_u.p, o->rho, d_pv.p, d_st.p);
+    k_test<<<1, kThreads, 0, st>>>(d_pe.p, nbE, d_pv.p, nbV, rhs_norm, primal_abs_eps, dual_abs_eps, o->relative_tolerance,
+                                   d_st.p);
+    return 0;
+  });
+  if (rc) return rc;
   std::vector<double> x(std::max(1, n3));
   HIP_TRY(hipMemcpy(x.data(), d_x.p, sizeof(double) * std::max(1, n3), hipMemcpyDeviceToHost));
   sm.admm_ms = ms_since(t_admm);

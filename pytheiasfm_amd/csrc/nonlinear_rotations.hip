@@ -28,10 +28,8 @@
 //
 // Determinism: no atomics of this file's own (the factorisation's fail flag is the only one, and it is only compared with
 // zero).  Every sum has one owner and a fixed order.  Two runs on one input are bit-identical.
-#include "ba_kernels.h"
-#include "wave_reduce.h"
-#include "device_util.h"
-#include "view_graph_plan.h"
+#include "dense_cholesky.h"
+#include "view_graph_device.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -44,7 +42,7 @@ namespace thip {
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kViewsPerBlock = kThreads / 64;   // k_column_norms, k_gradient: one wavefront per free view
+static_assert(kThreads == 64 * kViewsPerBlock, "k_column_norms, k_gradient: one wavefront per free view");
 constexpr int kRec = 24;                        // doubles per edge record: J_i [3][3] | J_j [3][3] | r [3] | 3 unused
 constexpr int kDefaultChunk = 4;                // LM iterations enqueued between two reads of the state
 constexpr int kMaxChunk = 64;
@@ -290,16 +288,16 @@ __global__ __launch_bounds__(kThreads) void k_linearise(int E, const int2* __res
 
 // The first linearisation ran with scale = 1; one wavefront per free view sums the squares of its three columns over its
 // incident edges (lane l takes edges l, l + 64, .. in order, then the butterfly) and writes scale = 1 / (1 + |column|).
-__global__ __launch_bounds__(kThreads) void k_column_norms(int m, const int* __restrict__ inc_off, const int* __restrict__ inc,
-                                                           const double* __restrict__ rec, double* __restrict__ scale) {
+__global__ __launch_bounds__(kThreads) void k_column_norms(ViewGraphLists vg, const double* __restrict__ rec,
+                                                           double* __restrict__ scale) {
   const int v = blockIdx.x * kViewsPerBlock + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (v >= m) return;   // wave-uniform
+  if (v >= vg.m) return;   // wave-uniform
   double s[3] = {0.0, 0.0, 0.0};
-  for (int k = inc_off[v] + lane; k < inc_off[v + 1]; k += 64) {
-    const double* J = rec + kRec * (size_t)(inc[k] >> 1) + 9 * (inc[k] & 1);
+  for_each_incident_edge(vg, v, lane, [&](int e, bool plus) {
+    const double* J = rec + kRec * (size_t)e + 9 * (int)plus;
 #pragma unroll
     for (int c = 0; c < 3; ++c) s[c] += (J[c] * J[c] + J[3 + c] * J[3 + c]) + J[6 + c] * J[6 + c];
-  }
+  });
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     const double t = wave_sum_butterfly(s[c]);
@@ -309,23 +307,22 @@ __global__ __launch_bounds__(kThreads) void k_column_norms(int m, const int* __r
 
 // g = Js' r, one wavefront per free view as above; part_g[block] = max |g / scale| over the workgroup's views (the
 // gradient of the unscaled problem, which the gradient tolerance is about).
-__global__ __launch_bounds__(kThreads) void k_gradient(int m, const int* __restrict__ inc_off, const int* __restrict__ inc,
-                                                       const double* __restrict__ rec, const double* __restrict__ scale,
-                                                       double* __restrict__ g, double* __restrict__ part_g,
-                                                       const NlState* __restrict__ st) {
+__global__ __launch_bounds__(kThreads) void k_gradient(ViewGraphLists vg, const double* __restrict__ rec,
+                                                       const double* __restrict__ scale, double* __restrict__ g,
+                                                       double* __restrict__ part_g, const NlState* __restrict__ st) {
   __shared__ double red[kViewsPerBlock];
   if (st->done || !st->fresh) return;
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int v = blockIdx.x * kViewsPerBlock + wv;
   double gm = 0.0;
-  if (v < m) {   // wave-uniform
+  if (v < vg.m) {   // wave-uniform
     double s[3] = {0.0, 0.0, 0.0};
-    for (int k = inc_off[v] + lane; k < inc_off[v + 1]; k += 64) {
-      const double* R = rec + kRec * (size_t)(inc[k] >> 1);
-      const double* J = R + 9 * (inc[k] & 1);
+    for_each_incident_edge(vg, v, lane, [&](int e, bool plus) {
+      const double* R = rec + kRec * (size_t)e;
+      const double* J = R + 9 * (int)plus;
 #pragma unroll
       for (int c = 0; c < 3; ++c) s[c] += (J[c] * R[18] + J[3 + c] * R[19]) + J[6 + c] * R[20];
-    }
+    });
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const double t = wave_sum_butterfly(s[c]);
@@ -380,13 +377,12 @@ __global__ __launch_bounds__(kThreads) void k_post(int init, int m, const int* _
     gmax = red[0];
     __syncthreads();
     if (init) {
-      double c = 0.0, q = 0.0;
-      for (int k = threadIdx.x; k < nbE; k += kThreads) c += part_cost[k];
+      double q = 0.0;
       for (int k = threadIdx.x; k < m; k += kThreads) {
         const double* w = x + 3 * (size_t)free_view[k];
         q += (w[0] * w[0] + w[1] * w[1]) + w[2] * w[2];
       }
-      cost = block_sum<kThreads>(c, red);
+      cost = block_sum_column<kThreads>(part_cost, nbE, 1, 0, red);
       xn = block_sum<kThreads>(q, red);
     }
   }
@@ -414,18 +410,15 @@ __global__ __launch_bounds__(kThreads) void k_post(int init, int m, const int* _
 // 1e32) / radius, and g into row 3m, the factorisation's right-hand-side row:
 //   thread t < m       : free view t -- its 3 x 3 diagonal block, sum of J' J over its incident edges, and its part of g
 //   thread t = m + p   : pair p = (a > b) -- block (a, b) = sum of J_a' J_b over the pair's edges
-__global__ __launch_bounds__(kThreads) void k_assemble(int m, int P, int lda, const int* __restrict__ inc_off,
-                                                       const int* __restrict__ inc, const int* __restrict__ pair_off,
-                                                       const int* __restrict__ pair_edge, const int2* __restrict__ pair_rc,
-                                                       const int2* __restrict__ edges, const int* __restrict__ idx,
-                                                       const double* __restrict__ rec, const double* __restrict__ g,
-                                                       double* __restrict__ A, const NlState* __restrict__ st) {
+__global__ __launch_bounds__(kThreads) void k_assemble(ViewGraphLists vg, int lda, const double* __restrict__ rec,
+                                                       const double* __restrict__ g, double* __restrict__ A,
+                                                       const NlState* __restrict__ st) {
   if (st->done) return;
-  const int t = blockIdx.x * kThreads + threadIdx.x;
+  const int t = blockIdx.x * kThreads + threadIdx.x, m = vg.m;
   double acc[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   if (t < m) {
-    for (int k = inc_off[t]; k < inc_off[t + 1]; ++k) {
-      const double* J = rec + kRec * (size_t)(inc[k] >> 1) + 9 * (inc[k] & 1);
+    for (int k = vg.inc_off[t]; k < vg.inc_off[t + 1]; ++k) {
+      const double* J = rec + kRec * (size_t)(vg.inc[k] >> 1) + 9 * (vg.inc[k] & 1);
 #pragma unroll
       for (int r = 0; r < 3; ++r)
 #pragma unroll
@@ -440,12 +433,12 @@ __global__ __launch_bounds__(kThreads) void k_assemble(int m, int P, int lda, co
       A[(size_t)(3 * t + r) * lda + 3 * t + r] = d + fmin(fmax(d, 1e-6), 1e32) / radius;
       A[(size_t)(3 * m) * lda + 3 * t + r] = g[3 * (size_t)t + r];
     }
-  } else if (t < m + P) {
+  } else if (t < m + vg.P) {
     const int p = t - m;
-    const int2 rc = pair_rc[p];
-    for (int k = pair_off[p]; k < pair_off[p + 1]; ++k) {
-      const int e = pair_edge[k];
-      const bool second_is_row = idx[edges[e].y] == rc.x;
+    const int2 rc = vg.pair_rc[p];
+    for (int k = vg.pair_off[p]; k < vg.pair_off[p + 1]; ++k) {
+      const int e = vg.pair_edge[k];
+      const bool second_is_row = vg.idx[vg.edges[e].y] == rc.x;
       const double* Ja = rec + kRec * (size_t)e + (second_is_row ? 9 : 0);
       const double* Jb = rec + kRec * (size_t)e + (second_is_row ? 0 : 9);
 #pragma unroll
@@ -543,16 +536,8 @@ __global__ __launch_bounds__(kThreads) void k_decide(DecideArgs a, const double*
   __syncthreads();
   if (flags[0]) return;
   double sum[4];
-  for (int c = 0; c < 2; ++c) {
-    double s = 0.0;
-    for (int k = threadIdx.x; k < a.nbE; k += kThreads) s += part_cand[2 * (size_t)k + c];
-    sum[c] = block_sum<kThreads>(s, red);
-  }
-  for (int c = 0; c < 2; ++c) {
-    double s = 0.0;
-    for (int k = threadIdx.x; k < a.nbM; k += kThreads) s += part_step[2 * (size_t)k + c];
-    sum[2 + c] = block_sum<kThreads>(s, red);
-  }
+  for (int c = 0; c < 2; ++c) sum[c] = block_sum_column<kThreads>(part_cand, a.nbE, 2, c, red);
+  for (int c = 0; c < 2; ++c) sum[2 + c] = block_sum_column<kThreads>(part_step, a.nbM, 2, c, red);
   if (threadIdx.x == 0) {
     const double failed = *fail_flag;
     *fail_flag = 0.0;
@@ -644,7 +629,7 @@ extern "C" int theia_hip_nonlinear_rotations(int32_t num_views, double* orientat
   for (int v = 0; v < n && fixed; ++v) if (fixed[v]) out[v] = 1;
   ViewGraphPlan g;
   fill_view_graph_lists(n, out, E, edges, &g);
-  const int m = g.m, P = g.P;
+  const int m = g.m;
   theia_nonlinear_rotation_summary sm{};
   sm.num_views_in_problem = m;
   if (m == 0) {   // every view of every edge is held: nothing to solve
@@ -658,47 +643,42 @@ extern "C" int theia_hip_nonlinear_rotations(int32_t num_views, double* orientat
   int rc;
   if ((rc = thip::ensure_device())) return rc;
   hipStream_t st = nullptr;
-  const int lda = n3 + 1;   // row n3: the right-hand side
-  const size_t dense = (size_t)(n3 + 1) * lda;
   const int nbE = grid_of(E, kThreads), nbM = grid_of(m, kThreads), nbV = grid_of(m, kViewsPerBlock);
   const int rows = o.max_num_iterations + 1;
-  DevBuf<double> d_A, d_work, d_flag, d_x, d_xc, d_rel, d_rec, d_scale, d_g, d_y, d_pc, d_pg, d_pcand, d_pstep, d_trace;
-  DevBuf<int> d_idx, d_free, d_inc_off, d_inc, d_pair_off, d_pair_edge;
-  DevBuf<int2> d_edges, d_pair_rc;
+  DenseSpd A;   // row n3: the right-hand side
+  DeviceViewGraph dg;
+  DevBuf<double> d_x, d_xc, d_rel, d_rec, d_scale, d_g, d_y, d_pc, d_pg, d_pcand, d_pstep, d_trace;
   DevBuf<NlState> d_st;
   const std::vector<double> ones(n3, 1.0);
   // the dense system first: when it does not fit, that is the answer
-  if ((rc = d_A.alloc(dense)) || (rc = d_work.alloc(dense_cholesky_workspace(n3))) || (rc = d_flag.alloc(1)) ||
-      (rc = d_x.up(orientations, 3 * (size_t)n)) || (rc = d_xc.up(orientations, 3 * (size_t)n)) ||
-      (rc = d_rel.up(relative_rotations, 3 * (size_t)E)) || (rc = d_edges.up(edges, E)) || (rc = d_idx.up(g.idx.data(), n)) ||
-      (rc = d_free.up(g.free_view.data(), m)) || (rc = d_inc_off.up(g.inc_off.data(), (size_t)m + 1)) ||
-      (rc = d_inc.up(g.inc.data(), g.inc.size())) || (rc = d_pair_off.up(g.pair_off.data(), g.pair_off.size())) ||
-      (rc = d_pair_edge.up(g.pair_edge.data(), g.pair_edge.size())) || (rc = d_pair_rc.up(g.pair_rc.data(), g.pair_rc.size())) ||
+  if ((rc = A.alloc(n3, 1)) || (rc = d_x.up(orientations, 3 * (size_t)n)) || (rc = d_xc.up(orientations, 3 * (size_t)n)) ||
+      (rc = d_rel.up(relative_rotations, 3 * (size_t)E)) || (rc = dg.up(g, edges, E, n)) ||
       (rc = d_rec.alloc(kRec * (size_t)E)) || (rc = d_scale.up(ones.data(), n3)) || (rc = d_g.alloc(n3)) ||
       (rc = d_y.alloc(n3)) || (rc = d_pc.alloc(nbE)) || (rc = d_pg.alloc(nbV)) || (rc = d_pcand.alloc(2 * (size_t)nbE)) ||
       (rc = d_pstep.alloc(2 * (size_t)nbM)) || (rc = d_trace.alloc(5 * (size_t)rows)) || (rc = d_st.alloc(1)))
     return rc;
+  const ViewGraphLists& vg = dg.lists;
 
   NlState hs{};
   hs.radius = 1e4; hs.decrease = 2.0; hs.fresh = 1; hs.step_successful = 1;
   HIP_TRY(hipMemcpy(d_st.p, &hs, sizeof(NlState), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemsetAsync(d_flag.p, 0, sizeof(double), st));
+  HIP_TRY(hipMemsetAsync(A.flag(), 0, sizeof(double), st));
   HIP_TRY(hipMemsetAsync(d_rec.p, 0, sizeof(double) * kRec * (size_t)E, st));
   const double b = o.robust_loss_width * o.robust_loss_width;
   const int* done = &d_st.p->done;
 
   auto linearise = [&]() {
-    k_linearise<<<nbE, kThreads, 0, st>>>(E, d_edges.p, d_idx.p, d_x.p, d_rel.p, d_scale.p, b, d_rec.p, d_pc.p, d_st.p);
+    k_linearise<<<nbE, kThreads, 0, st>>>(E, vg.edges, vg.idx, d_x.p, d_rel.p, d_scale.p, b, d_rec.p, d_pc.p, d_st.p);
   };
   auto gradient_and_post = [&](int init) {
-    k_gradient<<<nbV, kThreads, 0, st>>>(m, d_inc_off.p, d_inc.p, d_rec.p, d_scale.p, d_g.p, d_pg.p, d_st.p);
-    k_post<<<1, kThreads, 0, st>>>(init, m, d_free.p, d_x.p, d_pc.p, nbE, d_pg.p, nbV, o.max_num_iterations,
+    k_gradient<<<nbV, kThreads, 0, st>>>(vg, d_rec.p, d_scale.p, d_g.p, d_pg.p, d_st.p);
+    k_post<<<1, kThreads, 0, st>>>(init, m, vg.free_view, d_x.p, d_pc.p, nbE, d_pg.p, nbV, o.max_num_iterations,
                                    o.gradient_tolerance, d_trace.p, rows, THEIA_ROTATION_TERM_GRADIENT_TOLERANCE,
                                    THEIA_ROTATION_TERM_MAX_ITERATIONS, THEIA_ROTATION_TERM_MIN_RADIUS, d_st.p);
   };
   // ---- the first linearisation: unscaled, the Jacobi scaling from its columns, then scaled
   linearise();
-  k_column_norms<<<nbV, kThreads, 0, st>>>(m, d_inc_off.p, d_inc.p, d_rec.p, d_scale.p);
+  k_column_norms<<<nbV, kThreads, 0, st>>>(vg, d_rec.p, d_scale.p);
   linearise();
   gradient_and_post(1);
   HIP_TRY(hipGetLastError());
@@ -709,25 +689,19 @@ extern "C" int theia_hip_nonlinear_rotations(int32_t num_views, double* orientat
   const int chunk_size = std::max(1, std::min(chunk_env ? atoi(chunk_env) : kDefaultChunk, kMaxChunk));
   DecideArgs da{nbE, nbM, 3 * n, rows, THEIA_ROTATION_TERM_PARAMETER_TOLERANCE, THEIA_ROTATION_TERM_FUNCTION_TOLERANCE,
                 THEIA_ROTATION_TERM_FAILURE, o.function_tolerance, o.parameter_tolerance, o.max_trust_region_radius};
-  for (int enqueued = 0; !hs.done && enqueued < o.max_num_iterations;) {
-    const int chunk = std::min(chunk_size, o.max_num_iterations - enqueued);
-    for (int c = 0; c < chunk; ++c) {
-      HIP_TRY(hipMemsetAsync(d_A.p, 0, sizeof(double) * dense, st));
-      k_assemble<<<grid_of((size_t)m + P, kThreads), kThreads, 0, st>>>(m, P, lda, d_inc_off.p, d_inc.p, d_pair_off.p,
-                                                                       d_pair_edge.p, d_pair_rc.p, d_edges.p, d_idx.p,
-                                                                       d_rec.p, d_g.p, d_A.p, d_st.p);
-      dense_cholesky_factor(n3, 1, d_A.p, lda, d_work.p, d_flag.p, st, done);
-      dense_cholesky_back_substitute(n3, d_A.p, lda, d_work.p, 1, d_A.p + (size_t)n3 * lda, lda, d_y.p, n3, st, done);
-      k_step<<<nbM, kThreads, 0, st>>>(m, d_free.p, d_x.p, d_scale.p, d_y.p, d_xc.p, d_pstep.p, d_st.p);
-      k_candidate<<<nbE, kThreads, 0, st>>>(E, d_edges.p, d_idx.p, d_xc.p, d_rel.p, d_rec.p, d_y.p, b, d_pcand.p, d_st.p);
-      k_decide<<<1, kThreads, 0, st>>>(da, d_pcand.p, d_pstep.p, d_flag.p, d_x.p, d_xc.p, d_trace.p, d_st.p);
-      linearise();
-      gradient_and_post(0);
-    }
-    enqueued += chunk;
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(&hs, d_st.p, sizeof(NlState), hipMemcpyDeviceToHost));
-  }
+  rc = run_until_done(o.max_num_iterations, chunk_size, d_st.p, &hs, [&]() {
+    if (int bad = A.clear(st)) return bad;
+    k_assemble<<<grid_of((size_t)m + g.P, kThreads), kThreads, 0, st>>>(vg, A.lda, d_rec.p, d_g.p, A.A(), d_st.p);
+    A.factor(1, st, done);
+    A.back_substitute(1, A.rhs_row(0), A.lda, d_y.p, st, done);
+    k_step<<<nbM, kThreads, 0, st>>>(m, vg.free_view, d_x.p, d_scale.p, d_y.p, d_xc.p, d_pstep.p, d_st.p);
+    k_candidate<<<nbE, kThreads, 0, st>>>(E, vg.edges, vg.idx, d_xc.p, d_rel.p, d_rec.p, d_y.p, b, d_pcand.p, d_st.p);
+    k_decide<<<1, kThreads, 0, st>>>(da, d_pcand.p, d_pstep.p, A.flag(), d_x.p, d_xc.p, d_trace.p, d_st.p);
+    linearise();
+    gradient_and_post(0);
+    return 0;
+  });
+  if (rc) return rc;
   if (!hs.done) return set_error(THEIA_HIP_ERR_INTERNAL, "the loop ended without a termination");
 
   // ---- Ceres copies its state back unless the solve failed

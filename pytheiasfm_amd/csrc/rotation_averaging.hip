@@ -19,10 +19,8 @@
 // round trip the reference takes (math/rotation.cc:56-66).
 #include "ransac_device.h"
 #include "rotation_compose.h"
-#include "ba_kernels.h"
-#include "wave_reduce.h"
-#include "device_util.h"
-#include "view_graph_plan.h"
+#include "dense_cholesky.h"
+#include "view_graph_device.h"
 
 #include <algorithm>
 #include <chrono>
@@ -62,19 +60,16 @@ __global__ __launch_bounds__(kThreads) void k_residual(int E, const int2* __rest
 // The lower triangle of L_w and the rows of A'W e, into the zeroed (m + 3) x lda array:
 //   thread t < m       : free view t -- diagonal sum of w over its incident edges, rhs row c = sum of sign * w * e_c
 //   thread t = m + p   : pair p = (a > b) -- A[a][b] = -sum of w over the pair's edges
-// inc, pair_edge, pair_rc: view_graph_plan.h.  w == nullptr: unit weights (A'A, A'e).
-__global__ __launch_bounds__(kThreads) void k_assemble(int m, int P, int lda, const int* __restrict__ inc_off,
-                                                       const int* __restrict__ inc, const int* __restrict__ pair_off,
-                                                       const int* __restrict__ pair_edge, const int2* __restrict__ pair_rc,
-                                                       const double* __restrict__ w, const double* __restrict__ res,
-                                                       double* __restrict__ A) {
-  const int t = blockIdx.x * kThreads + threadIdx.x;
+// vg: view_graph_device.h.  w == nullptr: unit weights (A'A, A'e).
+__global__ __launch_bounds__(kThreads) void k_assemble(ViewGraphLists vg, int lda, const double* __restrict__ w,
+                                                       const double* __restrict__ res, double* __restrict__ A) {
+  const int t = blockIdx.x * kThreads + threadIdx.x, m = vg.m;
   if (t < m) {
     double d = 0.0, g0 = 0.0, g1 = 0.0, g2 = 0.0;
-    for (int k = inc_off[t]; k < inc_off[t + 1]; ++k) {
-      const int e = inc[k] >> 1;
+    for (int k = vg.inc_off[t]; k < vg.inc_off[t + 1]; ++k) {
+      const int e = vg.inc[k] >> 1;
       const double we = w ? w[e] : 1.0;
-      const double sw = (inc[k] & 1) ? we : -we;
+      const double sw = (vg.inc[k] & 1) ? we : -we;
       d += we;
       g0 += sw * res[3 * (size_t)e]; g1 += sw * res[3 * (size_t)e + 1]; g2 += sw * res[3 * (size_t)e + 2];
     }
@@ -82,16 +77,18 @@ __global__ __launch_bounds__(kThreads) void k_assemble(int m, int P, int lda, co
     A[(size_t)m * lda + t] = g0;
     A[(size_t)(m + 1) * lda + t] = g1;
     A[(size_t)(m + 2) * lda + t] = g2;
-  } else if (t < m + P) {
+  } else if (t < m + vg.P) {
     const int p = t - m;
     double s = 0.0;
-    for (int k = pair_off[p]; k < pair_off[p + 1]; ++k) s += w ? w[pair_edge[k]] : 1.0;
-    const int2 rc = pair_rc[p];
+    for (int k = vg.pair_off[p]; k < vg.pair_off[p + 1]; ++k) s += w ? w[vg.pair_edge[k]] : 1.0;
+    const int2 rc = vg.pair_rc[p];
     A[(size_t)rc.x * lda + rc.y] = -s;
   }
 }
 
-// ADMM x-update right-hand side (l1_solver.h:128): g = A' (b + z - u), [3][m].
+// ADMM x-update right-hand side (l1_solver.h:128): g = A' (b + z - u), [3][m].  This kernel and k_admm_view run once per
+// ADMM iteration, each followed by a host read: they take the two lists they walk as pointers, which keeps their
+// arguments within one 64-byte line (with the whole ViewGraphLists the L1 stage measured 0.8 % slower).
 __global__ __launch_bounds__(kThreads) void k_admm_rhs(int m, const int* __restrict__ inc_off, const int* __restrict__ inc,
                                                        const double* __restrict__ b, const double* __restrict__ z,
                                                        const double* __restrict__ u, double* __restrict__ g) {
@@ -126,7 +123,7 @@ __global__ __launch_bounds__(kThreads) void k_admm_edge(int E, int m, const int2
       const double bq = b[q], zq = z[q], uq = u[q];
       const double ax_hat = alpha * ax + (1.0 - alpha) * (zq + bq);
       const double v = (ax_hat - bq) + uq;
-      const double zn = fmax(0.0, v - kappa) - fmax(0.0, -v - kappa);
+      const double zn = soft_threshold(v, kappa);
       zold[q] = zq;
       z[q] = zn;
       u[q] = uq + ((ax_hat - zn) - bq);
@@ -187,17 +184,6 @@ __global__ __launch_bounds__(kThreads) void k_update(int m, const int* __restric
   if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
-// Second stage of every reduction: out[c] = sum over blocks of part[block][c], one workgroup, fixed order.
-__global__ __launch_bounds__(kThreads) void k_reduce(const double* __restrict__ part, int nblk, int ncol, double* __restrict__ out) {
-  __shared__ double red[kThreads];
-  for (int c = 0; c < ncol; ++c) {
-    double s = 0.0;
-    for (int b = threadIdx.x; b < nblk; b += kThreads) s += part[(size_t)b * ncol + c];
-    s = block_sum<kThreads>(s, red);
-    if (threadIdx.x == 0) out[c] = s;
-  }
-}
-
 }  // namespace
 }  // namespace thip
 
@@ -219,49 +205,37 @@ extern "C" int theia_hip_robust_rotation_averaging(int32_t num_views, double* or
   int rc = build_view_graph_plan(n, fixed, E, edges, "fixed", &g);
   if (rc) return rc;
   *summary = theia_rotation_summary{};
-  const int m = g.m, P = g.P;
+  const int m = g.m;
   if (m == 0) { summary->setup_ms = ms_since(t_start); return 0; }   // nothing moves
 
   if ((rc = thip::ensure_device())) return rc;
-  const int lda = m + 3;
   const int nbE = grid_of(E, kThreads), nbV = grid_of(m, kThreads);
-  DevBuf<double> d_aa, d_rel, d_res, d_w, d_A, d_work, d_flag, d_b, d_z, d_u, d_zold, d_g, d_T, d_x, d_part, d_sums;
-  DevBuf<int2> d_edges, d_pair_rc;
-  DevBuf<int> d_idx, d_free, d_inc_off, d_inc, d_pair_off, d_pair_edge;
-  const size_t dense = (size_t)(m + 3) * lda;
-  if ((rc = d_A.alloc(dense)) || (rc = d_work.alloc(dense_cholesky_workspace(m))) || (rc = d_flag.alloc(1)) ||
-      (rc = d_aa.up(orientations, 3 * (size_t)n)) || (rc = d_rel.up(relative_rotations, 3 * (size_t)E)) ||
-      (rc = d_edges.up(edges, E)) || (rc = d_idx.up(g.idx.data(), n)) || (rc = d_free.up(g.free_view.data(), m)) ||
-      (rc = d_inc_off.up(g.inc_off.data(), m + 1)) || (rc = d_inc.up(g.inc.data(), g.inc.size())) ||
-      (rc = d_pair_off.up(g.pair_off.data(), g.pair_off.size())) || (rc = d_pair_edge.up(g.pair_edge.data(), g.pair_edge.size())) ||
-      (rc = d_pair_rc.up(g.pair_rc.data(), g.pair_rc.size())) || (rc = d_res.alloc(3 * (size_t)E)) || (rc = d_w.alloc(E)) ||
+  DenseSpd L;   // L_w and the three rows of A'W e
+  DeviceViewGraph dg;
+  DevBuf<double> d_aa, d_rel, d_res, d_w, d_b, d_z, d_u, d_zold, d_g, d_T, d_x, d_part, d_sums;
+  if ((rc = L.alloc(m, 3)) || (rc = d_aa.up(orientations, 3 * (size_t)n)) || (rc = d_rel.up(relative_rotations, 3 * (size_t)E)) ||
+      (rc = dg.up(g, edges, E, n)) || (rc = d_res.alloc(3 * (size_t)E)) || (rc = d_w.alloc(E)) ||
       (rc = d_b.alloc(3 * (size_t)E)) || (rc = d_z.alloc(3 * (size_t)E)) || (rc = d_u.alloc(3 * (size_t)E)) ||
       (rc = d_zold.alloc(3 * (size_t)E)) || (rc = d_g.alloc(3 * (size_t)m)) || (rc = d_T.alloc(3 * (size_t)m)) ||
       (rc = d_x.alloc(3 * (size_t)m)) || (rc = d_part.alloc(3 * (size_t)std::max(nbE, nbV))) || (rc = d_sums.alloc(8)))
     return rc;
+  const ViewGraphLists& vg = dg.lists;
   hipStream_t st = nullptr;
   const double sigma = o->irls_loss_parameter_sigma;
   double sums[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   // residuals and weights of the current orientations, |e|^2 -> sums[6]
   auto residuals = [&]() {
-    k_residual<<<nbE, kThreads, 0, st>>>(E, d_edges.p, d_rel.p, d_aa.p, sigma, d_res.p, d_w.p, d_part.p);
-    k_reduce<<<1, kThreads, 0, st>>>(d_part.p, nbE, 1, d_sums.p + 6);
+    k_residual<<<nbE, kThreads, 0, st>>>(E, vg.edges, d_rel.p, d_aa.p, sigma, d_res.p, d_w.p, d_part.p);
+    k_sum_partials<kThreads><<<1, kThreads, 0, st>>>(d_part.p, nbE, 1, d_sums.p + 6);
   };
   // update with d_x, new residuals; returns the average step size (sums[5] / m)
   auto update = [&](double* avg) -> int {
-    k_update<<<nbV, kThreads, 0, st>>>(m, d_free.p, d_x.p, d_aa.p, d_part.p);
-    k_reduce<<<1, kThreads, 0, st>>>(d_part.p, nbV, 1, d_sums.p + 5);
+    k_update<<<nbV, kThreads, 0, st>>>(m, vg.free_view, d_x.p, d_aa.p, d_part.p);
+    k_sum_partials<kThreads><<<1, kThreads, 0, st>>>(d_part.p, nbV, 1, d_sums.p + 5);
     residuals();
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(sums, d_sums.p, sizeof(sums), hipMemcpyDeviceToHost));
     *avg = sums[5] / m;
-    return 0;
-  };
-  auto factor_failed = [&](bool* failed) -> int {
-    double flag = 0.0;
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(&flag, d_flag.p, sizeof(double), hipMemcpyDeviceToHost));
-    *failed = flag != 0.0;
     return 0;
   };
   auto give_back = [&]() -> int {
@@ -270,15 +244,13 @@ extern "C" int theia_hip_robust_rotation_averaging(int32_t num_views, double* or
   };
 
   // ---- L1 stage (SolveL1Regression, :164-185; L1Solver, math/l1_solver.h): factor A'A = L (x) I_3 once
-  HIP_TRY(hipMemsetAsync(d_A.p, 0, sizeof(double) * dense, st));
-  HIP_TRY(hipMemsetAsync(d_flag.p, 0, sizeof(double), st));
+  if ((rc = L.clear(st, true))) return rc;
   HIP_TRY(hipMemsetAsync(d_x.p, 0, sizeof(double) * 3 * m, st));
   residuals();
-  k_assemble<<<grid_of(m + P, kThreads), kThreads, 0, st>>>(m, P, lda, d_inc_off.p, d_inc.p, d_pair_off.p, d_pair_edge.p,
-                                                           d_pair_rc.p, nullptr, d_res.p, d_A.p);
-  dense_cholesky_factor(m, 1, d_A.p, lda, d_work.p, d_flag.p, st);   // row m (A'e, unused) rides along
+  k_assemble<<<grid_of(m + g.P, kThreads), kThreads, 0, st>>>(vg, L.lda, nullptr, d_res.p, L.A());
+  L.factor(1, st);   // row m (A'e, unused) rides along
   bool failed = false;
-  if ((rc = factor_failed(&failed))) return rc;
+  if ((rc = L.failed(&failed))) return rc;
   HIP_TRY(hipMemcpy(sums, d_sums.p, sizeof(sums), hipMemcpyDeviceToHost));
   summary->setup_ms = ms_since(t_start);
   if (failed) return set_error(THEIA_HIP_ERR_INTERNAL, "the Cholesky factorisation of A'A failed");
@@ -293,12 +265,12 @@ extern "C" int theia_hip_robust_rotation_averaging(int32_t num_views, double* or
     HIP_TRY(hipMemsetAsync(d_u.p, 0, sizeof(double) * 3 * E, st));
     const double rhs_norm = std::sqrt(sums[6]);
     for (int it = 0; it < max_admm; ++it) {
-      k_admm_rhs<<<nbV, kThreads, 0, st>>>(m, d_inc_off.p, d_inc.p, d_b.p, d_z.p, d_u.p, d_g.p);
-      dense_cholesky_solve_factored(m, d_A.p, lda, d_work.p, 3, d_g.p, m, d_T.p, d_x.p, m, st);
-      k_admm_edge<<<nbE, kThreads, 0, st>>>(E, m, d_edges.p, d_idx.p, d_x.p, d_b.p, d_z.p, d_zold.p, d_u.p, alpha, 1.0 / rho, d_part.p);
-      k_reduce<<<1, kThreads, 0, st>>>(d_part.p, nbE, 3, d_sums.p);
-      k_admm_view<<<nbV, kThreads, 0, st>>>(m, d_inc_off.p, d_inc.p, d_z.p, d_zold.p, d_u.p, rho, d_part.p);
-      k_reduce<<<1, kThreads, 0, st>>>(d_part.p, nbV, 2, d_sums.p + 3);
+      k_admm_rhs<<<nbV, kThreads, 0, st>>>(m, vg.inc_off, vg.inc, d_b.p, d_z.p, d_u.p, d_g.p);
+      L.solve_factored(3, d_g.p, d_T.p, d_x.p, st);
+      k_admm_edge<<<nbE, kThreads, 0, st>>>(E, m, vg.edges, vg.idx, d_x.p, d_b.p, d_z.p, d_zold.p, d_u.p, alpha, 1.0 / rho, d_part.p);
+      k_sum_partials<kThreads><<<1, kThreads, 0, st>>>(d_part.p, nbE, 3, d_sums.p);
+      k_admm_view<<<nbV, kThreads, 0, st>>>(m, vg.inc_off, vg.inc, d_z.p, d_zold.p, d_u.p, rho, d_part.p);
+      k_sum_partials<kThreads><<<1, kThreads, 0, st>>>(d_part.p, nbV, 2, d_sums.p + 3);
       HIP_TRY(hipGetLastError());
       HIP_TRY(hipMemcpy(sums, d_sums.p, sizeof(double) * 5, hipMemcpyDeviceToHost));
       ++summary->admm_iterations;
@@ -319,18 +291,17 @@ extern "C" int theia_hip_robust_rotation_averaging(int32_t num_views, double* or
   // ---- IRLS stage (SolveIRLS, :187-250): per iteration factor L_w with the three rows of A'W e forward-substituted
   const auto t_irls = std::chrono::steady_clock::now();
   for (int it = 0; it < o->max_num_irls_iterations; ++it) {
-    HIP_TRY(hipMemsetAsync(d_A.p, 0, sizeof(double) * dense, st));
-    k_assemble<<<grid_of(m + P, kThreads), kThreads, 0, st>>>(m, P, lda, d_inc_off.p, d_inc.p, d_pair_off.p, d_pair_edge.p,
-                                                             d_pair_rc.p, d_w.p, d_res.p, d_A.p);
-    dense_cholesky_factor(m, 3, d_A.p, lda, d_work.p, d_flag.p, st);
-    if ((rc = factor_failed(&failed))) return rc;
+    if ((rc = L.clear(st))) return rc;
+    k_assemble<<<grid_of(m + g.P, kThreads), kThreads, 0, st>>>(vg, L.lda, d_w.p, d_res.p, L.A());
+    L.factor(3, st);
+    if ((rc = L.failed(&failed))) return rc;
     if (failed) {
       summary->irls_ms = ms_since(t_irls);
       summary->final_squared_residual = sums[6];
       if ((rc = give_back())) return rc;
       return set_error(THEIA_HIP_ERR_INTERNAL, "the Cholesky factorisation of A'WA failed in IRLS iteration %d", it);
     }
-    dense_cholesky_back_substitute(m, d_A.p, lda, d_work.p, 3, d_A.p + (size_t)m * lda, lda, d_x.p, m, st);
+    L.back_substitute(3, L.rhs_row(0), L.lda, d_x.p, st);
     double avg = 0.0;
     if ((rc = update(&avg))) return rc;
     ++summary->irls_iterations;
@@ -339,29 +310,4 @@ extern "C" int theia_hip_robust_rotation_averaging(int32_t num_views, double* or
   summary->irls_ms = ms_since(t_irls);
   summary->final_squared_residual = sums[6];
   return give_back();
-}
-
-// Introspection for the parity tests: factor A once, then solve the k right-hand sides against the factor
-// (dense_cholesky_solve_factored: the forward and backward kernels of the ADMM solves).
-extern "C" int theia_hip_dense_spd_solve_multi(int32_t n, const double* A, int32_t k, const double* B, double* X) {
-  if (n < 0 || k < 1 || (n > 0 && (!A || !B || !X))) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "bad argument");
-  if (n == 0) return 0;
-  int rc = thip::ensure_device();
-  if (rc) return rc;
-  const int lda = n + 1;   // row n: the factorisation's right-hand-side row (zero, unused)
-  DevBuf<double> dA, dw, dflag, dB, dT, dX;
-  if ((rc = dA.alloc((size_t)(n + 1) * lda)) || (rc = dw.alloc(dense_cholesky_workspace(n))) || (rc = dflag.alloc(1)) ||
-      (rc = dB.up(B, (size_t)k * n)) || (rc = dT.alloc((size_t)k * n)) || (rc = dX.alloc((size_t)k * n)))
-    return rc;
-  HIP_TRY(hipMemset(dA.p, 0, sizeof(double) * (size_t)(n + 1) * lda));
-  HIP_TRY(hipMemcpy2D(dA.p, sizeof(double) * lda, A, sizeof(double) * n, sizeof(double) * n, n, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemset(dflag.p, 0, sizeof(double)));
-  dense_cholesky_factor(n, 1, dA.p, lda, dw.p, dflag.p, nullptr);
-  dense_cholesky_solve_factored(n, dA.p, lda, dw.p, k, dB.p, n, dT.p, dX.p, n, nullptr);
-  HIP_TRY(hipGetLastError());
-  double flag = 0.0;
-  HIP_TRY(hipMemcpy(X, dX.p, sizeof(double) * (size_t)k * n, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(&flag, dflag.p, sizeof(double), hipMemcpyDeviceToHost));
-  if (flag != 0.0) return set_error(THEIA_HIP_ERR_INTERNAL, "matrix is not positive definite");
-  return 0;
 }

@@ -2,16 +2,20 @@
 // smallest eigenvalue of normal equations summed on 3 x 3 view blocks (ligt_positions.hip, linear_positions.hip): the
 // owner sums that assemble the lower triangle from per-constraint 3 x 3 items without atomics, the host plan that lists
 // every block's items, the one-vector inverse iteration step with its stopping test on the device, and the view pairs'
-// sign vote.  spectral_shift.h has the shift that goes in front of the factorisation.
+// sign vote.  spectral_shift.h has the shift that goes in front of the factorisation.  SmallestEigenvector, at the end,
+// is the host driver of all of it: what used to be the last 120 lines of each of the two entry points.
 //
 // Determinism: every entry of H is a sum in the order of the plan by one owner, every norm a fixed tree (block_sum), the
 // votes are integers.
 #ifndef THEIA_HIP_SMALLEST_EIGENVECTOR_H_
 #define THEIA_HIP_SMALLEST_EIGENVECTOR_H_
 #include "ransac_device.h"
+#include "dense_cholesky.h"
+#include "spectral_shift.h"
 #include "wave_reduce.h"
 
 #include <algorithm>
+#include <chrono>
 #include <vector>
 
 namespace thip {
@@ -193,6 +197,116 @@ __global__ __launch_bounds__(THREADS) void k_sign_vote(int E, const int2* __rest
   }
   if (threadIdx.x == 0 && red[0] != 0) atomicAdd(votes, red[0]);
 }
+
+// The host side after a stage has its view index and its items' plan: H + mu I from a device array of 3 x 3 items, one
+// factorisation, the inverse iteration in chunks, the sign vote, the scatter.  The steps are called in the order they
+// are declared; what the two stages do differently (their items kernel, the *_ms field a phase is booked to, whether
+// there are view pairs to vote) stays between the calls.  Summary: theia_ligt_summary or theia_linear_triplet_summary.
+struct SmallestEigenvector {
+  static constexpr int kThreads = 256;
+  static constexpr int kChunk = 4;   // inverse iterations enqueued between two reads of the `done` flag
+  int n3 = 0, num_blocks = 0;
+  DenseSpd H;   // row n3: the factorisation's right-hand-side row (zero, unused)
+  DevBuf<double> d_full, d_x, d_b, d_y, d_T;
+  DevBuf<long long> d_seg_off;
+  DevBuf<int> d_seg_item, d_votes;
+  DevBuf<int2> d_block_rc;
+  DevBuf<InverseIterationState> d_st;
+  InverseIterationState hs{};
+  int votes = 0;
+  std::vector<double> x, full;
+
+  // The dense system of mf free views first: when it does not fit, that is the answer, before the host builds lists of
+  // its size.  want_full: system_out is asked for.
+  int alloc(int mf, bool want_full) {
+    n3 = 3 * mf;
+    int rc;
+    if ((rc = H.alloc(n3, 1)) || (want_full && (rc = d_full.alloc((size_t)n3 * n3)))) return rc;
+    return 0;
+  }
+  // the plan, the vectors, and everything cleared (enqueued, not waited for)
+  int upload(const BlockSegments& seg, hipStream_t st) {
+    num_blocks = (int)seg.block_rc.size();
+    int rc;
+    if ((rc = d_seg_off.up(seg.seg_off.data(), seg.seg_off.size())) || (rc = d_seg_item.up(seg.seg_item.data(), seg.seg_item.size())) ||
+        (rc = d_block_rc.up(seg.block_rc.data(), seg.block_rc.size())) || (rc = d_votes.alloc(1)) || (rc = d_x.alloc(n3)) ||
+        (rc = d_b.alloc(n3)) || (rc = d_y.alloc(n3)) || (rc = d_T.alloc(n3)) || (rc = d_st.alloc(1)) || (rc = H.clear(st, true)))
+      return rc;
+    HIP_TRY(hipMemsetAsync(d_votes.p, 0, sizeof(int), st));
+    HIP_TRY(hipMemsetAsync(d_st.p, 0, sizeof(InverseIterationState), st));
+    return 0;
+  }
+  // H from the items, system_out's copy of it, the shift and the start vector; waits for them
+  int assemble(const double* d_items, double shift_multiple, hipStream_t st) {
+    k_blocks<kThreads><<<grid_of(num_blocks, kThreads), kThreads, 0, st>>>(num_blocks, d_block_rc.p, d_seg_off.p, d_seg_item.p,
+                                                                          d_items, H.lda, H.A());
+    if (d_full.p)
+      k_full_system<kThreads><<<grid_of((size_t)n3 * n3, kThreads), kThreads, 0, st>>>(n3, H.lda, H.A(), d_full.p);
+    k_shift<kThreads><<<1, kThreads, 0, st>>>(n3, H.lda, H.A(), shift_multiple, d_x.p, d_b.p, &d_st.p->shift, &d_st.p->max_diag);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+  }
+  // factors H + mu I once; a failure leaves *out = *sm with the shift and is the error returned
+  template <class Summary>
+  int factor(hipStream_t st, Summary* sm, Summary* out) {
+    const auto t_factor = std::chrono::steady_clock::now();
+    H.factor(1, st);
+    bool failed = false;
+    if (int rc = H.failed(&failed)) return rc;
+    sm->factor_ms = ms_since(t_factor);
+    if (failed) {
+      HIP_TRY(hipMemcpy(&hs, d_st.p, sizeof(InverseIterationState), hipMemcpyDeviceToHost));
+      sm->shift = hs.shift;
+      *out = *sm;
+      return set_error(THEIA_HIP_ERR_INTERNAL, "the Cholesky factorisation of H + mu I failed (mu = %g)", hs.shift);
+    }
+    return 0;
+  }
+  // inverse iteration from x = 1 / sqrt(n) until the step is <= threshold or the cap
+  int iterate(int max_iterations, double threshold, hipStream_t st) {
+    const int* done = &d_st.p->done;
+    return run_until_done(max_iterations, kChunk, d_st.p, &hs, [&]() {
+      H.solve_factored(1, d_b.p, d_T.p, d_y.p, st, done);
+      k_iterate<kThreads><<<1, kThreads, 0, st>>>(n3, d_y.p, d_x.p, d_b.p, threshold, d_st.p);
+      return 0;
+    });
+  }
+  int vote(int E, const int2* edges, const int* idx, const double* R, const double* rel, hipStream_t st) {
+    k_sign_vote<kThreads><<<grid_of(E, kThreads), kThreads, 0, st>>>(E, edges, idx, d_x.p, R, rel, d_votes.p);
+    HIP_TRY(hipGetLastError());
+    return 0;
+  }
+  int fetch() {
+    x.resize(n3);
+    HIP_TRY(hipMemcpy(x.data(), d_x.p, sizeof(double) * (size_t)n3, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&votes, d_votes.p, sizeof(int), hipMemcpyDeviceToHost));
+    if (d_full.p) {
+      full.resize((size_t)n3 * n3);
+      HIP_TRY(hipMemcpy(full.data(), d_full.p, sizeof(double) * full.size(), hipMemcpyDeviceToHost));
+    }
+    return 0;
+  }
+  // idx [n]: >= 0 the view's index in the system, -1 the held view (the origin), -2 not in the system
+  template <class Summary>
+  void scatter(int n, const std::vector<int>& idx, double* positions_out, uint8_t* estimated_out, double* system_out,
+               int32_t* system_index_out, Summary* sm) const {
+    sm->iterations = hs.iterations;
+    sm->converged = hs.converged;
+    sm->eigenvalue = hs.eigenvalue;
+    sm->shift = hs.shift;
+    sm->sign_votes = votes;
+    sm->flipped = votes < 0;
+    const double sign = votes < 0 ? -1.0 : 1.0;
+    for (int v = 0; v < n; ++v) {
+      estimated_out[v] = idx[v] != -2;
+      if (idx[v] == -2) continue;
+      for (int c = 0; c < 3; ++c) positions_out[3 * (size_t)v + c] = idx[v] >= 0 ? sign * x[3 * (size_t)idx[v] + c] : 0.0;
+    }
+    if (system_out) std::copy(full.begin(), full.end(), system_out);
+    if (system_index_out) std::copy(idx.begin(), idx.end(), system_index_out);
+  }
+};
 
 }  // namespace thip
 #endif

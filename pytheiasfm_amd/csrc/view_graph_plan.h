@@ -4,6 +4,8 @@
 // two fix a view per connected component (build_view_graph_plan); the third fixes none and leaves out the views without
 // edges (it checks its graph itself, with view_graph_components, and calls fill_view_graph_lists), and so does the
 // fourth, which also leaves out the views its caller holds.
+// The device side -- the upload of these lists, the struct the kernels take them in, the walk of a free view's incident
+// edges -- is view_graph_device.h; this header stays host code only.
 //
 // The lists, as the kernels read them:
 //   inc[inc_off[t] .. inc_off[t + 1])            the edges incident to free view t, in edge order;

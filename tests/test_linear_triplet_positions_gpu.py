@@ -178,6 +178,27 @@ def test_bit_reproducible(name):
     assert (summ.eigenvalue, summ.shift) == (s2.eigenvalue, s2.shift)
 
 
+def test_iteration_cap():
+    """max_power_iterations below, at and just past one chunk of four enqueued iterations, and at the uncapped count N:
+    the count is min(cap, N), converged says whether the cap let the test pass, and stopping at the cap is no error (the
+    call returns 0 and gives the iterate it reached).  v12_sparse_noisy: the restatement needs 7 iterations at the default
+    threshold, and the device may stop one step apart from it."""
+    s, _ = ls.scene("v12_sparse_noisy")
+    p, _, summ, _ = run("v12_sparse_noisy")
+    N = summ.iterations
+    assert summ.converged == 1 and N >= 6
+    for cap in (1, 4, 5, N):
+        o = global_pose.LinearPositionEstimatorOptions()
+        o.max_power_iterations = cap
+        rc, pc, _, sc, _ = call(s, options=o, positions_out=np.full((s["num_views"], 3), 7.0))   # as in run()
+        print(f"cap {cap}: rc {rc}, iterations {sc.iterations}, converged {sc.converged} (uncapped: {N})")
+        assert rc == 0
+        assert sc.iterations == min(cap, N)
+        assert sc.converged == int(cap >= N)
+        if cap == N:
+            assert pc.tobytes() == p.tobytes()
+
+
 def test_views_outside_the_system_are_left_alone():
     _, r = ls.scene("v14_two_components")
     p, est, summ, extra = run("v14_two_components")
