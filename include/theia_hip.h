@@ -1215,6 +1215,19 @@ int theia_hip_selftest_svd9_team(int32_t team, int32_t with_v, int32_t count, co
 /* five_point_pre_team<16> (k_fit5_a_team) against five_point_pre.  corr [count][5][4] = (x1, y1, x2, y2); record per
  * problem, 137 doubles: ok | N [9][4] | M [10][10] (N and M only when ok). */
 int theia_hip_selftest_five_point_pre_team(int32_t count, const double* corr, double* team_out, double* single_out);
+/* Self-checks of the rotation maps of the global-pose stages, one lane per case in 256-thread workgroups, on `count`
+ * caller-supplied cases; the tests compare the results with 50-digit arithmetic.  No reference counterpart.
+ * THEIA_HIP_ERR_INVALID_ARGUMENT for count < 1, a null pointer or a width that is not positive and finite.
+ * rotation_maps (csrc/selftest_rotation_maps.hip): a, b [count][3] angle-axis; record per case, 18 doubles:
+ * angle_axis_to_rot(a) [3][3] row-major | rot_to_angle_axis of that matrix [3] | multiply_rotations(a, b) [3] |
+ * eigen_rot_to_rotvec of that matrix [3].
+ * pairwise_rotation_error (csrc/nonlinear_rotations.hip): the edge record of the NONLINEAR rotation estimator's
+ * linearisation for w_i, w_j, rel [count][3], both views free, unit Jacobi scale, SoftL1 of `width`; record per case, 22
+ * doubles: J_i [3][3] | J_j [3][3] (row-major, corrected) | corrected residual [3] | the logarithm's branch (0: trace >= 0;
+ * 1 + i: largest diagonal entry i). */
+int theia_hip_selftest_rotation_maps(int32_t count, const double* a, const double* b, double* out);
+int theia_hip_selftest_pairwise_rotation_error(int32_t count, const double* w_i, const double* w_j, const double* rel,
+                                               double width, double* out);
 
 /* The batch entry points above keep their device workspace and the pinned host blocks of their per-round transfers in
  * process-wide caches between calls (up to 6 GiB of device memory and 2 GiB of pinned host memory); the buffers of a

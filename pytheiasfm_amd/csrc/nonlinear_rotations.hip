@@ -26,6 +26,9 @@
 // chunk (lud_positions.hip's pattern).  The factorisation is in place and fills the lower triangle, so the array is cleared
 // before every assembly.
 //
+// theia_hip_selftest_pairwise_rotation_error at the bottom is test-only: k_selftest_edge runs linearise_edge, the per-edge
+// body of k_linearise, on caller-supplied vectors, for tests/test_wide_rotations_gpu.py to compare with 50-digit values.
+//
 // Determinism: no atomics of this file's own (the factorisation's fail flag is the only one, and it is only compared with
 // zero).  Every sum has one owner and a fixed order.  Two runs on one input are bit-identical.
 #include "dense_cholesky.h"
@@ -247,6 +250,24 @@ __device__ __forceinline__ void jacobian_columns(const EdgeEval& v, bool free_i,
   }
 }
 
+// The record of one edge at (wi, wj): o = (Js_i, Js_j, corrected residual), a held view's block left as it is.  Returns
+// rho; `branch` is the branch the logarithm took (LogCtx).  k_linearise and the self-check entry at the bottom share it.
+__device__ __forceinline__ double linearise_edge(const double* wi, const double* wj, const double* wr, bool free_i,
+                                                 bool free_j, const double* si, const double* sj, double b,
+                                                 double* __restrict__ o, int& branch) {
+  EdgeEval v;
+  edge_eval(wi, wj, wr, b, v);
+  double Ji[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, Jj[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  jacobian_columns<0>(v, free_i, free_j, si, sj, Ji, Jj);
+  jacobian_columns<1>(v, free_i, free_j, si, sj, Ji, Jj);
+  jacobian_columns<2>(v, free_i, free_j, si, sj, Ji, Jj);
+#pragma unroll
+  for (int q = 0; q < 9; ++q) { o[q] = Ji[q]; o[9 + q] = Jj[q]; }
+  o[18] = v.r[0] * v.sr; o[19] = v.r[1] * v.sr; o[20] = v.r[2] * v.sr;
+  branch = v.L.branch;
+  return v.rho;
+}
+
 // One lane per edge: the record rec[e] = (Js_i, Js_j, corrected residual) at x, and the blocks' sums of rho.  An edge
 // between two held views is not in the problem (Ceres drops a residual block whose parameter blocks are all constant).
 __global__ __launch_bounds__(kThreads) void k_linearise(int E, const int2* __restrict__ edges, const int* __restrict__ idx,
@@ -269,17 +290,8 @@ __global__ __launch_bounds__(kThreads) void k_linearise(int E, const int2* __res
         if (a >= 0) si[k] = scale[3 * (size_t)a + k];
         if (c >= 0) sj[k] = scale[3 * (size_t)c + k];
       }
-      EdgeEval v;
-      edge_eval(wi, wj, wr, b, v);
-      rho = v.rho;
-      double Ji[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, Jj[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-      jacobian_columns<0>(v, a >= 0, c >= 0, si, sj, Ji, Jj);
-      jacobian_columns<1>(v, a >= 0, c >= 0, si, sj, Ji, Jj);
-      jacobian_columns<2>(v, a >= 0, c >= 0, si, sj, Ji, Jj);
-      double* o = rec + kRec * (size_t)e;
-#pragma unroll
-      for (int q = 0; q < 9; ++q) { o[q] = Ji[q]; o[9 + q] = Jj[q]; }
-      o[18] = v.r[0] * v.sr; o[19] = v.r[1] * v.sr; o[20] = v.r[2] * v.sr;
+      int branch;
+      rho = linearise_edge(wi, wj, wr, a >= 0, c >= 0, si, sj, b, rec + kRec * (size_t)e, branch);
     }
   }
   const double s = block_sum<kThreads>(rho, red);
@@ -587,6 +599,24 @@ __global__ __launch_bounds__(kThreads) void k_decide(DecideArgs a, const double*
     for (int k = threadIdx.x; k < a.n3_views; k += kThreads) x[k] = xc[k];
 }
 
+// Self-check entry: one lane per case, both views free at unit Jacobi scale.  Record (22 doubles): the edge record's 21,
+// then the logarithm's branch.
+constexpr int kSelftestRec = 22;
+__global__ __launch_bounds__(kThreads) void k_selftest_edge(int count, const double* __restrict__ w_i,
+                                                            const double* __restrict__ w_j, const double* __restrict__ rel,
+                                                            double b, double* __restrict__ out) {
+  const int e = blockIdx.x * kThreads + threadIdx.x;
+  if (e >= count) return;
+  double wi[3], wj[3], wr[3];
+  const double one[3] = {1.0, 1.0, 1.0};
+#pragma unroll
+  for (int k = 0; k < 3; ++k) { wi[k] = w_i[3 * (size_t)e + k]; wj[k] = w_j[3 * (size_t)e + k]; wr[k] = rel[3 * (size_t)e + k]; }
+  double* o = out + kSelftestRec * (size_t)e;
+  int branch;
+  linearise_edge(wi, wj, wr, true, true, one, one, b, o, branch);
+  o[21] = (double)branch;
+}
+
 bool positive_finite(double v) { return v > 0.0 && std::isfinite(v); }
 bool nonnegative_finite(double v) { return v >= 0.0 && std::isfinite(v); }
 
@@ -727,5 +757,21 @@ extern "C" int theia_hip_nonlinear_rotations(int32_t num_views, double* orientat
   sm.final_gradient_max_norm = hs.gmax;
   sm.seconds = ms_since(t_start) * 1e-3;
   *summary = sm;
+  return 0;
+}
+
+extern "C" int theia_hip_selftest_pairwise_rotation_error(int32_t count, const double* w_i, const double* w_j,
+                                                          const double* rel, double width, double* out) {
+  if (count < 1 || count > (1 << 20)) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "count = %d", count);
+  if (!w_i || !w_j || !rel || !out) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "null pointer");
+  if (!positive_finite(width)) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "width must be positive and finite");
+  int rc = thip::ensure_device();
+  if (rc) return rc;
+  DevBuf<double> d_i, d_j, d_rel, d_out;
+  const size_t n3 = 3 * (size_t)count, rec = kSelftestRec * (size_t)count;
+  if ((rc = d_i.up(w_i, n3)) || (rc = d_j.up(w_j, n3)) || (rc = d_rel.up(rel, n3)) || (rc = d_out.alloc(rec))) return rc;
+  k_selftest_edge<<<grid_of(count, kThreads), kThreads, 0, nullptr>>>(count, d_i.p, d_j.p, d_rel.p, width * width, d_out.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(out, d_out.p, sizeof(double) * rec, hipMemcpyDeviceToHost));
   return 0;
 }
