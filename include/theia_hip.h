@@ -424,6 +424,12 @@ int theia_hip_ba_destroy(theia_ba_handle h);
 int theia_hip_ba_plan_info(theia_ba_handle h, int32_t* n, int32_t* k3_levels, double* k3_flops, int32_t* fused_runs,
                            int32_t* slow_path_tracks);
 
+/* Which kernel instances a run() of the handle dispatches to, for the tests: one line of text per kernel family, for
+ * example "k_lin_schur pd=3 models=all lossk=2 first=0" or "k_lin_schur_i pd=4 models=notrig lossk=0 bw=13 kmask=0",
+ * NUL-terminated in buf[cap].  The values come from the host functions the launch sites themselves branch on.
+ * THEIA_HIP_ERR_INVALID_ARGUMENT when cap is too small. */
+int theia_hip_ba_kernel_instances(theia_ba_handle h, char* buf, int32_t cap);
+
 
 /* Covariance blocks at the handle's current state for the two block-diagonal problems behind the
  * *WithCov entry points (bundle_adjustment.cc:288-386,420-499; GetCovarianceFor{Track,Tracks,View,Views},

@@ -79,6 +79,14 @@ class BaHandle:
         capi.check(L.theia_hip_ba_plan_info(self._h, C.byref(n), C.byref(lv), C.byref(fl), C.byref(runs), C.byref(slow)))
         return {"n": n.value, "k3_levels": lv.value, "k3_flops": fl.value, "fused_runs": runs.value, "slow_path_tracks": slow.value}
 
+    def kernel_instances(self):
+        """theia_hip_ba_kernel_instances: the kernel instances a run() dispatches to, one string per kernel family."""
+        L = capi.lib()
+        L.theia_hip_ba_kernel_instances.argtypes = [C.c_void_p, C.c_char_p, C.c_int32]
+        buf = C.create_string_buffer(4096)
+        capi.check(L.theia_hip_ba_kernel_instances(self._h, buf, len(buf)))
+        return buf.value.decode().splitlines()
+
     def snapshot(self):
         """Keep a device-resident copy of the current parameters (theia_hip_ba_snapshot_parameters)."""
         L = capi.lib()

@@ -835,6 +835,39 @@ __global__ __launch_bounds__(256) void k_scale_from_colsq(DevProblem P, const do
 
 }  // namespace
 
+// The instance of k_lin_schur / k_backsub_runs a problem takes: what the launch sites below branch on and what
+// theia_hip_ba_kernel_instances reports.
+FusedInstance lin_schur_instance(const DevProblem& P) {
+  FusedInstance f{};
+  f.pd = P.pd == 3 ? 3 : 4;
+  f.trig = (P.model_mask & ~kModelsNoTrig) != 0;   // FOV / fisheye groups present
+  f.lossk = loss_class(P.loss_type);
+  return f;
+}
+bool backsub_runs_applies(const DevProblem& P) {
+  static const bool off = getenv("THEIA_HIP_BACKSUB_TILES") != nullptr;   // development: the round-4 kernel (one wave per tile, gathers)
+  return !(off || P.ni || P.n_fruns == 0 || !P.camrot || !P.camrot_cand || !P.camdir || P.fused_bw);
+}
+FusedInstance backsub_runs_instance(const DevProblem& P) {
+  static const int wps = [] { const char* e = getenv("THEIA_HIP_BACKSUB_WAVES"); return e ? atoi(e) : 3; }();   // waves per SIMD the register allocation aims at (trivial loss: 3 with 56 B of spills measured 0.901 ms per iteration against 0.925 at 2 without)
+  FusedInstance f = lin_schur_instance(P);
+  f.waves = (wps == 3 && f.lossk == 0) ? 3 : 2;
+  return f;
+}
+bool backsub_runs_intr_applies(const DevProblem& P) {
+  static const bool off = getenv("THEIA_HIP_BACKSUB_TILES") != nullptr;
+  return !(off || !P.ni || !P.fused_bw || P.n_fruns == 0 || !P.camrot || !P.camrot_cand || !P.frun_stage);
+}
+FusedInstance backsub_runs_intr_instance(const DevProblem& P) {
+  constexpr unsigned kFR = (1u << 0) | (3u << 5);   // FOCAL_LENGTH | RADIAL_DISTORTION (ba_fused_intr.hip: kMaskFocalRadial)
+  FusedInstance f = lin_schur_instance(P);
+  f.lossk = P.loss_type == THEIA_LOSS_TRIVIAL ? 0 : 2;   // (two loss instances: the trivial loss, everything else with the full corrector)
+  f.waves = 2;
+  f.bw = P.fused_bw;
+  f.kmask = P.fused_kmask == kFR;
+  return f;
+}
+
 void launch_cam_prep(const DevProblem& P, const double* cam, const double* intr, double* camrot, hipStream_t st, const double* ycam) {
   if (P.nc > 0) k_cam_prep<<<(P.nc + 255) / 256, 256, 0, st>>>(P, cam, intr, camrot, ycam);
 }
@@ -845,11 +878,12 @@ void launch_linearize_fused(const DevProblem& P, const double* cam, const double
   if (!P.camrot_current || P.n_sum_items == 0) launch_cam_prep(P, cam, P.intr, P.camrot, st);   // (otherwise k_schur_sum left the run queue's head at zero)
   static const int wgs = [] { const char* e = getenv("THEIA_HIP_FUSED_WGS"); return e ? std::max(1, atoi(e)) : 512; }();   // 2 per CU
   const int grid = std::min(P.n_fruns, wgs);
-  const bool trig = (P.model_mask & ~kModelsNoTrig) != 0;   // FOV / fisheye groups present
+  const FusedInstance fi = lin_schur_instance(P);
+  const bool trig = fi.trig;
   {
-    const int lk = loss_class(P.loss_type);
+    const int lk = fi.lossk;
     static const bool stamps = getenv("THEIA_HIP_FUSED_STAMPS") != nullptr;   // development: instrumented instance + report
-    if (stamps && P.pd == 3 && !trig && lk == 0) {
+    if (stamps && fi.pd == 3 && !trig && lk == 0) {
       static int launches = 0;
       k_lin_schur<3, 4, kModelsNoTrig, 0, true><<<grid, 256, 0, st>>>(P, pts, radius, Vinv, tile_part);
       if (++launches % 16 == 0) {
@@ -871,7 +905,7 @@ void launch_linearize_fused(const DevProblem& P, const double* cam, const double
       if (lk == 0) k_lin_schur<PD_, 4, M_, 0><<<grid, 256, 0, st>>>(P, pts, radius, Vinv, tile_part); \
       else if (lk == 1) k_lin_schur<PD_, 4, M_, 1><<<grid, 256, 0, st>>>(P, pts, radius, Vinv, tile_part); \
       else k_lin_schur<PD_, 4, M_, 2><<<grid, 256, 0, st>>>(P, pts, radius, Vinv, tile_part); } while (0)
-    if (P.pd == 3) { if (trig) THIP_LS(3, kModelsAll); else THIP_LS(3, kModelsNoTrig); }
+    if (fi.pd == 3) { if (trig) THIP_LS(3, kModelsAll); else THIP_LS(3, kModelsNoTrig); }
     else { if (trig) THIP_LS(4, kModelsAll); else THIP_LS(4, kModelsNoTrig); }
 #undef THIP_LS
   }
@@ -889,13 +923,14 @@ void launch_linearize_fused_first(const DevProblem& P, const double* ones_c, con
   launch_cam_prep(Q, cam, Q.intr, Q.camrot, st);
   static const int wgs = [] { const char* e = getenv("THEIA_HIP_FUSED_WGS"); return e ? std::max(1, atoi(e)) : 512; }();
   const int grid = std::min(P.n_fruns, wgs);
-  const bool trig = (P.model_mask & ~kModelsNoTrig) != 0;
-  const int lk = loss_class(P.loss_type);
+  const FusedInstance fi = lin_schur_instance(P);
+  const bool trig = fi.trig;
+  const int lk = fi.lossk;
 #define THIP_LS1(PD_, M_) do { \
     if (lk == 0) k_lin_schur<PD_, 4, M_, 0, false, true><<<grid, 256, 0, st>>>(Q, pts, radius, Vinv, tile_part, scale_p); \
     else if (lk == 1) k_lin_schur<PD_, 4, M_, 1, false, true><<<grid, 256, 0, st>>>(Q, pts, radius, Vinv, tile_part, scale_p); \
     else k_lin_schur<PD_, 4, M_, 2, false, true><<<grid, 256, 0, st>>>(Q, pts, radius, Vinv, tile_part, scale_p); } while (0)
-  if (P.pd == 3) { if (trig) THIP_LS1(3, kModelsAll); else THIP_LS1(3, kModelsNoTrig); }
+  if (fi.pd == 3) { if (trig) THIP_LS1(3, kModelsAll); else THIP_LS1(3, kModelsNoTrig); }
   else { if (trig) THIP_LS1(4, kModelsAll); else THIP_LS1(4, kModelsNoTrig); }
 #undef THIP_LS1
   k_schur_sum<<<(P.n_sum_items + 3) / 4, 256, 0, st>>>(P.n_sum_items, P.sum_items, P.sum_src, P.fpart, rb.S, P.n, rb.rhs, rb.gc, rb.colsq, P.frun_next);
@@ -907,19 +942,18 @@ void launch_linearize_fused_first(const DevProblem& P, const double* ones_c, con
 
 // K4 + K5 over the runs of the fused plan (k_backsub_runs); false: not applicable (the caller takes k_backsub)
 bool launch_backsub_runs(const DevProblem& P, const double* pts, double* cand_pts, const double* Vinv, double* tile_part, hipStream_t st) {
-  static const bool off = getenv("THEIA_HIP_BACKSUB_TILES") != nullptr;   // development: the round-4 kernel (one wave per tile, gathers)
-  if (off || P.ni || P.n_fruns == 0 || !P.camrot || !P.camrot_cand || !P.camdir || P.fused_bw) return false;
+  if (!backsub_runs_applies(P)) return false;
   static const int wgs_env = [] { const char* e = getenv("THEIA_HIP_BACKSUB_WGS"); return e ? std::max(1, atoi(e)) : 0; }();
-  const bool trig = (P.model_mask & ~kModelsNoTrig) != 0;
-  const int lk = loss_class(P.loss_type);
-  static const int wps = [] { const char* e = getenv("THEIA_HIP_BACKSUB_WAVES"); return e ? atoi(e) : 3; }();   // waves per SIMD the register allocation aims at (trivial loss: 3 with 56 B of spills measured 0.901 ms per iteration against 0.925 at 2 without)
-  const int grid = std::min(P.n_fruns, wgs_env ? wgs_env : 256 * (wps == 3 && lk == 0 ? 3 : 2));
+  const FusedInstance fi = backsub_runs_instance(P);
+  const bool trig = fi.trig;
+  const int lk = fi.lossk;
+  const int grid = std::min(P.n_fruns, wgs_env ? wgs_env : 256 * fi.waves);
 #define THIP_BS(PD_, M_) do { \
-    if (wps == 3 && lk == 0) k_backsub_runs<PD_, 4, M_, 0, 3><<<grid, 256, 0, st>>>(P, pts, cand_pts, Vinv, tile_part); \
+    if (fi.waves == 3) k_backsub_runs<PD_, 4, M_, 0, 3><<<grid, 256, 0, st>>>(P, pts, cand_pts, Vinv, tile_part); \
     else if (lk == 0) k_backsub_runs<PD_, 4, M_, 0, 2><<<grid, 256, 0, st>>>(P, pts, cand_pts, Vinv, tile_part); \
     else if (lk == 1) k_backsub_runs<PD_, 4, M_, 1, 2><<<grid, 256, 0, st>>>(P, pts, cand_pts, Vinv, tile_part); \
     else k_backsub_runs<PD_, 4, M_, 2, 2><<<grid, 256, 0, st>>>(P, pts, cand_pts, Vinv, tile_part); } while (0)
-  if (P.pd == 3) { if (trig) THIP_BS(3, kModelsAll); else THIP_BS(3, kModelsNoTrig); }
+  if (fi.pd == 3) { if (trig) THIP_BS(3, kModelsAll); else THIP_BS(3, kModelsNoTrig); }
   else { if (trig) THIP_BS(4, kModelsAll); else THIP_BS(4, kModelsNoTrig); }
 #undef THIP_BS
   return true;
@@ -928,17 +962,17 @@ bool launch_backsub_runs(const DevProblem& P, const double* pts, double* cand_pt
 // the same over the runs of the compound-block plan (free intrinsics): y = the solved step, intrinsics slots first
 bool launch_backsub_runs_intr(const DevProblem& P, const double* pts, double* cand_pts, const double* Vinv, double* tile_part,
                               const double* y, hipStream_t st) {
-  static const bool off = getenv("THEIA_HIP_BACKSUB_TILES") != nullptr;
-  if (off || !P.ni || !P.fused_bw || P.n_fruns == 0 || !P.camrot || !P.camrot_cand || !P.frun_stage) return false;
+  if (!backsub_runs_intr_applies(P)) return false;
   constexpr unsigned kFR = (1u << 0) | (3u << 5);   // FOCAL_LENGTH | RADIAL_DISTORTION (ba_fused_intr.hip: kMaskFocalRadial)
-  const bool trig = (P.model_mask & ~kModelsNoTrig) != 0;
-  const bool trivial = P.loss_type == THEIA_LOSS_TRIVIAL;
+  const FusedInstance fi = backsub_runs_intr_instance(P);
+  const bool trig = fi.trig;
+  const bool trivial = fi.lossk == 0;
   const int grid = std::min(P.n_fruns, 512);
 #define THIP_BSI2(PD_, M_, LK_) do { \
-    if (P.fused_kmask == kFR) k_backsub_runs<PD_, 4, M_, LK_, 2, true, kFR><<<grid, 256, 0, st>>>(P, pts, cand_pts, Vinv, tile_part, y); \
+    if (fi.kmask) k_backsub_runs<PD_, 4, M_, LK_, 2, true, kFR><<<grid, 256, 0, st>>>(P, pts, cand_pts, Vinv, tile_part, y); \
     else k_backsub_runs<PD_, 4, M_, LK_, 2, true, 0u><<<grid, 256, 0, st>>>(P, pts, cand_pts, Vinv, tile_part, y); } while (0)
 #define THIP_BSI(PD_, M_) do { if (trivial) THIP_BSI2(PD_, M_, 0); else THIP_BSI2(PD_, M_, 2); } while (0)
-  if (P.pd == 3) { if (trig) THIP_BSI(3, kModelsAll); else THIP_BSI(3, kModelsNoTrig); }
+  if (fi.pd == 3) { if (trig) THIP_BSI(3, kModelsAll); else THIP_BSI(3, kModelsNoTrig); }
   else { if (trig) THIP_BSI(4, kModelsAll); else THIP_BSI(4, kModelsNoTrig); }
 #undef THIP_BSI
 #undef THIP_BSI2

@@ -554,27 +554,40 @@ __global__ void k_scatter_colsq(DevProblem P, const double* __restrict__ colsq_r
 
 }  // namespace
 
+// FOCAL_LENGTH | RADIAL_DISTORTION on the perspective / double-sphere / unified models (parameters 0, 5, 6): the pipelines' default
+constexpr unsigned kMaskFocalRadial = (1u << 0) | (3u << 5);
+
+// The instance of k_lin_schur_i a problem takes: what the launch site below branches on and what
+// theia_hip_ba_kernel_instances reports.  bw: 9 (up to three rows), 10 (four), 13 (up to seven), else 16 (up to ten).
+FusedInstance lin_schur_intr_instance(const DevProblem& P) {
+  FusedInstance f{};
+  f.pd = P.pd == 3 ? 3 : 4;
+  f.trig = (P.model_mask & ~kModelsNoTrig) != 0;
+  f.lossk = P.loss_type == THEIA_LOSS_TRIVIAL ? 0 : 2;   // (two loss instances: the trivial loss without corrector code, everything else with the full corrector)
+  f.bw = (P.fused_bw == 9 || P.fused_bw == 10 || P.fused_bw == 13) ? P.fused_bw : 16;
+  f.kmask = f.bw == 9 && P.fused_kmask == kMaskFocalRadial;
+  return f;
+}
+
 void launch_linearize_fused_intr(const DevProblem& P, const double* cam, const double* pts, const double* radius,
                                  const ReduceBuf& rb, double* Vinv, double* tile_part, hipStream_t st) {
   if (P.n_fruns == 0) return;
   launch_cam_prep(P, cam, P.intr, P.camrot, st);
   static const int wgs = [] { const char* e = getenv("THEIA_HIP_FUSED_WGS"); return e ? std::max(1, atoi(e)) : 512; }();
   const int grid = std::min(P.n_fruns, wgs);
-  const bool trig = (P.model_mask & ~kModelsNoTrig) != 0;
-// FOCAL_LENGTH | RADIAL_DISTORTION on the perspective / double-sphere / unified models (parameters 0, 5, 6): the pipelines' default
-constexpr unsigned kMaskFocalRadial = (1u << 0) | (3u << 5);
+  const FusedInstance fi = lin_schur_intr_instance(P);
+  const bool trig = fi.trig;
 #define THIP_LSI2(PD_, M_, LK_)                                                                              \
   do {                                                                                                         \
-    if (P.fused_bw == 9 && P.fused_kmask == kMaskFocalRadial)                                                     \
+    if (fi.kmask)                                                                                                \
       k_lin_schur_i<PD_, 4, M_, 3, kMaskFocalRadial, LK_><<<grid, 256, 0, st>>>(P, pts, radius, Vinv, tile_part);    \
-    else if (P.fused_bw == 9) k_lin_schur_i<PD_, 4, M_, 3, 0u, LK_><<<grid, 256, 0, st>>>(P, pts, radius, Vinv, tile_part); \
-    else if (P.fused_bw == 10) k_lin_schur_i<PD_, 4, M_, 4, 0u, LK_><<<grid, 256, 0, st>>>(P, pts, radius, Vinv, tile_part); \
-    else if (P.fused_bw == 13) k_lin_schur_i<PD_, 4, M_, 7, 0u, LK_><<<grid, 256, 0, st>>>(P, pts, radius, Vinv, tile_part);   /* up to seven rows */ \
+    else if (fi.bw == 9) k_lin_schur_i<PD_, 4, M_, 3, 0u, LK_><<<grid, 256, 0, st>>>(P, pts, radius, Vinv, tile_part); \
+    else if (fi.bw == 10) k_lin_schur_i<PD_, 4, M_, 4, 0u, LK_><<<grid, 256, 0, st>>>(P, pts, radius, Vinv, tile_part); \
+    else if (fi.bw == 13) k_lin_schur_i<PD_, 4, M_, 7, 0u, LK_><<<grid, 256, 0, st>>>(P, pts, radius, Vinv, tile_part);   /* up to seven rows */ \
     else k_lin_schur_i<PD_, 4, M_, 10, 0u, LK_><<<grid, 256, 0, st>>>(P, pts, radius, Vinv, tile_part);   /* 16: up to ten rows */ \
   } while (0)
-  // (two loss instances: the trivial loss without corrector code, everything else with the full corrector)
-#define THIP_LSI(PD_, M_) do { if (P.loss_type == THEIA_LOSS_TRIVIAL) THIP_LSI2(PD_, M_, 0); else THIP_LSI2(PD_, M_, 2); } while (0)
-  if (P.pd == 3) { if (trig) THIP_LSI(3, kModelsAll); else THIP_LSI(3, kModelsNoTrig); }
+#define THIP_LSI(PD_, M_) do { if (fi.lossk == 0) THIP_LSI2(PD_, M_, 0); else THIP_LSI2(PD_, M_, 2); } while (0)
+  if (fi.pd == 3) { if (trig) THIP_LSI(3, kModelsAll); else THIP_LSI(3, kModelsNoTrig); }
   else { if (trig) THIP_LSI(4, kModelsAll); else THIP_LSI(4, kModelsNoTrig); }
 #undef THIP_LSI2
 #undef THIP_LSI

@@ -984,13 +984,28 @@ void launch_inner_cost(const InnerArgs& A0, double* part, double* out2, hipStrea
   k_inner_cost_reduce<<<1, 256, 0, st>>>(A, part, nb, out2);
 }
 
+// The instances of the three sweep kernels a problem takes: what launch_inner_sweep branches on and what
+// theia_hip_ba_kernel_instances reports.
+InnerInstance inner_instance(const DevProblem& P) {
+  InnerInstance f{};
+  f.trig = (P.model_mask & ~kModelsNoTrig) != 0;   // FOV / fisheye groups present
+  f.lossk = inner_loss_class(P.loss_type);
+  f.lean = !f.trig && f.lossk < 2;   // no FOV / fisheye group, no log / atan loss
+  f.lossk1 = f.lossk == 0 ? 0 : 1;
+  f.priors = P.n_priors > 0;
+  f.kc = P.intr_rows == 4 ? 4 : 10;   // 4: no group frees more than four parameters (create())
+  f.pd = P.pd == 3 ? 3 : 4;
+  return f;
+}
+
 void launch_inner_sweep(const InnerArgs& A0, hipStream_t st, int stages) {   // stages: 1 cameras, 2 intrinsics groups, 4 points
   const InnerArgs A = normalised(A0);
   static const int skip = [] { const char* e = getenv("THEIA_HIP_INNER_SKIP"); return e ? atoi(e) : 0; }();   // development switch
-  const bool lean = (A.P.model_mask & ~kModelsNoTrig) == 0 && inner_loss_class(A.P.loss_type) < 2;   // no FOV / fisheye group, no log / atan loss
-  const int lk1 = inner_loss_class(A.P.loss_type) == 0 ? 0 : 1;
+  const InnerInstance ii = inner_instance(A.P);
+  const bool lean = ii.lean;
+  const int lk1 = ii.lossk1;
   if (A.P.nc > 0 && (stages & 1) && !(skip & 1)) {
-    if (A.P.n_priors > 0) {
+    if (ii.priors) {
       if (lean && lk1 == 0) k_inner_views<kModelsNoTrig, 0, true><<<A.P.nc, 256, 0, st>>>(A);
       else if (lean) k_inner_views<kModelsNoTrig, 1, true><<<A.P.nc, 256, 0, st>>>(A);
       else k_inner_views<kModelsAll, 2, true><<<A.P.nc, 256, 0, st>>>(A);
@@ -1011,7 +1026,7 @@ void launch_inner_sweep(const InnerArgs& A0, hipStream_t st, int stages) {   // 
     (void)hipStreamIsCapturing(st, &cap);
     static const bool single = getenv("THEIA_HIP_INNER_GROUPS_SINGLE") != nullptr;
     const int parts = (A.grp_wgs > 1 && A.grp_part && A.grp_bar) ? A.grp_wgs : 1;   // the summation order of BOTH launches
-    const bool compact = A.P.intr_rows == 4;   // no group frees more than four parameters (create())
+    const bool compact = ii.kc == 4;
     if (parts > 1 && cap == hipStreamCaptureStatusNone && !single) {
       if (hipMemsetAsync(A.grp_bar, 0, sizeof(int) * (2 * (size_t)A.P.ng_total + 2), st) == hipSuccess) {
         InnerArgs Ac = A;
@@ -1045,13 +1060,13 @@ void launch_inner_sweep(const InnerArgs& A0, hipStream_t st, int stages) {   // 
     k_inner_cam_blocks<<<(A.P.nc + 255) / 256, 256, 0, st>>>(A);
     if (A.P.ntiles > 0) {
       const unsigned nb = (unsigned)(A.P.ntiles + 3) / 4;
-      const bool trig = (A.P.model_mask & ~kModelsNoTrig) != 0;   // FOV / fisheye groups present
-      const int lk = inner_loss_class(A.P.loss_type);
+      const bool trig = ii.trig;
+      const int lk = ii.lossk;
 #define THIP_IT(PD_, M_) do { \
         if (lk == 0) k_inner_tracks<PD_, M_, 0><<<nb, 256, 0, st>>>(A); \
         else if (lk == 1) k_inner_tracks<PD_, M_, 1><<<nb, 256, 0, st>>>(A); \
         else k_inner_tracks<PD_, M_, 2><<<nb, 256, 0, st>>>(A); } while (0)
-      if (A.P.pd == 3) { if (trig) THIP_IT(3, kModelsAll); else THIP_IT(3, kModelsNoTrig); }
+      if (ii.pd == 3) { if (trig) THIP_IT(3, kModelsAll); else THIP_IT(3, kModelsNoTrig); }
       else { if (trig) THIP_IT(4, kModelsAll); else THIP_IT(4, kModelsNoTrig); }
 #undef THIP_IT
     }

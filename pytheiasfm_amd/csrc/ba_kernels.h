@@ -185,6 +185,35 @@ void launch_inner_cost(const InnerArgs& A, double* part, double* out2, hipStream
 void launch_inner_norms_cost(const InnerArgs& A, const double* cam0, const double* pts0, const double* intr0, double* out4, double* part,
                              hipStream_t st);
 
+// Which template instance the launch sites of the fused and the inner-iteration kernels take.  Each launch site branches
+// on the value its file's helper returns, and theia_hip_ba_kernel_instances (ba_query.hip) prints the same value: the
+// report cannot drift from the dispatch.
+struct FusedInstance {   // k_lin_schur, k_backsub_runs (ba_fused.hip), k_lin_schur_i (ba_fused_intr.hip)
+  int pd;          // point parametrisation: 3 or 4
+  bool trig;       // kModelsAll (an FOV or fisheye group is present), else kModelsNoTrig
+  int lossk;       // LOSSK of the instance
+  int waves;       // k_backsub_runs: waves per SIMD the register allocation aims at (2 or 3)
+  int bw;          // free intrinsics: the compound block width (9, 10, 13, 16), else 0
+  bool kmask;      // free intrinsics: the FOCAL_LENGTH | RADIAL_DISTORTION instance
+};
+FusedInstance lin_schur_instance(const DevProblem& P);          // launch_linearize_fused, launch_linearize_fused_first
+FusedInstance lin_schur_intr_instance(const DevProblem& P);     // launch_linearize_fused_intr
+bool backsub_runs_applies(const DevProblem& P);                 // launch_backsub_runs takes the step (else: k_backsub)
+FusedInstance backsub_runs_instance(const DevProblem& P);
+bool backsub_runs_intr_applies(const DevProblem& P);            // the same for launch_backsub_runs_intr
+FusedInstance backsub_runs_intr_instance(const DevProblem& P);
+struct InnerInstance {   // k_inner_views, k_inner_groups, k_inner_tracks (ba_inner.hip)
+  bool lean;       // k_inner_views / k_inner_groups: kModelsNoTrig with loss class lossk1; otherwise <kModelsAll, 2>
+  int lossk1;      // 0 trivial, 1 any other loss (only read when lean)
+  bool priors;     // k_inner_views: the instance with camera priors
+  int kc;          // k_inner_groups: rows per group, 4 or 10
+  int pd; bool trig; int lossk;   // k_inner_tracks
+};
+InnerInstance inner_instance(const DevProblem& P);              // launch_inner_sweep
+// which assembly launch_linearize takes for the tracks inside a wave tile
+enum LinRoute { LIN_NONE = 0, LIN_FUSED, LIN_FUSED_INTR, LIN_GATHER_INTR, LIN_GATHER };
+LinRoute linearize_route(const DevProblem& P);
+
 void launch_colnorm(const DevProblem& P, const double* cam, const double* pts, double* colsq_c,
                     double* colsq_p, double* colsq_i, hipStream_t st);
 void launch_build_scale_red(const DevProblem& P, double* scale_red, hipStream_t st);

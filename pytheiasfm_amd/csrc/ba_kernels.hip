@@ -1488,18 +1488,27 @@ void launch_make_scale(int count, const double* colsq, double* scale, hipStream_
   k_make_scale<<<(count + 255) / 256, 256, 0, st>>>(count, colsq, scale);
 }
 
+LinRoute linearize_route(const DevProblem& P) {
+  if (P.ntiles == 0) return LIN_NONE;
+  if (P.n_fruns > 0 && P.ni == 0) return LIN_FUSED;              // fused linearise + Schur (ba_fused.hip)
+  if (P.n_fruns > 0 && P.fused_bw > 0) return LIN_FUSED_INTR;    // the same with compound [extrinsics | intrinsics] blocks (ba_fused_intr.hip)
+  if (P.rec && P.ni > 0) return LIN_GATHER_INTR;                 // intrinsics optimised: 16-wide camera-side blocks on the gather lists
+  if (P.rec && P.ni == 0) return LIN_GATHER;
+  return LIN_NONE;
+}
+
 void launch_linearize(const DevProblem& P, const double* cam, const double* pts, const double* radius,
                       const ReduceBuf& rb, double* Vinv, double* gp, double* tile_part, hipStream_t st) {
-  if (P.ntiles == 0) return;
-  if (P.n_fruns > 0 && P.ni == 0) {   // fused linearise + Schur (ba_fused.hip)
+  const LinRoute route = linearize_route(P);
+  if (route == LIN_FUSED) {
     launch_linearize_fused(P, cam, pts, radius, rb, Vinv, tile_part, st);
     return;
   }
-  if (P.n_fruns > 0 && P.fused_bw > 0) {   // the same with compound [extrinsics | intrinsics] blocks (ba_fused_intr.hip)
+  if (route == LIN_FUSED_INTR) {
     launch_linearize_fused_intr(P, cam, pts, radius, rb, Vinv, tile_part, st);
     return;
   }
-  if (P.rec && P.ni > 0) {   // intrinsics optimised: 16-wide camera-side blocks on the gather lists
+  if (route == LIN_GATHER_INTR) {
     const int g = tile_blocks(P.ntiles);
 #define THIP_INTR(PD_, KI_)                                                                              \
     do {                                                                                                   \
@@ -1511,7 +1520,7 @@ void launch_linearize(const DevProblem& P, const double* cam, const double* pts,
 #undef THIP_INTR
     return;
   }
-  if (P.rec && P.ni == 0) {
+  if (route == LIN_GATHER) {
     const int g = tile_blocks(P.ntiles);
     if (P.pd == 3) k_lin_obs<3><<<g, kBlock, 0, st>>>(P, cam, pts, radius, Vinv, gp, tile_part);
     else k_lin_obs<4><<<g, kBlock, 0, st>>>(P, cam, pts, radius, Vinv, gp, tile_part);

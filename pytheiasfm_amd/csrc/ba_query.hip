@@ -1,10 +1,58 @@
 // ba_query.hip -- the entry points that read a BA handle without running a solve: evaluation of residuals and Jacobians,
 // the covariance blocks, the reduced system of one linearisation, and the dense SPD solve the tests call directly.
 #include <cmath>
+#include <cstdio>
+#include <string>
 
 #include "ba_handle.h"
 
 extern "C" {
+
+// One line per kernel family a run() of the handle launches, from the helpers the launch sites branch on (ba_kernels.h).
+int theia_hip_ba_kernel_instances(theia_ba_handle h, char* buf, int32_t cap) {
+  if (!h || !buf || cap <= 0) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  std::string out;
+  auto line = [&out](const char* fmt, auto... a) { char t[160]; snprintf(t, sizeof(t), fmt, a...); out += t; out += '\n'; };
+  auto models = [](bool trig) { return trig ? "all" : "notrig"; };
+  if (h->idh) {
+    line("inverse_depth");
+  } else {
+    const DevProblem& P = h->P;
+    const LinRoute route = linearize_route(P);
+    if (route == LIN_FUSED) {
+      const FusedInstance f = lin_schur_instance(P);
+      line("k_lin_schur pd=%d models=%s lossk=%d first=0", f.pd, models(f.trig), f.lossk);
+      if (scale_fold_applies(h)) line("k_lin_schur pd=%d models=%s lossk=%d first=1", f.pd, models(f.trig), f.lossk);
+      if (backsub_runs_applies(P)) {
+        const FusedInstance b = backsub_runs_instance(P);
+        line("k_backsub_runs pd=%d models=%s lossk=%d waves=%d intr=0 kmask=0", b.pd, models(b.trig), b.lossk, b.waves);
+      } else line("k_backsub pd=%d intr=0 rot=1", P.pd);
+    } else if (route == LIN_FUSED_INTR) {
+      const FusedInstance f = lin_schur_intr_instance(P);
+      line("k_lin_schur_i pd=%d models=%s lossk=%d bw=%d kmask=%d", f.pd, models(f.trig), f.lossk, f.bw, (int)f.kmask);
+      if (backsub_runs_intr_applies(P)) {
+        const FusedInstance b = backsub_runs_intr_instance(P);
+        line("k_backsub_runs pd=%d models=%s lossk=%d waves=%d intr=1 kmask=%d", b.pd, models(b.trig), b.lossk, b.waves, (int)b.kmask);
+      } else line("k_backsub pd=%d intr=1 rot=1", P.pd);
+    } else if (route == LIN_GATHER_INTR) {
+      line("k_lin_obs_intr pd=%d ki=%d", P.pd, P.intr_rows == 4 ? 4 : 10);
+      line("k_backsub pd=%d intr=1 rot=0", P.pd);
+    } else if (route == LIN_GATHER) {
+      line("k_lin_obs pd=%d", P.pd);
+      line("k_backsub pd=%d intr=0 rot=0", P.pd);
+    }
+    if (P.long_nobs > 0) line("k_long pd=%d intr=%d", P.pd, P.ni ? 1 : 0);
+    if (h->inner && h->opt.use_inner_iterations != 0) {
+      const InnerInstance i = inner_instance(P);
+      if (P.nc > 0) line("k_inner_views models=%s lossk=%d priors=%d", models(!i.lean), i.lean ? i.lossk1 : 2, (int)i.priors);
+      if (P.ni > 0 && P.ng_total > 0) line("k_inner_groups models=%s lossk=%d kc=%d", models(!i.lean), i.lean ? i.lossk1 : 2, i.kc);
+      if (P.ntiles > 0) line("k_inner_tracks pd=%d models=%s lossk=%d", i.pd, models(i.trig), i.lossk);
+    }
+  }
+  if ((size_t)cap <= out.size()) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "kernel_instances: buffer too small");
+  std::memcpy(buf, out.c_str(), out.size() + 1);
+  return 0;
+}
 
 int theia_hip_ba_evaluate(theia_ba_handle h, double* cost, double* residuals, double* jac_cam, double* jac_pt, uint8_t* valid) {
   return theia_hip_ba_evaluate_ex(h, cost, residuals, jac_cam, jac_pt, nullptr, valid);

@@ -112,6 +112,12 @@ __global__ void k_lm_control(LmState* st, const double* __restrict__ sa, const d
                              const LmCtl* __restrict__ cp) {
   lm_control_body(st, sa, sb, cp);
 }
+// The trace entry of an accepted step waits for the gradient at the accepted point, which the next body's linearisation
+// brings (pending_grad).  A solve that ends with that step has no next body: run() linearises once more and this fills it.
+__global__ void k_lm_pending_gradient(LmState* st, const double* __restrict__ sa, double* __restrict__ tg) {
+  if (st->pending_grad >= 0) tg[st->pending_grad] = sa[SC_GMAX];
+  st->pending_grad = -1;
+}
 // The tile reduction of the trial step (launch_reduce_tiles cfg 1 -> scalB) and the step control in one launch.
 __global__ __launch_bounds__(1024) void k_reduce_control(int ntiles, const double* __restrict__ part,
                                                          const int* __restrict__ f2s, const int* __restrict__ fmaxflag,
@@ -1014,6 +1020,13 @@ int theia_hip_ba_run(theia_ba_handle h, theia_ba_summary* S) {
       S->num_linearize_launches++;
     }
     if (st.done) break;
+  }
+  if (ctl.trace_capacity && st.pending_grad >= 0 && st.term != THEIA_TERM_FAILURE) {
+    // the last step was accepted at the iteration cap (or the time ran out after it): the gradient its trace entry reports
+    // is the one at the accepted point (ceres evaluates it as part of the successful step), so linearise there once more
+    if ((rc = enqueue_linearize(h, -1, false))) return rc;
+    k_lm_pending_gradient<<<1, 1, 0, h->stream>>>(dst, h->rb.scal, h->tr_g.p);
+    HIP_TRYR(hipStreamSynchronize(h->stream));
   }
   if (ctl.trace_capacity) {
     const int k = std::min(st.trace_size, S->trace_capacity);
