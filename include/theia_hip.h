@@ -627,6 +627,68 @@ int theia_hip_nonlinear_rotations(int32_t num_views, double* orientations /* [n]
                                   theia_nonlinear_rotation_summary* summary, double* trace_out /* optional */,
                                   int32_t trace_capacity);
 
+/* NonlinearPositionEstimator::EstimatePositions (global_pose_estimation/nonlinear_position_estimator.cc:136-206 with
+ * pairwise_translation_error.h:65-100; the NONLINEAR global position estimator, the default of
+ * ReconstructionEstimatorOptions, global_reconstruction_estimator.cc:431): Ceres' Levenberg-Marquardt solve over one
+ * PairwiseTranslationError block per pair and one per observation of a selected track, under
+ * HuberLoss(robust_loss_width), restated on the device in FP64 (csrc/nonlinear_positions.hip).  The
+ * unknowns are 3-vectors: the positions [num_views][3] and the points [num_points][3], both in/out.
+ *   camera-to-camera (:226-259): edges [num_edges][2] = (i, j) with relative_translations [num_edges][3] =
+ *     TwoViewInfo::position_2; direction t = R(orientations[i])' position_2 (ceres::AngleAxisToRotationMatrix), weight 1,
+ *     scale = scale_estimates[e] (TwoViewInfo::scale_estimate), NULL = all -1; repeated and reversed pairs add up
+ *   point-to-camera (:382-412): track t = observations track_offsets[t] .. track_offsets[t + 1] - 1 of obs_view [N] /
+ *     obs_feature [N][2] (normalised), one edge each from the view to the point; direction
+ *     normalize(R(w_ray)' [x, y, 1]) with w_ray = ray_orientations[view], NULL = orientations (the reference rotates the
+ *     ray by the camera's own stored orientation, :68-75); weight point_to_camera_weight, scale -1
+ *   residual with d = x_second - x_first: scale > 0: w (d - scale t); otherwise w (d / |d| - t), and with |d| < 1e-12 the
+ *     norm is the constant 1.  The Jacobians are closed forms of the branch taken.
+ * The solver is that of theia_hip_nonlinear_rotations: TrustRegionMinimizer + LevenbergMarquardtStrategy of Ceres 2.2 on
+ * the dense normal equations of order 3 (free views + points); the points are not Schur-eliminated (DESIGN.md 3.6l on
+ * the reference's choice of linear solver).  fixed [num_views] non-zero = held constant (no columns, not in |x|, bits
+ * unchanged), or NULL; a view without an edge is left untouched; a pair between two held views is not in the problem;
+ * points are never held.  The gauge (a translation, and a scale too where no edge carries a scale estimate) is free
+ * unless views are held: only the LM diagonal makes the system definite then.
+ * trace_out and the return value as theia_hip_nonlinear_rotations; summary->termination takes the THEIA_ROTATION_TERM_*
+ * values above, which name the rules of the loop the two stages share.  After THEIA_ROTATION_TERM_FAILURE positions and
+ * points are as passed in, otherwise they hold the last accepted iterate; with nothing free the call returns 0 with
+ * THEIA_ROTATION_TERM_NONE.
+ * THEIA_HIP_ERR_INVALID_ARGUMENT (checked before the device is touched; arrays untouched, summary zeroed): no views; no
+ * edges of either kind; an index out of range; an edge from a view to itself; a non-finite input; a width, a weight or a
+ * maximum radius that is not positive and finite; a tolerance that is negative or not finite; max_num_iterations < 0;
+ * num_points > 0 with a null array; track_offsets that do not start at 0 and increase strictly; an observation naming a
+ * view twice in one track.
+ * THEIA_HIP_ERR_OUT_OF_MEMORY: the dense (3m + 1)^2 array of doubles does not fit on the device. */
+typedef struct theia_nonlinear_position_options {
+  int32_t max_num_iterations;      /* 400 */
+  int32_t reserved;
+  double robust_loss_width;        /* 0.1 */
+  double function_tolerance;       /* 1e-6 */
+  double gradient_tolerance;       /* 1e-10 */
+  double parameter_tolerance;      /* 1e-8 */
+  double max_trust_region_radius;  /* 1e16 */
+} theia_nonlinear_position_options;
+typedef struct theia_nonlinear_position_summary {
+  int32_t iterations;              /* as theia_nonlinear_rotation_summary */
+  int32_t num_successful_steps, num_unsuccessful_steps, num_invalid_steps;
+  int32_t termination;             /* THEIA_ROTATION_TERM_* */
+  int32_t num_views_in_problem;    /* the views that take columns */
+  int32_t trace_size;
+  int32_t num_points_in_problem;
+  int32_t num_camera_edges_in_problem;   /* pairs with a free end */
+  int32_t num_point_edges_in_problem;
+  double initial_cost, final_cost, final_radius, final_gradient_max_norm, seconds;
+} theia_nonlinear_position_summary;
+int theia_hip_nonlinear_positions(int32_t num_views, const double* orientations /* [n][3] */,
+                                  double* positions /* [n][3], in/out */, const uint8_t* fixed /* [n] or NULL */,
+                                  int32_t num_edges, const int32_t* edges, const double* relative_translations,
+                                  const double* scale_estimates /* [E] or NULL */, int32_t num_points,
+                                  double* points /* [T][3], in/out, or NULL */, const int32_t* track_offsets /* [T + 1] */,
+                                  const int32_t* obs_view, const double* obs_feature,
+                                  const double* ray_orientations /* [n][3] or NULL */, double point_to_camera_weight,
+                                  const theia_nonlinear_position_options* options /*NULL = defaults*/,
+                                  theia_nonlinear_position_summary* summary, double* trace_out /* optional */,
+                                  int32_t trace_capacity);
+
 /* LeastUnsquaredDeviationPositionEstimator::EstimatePositions (global_pose_estimation/
  * least_unsquared_deviation_position_estimator.cc:75-213; pybind sfm.cc:1196-1204, 1707-1726, the default
  * LEAST_UNSQUARED_DEVIATION position stage of the global pipeline): per pair e = (i, j) the rows c_j - c_i - s_e d_e with

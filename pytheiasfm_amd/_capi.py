@@ -197,7 +197,27 @@ class NonlinearRotationSummary(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
-# theia_hip.h THEIA_ROTATION_TERM_*
+class NonlinearPositionOptions(C.Structure):
+    """theia_nonlinear_position_options."""
+    _fields_ = [("max_num_iterations", C.c_int32), ("reserved", C.c_int32), ("robust_loss_width", C.c_double),
+                ("function_tolerance", C.c_double), ("gradient_tolerance", C.c_double),
+                ("parameter_tolerance", C.c_double), ("max_trust_region_radius", C.c_double)]
+
+
+class NonlinearPositionSummary(C.Structure):
+    """theia_nonlinear_position_summary."""
+    _fields_ = [("iterations", C.c_int32), ("num_successful_steps", C.c_int32), ("num_unsuccessful_steps", C.c_int32),
+                ("num_invalid_steps", C.c_int32), ("termination", C.c_int32), ("num_views_in_problem", C.c_int32),
+                ("trace_size", C.c_int32), ("num_points_in_problem", C.c_int32),
+                ("num_camera_edges_in_problem", C.c_int32), ("num_point_edges_in_problem", C.c_int32),
+                ("initial_cost", C.c_double), ("final_cost", C.c_double), ("final_radius", C.c_double),
+                ("final_gradient_max_norm", C.c_double), ("seconds", C.c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+# theia_hip.h THEIA_ROTATION_TERM_* (the NONLINEAR position stage reports them too)
 ROTATION_TERM_NONE, ROTATION_TERM_GRADIENT_TOLERANCE, ROTATION_TERM_FUNCTION_TOLERANCE = 0, 1, 2
 ROTATION_TERM_PARAMETER_TOLERANCE, ROTATION_TERM_MAX_ITERATIONS, ROTATION_TERM_FAILURE, ROTATION_TERM_MIN_RADIUS = 3, 4, 5, 6
 
@@ -284,7 +304,7 @@ EXPORTED_SYMBOLS = [
     "theia_hip_ba_reset_parameters", "theia_hip_estimate_tracks", "theia_hip_ba_set_shard", "theia_hip_ba_snapshot_parameters", "theia_hip_ba_restore_parameters", "theia_hip_ba_set_options", "theia_hip_ba_run", "theia_hip_ba_download",
     "theia_hip_ba_destroy", "theia_hip_ba_covariance", "theia_hip_ba_evaluate", "theia_hip_ba_evaluate_ex", "theia_hip_ba_reduced_system",
     "theia_hip_ba_set_allreduce", "theia_hip_ba_set_inner_global", "theia_hip_ba_plan_info", "theia_hip_ba_kernel_instances", "theia_hip_rccl_unique_id", "theia_hip_rccl_comm_create",
-    "theia_hip_optimize_relative_position_batch", "theia_hip_rccl_comm_destroy", "theia_hip_rccl_comm_count", "theia_hip_ba_set_rccl", "theia_hip_dense_spd_solve", "theia_hip_dense_spd_solve_multi", "theia_hip_tile_sparse_spd_solve", "theia_hip_tile_sparse_spd_solve_sharded", "theia_hip_robust_rotation_averaging", "theia_hip_linear_rotations", "theia_hip_nonlinear_rotations", "theia_hip_lud_positions", "theia_hip_ligt_positions", "theia_hip_linear_triplet_positions", "theia_hip_filter_view_pairs_from_relative_translation", "theia_hip_translation_filter_last_stats", "theia_hip_filter_view_pairs_from_orientation", "theia_ransac_params_default",
+    "theia_hip_optimize_relative_position_batch", "theia_hip_rccl_comm_destroy", "theia_hip_rccl_comm_count", "theia_hip_ba_set_rccl", "theia_hip_dense_spd_solve", "theia_hip_dense_spd_solve_multi", "theia_hip_tile_sparse_spd_solve", "theia_hip_tile_sparse_spd_solve_sharded", "theia_hip_robust_rotation_averaging", "theia_hip_linear_rotations", "theia_hip_nonlinear_rotations", "theia_hip_nonlinear_positions", "theia_hip_lud_positions", "theia_hip_ligt_positions", "theia_hip_linear_triplet_positions", "theia_hip_filter_view_pairs_from_relative_translation", "theia_hip_translation_filter_last_stats", "theia_hip_filter_view_pairs_from_orientation", "theia_ransac_params_default",
     "theia_hip_ransac_estimate_batch", "theia_hip_five_point_relative_pose",
     "theia_hip_pose_from_three_points", "theia_hip_sqpnp", "theia_hip_dls_pnp", "theia_hip_dls_macaulay_terms", "theia_hip_four_point_pose_and_focal_length", "theia_hip_four_point_focal_length_radial_distortion", "theia_hip_four_point_focal_length_radial_distortion_ex", "theia_hip_release_scratch", "theia_hip_guided_knn", "theia_hip_randint_stream", "theia_hip_selftest_wave_primitives",
     "theia_hip_selftest_eig_team", "theia_hip_selftest_svd9_team", "theia_hip_selftest_five_point_pre_team",
@@ -343,6 +363,10 @@ def lib():
     L.theia_hip_nonlinear_rotations.argtypes = [C.c_int32, c_double_p, c_uint8_p, C.c_int32, c_int32_p, c_double_p,
                                                 C.POINTER(NonlinearRotationOptions), C.POINTER(NonlinearRotationSummary),
                                                 c_double_p, C.c_int32]
+    L.theia_hip_nonlinear_positions.argtypes = [
+        C.c_int32, c_double_p, c_double_p, c_uint8_p, C.c_int32, c_int32_p, c_double_p, c_double_p, C.c_int32, c_double_p,
+        c_int32_p, c_int32_p, c_double_p, c_double_p, C.c_double, C.POINTER(NonlinearPositionOptions),
+        C.POINTER(NonlinearPositionSummary), c_double_p, C.c_int32]
     L.theia_hip_lud_positions.argtypes = [C.c_int32, c_double_p, c_uint8_p, C.c_int32, c_int32_p, c_double_p,
                                           C.POINTER(LudOptions), c_double_p, C.POINTER(LudSummary)]
     L.theia_hip_ligt_positions.argtypes = [C.c_int32, c_double_p, C.c_int32, c_int32_p, c_int32_p, c_double_p, C.c_int32,

@@ -1,5 +1,5 @@
 // view_graph_device.h -- the device side of view_graph_plan.h for the stages that walk a view graph
-// (rotation_averaging.hip, lud_positions.hip, linear_rotations.hip, nonlinear_rotations.hip): the owner that uploads the
+// (rotation_averaging.hip, lud_positions.hip, linear_rotations.hip, nonlinear_rotations.hip, nonlinear_positions.hip): the owner that uploads the
 // plan's lists once, the struct of their pointers that the kernels take by value, and the device idioms these stages
 // share -- the second stage of a block-partial sum, the walk of one wavefront over a free view's edges, the shrinkage
 // of the L1 ADMMs.

@@ -3,7 +3,8 @@
 // the two CSR lists their kernels assemble the Laplacian-shaped system from without atomics.  Host code only.  The first
 // two fix a view per connected component (build_view_graph_plan); the third fixes none and leaves out the views without
 // edges (it checks its graph itself, with view_graph_components, and calls fill_view_graph_lists), and so does the
-// fourth, which also leaves out the views its caller holds.
+// fourth, which also leaves out the views its caller holds.  nonlinear_positions.hip does as the fourth on a graph whose
+// nodes are the views and the track points.
 // The device side -- the upload of these lists, the struct the kernels take them in, the walk of a free view's incident
 // edges -- is view_graph_device.h; this header stays host code only.
 //

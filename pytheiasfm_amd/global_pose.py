@@ -16,7 +16,10 @@ through theia_hip_lud_positions (csrc/lud_positions.hip), or, from the tracks' f
 translations, through theia_hip_ligt_positions (pytheia.sfm.LiGTPositionEstimator, sfm.cc:1728-1747 ->
 global_pose_estimation/LiGT_position_estimator.{h,cc}; csrc/ligt_positions.hip), or, from the pairs' relative poses and
 the features together, through theia_hip_linear_triplet_positions (pytheia.sfm.LinearPositionEstimator ->
-global_pose_estimation/linear_position_estimator.{h,cc}; csrc/linear_positions.hip).
+global_pose_estimation/linear_position_estimator.{h,cc}; csrc/linear_positions.hip), or, by the Ceres solve over the
+pairs' rotated translations and the rays of a few selected tracks, through theia_hip_nonlinear_positions
+(NonlinearPositionEstimator -> global_pose_estimation/nonlinear_position_estimator.{h,cc}, the reference's default
+position stage; csrc/nonlinear_positions.hip).
 
 Between them sit the two view-graph filters (sfm/filter_view_pairs_from_orientation.{h,cc} after the rotations,
 sfm/filter_view_pairs_from_relative_translation.{h,cc}, the 1DSfM test, before the positions): csrc/view_pair_filters.hip
@@ -396,6 +399,9 @@ def _matrix_to_angle_axis(R):
 
 
 class GlobalPositionEstimatorType(enum.IntEnum):  # reconstruction_estimator_options.h:80-85 (pybind sfm.cc:1196-1204)
+    # all four on the device: NONLINEAR (NonlinearPositionEstimator, the reference's default), LINEAR_TRIPLET
+    # (LinearPositionEstimator), LEAST_UNSQUARED_DEVIATION (LeastUnsquaredDeviationPositionEstimator), LIGT
+    # (LiGTPositionEstimator)
     NONLINEAR = 0
     LINEAR_TRIPLET = 1
     LEAST_UNSQUARED_DEVIATION = 2
@@ -754,6 +760,255 @@ class LinearPositionEstimator(_TrackPositionEstimator):
         capi.check(rc)
         self.last_summary = s
         return {v: p[k].copy() for k, v in enumerate(views) if est[k]}
+
+
+class NonlinearPositionEstimatorOptions:  # nonlinear_position_estimator.h:63-82
+    def __init__(self):
+        self.rng = None                   # a ransac.RandomNumberGenerator; None: one seeded from the clock at construction
+        self.num_threads = 1              # held and ignored (checked > 0): the edges are lanes of the launches
+        self.max_num_iterations = 400
+        self.robust_loss_width = 0.1
+        self.min_num_points_per_view = 0
+        self.point_to_camera_weight = 0.5
+        # ceres::Solver::Options as the reference leaves them; here so that every stopping rule can be reached
+        self.function_tolerance = 1e-6
+        self.gradient_tolerance = 1e-10
+        self.parameter_tolerance = 1e-8
+        self.max_trust_region_radius = 1e16
+
+    def to_c(self):
+        o = capi.NonlinearPositionOptions()
+        o.max_num_iterations = int(self.max_num_iterations)
+        o.robust_loss_width = float(self.robust_loss_width)
+        o.function_tolerance = float(self.function_tolerance)
+        o.gradient_tolerance = float(self.gradient_tolerance)
+        o.parameter_tolerance = float(self.parameter_tolerance)
+        o.max_trust_region_radius = float(self.max_trust_region_radius)
+        return o
+
+
+def nonlinear_positions(orientations, positions, edges, relative_translations, scale_estimates=None, fixed=None,
+                        points=None, track_offsets=None, obs_view=None, obs_feature=None, ray_orientations=None,
+                        point_to_camera_weight=0.5, options=None, want_trace=False):
+    """theia_hip_nonlinear_positions on arrays: orientations [n][3] angle-axis, positions [n][3] the start (not
+    modified), edges [E][2] view indices with relative_translations [E][3] = TwoViewInfo::position_2 and scale_estimates
+    [E] or None (all -1), fixed: [n] booleans or None (no view held).  points [T][3] the start of the track points (not
+    modified) with track t = observations track_offsets[t] .. track_offsets[t + 1] - 1 of obs_view [N] / obs_feature
+    [N][2] (normalised), or None: no point part; ray_orientations [n][3] or None (= orientations).
+    point_to_camera_weight is the weight of every point-to-camera edge as the call takes it (the estimator class scales
+    the option by the edge counts first).  Returns (return code, new positions [n][3], new points [T][3],
+    NonlinearPositionSummary) and, with want_trace, the trace [rows][5] = (cost, gradient max norm, step norm, radius,
+    accepted) as a fifth entry.  Positions and points are the input on a refusal and after a FAILURE termination, the
+    last accepted iterate otherwise."""
+    o = (options or NonlinearPositionEstimatorOptions()).to_c()
+    aa = np.ascontiguousarray(np.asarray(orientations, dtype=np.float64).reshape(-1, 3))
+    x = np.array(positions, dtype=np.float64).reshape(-1, 3)
+    n = aa.shape[0]
+    if x.shape[0] != n:
+        raise ValueError("one position per view")
+    e, r = _pair_arrays(np.zeros((0, 2), dtype=np.int32) if edges is None else edges,
+                        np.zeros((0, 3)) if relative_translations is None else relative_translations, "relative translation")
+    se = None if scale_estimates is None else np.ascontiguousarray(np.asarray(scale_estimates, dtype=np.float64).reshape(-1))
+    if se is not None and se.shape[0] != e.shape[0]:
+        raise ValueError("one scale estimate per edge")
+    f = None if fixed is None else np.ascontiguousarray(np.asarray(fixed, dtype=bool).astype(np.uint8))
+    if f is not None and f.shape != (n,):
+        raise ValueError("fixed must have one entry per view")
+    ray = None if ray_orientations is None else np.ascontiguousarray(np.asarray(ray_orientations, dtype=np.float64).reshape(-1, 3))
+    if ray is not None and ray.shape[0] != n:
+        raise ValueError("one ray orientation per view")
+    pts = off = ov = of = None
+    T = 0
+    if points is not None:
+        pts = np.array(points, dtype=np.float64).reshape(-1, 3)
+        T = pts.shape[0]
+        off = np.ascontiguousarray(np.asarray(track_offsets, dtype=np.int32).reshape(-1))
+        ov = np.ascontiguousarray(np.asarray(obs_view, dtype=np.int32).reshape(-1))
+        of = np.ascontiguousarray(np.asarray(obs_feature, dtype=np.float64).reshape(-1, 2))
+        if off.shape[0] != T + 1:
+            raise ValueError("track_offsets needs num_points + 1 entries")
+        if ov.shape[0] != of.shape[0] or int(off.max()) > ov.shape[0]:
+            raise ValueError("one view and one feature per observation, and offsets within them")
+    rows = max(0, int(o.max_num_iterations)) + 1 if want_trace else 0
+    trace = np.zeros((rows, 5)) if want_trace else None
+    s = capi.NonlinearPositionSummary()
+    rc = capi.lib().theia_hip_nonlinear_positions(
+        n, capi.ptr(aa, C.c_double), capi.ptr(x, C.c_double), capi.ptr(f, C.c_uint8), e.shape[0], capi.ptr(e, C.c_int32),
+        capi.ptr(r, C.c_double), capi.ptr(se, C.c_double), T, capi.ptr(pts if T else None, C.c_double),
+        capi.ptr(off, C.c_int32), capi.ptr(ov, C.c_int32), capi.ptr(of, C.c_double), capi.ptr(ray, C.c_double),
+        float(point_to_camera_weight), C.byref(o), C.byref(s), capi.ptr(trace, C.c_double), rows)
+    if pts is None:
+        pts = np.zeros((0, 3))
+    if want_trace:
+        return rc, x, pts, s, trace[:s.trace_size].copy()
+    return rc, x, pts, s
+
+
+class NonlinearPositionEstimator(_TrackPositionEstimator):
+    """NonlinearPositionEstimator(options, reconstruction) with EstimatePositions(view_pairs, orientations) -> dict,
+    SetViewsFixed(view_ids) and EstimateRemainingPositionsInRecon(fixed_views, views_in_subrecon, view_pairs) ->
+    (bool, dict) (global_pose_estimation/nonlinear_position_estimator.{h,cc}).  reconstruction: the array-backed
+    sfm.Reconstruction (ids are dense indices); view_pairs: {(id1, id2): TwoViewInfo}, whose position_2 and scale_estimate
+    are read; orientations: {view_id: angle-axis}.  The reference's bool is in last_success (the solution is usable:
+    any termination but FAILURE), the summary in last_summary, the points of the selected tracks in
+    triangulated_points.
+
+    Host logic as the reference's; where it walks a hash container a stated rule stands in:
+      * empty pairs or orientations: last_success = False and {} (:141-145);
+      * random start (:208-224), when no view is fixed: every view with an orientation that a pair names gets
+        100 * RandVector3d(), three RandDouble(-1, 1) draws taken as x, y, z, from options.rng (or the generator seeded
+        from the clock at construction); the views are taken in increasing id; the stream is left where the draws end;
+      * a pair lacking a position on either side is skipped (:235-238); the pairs are taken in the dict's order;
+      * track selection (:297-380) with min_num_points_per_view > 0: the positioned views in increasing id, a view with
+        fewer features than the minimum skipped, its tracks not yet selected ordered by (-number of views, track id),
+        and taken from the front until the view has its minimum; each taken track counts toward every positioned view
+        that sees it.  The weight of a point-to-camera edge is point_to_camera_weight * (camera edges) / (sum of the
+        per-view counts); with a zero sum there is no point part;
+      * an estimated selected track starts at points[t][:3] / points[t][3] and adds one edge per observation of a
+        positioned view, its ray turned by the view's own stored orientation, reconstruction.cam_ext[:, 3:6] (the
+        reference's GetRotatedFeatureRay, :68-75, sets the solve's orientation on a temporary and then asks the
+        original camera); an un-estimated one draws its three random numbers and adds no edge (:279-287); the tracks
+        are taken in increasing id;
+      * gauge (:168-176): with no fixed view the smallest positioned view id is set to zero and recorded as fixed, not
+        held, so the first solve holds nothing; a later call on the same object holds that view and skips the random
+        start, and needs the view's position: through EstimatePositions there is none, the reference's FindOrDie, and
+        INVALID_ARGUMENT is raised."""
+
+    def __init__(self, options, reconstruction, normalized_features=None):
+        super().__init__(options, reconstruction, normalized_features)   # CHECK_GT(options.num_threads, 0)
+        if not options.min_num_points_per_view >= 0:
+            raise capi.TheiaHipError(capi.THEIA_HIP_ERR_INVALID_ARGUMENT, "min_num_points_per_view must be >= 0")
+        if not options.point_to_camera_weight > 0:
+            raise capi.TheiaHipError(capi.THEIA_HIP_ERR_INVALID_ARGUMENT, "point_to_camera_weight must be > 0")
+        if not options.robust_loss_width > 0:
+            raise capi.TheiaHipError(capi.THEIA_HIP_ERR_INVALID_ARGUMENT, "robust_loss_width must be > 0")
+        from . import ransac
+        self._rng = options.rng if options.rng is not None else ransac.RandomNumberGenerator()
+        self._fixed = set()
+        self.triangulated_points = {}
+        self.last_success = None
+
+    def SetViewsFixed(self, fixed_views):
+        self._fixed = {int(v) for v in fixed_views}
+
+    def EstimatePositions(self, view_pairs, orientations):
+        return self._estimate(view_pairs, orientations, {})
+
+    def EstimateRemainingPositionsInRecon(self, fixed_views, views_in_subrecon, view_pairs):
+        r = self.reconstruction
+        ids = sorted(int(v) for v in views_in_subrecon if 0 <= int(v) < r.NumViews())
+        orientations = {v: np.array(r.cam_ext[v, 3:6], dtype=np.float64) for v in ids}
+        positions = {v: np.array(r.cam_ext[v, :3], dtype=np.float64) for v in ids}
+        self._fixed = {int(v) for v in fixed_views}
+        out = self._estimate(view_pairs, orientations, positions)
+        return self.last_success, out
+
+    def _random_vector(self):
+        return 100.0 * np.array([self._rng.RandDouble(-1.0, 1.0) for _ in range(3)])
+
+    def _find_tracks(self, positions):
+        """FindTracksForProblem: ({track: estimated} in selection order, the sum of the per-view counts)."""
+        r, k = self.reconstruction, int(self.options.min_num_points_per_view)
+        ov = np.asarray(r.obs_view, dtype=np.int64)
+        ot = np.asarray(r.obs_track, dtype=np.int64)
+        nv, nt = r.NumViews(), r.NumTracks()
+        views_of = np.bincount(ot, minlength=nt)
+        by_view, by_track = np.argsort(ov, kind="stable"), np.argsort(ot, kind="stable")
+        view_off = np.concatenate([[0], np.cumsum(np.bincount(ov, minlength=nv))])
+        track_off = np.concatenate([[0], np.cumsum(views_of)])
+        per_view = {v: 0 for v in positions}
+        chosen = {}
+        for v in sorted(positions):
+            if not 0 <= v < nv:
+                continue
+            mine = ot[by_view[view_off[v]:view_off[v + 1]]]
+            if len(mine) < k:
+                continue
+            cand = sorted((int(t) for t in mine if int(t) not in chosen), key=lambda t: (-int(views_of[t]), t))[:k]
+            for t in cand:
+                if per_view[v] >= k:
+                    break
+                chosen[t] = bool(r.track_estimated[t])
+                for w in ov[by_track[track_off[t]:track_off[t + 1]]]:
+                    if int(w) in per_view:
+                        per_view[int(w)] += 1
+        return chosen, sum(per_view.values())
+
+    def _estimate(self, view_pairs, orientations, positions):
+        self.last_summary = capi.NonlinearPositionSummary()
+        self.triangulated_points = {}
+        if not view_pairs or not orientations:
+            self.last_success = False
+            return {}
+        orientations = {int(v): np.asarray(w, dtype=np.float64).reshape(3) for v, w in orientations.items()}
+        positions = {int(v): np.asarray(p, dtype=np.float64).reshape(3).copy() for v, p in positions.items()}
+        if not self._fixed:
+            named = {int(v) for pair in view_pairs for v in pair}
+            for v in sorted(orientations):
+                if v in named:
+                    positions[v] = self._random_vector()
+        views = sorted(positions)
+        index = {v: k for k, v in enumerate(views)}
+        kept = [(int(a), int(b), info) for (a, b), info in view_pairs.items() if int(a) in index and int(b) in index]
+        missing = sorted(v for v in views if v not in orientations)
+        if missing:                     # FindOrDie(orientations, view_id)
+            raise capi.TheiaHipError(capi.THEIA_HIP_ERR_INVALID_ARGUMENT, f"view {missing[0]} has no orientation")
+        edges = np.array([(index[a], index[b]) for a, b, _ in kept], dtype=np.int32).reshape(-1, 2)
+        rel = np.array([np.asarray(info.position_2, dtype=np.float64).reshape(3) for _, _, info in kept]).reshape(-1, 3)
+        scales = np.array([float(info.scale_estimate) for _, _, info in kept])
+        point_args, tracks, weight = {}, [], float(self.options.point_to_camera_weight)
+        if self.options.min_num_points_per_view > 0:
+            chosen, count = self._find_tracks(positions)
+            if count > 0:
+                weight = weight * float(len(kept)) / float(count)
+                r = self.reconstruction
+                feats = self._features()
+                ov = np.asarray(r.obs_view, dtype=np.int64)
+                ot = np.asarray(r.obs_track, dtype=np.int64)
+                start, offsets, obs_v, obs_f = [], [0], [], []
+                by_track = np.argsort(ot, kind="stable")
+                track_off = np.concatenate([[0], np.cumsum(np.bincount(ot, minlength=r.NumTracks()))])
+                for t in sorted(chosen):
+                    if not chosen[t]:
+                        self.triangulated_points[t] = self._random_vector()
+                        continue
+                    self.triangulated_points[t] = np.array(r.points[t][:3] / r.points[t][3], dtype=np.float64)
+                    rows = [k for k in by_track[track_off[t]:track_off[t + 1]] if int(ov[k]) in index]
+                    if not rows:
+                        continue
+                    tracks.append(t)
+                    start.append(self.triangulated_points[t])
+                    obs_v += [index[int(ov[k])] for k in rows]
+                    obs_f += [feats[k] for k in rows]
+                    offsets.append(len(obs_v))
+                if tracks:
+                    ray = np.array([np.asarray(r.cam_ext[v, 3:6], dtype=np.float64) if 0 <= v < r.NumViews()
+                                    else orientations[v] for v in views])
+                    point_args = dict(points=np.array(start), track_offsets=offsets, obs_view=obs_v,
+                                      obs_feature=np.array(obs_f).reshape(-1, 2), ray_orientations=ray)
+        fixed = None
+        if not self._fixed:
+            if views:
+                positions[views[0]] = np.zeros(3)
+                self._fixed.add(views[0])
+        else:
+            missing = sorted(v for v in self._fixed if v not in index)
+            if missing:                 # FindOrDie(*positions, v_id)
+                raise capi.TheiaHipError(capi.THEIA_HIP_ERR_INVALID_ARGUMENT, f"fixed view {missing[0]} has no position")
+            fixed = np.array([v in self._fixed for v in views])
+        if not kept and not tracks:     # Ceres has nothing to solve
+            self.last_success = False
+            return positions
+        aa = np.array([orientations[v] for v in views])
+        x0 = np.array([positions[v] for v in views])
+        rc, x, pts, s = nonlinear_positions(aa, x0, edges, rel, scales, fixed, point_to_camera_weight=weight,
+                                            options=self.options, **point_args)
+        capi.check(rc)
+        self.last_summary = s
+        self.last_success = s.termination != capi.ROTATION_TERM_FAILURE
+        for k, t in enumerate(tracks):
+            self.triangulated_points[t] = pts[k].copy()
+        return {v: x[k].copy() for k, v in enumerate(views)}
 
 
 class FilterViewPairsFromRelativeTranslationOptions:  # filter_view_pairs_from_relative_translation.h:48-66

@@ -28,6 +28,7 @@ from .global_pose import (GlobalRotationEstimatorType, RobustRotationEstimator, 
                           LeastUnsquaredDeviationPositionEstimator, LeastUnsquaredDeviationPositionEstimatorOptions,
                           LiGTPositionEstimator, LiGTPositionEstimatorOptions,
                           LinearPositionEstimator, LinearPositionEstimatorOptions,
+                          NonlinearPositionEstimator, NonlinearPositionEstimatorOptions,
                           FilterViewPairsFromOrientation, FilterViewPairsFromRelativeTranslation,
                           FilterViewPairsFromRelativeTranslationOptions)
 
