@@ -111,7 +111,7 @@ struct theia_ba_handle_s {
   hipStream_t stream = nullptr;
   static constexpr int kMaxChunk = 8;   // LM iterations enqueued per host synchronisation
   hipEvent_t ev[kMaxChunk][6] = {};
-  PoolBuf<char> lm_state;                // LmState (device): radius, cost, counters, termination
+  PoolBuf<char> lm_state;                // LmState (device): radius, cost, counters, termination; then the trace head (kLmBlockBytes)
   PoolBuf<char> lm_ctl;                  // LmCtl (device): per-run tolerances, caps, trace pointers
   hipGraph_t graph = nullptr;           // one captured LM iteration (no all-reduce callback, no phase timing)
   hipGraphExec_t graph_exec = nullptr;
@@ -120,8 +120,8 @@ struct theia_ba_handle_s {
     if (graph_exec) { (void)hipGraphExecDestroy(graph_exec); graph_exec = nullptr; }
     if (graph) { (void)hipGraphDestroy(graph); graph = nullptr; }
   }
-  PoolBuf<double> tr_cost, tr_g, tr_step, tr_radius;
-  PoolBuf<int> tr_acc;
+  PoolBuf<double> tr_tail;               // trace entries kTraceHead .. of the five arrays (LmCtl::tt), allocated when asked for
+  size_t tr_tail_cap = 0;                // entries per array
   // host-side bookkeeping
   HBuf<int64_t> perm;              // sorted obs index -> original obs index (a block of the pinned host cache: no page faults)
   std::vector<int> cam_red, grp_red, grp_k;
@@ -187,7 +187,7 @@ struct theia_ba_handle_s {
   PoolBuf<double> fpart, camrot, camrot_cand, camdir;
   int n_fruns = 0, n_sum_items = 0;
   double* h_scal = nullptr;  // pinned: [scalA(16) | scalB(16) | stop flag out / in (2) | spare]
-  char* h_state = nullptr;   // pinned: LmState read-back
+  char* h_state = nullptr;   // pinned: read-back of lm_state (kLmBlockBytes)
   int cur = 0;
   bool have_scale = false;
   bool camrot_valid = false;     // P.camrot holds the per-camera blocks of the current state (k_lm_accept keeps it so on accepted steps)
@@ -269,13 +269,27 @@ struct LmState {
   int inner_enabled;   // inner iterations still running (they switch themselves off: inner_iteration_tolerance)
   int use_inner;       // this body's candidate is the point the inner iterations ended at (k_lm_accept copies that one)
 };
+// The five trace arrays (cost, gradient max norm, step norm, radius, accepted) are cut in two: entries [0, kTraceHead) sit
+// right behind the LmState, so that the read-back of the state every chunk of iterations ends with brings them along and a
+// solve whose trace fits needs no copy of its own; the entries beyond are one block (LmCtl::tt), copied after the loop.
+constexpr int kTraceHead = 64;
+constexpr size_t kLmStateBytes = 256;                                            // offset of the trace head in lm_state / h_state
+constexpr size_t kLmBlockBytes = kLmStateBytes + 5 * sizeof(double) * kTraceHead;
+static_assert(sizeof(LmState) <= kLmStateBytes, "the trace head would overlap the state");
 struct LmCtl {   // per-run control block, device resident so that a captured graph of the iteration stays valid
   int max_iterations, trace_capacity;
   double function_tolerance, gradient_tolerance, parameter_tolerance, max_radius, fixed_cost;
-  double *tc, *tg, *ts, *tr;
-  int* ta;
+  double* th;          // trace head [5][kTraceHead] (array 4 holds ints), null = no trace
+  double* tt;          // trace tail [5][tt_cap]: entry k >= kTraceHead of array a at tt[a * tt_cap + k - kTraceHead]
+  int tt_cap;
   const double* inner_scal;   // [4] = {|x - x_inner|^2, |x_inner|^2, cost at x_inner, invalid}, null = no inner iterations
 };
+// entry k of trace array a (0 cost, 1 gradient, 2 step, 3 radius; 4 accepted: reinterpret as int*, int index k)
+__host__ __device__ inline double* lm_trace_array(const LmCtl& c, int a, int k, int* idx) {
+  if (k < kTraceHead) { *idx = k; return c.th + (size_t)a * kTraceHead; }
+  *idx = k - kTraceHead;
+  return c.tt + (size_t)a * c.tt_cap;
+}
 
 // the handle-level functions of ba_solver.hip
 int validate(const theia_ba_problem* p, const theia_ba_options* o);

@@ -1016,8 +1016,7 @@ int ba_create_impl(const theia_ba_problem* p, const theia_ba_options* o, theia_b
   PoolStreamScope pool_scope(h->stream);   // blocks that go back to the caches inside this call are tagged with an event on it
   for (auto& row : h->ev) for (auto& e : row) HIP_TRYR(hipEventCreate(&e));
   HIP_TRYR(hipHostMalloc((void**)&h->h_scal, sizeof(double) * 40, hipHostMallocDefault));
-  HIP_TRYR(hipHostMalloc((void**)&h->h_state, 1024, hipHostMallocDefault));
-  static_assert(sizeof(LmState) <= 1024, "pinned read-back block too small");
+  HIP_TRYR(hipHostMalloc((void**)&h->h_state, kLmBlockBytes, hipHostMallocDefault));
 
   // THEIA_HIP_CREATE_TIMING=1: wall time of the create() stages on stderr
   const bool ctiming = getenv("THEIA_HIP_CREATE_TIMING") != nullptr;
@@ -1427,7 +1426,7 @@ int ba_create_impl(const theia_ba_problem* p, const theia_ba_options* o, theia_b
   if (h->gp.n) HIP_TRYR(hipMemsetAsync(h->gp.p, 0, sizeof(double) * h->gp.n, st));
   AL(tile_part, (size_t)5 * std::max(1, h->ntiles_all)); AL(scalB, 16); AL(red_part, (size_t)8 * kReduceBlocks);
   AL(chol_work, dense_cholesky_workspace(h->n));
-  AL(lm_state, sizeof(LmState)); AL(lm_ctl, sizeof(LmCtl));
+  AL(lm_state, kLmBlockBytes); AL(lm_ctl, sizeof(LmCtl));
   tick("allocations + uploads");
   {
     std::vector<int> pc, pk;

@@ -21,9 +21,11 @@
 namespace {
 
 __device__ void lm_trace(LmState* st, const LmCtl& c, double cost, double g, double step, double radius, int acc) {
-  if (!c.tc || st->trace_size >= c.trace_capacity) return;
+  if (!c.th || st->trace_size >= c.trace_capacity) return;
   const int k = st->trace_size++;
-  c.tc[k] = cost; c.tg[k] = g; c.ts[k] = step; c.tr[k] = radius; c.ta[k] = acc;
+  int i;
+  lm_trace_array(c, 0, k, &i)[i] = cost; lm_trace_array(c, 1, k, &i)[i] = g; lm_trace_array(c, 2, k, &i)[i] = step;
+  lm_trace_array(c, 3, k, &i)[i] = radius; reinterpret_cast<int*>(lm_trace_array(c, 4, k, &i))[i] = acc;
 }
 
 // One pass of the TrustRegionMinimizer loop body (ceres trust_region_minimizer.cc; the
@@ -32,14 +34,13 @@ __device__ void lm_trace(LmState* st, const LmCtl& c, double cost, double g, dou
 __device__ void lm_control_body(LmState* st, const double* __restrict__ sa, const double* __restrict__ sb,
                                 const LmCtl* __restrict__ cp) {
   const LmCtl c = *cp;
-  double* tg = c.tg; double* tc = c.tc;
   st->accepted = 0; st->use_inner = 0;
   if (st->done) return;
   st->bodies++;
   const double x_cost = sa[SC_COST];
   const double gmax = sa[SC_GMAX];
   st->x_cost = x_cost; st->gmax = gmax;
-  if (st->pending_grad >= 0 && tg) tg[st->pending_grad] = gmax;
+  if (st->pending_grad >= 0 && c.th) { int i; lm_trace_array(c, 1, st->pending_grad, &i)[i] = gmax; }
   st->pending_grad = -1;
   if (st->first) {
     st->first = 0;
@@ -98,7 +99,7 @@ __device__ void lm_control_body(LmState* st, const double* __restrict__ sa, cons
     st->decrease_factor = 2.0; st->step_successful = 1;
     st->num_successful++;
     if (cand_cost < st->minimum_cost) st->minimum_cost = cand_cost;
-    if (tc && st->trace_size < c.trace_capacity) st->pending_grad = st->trace_size;
+    if (c.th && st->trace_size < c.trace_capacity) st->pending_grad = st->trace_size;
     lm_trace(st, c, cand_cost + c.fixed_cost, -1.0, step_norm, st->radius, 1);
   } else {
     st->radius /= st->decrease_factor; st->decrease_factor *= 2.0; st->step_successful = 0;
@@ -114,8 +115,9 @@ __global__ void k_lm_control(LmState* st, const double* __restrict__ sa, const d
 }
 // The trace entry of an accepted step waits for the gradient at the accepted point, which the next body's linearisation
 // brings (pending_grad).  A solve that ends with that step has no next body: run() linearises once more and this fills it.
-__global__ void k_lm_pending_gradient(LmState* st, const double* __restrict__ sa, double* __restrict__ tg) {
-  if (st->pending_grad >= 0) tg[st->pending_grad] = sa[SC_GMAX];
+__global__ void k_lm_pending_gradient(LmState* st, const double* __restrict__ sa, const LmCtl* __restrict__ cp) {
+  const LmCtl c = *cp;
+  if (st->pending_grad >= 0 && c.th) { int i; lm_trace_array(c, 1, st->pending_grad, &i)[i] = sa[SC_GMAX]; }
   st->pending_grad = -1;
 }
 // The tile reduction of the trial step (launch_reduce_tiles cfg 1 -> scalB) and the step control in one launch.
@@ -165,8 +167,18 @@ __global__ void k_xnorm_reduce(const double* __restrict__ part, int nblocks, dou
   out2[0] = a; out2[1] = b;
 }
 __global__ void k_xnorm_set(LmState* st, const double* __restrict__ in2) { st->x_norm = sqrt(in2[0] + in2[1]); }
-__global__ void k_lm_init_state(LmState* dst, LmState v) { *dst = v; }
-__global__ void k_lm_init_ctl(LmCtl* dst, LmCtl v) { *dst = v; }
+// the two above in one launch (no all-reduce between them)
+__global__ void k_xnorm_reduce_set(const double* __restrict__ part, int nblocks, double* __restrict__ out2, LmState* st) {
+  double a = 0.0, b = 0.0;
+  for (int k = 0; k < nblocks; ++k) { a += part[2 * k]; b += part[2 * k + 1]; }
+  out2[0] = a; out2[1] = b;
+  st->x_norm = sqrt(a + b);
+}
+// start of a solve: the initial state and the control block travel as kernel arguments, the trial-step scalars are cleared
+__global__ void k_lm_init(LmState* st, LmState sv, LmCtl* ctl, LmCtl cv, double* __restrict__ scalB) {
+  *st = sv; *ctl = cv;
+  for (int q = 0; q < 16; ++q) scalB[q] = 0.0;
+}
 
 // Packed all-reduce buffer: [tiles (64x64, zero padded) | rhs | colsq | g_c | 8 scalars].  S outside the
 // structurally non-zero tiles is zero on every rank, so only those tiles are summed across ranks
@@ -849,32 +861,33 @@ int theia_hip_ba_run(theia_ba_handle h, theia_ba_summary* S) {
   const bool inner = h->inner && O.use_inner_iterations != 0;
   st.inner_enabled = inner ? 1 : 0;
   LmState* dst = reinterpret_cast<LmState*>(h->lm_state.p);
-  // the initial state and the control block travel as kernel arguments (k_lm_init): no host buffer whose
-  // lifetime would need a synchronisation before the first iteration
-  k_lm_init_state<<<1, 1, 0, h->stream>>>(dst, st);
-  // |x| of the variable blocks at the start: summed on the device (points per shard, all-reduced)
-  HIP_TRYR(hipMemsetAsync(h->scalB.p, 0, sizeof(double) * 16, h->stream));
-  if (h->xnorm_part.n < 2 * (size_t)kXnormBlocks && (rc = h->xnorm_part.alloc(2 * kXnormBlocks))) return rc;
-  k_xnorm_partial<<<kXnormBlocks, 256, 0, h->stream>>>(h->P, h->cam[0].p, h->pts[0].p, h->intr[0].p, h->xnorm_part.p);
-  k_xnorm_reduce<<<1, 1, 0, h->stream>>>(h->xnorm_part.p, kXnormBlocks, h->scalB.p);
-  rc = do_allreduce(h, h->scalB.p, 1, THEIA_REDUCE_SUM);
-  if (rc) return rc;
-  k_xnorm_set<<<1, 1, 0, h->stream>>>(dst, h->scalB.p);
   LmCtl ctl;
   ctl.max_iterations = O.max_num_iterations;
   ctl.trace_capacity = S->trace_cost ? S->trace_capacity : 0;
   ctl.function_tolerance = O.function_tolerance; ctl.gradient_tolerance = O.gradient_tolerance;
   ctl.parameter_tolerance = O.parameter_tolerance; ctl.max_radius = O.max_trust_region_radius; ctl.fixed_cost = h->fixed_cost;
-  const size_t tcap = (size_t)std::max(1, ctl.trace_capacity);
-  if (h->tr_cost.n < tcap) {
-    if ((rc = h->tr_cost.alloc(tcap)) || (rc = h->tr_g.alloc(tcap)) || (rc = h->tr_step.alloc(tcap)) ||
-        (rc = h->tr_radius.alloc(tcap)) || (rc = h->tr_acc.alloc(tcap)))
-      return rc;
+  // the trace: its first kTraceHead entries behind the state, the rest (a longer trace only) in a block of its own
+  const size_t tail = (size_t)std::max(0, ctl.trace_capacity - kTraceHead);
+  if (tail > h->tr_tail_cap) {
+    if ((rc = h->tr_tail.alloc(5 * tail))) return rc;
+    h->tr_tail_cap = tail;
   }
-  ctl.tc = ctl.trace_capacity ? h->tr_cost.p : nullptr;
-  ctl.tg = h->tr_g.p; ctl.ts = h->tr_step.p; ctl.tr = h->tr_radius.p; ctl.ta = h->tr_acc.p;
+  ctl.th = ctl.trace_capacity ? reinterpret_cast<double*>(h->lm_state.p + kLmStateBytes) : nullptr;
+  ctl.tt = h->tr_tail.p; ctl.tt_cap = (int)h->tr_tail_cap;
   ctl.inner_scal = inner ? h->in_scal.p : nullptr;
-  k_lm_init_ctl<<<1, 1, 0, h->stream>>>(reinterpret_cast<LmCtl*>(h->lm_ctl.p), ctl);
+  if (h->xnorm_part.n < 2 * (size_t)kXnormBlocks && (rc = h->xnorm_part.alloc(2 * kXnormBlocks))) return rc;
+  // the initial state and the control block travel as kernel arguments: no host buffer whose lifetime would need a
+  // synchronisation before the first iteration
+  k_lm_init<<<1, 1, 0, h->stream>>>(dst, st, reinterpret_cast<LmCtl*>(h->lm_ctl.p), ctl, h->scalB.p);
+  // |x| of the variable blocks at the start: summed on the device (points per shard, all-reduced)
+  k_xnorm_partial<<<kXnormBlocks, 256, 0, h->stream>>>(h->P, h->cam[0].p, h->pts[0].p, h->intr[0].p, h->xnorm_part.p);
+  if (h->allreduce) {
+    k_xnorm_reduce<<<1, 1, 0, h->stream>>>(h->xnorm_part.p, kXnormBlocks, h->scalB.p);
+    if ((rc = do_allreduce(h, h->scalB.p, 1, THEIA_REDUCE_SUM))) return rc;
+    k_xnorm_set<<<1, 1, 0, h->stream>>>(dst, h->scalB.p);
+  } else {
+    k_xnorm_reduce_set<<<1, 1, 0, h->stream>>>(h->xnorm_part.p, kXnormBlocks, h->scalB.p, dst);
+  }
   const LmCtl* dctl = reinterpret_cast<const LmCtl*>(h->lm_ctl.p);
   const int nxt = 1;
   // one LM iteration ("body"): linearise + Schur, solve, trial step, step control, accept
@@ -1007,7 +1020,8 @@ int theia_hip_ba_run(theia_ba_handle h, theia_ba_summary* S) {
     HIP_TRYR(hipGetLastError());   // a rejected launch configuration would otherwise go unnoticed
     // read-back through the handle's pinned block: an asynchronous copy needs a peer that outlives the call (HIP may
     // pin pageable pages and run the DMA later; stack temporaries were the round-1 corruption)
-    HIP_TRYR(hipMemcpyAsync(h->h_state, dst, sizeof(st), hipMemcpyDeviceToHost, h->stream));
+    // (with a trace: the state and the trace head behind it in the one copy)
+    HIP_TRYR(hipMemcpyAsync(h->h_state, dst, ctl.trace_capacity ? kLmBlockBytes : sizeof(st), hipMemcpyDeviceToHost, h->stream));
     HIP_TRYR(hipStreamSynchronize(h->stream));
     std::memcpy(&st, h->h_state, sizeof(st));
     const int ran = (int)std::min<long long>(nb, std::max<long long>(0, (long long)st.bodies - (bodies_enqueued - nb)));
@@ -1025,18 +1039,21 @@ int theia_hip_ba_run(theia_ba_handle h, theia_ba_summary* S) {
     // the last step was accepted at the iteration cap (or the time ran out after it): the gradient its trace entry reports
     // is the one at the accepted point (ceres evaluates it as part of the successful step), so linearise there once more
     if ((rc = enqueue_linearize(h, -1, false))) return rc;
-    k_lm_pending_gradient<<<1, 1, 0, h->stream>>>(dst, h->rb.scal, h->tr_g.p);
+    k_lm_pending_gradient<<<1, 1, 0, h->stream>>>(dst, h->rb.scal, dctl);
+    HIP_TRYR(hipMemcpyAsync(h->h_state, dst, kLmBlockBytes, hipMemcpyDeviceToHost, h->stream));   // the head again, with that entry
     HIP_TRYR(hipStreamSynchronize(h->stream));
   }
   if (ctl.trace_capacity) {
+    // the stream has drained: the head is read from the handle's pinned block, only a longer trace copies its rest
     const int k = std::min(st.trace_size, S->trace_capacity);
     S->trace_size = k;
-    if (k) {
-      HIP_TRYR(hipMemcpy(S->trace_cost, h->tr_cost.p, sizeof(double) * k, hipMemcpyDeviceToHost));
-      if (S->trace_gradient_max_norm) HIP_TRYR(hipMemcpy(S->trace_gradient_max_norm, h->tr_g.p, sizeof(double) * k, hipMemcpyDeviceToHost));
-      if (S->trace_step_norm) HIP_TRYR(hipMemcpy(S->trace_step_norm, h->tr_step.p, sizeof(double) * k, hipMemcpyDeviceToHost));
-      if (S->trace_radius) HIP_TRYR(hipMemcpy(S->trace_radius, h->tr_radius.p, sizeof(double) * k, hipMemcpyDeviceToHost));
-      if (S->trace_accepted) HIP_TRYR(hipMemcpy(S->trace_accepted, h->tr_acc.p, sizeof(int) * k, hipMemcpyDeviceToHost));
+    const int kh = std::min(k, kTraceHead), kt = k - kh;
+    void* out[5] = {S->trace_cost, S->trace_gradient_max_norm, S->trace_step_norm, S->trace_radius, S->trace_accepted};
+    for (int a = 0; a < 5 && k; ++a) {
+      if (!out[a]) continue;
+      const size_t es = a == 4 ? sizeof(int) : sizeof(double);
+      std::memcpy(out[a], h->h_state + kLmStateBytes + sizeof(double) * kTraceHead * a, es * kh);
+      if (kt) HIP_TRYR(hipMemcpy(static_cast<char*>(out[a]) + es * kh, h->tr_tail.p + (size_t)a * h->tr_tail_cap, es * kt, hipMemcpyDeviceToHost));
     }
   }
   if (O.verbose)

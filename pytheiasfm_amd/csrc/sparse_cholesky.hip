@@ -99,6 +99,12 @@ __global__ __launch_bounds__(256) void k_sp_trsm(double* __restrict__ A, int lda
 // (a level has <= ~130 such tiles on 256 CUs).  Nobody stores L(K, K): the diagonal tile is read by every workgroup of its
 // column while it is being factored, and neither the updates nor the back-substitution read it (they use Linv).
 //   blocks [0, npotrf): owners {k0, nb, slot} -> Linv, fail flag;  blocks npotrf ..: {row0, h, k0, nb, slot}
+// RB = 16-row blocks of an off-diagonal tile per workgroup, 4 / RB workgroups per tile.  Every workgroup pays the whole
+// factorisation (~17 us) and holds 67 KB of LDS, so a launch with more workgroups than the device keeps resident runs a second
+// round of that chain: chol_plan_solve_phase picks the finest split that does not add a round (C4's level 0: 45 + 4 x 135
+// workgroups against 512 places took two rounds, 34 us; with RB = 2 it takes one).  An entry's MFMA sequence does not depend
+// on RB: the same bits.
+template <int RB>
 __global__ __launch_bounds__(256) void k_sp_potrf_trsm(double* __restrict__ A, int lda, const int* __restrict__ potrf_items, int npotrf,
                                                        const int* __restrict__ trsm_items, double* __restrict__ Linv,
                                                        double* __restrict__ fail_flag) {
@@ -110,38 +116,43 @@ __global__ __launch_bounds__(256) void k_sp_potrf_trsm(double* __restrict__ A, i
     potrf64_wg_core<false>(A, lda, it[0], it[1], Ls, Zs, rdiag, Linv + (size_t)it[2] * NB * NB, fail_flag);
     return;
   }
-  // FOUR workgroups per tile, 16 of its rows each (wave = 16 of the 64 columns): the 64 x 64 x 64 product would keep this
-  // CU's matrix cores busy for 4096 cycles behind the factorisation (k_sp_update has the arithmetic)
-  const int* it = trsm_items + 5 * ((blockIdx.x - npotrf) >> 2);
-  const int rb = (blockIdx.x - npotrf) & 3;
+  // 4 / RB workgroups per tile, 16 * RB of its rows each (wave = 16 of the 64 columns): the 64 x 64 x 64 product would keep
+  // this CU's matrix cores busy for 4096 cycles behind the factorisation (k_sp_update has the arithmetic)
+  constexpr int WPT = 4 / RB;   // workgroups per tile
+  const int* it = trsm_items + 5 * ((blockIdx.x - npotrf) / WPT);
+  const int rb0 = RB * ((blockIdx.x - npotrf) % WPT);   // this workgroup's first 16-row block
   const int row0 = it[0], h = it[1], k0 = it[2], nb = it[3];
-  if (16 * rb >= h) return;
+  if (16 * rb0 >= h) return;
   const int tid = threadIdx.x;
   // the workgroup's rows of P are fetched before the factorisation and parked in registers: their HBM latency hides behind
   // the panel chain
-  double pv[4];
+  double pv[4 * RB];
 #pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int t = tid + 256 * q, r = 16 * rb + (t >> 6), c = t & 63;
+  for (int q = 0; q < 4 * RB; ++q) {
+    const int t = tid + 256 * q, r = 16 * rb0 + (t >> 6), c = t & 63;
     pv[q] = A[(size_t)(row0 + min(r, h - 1)) * lda + k0 + min(c, nb - 1)];
   }
   potrf64_wg_core<false>(A, lda, k0, nb, Ls, Zs, rdiag, nullptr, nullptr);
   __syncthreads();
 #pragma unroll
-  for (int q = 0; q < 4; ++q) {
+  for (int q = 0; q < 4 * RB; ++q) {
     const int t = tid + 256 * q, r = t >> 6, c = t & 63;
-    Ls[r][c] = (16 * rb + r < h && c < nb) ? pv[q] : 0.0;   // rows 0 .. 15 of Ls: the workgroup's rows of P
+    Ls[r][c] = (16 * rb0 + r < h && c < nb) ? pv[q] : 0.0;   // rows 0 .. 16 RB - 1 of Ls: the workgroup's rows of P
   }
   __syncthreads();
   const int wv = tid >> 6, lane = tid & 63, li = lane & 15, lk = lane >> 4;
-  double4_t acc = (double4_t){0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-  for (int kk = 0; kk < NB; kk += 4)
-    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Ls[li][kk + lk], Zs[16 * wv + li][kk + lk], acc, 0, 0, 0);
+  for (int j = 0; j < RB; ++j) {
+    if (16 * (rb0 + j) >= h) break;   // (beyond a short tile, or the rhs row)
+    double4_t acc = (double4_t){0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-  for (int reg = 0; reg < 4; ++reg) {
-    const int r = 16 * rb + lk + 4 * reg, c = 16 * wv + li;
-    if (r < h && c < nb) A[(size_t)(row0 + r) * lda + k0 + c] = acc[reg];
+    for (int kk = 0; kk < NB; kk += 4)
+      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Ls[16 * j + li][kk + lk], Zs[16 * wv + li][kk + lk], acc, 0, 0, 0);
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+      const int r = 16 * (rb0 + j) + lk + 4 * reg, c = 16 * wv + li;
+      if (r < h && c < nb) A[(size_t)(row0 + r) * lda + k0 + c] = acc[reg];
+    }
   }
 }
 
@@ -819,6 +830,26 @@ double chol_plan_flops(const CholPlan* pl) {
 }
 int chol_plan_levels(const CholPlan* pl) { return pl && !pl->dense ? pl->nlev : (pl ? pl->nt : 0); }
 
+namespace {
+// workgroups of k_sp_potrf_trsm the device keeps resident at once (its 67 KB of LDS decide: two per CU on MI355X).
+// THEIA_HIP_K3_TRSM_SLOTS (development, read once) replaces the number: a huge one gives every level four workgroups per
+// tile, as before the rule; a small one takes small systems through the coarser splits.
+int potrf_trsm_slots() {
+  static const int slots = [] {
+    constexpr int kNoLimit = 1 << 28;
+    if (const char* e = getenv("THEIA_HIP_K3_TRSM_SLOTS")) return std::max(1, std::min(atoi(e), kNoLimit));
+    int dev = 0, cus = 0, per_cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_sp_potrf_trsm<1>, 256, 0) != hipSuccess || cus <= 0 || per_cu <= 0) {
+      (void)hipGetLastError();
+      return kNoLimit;
+    }
+    return cus * per_cu;
+  }();
+  return slots;
+}
+}  // namespace
+
 // phase 0: mirror + forward levels [0, lev_split) (a sharded plan's private columns; nothing but the mirror otherwise);
 // phase 1: forward levels [lev_split, nlev), then the whole back-substitution.  chol_plan_solve = both.
 void chol_plan_solve_phase(const CholPlan* pl, int phase, double* A, int lda, double* b, double* work, double* fail_flag, hipStream_t st) {
@@ -844,7 +875,13 @@ void chol_plan_solve_phase(const CholPlan* pl, int phase, double* A, int lda, do
       if (lv.npotrf) k_sp_potrf<<<lv.npotrf, 256, 0, st>>>(A, lda, pg + lv.potrf_off, Linv, fail_flag);
       if (lv.ntrsm) k_sp_trsm<<<lv.ntrsm, 256, 0, st>>>(A, lda, pg + lv.trsm_off, Linv);
     } else if (lv.npotrf + lv.ntrsm) {
-      k_sp_potrf_trsm<<<lv.npotrf + 4 * lv.ntrsm, 256, 0, st>>>(A, lda, pg + lv.potrf_off, lv.npotrf, pg + lv.trsm_off, Linv, fail_flag);
+      // workgroups per off-diagonal tile: the finest split that needs no more rounds of resident workgroups than one
+      // workgroup per tile does (k_sp_potrf_trsm)
+      const int slots = potrf_trsm_slots();
+      auto rounds = [&](int wpt) { return (lv.npotrf + wpt * lv.ntrsm + slots - 1) / slots; };
+      const int wpt = rounds(4) == rounds(1) ? 4 : (rounds(2) == rounds(1) ? 2 : 1);
+      auto* kern = wpt == 4 ? k_sp_potrf_trsm<1> : (wpt == 2 ? k_sp_potrf_trsm<2> : k_sp_potrf_trsm<4>);
+      kern<<<lv.npotrf + wpt * lv.ntrsm, 256, 0, st>>>(A, lda, pg + lv.potrf_off, lv.npotrf, pg + lv.trsm_off, Linv, fail_flag);
     }
     if (lv.nupd) k_sp_update<<<4 * lv.nupd, 256, 0, st>>>(A, lda, pg + lv.upd_off, pg + lv.upd_src_off);
   }
