@@ -1256,6 +1256,42 @@ int theia_hip_four_point_focal_length_radial_distortion(int32_t num, const doubl
 int theia_hip_guided_knn(int32_t num_groups, const int64_t* q_off, const int32_t* q_idx, const int64_t* c_off,
                          const int32_t* c_idx, int32_t n1, int32_t n2, int32_t dim, const float* desc1, const float* desc2,
                          float* nn_dist, int32_t* nn_index);
+/* BruteForceFeatureMatcher::MatchImagePair (matching/brute_force_feature_matcher.cc:48-115) as FeatureMatcher::MatchImages
+ * (matching/feature_matcher.cc:104-228) drives it, for a whole match graph.  The squared L2 distance of two float descriptors is
+ * taken in the expansion matching/distance.h:46-47 names, every operation fixed: dot = fmaf chain over k ascending from +0 (ONE
+ * accumulator: the FP32 MFMA), nrm = the same chain over d[k] * d[k], d = max(fmaf(-2, dot, nrm1 + nrm2), 0).  The two nearest
+ * per query are taken under (distance, candidate index) ascending (the reference's partial_sort leaves ties open); the ratio
+ * test is (double)d0 < (double)(lowes_ratio * lowes_ratio) * (double)d1 with the product in float, as the reference's types make
+ * it (:56-57, :77).  The reverse pass reads the same matrix by columns.  Stated deviations: a side with one candidate has
+ * d1 = +inf / index -1 and passes the ratio test, a side with none yields no match (the reference reads past its vector there).
+ * Both entry points return THEIA_HIP_ERR_INVALID_ARGUMENT (outputs untouched) for a descriptor with a NaN or infinite value or
+ * with a squared norm beyond FLT_MAX: every distance to it would be NaN. */
+typedef struct theia_brute_force_options {
+  int32_t keep_only_symmetric_matches;  /* feature_matcher_options.h:66-87: true */
+  int32_t use_lowes_ratio;              /* true */
+  float lowes_ratio;                    /* 0.8f */
+  int32_t min_num_feature_matches;      /* 30 */
+  int32_t max_pairs_per_launch;         /* 0 = as many pairs per chunk as the library's workspace budget holds; the result does
+                                         * not depend on it */
+} theia_brute_force_options;
+void theia_hip_brute_force_options_default(theia_brute_force_options* options);
+/* One pair, the search alone (no ratio test, no pair rule): desc1 [n1][dim], desc2 [n2][dim]; fwd_dist / fwd_index [n1][2] = the
+ * two nearest features of image 2 for every feature of image 1, rev_dist / rev_index [n2][2] the two nearest of image 1 for
+ * every feature of image 2; +inf / -1 where the other side has fewer than two features. */
+int theia_hip_brute_force_knn2(int32_t n1, int32_t n2, int32_t dim, const float* desc1, const float* desc2, float* fwd_dist,
+                               int32_t* fwd_index, float* rev_dist, int32_t* rev_index);
+/* The whole rule for num_pairs image pairs: image i has the rows feat_off[i] .. feat_off[i+1] of descriptors [total][dim]
+ * (uploaded once per call), pair k matches image pair_image1[k] against pair_image2[k].  Per pair: the forward matches in
+ * ascending feature1 index; with keep_only_symmetric_matches, i -> j stays iff j passed the reverse test and its nearest is i
+ * (IntersectMatches, feature_matcher_utils.cc:48-70); pair_ok[k] = final count >= min_num_feature_matches (:114; the early
+ * return of :82-84 is implied), and a pair that is not ok returns no matches.  match_off [num_pairs + 1]; match_feature1 /
+ * match_feature2 / match_distance hold the matches of all pairs, capacity = the sum over the pairs of image 1's feature count.
+ * THEIA_HIP_ERR_INVALID_ARGUMENT (outputs untouched) for bad sizes, null arrays, image indices out of range or offsets that
+ * decrease; zero pairs and images without features are valid. */
+int theia_hip_brute_force_match_pairs(int32_t num_images, const int64_t* feat_off, int32_t dim, const float* descriptors,
+                                      int32_t num_pairs, const int32_t* pair_image1, const int32_t* pair_image2,
+                                      const theia_brute_force_options* options, uint8_t* pair_ok, int64_t* match_off,
+                                      int32_t* match_feature1, int32_t* match_feature2, float* match_distance);
 /* n draws of RandomNumberGenerator(seed).RandInt(lo, hi) (util/random.cc:46-84): host code that follows the reference's
  * generator outside the RANSAC sampler (the random candidates of GuidedEpipolarMatcher::FindFeaturesNearEpipolarLines). */
 int theia_hip_randint_stream(uint32_t seed, int32_t n, int32_t lo, int32_t hi, int32_t* out);

@@ -18,6 +18,7 @@ THEIA_HIP_ERR_INVALID_ARGUMENT, THEIA_HIP_ERR_NO_DEVICE, THEIA_HIP_ERR_UNSUPPORT
 THEIA_HIP_ERR_OUT_OF_MEMORY, THEIA_HIP_ERR_INTERNAL = -4, -5
 
 c_double_p = C.POINTER(C.c_double)
+c_float_p = C.POINTER(C.c_float)
 c_int32_p = C.POINTER(C.c_int32)
 c_int64_p = C.POINTER(C.c_int64)
 c_uint8_p = C.POINTER(C.c_uint8)
@@ -295,6 +296,12 @@ class K3Info(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class BruteForceOptions(C.Structure):
+    """theia_brute_force_options (feature_matcher_options.h:66-87)."""
+    _fields_ = [("keep_only_symmetric_matches", C.c_int32), ("use_lowes_ratio", C.c_int32), ("lowes_ratio", C.c_float),
+                ("min_num_feature_matches", C.c_int32), ("max_pairs_per_launch", C.c_int32)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p)
 
 # every symbol include/theia_hip.h declares (checked by tests/test_capi_symbols.py)
@@ -306,7 +313,7 @@ EXPORTED_SYMBOLS = [
     "theia_hip_ba_set_allreduce", "theia_hip_ba_set_inner_global", "theia_hip_ba_plan_info", "theia_hip_ba_kernel_instances", "theia_hip_rccl_unique_id", "theia_hip_rccl_comm_create",
     "theia_hip_optimize_relative_position_batch", "theia_hip_rccl_comm_destroy", "theia_hip_rccl_comm_count", "theia_hip_ba_set_rccl", "theia_hip_dense_spd_solve", "theia_hip_dense_spd_solve_multi", "theia_hip_tile_sparse_spd_solve", "theia_hip_tile_sparse_spd_solve_sharded", "theia_hip_robust_rotation_averaging", "theia_hip_linear_rotations", "theia_hip_nonlinear_rotations", "theia_hip_nonlinear_positions", "theia_hip_lud_positions", "theia_hip_ligt_positions", "theia_hip_linear_triplet_positions", "theia_hip_filter_view_pairs_from_relative_translation", "theia_hip_translation_filter_last_stats", "theia_hip_filter_view_pairs_from_orientation", "theia_ransac_params_default",
     "theia_hip_ransac_estimate_batch", "theia_hip_five_point_relative_pose",
-    "theia_hip_pose_from_three_points", "theia_hip_sqpnp", "theia_hip_dls_pnp", "theia_hip_dls_macaulay_terms", "theia_hip_four_point_pose_and_focal_length", "theia_hip_four_point_focal_length_radial_distortion", "theia_hip_four_point_focal_length_radial_distortion_ex", "theia_hip_release_scratch", "theia_hip_guided_knn", "theia_hip_randint_stream", "theia_hip_selftest_wave_primitives",
+    "theia_hip_pose_from_three_points", "theia_hip_sqpnp", "theia_hip_dls_pnp", "theia_hip_dls_macaulay_terms", "theia_hip_four_point_pose_and_focal_length", "theia_hip_four_point_focal_length_radial_distortion", "theia_hip_four_point_focal_length_radial_distortion_ex", "theia_hip_release_scratch", "theia_hip_guided_knn", "theia_hip_brute_force_options_default", "theia_hip_brute_force_knn2", "theia_hip_brute_force_match_pairs", "theia_hip_randint_stream", "theia_hip_selftest_wave_primitives",
     "theia_hip_selftest_eig_team", "theia_hip_selftest_svd9_team", "theia_hip_selftest_five_point_pre_team",
     "theia_hip_selftest_rotation_maps", "theia_hip_selftest_pairwise_rotation_error",
     "theia_hip_rng_seed", "theia_hip_rng_rand_int", "theia_hip_rng_rand_double", "theia_hip_rng_rand_gaussian", "theia_hip_rng_discard", "theia_hip_ransac_estimate_streams",
@@ -387,6 +394,11 @@ def lib():
     L.theia_hip_selftest_five_point_pre_team.argtypes = [C.c_int32, c_double_p, c_double_p, c_double_p]
     L.theia_hip_selftest_rotation_maps.argtypes = [C.c_int32, c_double_p, c_double_p, c_double_p]
     L.theia_hip_selftest_pairwise_rotation_error.argtypes = [C.c_int32, c_double_p, c_double_p, c_double_p, C.c_double, c_double_p]
+    L.theia_hip_brute_force_options_default.argtypes = [C.POINTER(BruteForceOptions)]
+    L.theia_hip_brute_force_options_default.restype = None
+    L.theia_hip_brute_force_knn2.argtypes = [C.c_int32, C.c_int32, C.c_int32, c_float_p, c_float_p, c_float_p, c_int32_p, c_float_p, c_int32_p]
+    L.theia_hip_brute_force_match_pairs.argtypes = [C.c_int32, c_int64_p, C.c_int32, c_float_p, C.c_int32, c_int32_p, c_int32_p,
+                                                    C.POINTER(BruteForceOptions), c_uint8_p, c_int64_p, c_int32_p, c_int32_p, c_float_p]
     _lib = L
     return L
 
