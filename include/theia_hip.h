@@ -1292,6 +1292,53 @@ int theia_hip_brute_force_match_pairs(int32_t num_images, const int64_t* feat_of
                                       int32_t num_pairs, const int32_t* pair_image1, const int32_t* pair_image2,
                                       const theia_brute_force_options* options, uint8_t* pair_ok, int64_t* match_off,
                                       int32_t* match_feature1, int32_t* match_feature2, float* match_distance);
+/* TrackBuilder (sfm/track_builder.cc:62-77, :156-209 over math/graph/connected_components.h:87-119, then
+ * Reconstruction::AddTrack, reconstruction.cc:314-351) for a whole match graph in one call: the indexed matches in the CSR form
+ * theia_hip_brute_force_match_pairs and the indexed verification return, the tracks in the flat form theia_ba_problem takes
+ * (obs_view / obs_track are its obs_cam / obs_pt).  A node is one (view, feature), an edge one match; the edge order is pair
+ * order, then match order; a pair or a match may appear more than once.  The reference's rule:
+ *   1. for each edge in order, both endpoints become components of size 1 if they are new; then, unless the endpoints already
+ *      share a component or size(a) + size(b) > max_track_length, the two components merge (the partition depends on the order);
+ *   2. a component of fewer than min_track_length nodes is dropped (counted before rule 3);
+ *   3. of the features a component holds in one view the first is kept, the others are num_inconsistent_features;
+ *   4. every track has >= 2 observations: min_track_length < 2, max_track_length <= 0 and an edge inside one view are refused.
+ * What the reference leaves to hash order is stated here: a node's id is feat_off[view] + feature; rule 3 keeps the LOWEST
+ * feature index of a view; tracks are in ascending order of their smallest node id; the observations of a track are in ascending
+ * node id (by view, then feature).  Stated deviations: the node key is the feature INDEX (the reference keys on coordinates, so
+ * two indices of one view with equal coordinates are one node there; the Python mirror merges them before the call);
+ * BuildTracksIncremental is not built.  The components without the cap are found on the device; those larger than
+ * max_track_length are replayed on the host over their own edges in input order (stats says how many).
+ * Outputs, sized by the caller: track_off [match_off[num_pairs] + 1]; obs_view / obs_feature / obs_track
+ * [min(2 * match_off[num_pairs], feat_off[num_views])]; the first num_tracks + 1 / num_observations entries are written.
+ * THEIA_HIP_ERR_INVALID_ARGUMENT (nothing written): the refusals of rule 4, a feature index outside its view, a view index
+ * outside [0, num_views), offsets that do not start at 0 or that decrease, feat_off[num_views] or match_off[num_pairs] >= 2^31,
+ * null arrays.  Zero pairs or zero matches: 0, num_tracks = 0, track_off[0] = 0.  THEIA_HIP_ERR_NO_DEVICE without a device:
+ * there is no CPU fallback.  The result is the same on every run. */
+typedef struct theia_track_builder_options {
+  int32_t min_track_length;   /* reconstruction_builder.h:81-85: 2 */
+  int32_t max_track_length;   /* 50 */
+} theia_track_builder_options;
+typedef struct theia_track_builder_stats {
+  int64_t num_nodes;                      /* (view, feature) pairs that appear in a match */
+  int64_t num_components;                 /* without the cap */
+  int64_t num_oversized_components;       /* of those, larger than max_track_length: replayed on the host */
+  int64_t num_replayed_correspondences;   /* the edges of the oversized components */
+  int64_t num_small_components;           /* dropped by rule 2 (after the cap) */
+  int64_t num_inconsistent_features;      /* dropped by rule 3 */
+  int64_t num_tracks;
+  int64_t num_observations;
+} theia_track_builder_stats;
+/* host clock around the phases of the calling thread's last theia_hip_build_tracks that reached the device, each ended by a
+ * device synchronise */
+typedef struct theia_track_builder_timings {
+  double upload_ms, components_ms, replay_ms, emit_ms, download_ms, total_ms;
+} theia_track_builder_timings;
+void theia_hip_track_builder_options_default(theia_track_builder_options* options);
+int theia_hip_build_tracks(int32_t num_views, const int64_t* feat_off, int32_t num_pairs, const int32_t* pair_view1,
+                           const int32_t* pair_view2, const int64_t* match_off, const int32_t* feature1, const int32_t* feature2,
+                           const theia_track_builder_options* options, int64_t* track_off, int32_t* obs_view,
+                           int32_t* obs_feature, int32_t* obs_track, theia_track_builder_stats* stats);
+int theia_hip_track_builder_last_timings(theia_track_builder_timings* out);
 /* n draws of RandomNumberGenerator(seed).RandInt(lo, hi) (util/random.cc:46-84): host code that follows the reference's
  * generator outside the RANSAC sampler (the random candidates of GuidedEpipolarMatcher::FindFeaturesNearEpipolarLines). */
 int theia_hip_randint_stream(uint32_t seed, int32_t n, int32_t lo, int32_t hi, int32_t* out);

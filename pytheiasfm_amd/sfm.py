@@ -31,6 +31,8 @@ from .global_pose import (GlobalRotationEstimatorType, RobustRotationEstimator, 
                           NonlinearPositionEstimator, NonlinearPositionEstimatorOptions,
                           FilterViewPairsFromOrientation, FilterViewPairsFromRelativeTranslation,
                           FilterViewPairsFromRelativeTranslationOptions)
+from .tracks import (TrackBuilder, AddFeatureCorrespondencesToTrackBuilder,  # noqa: F401  (pyTheia's names)
+                     AddFullFeatureCorrespondencesToTrackBuilder)
 
 kInvalidViewId = 0xFFFFFFFF
 
