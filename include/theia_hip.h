@@ -924,6 +924,42 @@ int theia_hip_filter_view_pairs_from_orientation(
     const double* rotation_2 /*[n_pairs][3]*/, double max_relative_rotation_difference_degrees,
     uint8_t* removed);
 
+/* FilterViewGraphCyclesByRotation (sfm/filter_view_graph_cycles_by_rotation.cc:54-145; pybind sfm.cc:926), the one filter
+ * that needs no global orientations: for every triangle a < b < c (in view index) of the view graph,
+ * loop = R_bc * R_ab * R_ac' (:70-71), every R the ceres::AngleAxisToRotationMatrix of that pair's rotation_2 in ascending
+ * orientation, and the triangle's error is RadToDeg(|RotationMatrixToAngleAxis(loop)|) (:72-79).
+ * removed[e] = !(the smallest error over the triangles of pair e < max_loop_error_degrees), strict as :132; a pair in no
+ * triangle is removed.  A NaN error validates nothing: the minimum ignores it, and a pair whose errors are all NaN reports
+ * +inf.  A NaN or negative threshold removes every pair (the reference has no CHECK here).
+ * Extension: a pair may be listed (b, a) with b > a; its rotation_2 then belongs to that orientation and the ascending
+ * matrix is its transpose (the reference's ViewIdPair is always ascending).
+ * Every output is a minimum or an integer sum, so two calls on the same input give the same bytes.  num_triangles counts
+ * every triangle once.  n_pairs == 0: returns 0, launches nothing, num_triangles = 0.
+ * THEIA_HIP_ERR_INVALID_ARGUMENT (nothing launched, outputs untouched): a view index out of range, a pair naming one view
+ * twice, an unordered pair listed twice, a NULL pairs, rotation_2 or removed with n_pairs > 0.
+ * THEIA_HIP_ERR_OUT_OF_MEMORY: the workspace, 133 bytes per pair and 8 per view. */
+int theia_hip_filter_view_graph_cycles_by_rotation(
+    int32_t n_views, int32_t n_pairs, const int32_t* pairs /*[n_pairs][2] (first, second)*/,
+    const double* rotation_2 /*[n_pairs][3] = TwoViewInfo::rotation_2 of (first, second)*/,
+    double max_loop_error_degrees,
+    uint8_t* removed                 /* [n_pairs] */,
+    double*  min_loop_error_degrees  /* optional [n_pairs]: smallest loop error over the pair's triangles, +inf if none */,
+    int32_t* triangles_per_pair      /* optional [n_pairs] */,
+    int64_t* num_triangles           /* optional: triangles of the graph, each counted once */);
+
+/* RemoveDisconnectedViewPairs (sfm/view_graph/remove_disconnected_view_pairs.cc:48-95; pybind sfm.cc:940), which the
+ * reference pipeline runs after every filter: only the largest connected component of the view graph stays.  Largest by
+ * number of views; among equally large components the one holding the smallest view index (the reference takes whichever
+ * its hash map yields first, :62-69).  A view of another component gets removed_views = 1 and every pair naming it
+ * removed_pairs = 1.  A view that no pair names is neither kept nor removed: removed_views = 0, component = -1.
+ * No pairs: nothing is removed, returns 0.  Runs on the host (a union-find over n_views nodes) and never initialises a device.
+ * THEIA_HIP_ERR_INVALID_ARGUMENT (outputs untouched): a view index out of range, a pair naming one view twice, an unordered
+ * pair listed twice, a NULL pairs, removed_pairs or removed_views with n_pairs > 0. */
+int theia_hip_remove_disconnected_view_pairs(
+    int32_t n_views, int32_t n_pairs, const int32_t* pairs /*[n_pairs][2]*/,
+    uint8_t* removed_pairs /*[n_pairs]*/, uint8_t* removed_views /*[n_views]*/,
+    int32_t* component /* optional [n_views]: smallest view index of the view's component, -1 for a view no pair names */);
+
 /* Multi-GPU (one process per GPU): tracks are sharded by the caller; each
  * rank's handle holds its shard plus ALL cameras.  The reduced camera system
  * (and the scalar reductions) are summed across ranks through this callback,

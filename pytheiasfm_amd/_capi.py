@@ -335,7 +335,7 @@ EXPORTED_SYMBOLS = [
     "theia_hip_ba_reset_parameters", "theia_hip_estimate_tracks", "theia_hip_ba_set_shard", "theia_hip_ba_snapshot_parameters", "theia_hip_ba_restore_parameters", "theia_hip_ba_set_options", "theia_hip_ba_run", "theia_hip_ba_download",
     "theia_hip_ba_destroy", "theia_hip_ba_covariance", "theia_hip_ba_evaluate", "theia_hip_ba_evaluate_ex", "theia_hip_ba_reduced_system",
     "theia_hip_ba_set_allreduce", "theia_hip_ba_set_inner_global", "theia_hip_ba_plan_info", "theia_hip_ba_kernel_instances", "theia_hip_rccl_unique_id", "theia_hip_rccl_comm_create",
-    "theia_hip_optimize_relative_position_batch", "theia_hip_rccl_comm_destroy", "theia_hip_rccl_comm_count", "theia_hip_ba_set_rccl", "theia_hip_dense_spd_solve", "theia_hip_dense_spd_solve_multi", "theia_hip_tile_sparse_spd_solve", "theia_hip_tile_sparse_spd_solve_sharded", "theia_hip_robust_rotation_averaging", "theia_hip_linear_rotations", "theia_hip_nonlinear_rotations", "theia_hip_nonlinear_positions", "theia_hip_lud_positions", "theia_hip_ligt_positions", "theia_hip_linear_triplet_positions", "theia_hip_filter_view_pairs_from_relative_translation", "theia_hip_translation_filter_last_stats", "theia_hip_filter_view_pairs_from_orientation", "theia_ransac_params_default",
+    "theia_hip_optimize_relative_position_batch", "theia_hip_rccl_comm_destroy", "theia_hip_rccl_comm_count", "theia_hip_ba_set_rccl", "theia_hip_dense_spd_solve", "theia_hip_dense_spd_solve_multi", "theia_hip_tile_sparse_spd_solve", "theia_hip_tile_sparse_spd_solve_sharded", "theia_hip_robust_rotation_averaging", "theia_hip_linear_rotations", "theia_hip_nonlinear_rotations", "theia_hip_nonlinear_positions", "theia_hip_lud_positions", "theia_hip_ligt_positions", "theia_hip_linear_triplet_positions", "theia_hip_filter_view_pairs_from_relative_translation", "theia_hip_translation_filter_last_stats", "theia_hip_filter_view_pairs_from_orientation", "theia_hip_filter_view_graph_cycles_by_rotation", "theia_hip_remove_disconnected_view_pairs", "theia_ransac_params_default",
     "theia_hip_ransac_estimate_batch", "theia_hip_five_point_relative_pose",
     "theia_hip_pose_from_three_points", "theia_hip_sqpnp", "theia_hip_dls_pnp", "theia_hip_dls_macaulay_terms", "theia_hip_four_point_pose_and_focal_length", "theia_hip_four_point_focal_length_radial_distortion", "theia_hip_four_point_focal_length_radial_distortion_ex", "theia_hip_release_scratch", "theia_hip_guided_knn", "theia_hip_brute_force_options_default", "theia_hip_brute_force_knn2", "theia_hip_brute_force_match_pairs", "theia_hip_track_builder_options_default", "theia_hip_build_tracks", "theia_hip_track_builder_last_timings", "theia_hip_randint_stream", "theia_hip_selftest_wave_primitives",
     "theia_hip_selftest_eig_team", "theia_hip_selftest_svd9_team", "theia_hip_selftest_five_point_pre_team",
@@ -413,6 +413,9 @@ def lib():
     L.theia_hip_translation_filter_last_stats.argtypes = [C.POINTER(TranslationFilterStats)]
     L.theia_hip_filter_view_pairs_from_orientation.argtypes = [C.c_int32, C.c_int32, c_int32_p, c_double_p, c_uint8_p,
                                                                c_double_p, C.c_double, c_uint8_p]
+    L.theia_hip_filter_view_graph_cycles_by_rotation.argtypes = [C.c_int32, C.c_int32, c_int32_p, c_double_p, C.c_double,
+                                                                 c_uint8_p, c_double_p, c_int32_p, c_int64_p]
+    L.theia_hip_remove_disconnected_view_pairs.argtypes = [C.c_int32, C.c_int32, c_int32_p, c_uint8_p, c_uint8_p, c_int32_p]
     L.theia_hip_selftest_eig_team.argtypes = [C.c_int32, C.c_int32, C.c_int32, c_double_p, c_int32_p, c_double_p, c_double_p]
     L.theia_hip_selftest_svd9_team.argtypes = [C.c_int32, C.c_int32, C.c_int32, c_double_p, c_double_p, c_double_p]
     L.theia_hip_selftest_five_point_pre_team.argtypes = [C.c_int32, c_double_p, c_double_p, c_double_p]

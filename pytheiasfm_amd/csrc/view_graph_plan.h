@@ -103,6 +103,25 @@ inline int view_graph_components(int n, int E, const int32_t* edges, std::vector
   return 0;
 }
 
+// What the view-graph prunings (view_graph_pruning.hip) refuse in their pair list: a view out of range, a self-pair, an
+// unordered pair named twice -- the conditions view_pair_filters.hip checks with its file-local copy of this function.
+inline int check_pairs(int n_views, int n_pairs, const int32_t* pairs) {
+  std::vector<uint64_t> keys((size_t)n_pairs);
+  for (int e = 0; e < n_pairs; ++e) {
+    const int i = pairs[2 * e], j = pairs[2 * e + 1];
+    if (i < 0 || i >= n_views || j < 0 || j >= n_views)
+      return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "pair %d names a view out of range", e);
+    if (i == j) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "pair %d names view %d twice", e, i);
+    keys[e] = ((uint64_t)std::min(i, j) << 32) | (uint64_t)std::max(i, j);
+  }
+  std::sort(keys.begin(), keys.end());
+  for (int e = 1; e < n_pairs; ++e)
+    if (keys[e] == keys[e - 1])
+      return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "the pair (%d, %d) is listed twice", (int)(keys[e] >> 32),
+                       (int)(keys[e] & 0xFFFFFFFFu));
+  return 0;
+}
+
 // Checks the edges and builds the plan.  fixed: [n] flags or null; no view flagged: view 0 is fixed.  `word` names a
 // fixed view in the error text ("fixed" for rotations, "held" for positions).  THEIA_HIP_ERR_INVALID_ARGUMENT: an edge
 // names a view out of range; a connected component has no fixed view (the system would be singular).

@@ -35,6 +35,14 @@ __device__ __forceinline__ unsigned row16_min_u32(unsigned v) {
   return v;
 }
 
+__device__ __forceinline__ int row16_sum_i32(int v) {   // the four row-local levels of wave_sum_butterfly(int)
+  v += __builtin_amdgcn_mov_dpp(v, 0x128, 0xf, 0xf, false);
+  v += __builtin_amdgcn_mov_dpp(v, 0x124, 0xf, 0xf, false);
+  v += __builtin_amdgcn_mov_dpp(v, 0x4E, 0xf, 0xf, false);
+  v += __builtin_amdgcn_mov_dpp(v, 0xB1, 0xf, 0xf, false);
+  return v;
+}
+
 // The XOR butterfly  for (off = 32; off > 0; off >>= 1) v += shfl_xor(v, off)  without its twelve ds_bpermute_b32: the levels 32
 // and 16 on gfx950's v_permlane32_swap / v_permlane16_swap (both halves of the swap added: lane l gets v[l] + v[l ^ off],
 // the addition commutes), the level 8 by a row rotation, and the levels 4, 2, 1 by ANY lane of the partner's residue class

@@ -25,6 +25,10 @@ Between them sit the two view-graph filters (sfm/filter_view_pairs_from_orientat
 sfm/filter_view_pairs_from_relative_translation.{h,cc}, the 1DSfM test, before the positions): csrc/view_pair_filters.hip
 behind filter_pairs_from_orientation / filter_translations_1dsfm on arrays and FilterViewPairsFromOrientation /
 FilterViewPairsFromRelativeTranslation on the {(id1, id2): TwoViewInfo} dict that stands in for the ViewGraph.
+The two prunings that need no orientations (sfm/filter_view_graph_cycles_by_rotation.{h,cc} before the first rotation
+stage, sfm/view_graph/remove_disconnected_view_pairs.{h,cc} after every filter) are csrc/view_graph_pruning.hip behind
+filter_cycles_by_rotation / remove_disconnected_pairs on arrays and FilterViewGraphCyclesByRotation /
+RemoveDisconnectedViewPairs on the dict.
 """
 import ctypes as C
 import enum
@@ -1137,3 +1141,71 @@ def FilterViewPairsFromOrientation(orientations, max_relative_rotation_differenc
         if gone:
             del view_pairs[k]
     return int(removed.sum())
+
+
+def filter_cycles_by_rotation(num_views, pairs, rotation_2, max_loop_error_degrees, want=()):
+    """theia_hip_filter_view_graph_cycles_by_rotation on arrays: pairs [E][2] view indices (every unordered pair at most
+    once, in either order), rotation_2 [E][3] of the pair as listed.  want: names of the optional outputs to fetch, out of
+    "min_loop_error_degrees" [E], "triangles_per_pair" [E] and "num_triangles" (an int).  Returns (return code, removed
+    [E] bool, dict of the outputs asked for); on a refusal removed is all False and the dict is empty."""
+    e, r = _pair_arrays(pairs, rotation_2, "rotation_2")
+    unknown = set(want) - {"min_loop_error_degrees", "triangles_per_pair", "num_triangles"}
+    if unknown:
+        raise ValueError(f"unknown outputs {sorted(unknown)}")
+    E = e.shape[0]
+    removed = np.zeros(E, dtype=np.uint8)
+    bufs = dict(min_loop_error_degrees=np.full(E, np.inf), triangles_per_pair=np.zeros(E, dtype=np.int32),
+                num_triangles=np.zeros(1, dtype=np.int64))
+    arg = lambda k, ct: capi.ptr(bufs[k] if k in want else None, ct)
+    rc = capi.lib().theia_hip_filter_view_graph_cycles_by_rotation(
+        int(num_views), E, capi.ptr(e, C.c_int32), capi.ptr(r, C.c_double), float(max_loop_error_degrees),
+        capi.ptr(removed, C.c_uint8), arg("min_loop_error_degrees", C.c_double), arg("triangles_per_pair", C.c_int32),
+        arg("num_triangles", C.c_int64))
+    bufs["num_triangles"] = int(bufs["num_triangles"][0])
+    return rc, removed.astype(bool), ({k: bufs[k] for k in want} if rc == 0 else {})
+
+
+def remove_disconnected_pairs(num_views, pairs):
+    """theia_hip_remove_disconnected_view_pairs on arrays (host code: no device is touched).  Returns (return code,
+    removed_pairs [E] bool, removed_views [num_views] bool, component [num_views] int32: the smallest view index of the
+    view's component, -1 for a view no pair names); on a refusal nothing is marked and component is all -1."""
+    e = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+    n = int(num_views)
+    removed_pairs = np.zeros(e.shape[0], dtype=np.uint8)
+    removed_views = np.zeros(max(n, 0), dtype=np.uint8)
+    component = np.full(max(n, 0), -1, dtype=np.int32)
+    rc = capi.lib().theia_hip_remove_disconnected_view_pairs(
+        n, e.shape[0], capi.ptr(e, C.c_int32), capi.ptr(removed_pairs, C.c_uint8), capi.ptr(removed_views, C.c_uint8),
+        capi.ptr(component, C.c_int32))
+    return rc, removed_pairs.astype(bool), removed_views.astype(bool), component
+
+
+def FilterViewGraphCyclesByRotation(max_loop_error_degrees, view_pairs):
+    """FilterViewGraphCyclesByRotation(max_loop_error_degrees, view_graph) on the dict: a pair that lies in no triangle
+    whose chained rotations close to within the angle is deleted; returns how many were.  A key (id2, id1) with
+    id2 > id1 is taken as listed: its rotation_2 belongs to that orientation."""
+    views, pos = _graph_views(view_pairs)
+    keys = list(view_pairs)
+    pairs = np.array([(pos[int(a)], pos[int(b)]) for a, b in keys], dtype=np.int32).reshape(-1, 2)
+    rel = np.array([np.asarray(view_pairs[k].rotation_2, dtype=np.float64).reshape(3) for k in keys]).reshape(-1, 3)
+    rc, removed, _ = filter_cycles_by_rotation(len(views), pairs, rel, max_loop_error_degrees)
+    capi.check(rc)
+    for k, gone in zip(keys, removed):
+        if gone:
+            del view_pairs[k]
+    return int(removed.sum())
+
+
+def RemoveDisconnectedViewPairs(view_pairs):
+    """RemoveDisconnectedViewPairs(view_graph) on the dict: the pairs outside the largest connected component (among
+    equally large ones, the one with the smallest view id stays) are deleted; returns the set of the removed view ids,
+    as the binding does."""
+    views, pos = _graph_views(view_pairs)
+    keys = list(view_pairs)
+    pairs = np.array([(pos[int(a)], pos[int(b)]) for a, b in keys], dtype=np.int32).reshape(-1, 2)
+    rc, removed_pairs, removed_views, _ = remove_disconnected_pairs(len(views), pairs)
+    capi.check(rc)
+    for k, gone in zip(keys, removed_pairs):
+        if gone:
+            del view_pairs[k]
+    return {v for v, gone in zip(views, removed_views) if gone}

@@ -30,7 +30,8 @@ from .global_pose import (GlobalRotationEstimatorType, RobustRotationEstimator, 
                           LinearPositionEstimator, LinearPositionEstimatorOptions,
                           NonlinearPositionEstimator, NonlinearPositionEstimatorOptions,
                           FilterViewPairsFromOrientation, FilterViewPairsFromRelativeTranslation,
-                          FilterViewPairsFromRelativeTranslationOptions)
+                          FilterViewPairsFromRelativeTranslationOptions,
+                          FilterViewGraphCyclesByRotation, RemoveDisconnectedViewPairs)
 from .tracks import (TrackBuilder, AddFeatureCorrespondencesToTrackBuilder,  # noqa: F401  (pyTheia's names)
                      AddFullFeatureCorrespondencesToTrackBuilder)
 
