@@ -342,8 +342,12 @@ __global__ __launch_bounds__(64 * TPS, THIP_FUSED_WAVES) void k_lin_schur(DevPro
   __shared__ __attribute__((aligned(16))) double s_rec[SUB * RD];
   __shared__ __attribute__((aligned(16))) double s_cam[kFusedMaxStage * kCamLds];
   __shared__ uint8_t s_tslot[SUBT * kRowBytes];   // (track, local camera) -> record slot, valid where the mask bit is set
-  __shared__ unsigned s_tmask[SUBT];              // local cameras of a track
+  // local cameras of the track in a slot, one table per sub-chunk parity.  A table is all zero when phase L starts on it: the
+  // slots of a run with unequal slices are not dense (ba_plan.hip: shape_slices), a slot without a track must match no target
+  __shared__ unsigned s_tmask[2 * SUBT];
+  __shared__ unsigned short s_slice[16];          // unequal slices of the run: lane offset | width << 8
   static_assert(SUB * 18 <= SUB * RD, "slice-combination scratch does not fit the record buffer");
+  static_assert(kFusedMaxSlices <= 16, "slice table too short");
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const double radius = *radius_p;
   const double inv_radius = 1.0 / radius;
@@ -357,8 +361,9 @@ __global__ __launch_bounds__(64 * TPS, THIP_FUSED_WAVES) void k_lin_schur(DevPro
   // in-order memory counter, the drain of the previous run's partial-block stores -- is off the path between two runs
   int pending = 0;
   if (tid == 0) pending = atomicAdd(P.frun_next, 1);
+  for (int j = tid; j < 2 * SUBT; j += SUB) s_tmask[j] = 0u;
   for (;;) {
-  __syncthreads();   // the previous run's slice combination is done with the LDS scratch (and s_next, s_cam)
+  __syncthreads();   // the previous run's slice combination is done with the LDS scratch (and s_next, s_cam, s_slice)
   if (tid == 0) s_next = pending;
   __syncthreads();
   const int rix = __builtin_amdgcn_readfirstlane(s_next);   // (scalar: the run's fields and the tile geometry are s_loads)
@@ -379,11 +384,22 @@ __global__ __launch_bounds__(64 * TPS, THIP_FUSED_WAVES) void k_lin_schur(DevPro
   __syncthreads();   // s_cam complete
 
   // ---- phase-S role: which target block / per-camera row this lane owns, which tracks it walks
-  const int G = run.gp & 0xff, PS = run.gp >> 8; // waves per slice (1, 2, 4) / slices per wave (>= 1, only with G == 1)
+  const int G = run.gp & 0xff, PS = (run.gp >> 8) & 0xff; // waves per slice (1, 2, 4) / slices per wave (>= 1, only with G == 1)
+  const bool unequal = (run.gp & kFusedUnequalSlices) != 0;   // G == 1: slice g owns the first `width` targets on the lanes from `offset` (listed behind the run's targets)
   int tix, t0, tstride;
   bool slice_ok = true;
   const int B = 64 / PS;
-  if (G == 1) { const int g = lane / B; tix = lane - g * B; slice_ok = g < PS; t0 = wv * PS + g; tstride = NWV * PS; }
+  if (unequal) {
+    int g = 0, at = 0;
+    slice_ok = false;
+    for (int j = 0; j < PS; ++j) {   // (scalar loads: PS <= kFusedMaxSlices entries, offsets ascending, offset + width <= 64)
+      const int us = P.frun_tgt[run.tgt_off + run.ntgt + j], oj = us & 0xff, wj = us >> 8;
+      if (lane >= oj && lane < oj + wj) { g = j; at = oj; slice_ok = true; }
+      if (tid == j) s_slice[j] = (unsigned short)us;
+    }
+    tix = lane - at; t0 = wv * PS + g; tstride = NWV * PS;
+  }
+  else if (G == 1) { const int g = lane / B; tix = lane - g * B; slice_ok = g < PS; t0 = wv * PS + g; tstride = NWV * PS; }
   else { tix = (wv % G) * 64 + lane; t0 = wv / G; tstride = NWV / G; }
   const bool has_tgt = slice_ok && tix < run.ntgt;
   int la = 0, lb = 0;
@@ -411,7 +427,8 @@ __global__ __launch_bounds__(64 * TPS, THIP_FUSED_WAVES) void k_lin_schur(DevPro
     const int scn = min(sc + 1, nsc - 1);   // (the last sub-chunk reloads itself: unconditional loads, nothing is used)
     pre_level1<PD, TPS>(P, run, scn, wv, lane, ntile, ntile_ok, nxt);
     if (P.fused_dbg & 16) __builtin_amdgcn_s_setprio(1);   // development: issue priority to the latency-bound phase
-    fused_phase_l5<PD, MODELS, LOSSK, STAMPS, FIRST>(P, cur, s_cam, run.W, tile, tile_ok, wv, lane, inv_radius, Vinv, tile_part, s_rec, s_tslot, s_tmask, stamps, scale_out);
+    unsigned* const tmask = s_tmask + (sc & 1) * SUBT;
+    fused_phase_l5<PD, MODELS, LOSSK, STAMPS, FIRST>(P, cur, s_cam, run.W, tile, tile_ok, wv, lane, inv_radius, Vinv, tile_part, s_rec, s_tslot, tmask, stamps, scale_out);
     sk.lap(stamps, 1);
     pre_level2<PD>(P, pts, nxt);
     if (P.fused_dbg & 16) __builtin_amdgcn_s_setprio(0);
@@ -424,11 +441,12 @@ __global__ __launch_bounds__(64 * TPS, THIP_FUSED_WAVES) void k_lin_schur(DevPro
     if (!(P.fused_dbg & 1)) {
       const int last_tile = min(run.tile0 + TPS * sc + TPS - 1, run.tile0 + run.ntiles - 1);
       const int ntr = P.tile_trk_end[last_tile];
-      fused_phase_s<PD, RD>(s_rec, s_tslot, s_tmask, ntr, tstride, t0, slice_ok, tbits, la, lb, diag_core, dP, dbase, dbit, dlc, da, acc, dacc);
+      fused_phase_s<PD, RD>(s_rec, s_tslot, tmask, ntr, tstride, t0, slice_ok, tbits, la, lb, diag_core, dP, dbase, dbit, dlc, da, acc, dacc);
     }
     sk.lap(stamps, 8);
     if (!(P.fused_dbg & 32)) __builtin_amdgcn_s_setprio(0);
     __syncthreads();
+    if (tid < SUBT) tmask[tid] = 0u;   // (written again two sub-chunks on, behind the barriers of the next one)
     sk.lap(stamps, 9);
     if constexpr (STAMPS) stamps[11] += 1;
     cur = nxt; tile = ntile; tile_ok = ntile_ok;
@@ -449,10 +467,20 @@ __global__ __launch_bounds__(64 * TPS, THIP_FUSED_WAVES) void k_lin_schur(DevPro
     for (int e = tid; e < run.ntgt * 18; e += SUB) {
       const int k = e / 18, q = e - 18 * k;
       double v = scratch[k * 18 + q];   // (replica 0 of target k is thread k)
+      if (unequal) {   // the slices that own target k, slice by slice over the waves
+#pragma unroll 1
+        for (int j = 0; j < PS; ++j) {
+          const int us = s_slice[j], oj = us & 0xff, wj = us >> 8;
+          if (k >= wj) break;   // (widths do not increase)
+#pragma unroll 1
+          for (int w = (j == 0) ? 1 : 0; w < NWV; ++w) v += scratch[(w * 64 + oj + k) * 18 + q];
+        }
+      } else {
 #pragma unroll 1
       for (int r = 1; r < nrep; ++r) {
         const int oth = (G == 1) ? ((r / PS) * 64 + (r % PS) * B + k) : (k + r * G * 64);
         v += scratch[oth * 18 + q];
+      }
       }
       out[(size_t)k * 36 + 18 * h + q] = v;
     }

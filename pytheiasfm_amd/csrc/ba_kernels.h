@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "dense_cholesky.h"
+#include "ba_fused_slices.h"
 
 namespace thip {
 
@@ -19,6 +20,8 @@ struct FusedRun {
   int part_off;          // doubles offset of the run's partial sums: [ntgt][36] then [W][6][3]
   int gp;                // G | PS << 8.  G = consumer waves per track slice: 1, 2 or 4 (64 G >= max(ntgt, 6 W));
                          // PS = track slices per consumer wave (only with G == 1): floor(64 / PS) >= ntgt, 6 W <= 64
+                         // | kFusedUnequalSlices (ba_fused_slices.h; k_lin_schur, G == 1): the PS slices are listed behind the run's
+                         // targets, frun_tgt[tgt_off + ntgt + g] = lane offset | width << 8 -- slice g owns the first `width` targets
   int stage_off, nstage; // ba_fused.hip: frun_stage[stage_off + k] = camera index of the k-th per-camera block the run keeps in
                          // LDS: its W local cameras, then the CONSTANT cameras its tracks see (obs_lc = 0x80 | index among them)
 };

@@ -10,6 +10,7 @@
 
 #include "ba_handle.h"
 #include "ba_host_rules.h"
+#include "ba_plan_stats.h"
 
 namespace {
 
@@ -514,6 +515,15 @@ inline int fused_run_cameras(int bw) {
 // lanes of a target block (ba_fused_intr.hip: lanes_per_target): three rows per lane up to width 10, four at 13
 inline int fused_lanes_per_target(int bw) { return bw == 0 ? 1 : (bw <= 10 ? (bw + 2) / 3 : (bw + 3) / 4); }
 
+// What one more run costs k_lin_schur, in wave steps of phase S (the unit of ba_plan_stats.h): run setup is 4 % and the slice
+// combination with its stores 11 % of the kernel where phase S is 38 %, over the 2102 runs and 339 k issued
+// steps of the C4 plan: 0.15 / 0.38 x 339 k / 2102 = 64.
+constexpr double kFusedRunCostSteps = 64.0;
+
+// runs whose dealt slot rows differed from the closed form their shape was chosen on (shape_slices: they keep equal slices);
+// THEIA_HIP_CREATE_TIMING prints it, zero on every plan measured
+inline std::atomic<long long>& shape_mismatches() { static std::atomic<long long> n{0}; return n; }
+
 struct FusedHost {
   std::vector<FusedRun> runs;
   std::vector<int> cams, stage, tile_trk_end, sum_items, sum_src;
@@ -565,8 +575,13 @@ void build_fused_segment(const theia_ba_handle_s* h, const std::vector<int64_t>&
   std::vector<int64_t> run_pairs;      // unique keys hi * 2^32 | lo of co-visible reduced cameras (hi >= lo), sorted by finalize_run
   std::vector<int> tc;
   std::vector<int64_t> tp;
-  int serial = 1, prev_serial = 0;
-  std::vector<int> prev_tc;
+  int serial = 1;
+  // camera sets that joined the open run (a small direct-mapped table, entries of other runs are stale by their stamp): a track
+  // with one of them brings nothing new -- at C4 a run sees three to six distinct sets, and probing a track's <= 55 pairs twice
+  // was most of this function
+  struct SeenSet { int stamp = 0, n = 0; int cams[kFusedMaxCams]; };
+  constexpr int kSeenSets = 64;
+  std::vector<SeenSet> seen_sets(kSeenSets);
   std::vector<int> cam_stamp((size_t)std::max(1, h->ncp), 0);
   std::vector<uint8_t> cam_local((size_t)std::max(1, h->ncp), 0);   // camera -> index in the closing run's sorted table
   // CONSTANT cameras the open run's tracks see (the fused kernels stage their blocks in LDS behind the local cameras'), in order
@@ -609,8 +624,121 @@ void build_fused_segment(const theia_ba_handle_s* h, const std::vector<int64_t>&
     run_ntiles++;
     t_len = 0; t_tracks = 0;
   };
+  // the tracks of the open run: first observation, length, highest variable camera, wave tile, targets it needs (shape_slices)
+  struct RunTrack { int s0, cmax, tile; uint8_t len, need; };
+  std::vector<RunTrack> run_trk;
+  int run_kmin = 64;   // fewest variable cameras of a track of the open run
+  std::vector<int> need_desc, sc_gt, sc_n, sc_first, slot_of, sc_slots, by_need;
+  const bool unequal_slices = !getenv("THEIA_HIP_FUSED_EQUAL_SLICES");   // (the switch: A/B measurements; read per plan)
+  // Unequal track slices (k_lin_schur, one wave per slice row: G == 1).  The targets of a run are sorted by (la, lb), la >= lb,
+  // so a track whose highest local camera is m has all its pairs among the first need = 1 + index of (m, m) targets: a slice
+  // that owns only a PREFIX of the targets serves every track with need <= its width.  Slice 0 keeps all ntgt targets, the
+  // others share the remaining lanes, and the tracks of a sub-chunk are dealt to the slots (row, slice) they fit -- most
+  // demanding first, to the emptiest slice -- instead of in order.  The shape is the one with the fewest slot rows (= wave steps
+  // that run the pair products, ba_plan_stats.h) over the run's sub-chunks; equal slices stay unless it saves 1/16 of them.
+  // A pure function of the run's tracks in plan order.
+  auto shape_slices = [&](FusedRun& r) {
+    const int PS0 = r.gp >> 8, ntrk = (int)run_trk.size(), nsc = (run_ntiles + tps - 1) / tps;
+    // (a track of k cameras needs its own k (k + 1) / 2 pairs at least: where not even the shortest fits beside slice 0 -- the
+    // long-track runs of C4 -- nothing below is looked at; a run of a few tracks has no rows to save)
+    if (r.ntgt < 2 || ntrk < 8 || r.ntgt + std::max(1, run_kmin * (run_kmin + 1) / 2) > 64) return;
+    int hist[66] = {0}, diag_at[kFusedMaxCams] = {0};   // diag_at[m]: the targets up to and including (m, m)
+    for (int k = 0; k < r.ntgt; ++k) { const unsigned us = fp.tgts[(size_t)r.tgt_off + k]; if ((us & 0xff) == (us >> 8)) diag_at[us & 0xff] = k + 1; }
+    int least = 64;
+    for (RunTrack& t : run_trk) { t.need = (uint8_t)(t.cmax >= 0 ? diag_at[cam_local[t.cmax]] : 0); hist[t.need]++; least = std::min<int>(least, t.need); }
+    if (r.ntgt + std::max(1, least) > 64) return;   // (the same with the needs themselves)
+    const size_t NW = (size_t)r.ntgt + 1;           // needs are 0 .. ntgt
+    need_desc.clear();   // the run's needs, descending
+    for (int v = 64; v >= 0; --v) need_desc.insert(need_desc.end(), (size_t)hist[v], v);
+    sc_gt.assign((size_t)nsc * NW, 0); sc_n.assign((size_t)nsc, 0); sc_first.assign((size_t)nsc + 1, ntrk);
+    for (int i = ntrk - 1; i >= 0; --i) {   // (tracks joined in tile order: a sub-chunk's tracks are one range of run_trk)
+      const int sc = (run_trk[i].tile - run_tile0) / tps;
+      sc_first[sc] = i; sc_n[sc]++;
+      if (run_trk[i].need > 0) sc_gt[(size_t)sc * NW + run_trk[i].need - 1]++;
+    }
+    for (int sc = 0; sc < nsc; ++sc)   // sc_gt[sc][v] = tracks of the sub-chunk with need > v
+      for (int v = r.ntgt - 2; v >= 0; --v) sc_gt[(size_t)sc * NW + v] += sc_gt[(size_t)sc * NW + v + 1];
+    for (int sc = nsc - 1; sc >= 0; --sc) if (sc_n[sc] == 0) sc_first[sc] = sc_first[sc + 1];
+    // slot rows of a shape over the sub-chunks (-1: a sub-chunk would need more than the 128 slots of the kernel's tables)
+    auto rows_of = [&](const int* wid, int p) -> long long {
+      long long rows = 0;
+      for (int sc = 0; sc < nsc; ++sc) {
+        int rs = (sc_n[sc] + p - 1) / p;
+        for (int j = 1; j < p; ++j) {
+          const int over = sc_gt[(size_t)sc * NW + wid[j]];   // these tracks need a slice wider than wid[j]
+          if (!over) continue;
+          int wider = 0;
+          while (wider < j && wid[wider] > wid[j]) ++wider;
+          rs = std::max(rs, (over + wider - 1) / std::max(1, wider));
+        }
+        if (rs * p > kFusedTileTracks * tps) return -1;
+        rows += rs;
+      }
+      return rows;
+    };
+    int eq[kFusedMaxSlices];
+    for (int j = 0; j < PS0; ++j) eq[j] = r.ntgt;
+    const long long rows_eq = rows_of(eq, PS0);
+    // candidates: for a number of rows R of the whole run, slice j must take the tracks ranked j R .. (j + 1) R - 1 by need
+    int best[kFusedMaxSlices], bestp = 0, last[kFusedMaxSlices], lastp = 0, tried = 0;
+    long long best_rows = -1;
+    for (int R = (ntrk + kFusedMaxSlices - 1) / kFusedMaxSlices; R < ntrk && tried < 2; ++R) {
+      int wid[kFusedMaxSlices], p = 0, sum = 0;
+      for (int j = 0; j * R < ntrk && p < kFusedMaxSlices && sum <= 64; ++j) {
+        const int w = j == 0 ? r.ntgt : need_desc[(size_t)j * R];
+        if (w == 0) break;   // (tracks without a variable camera fit any slice)
+        wid[p++] = w; sum += w;
+      }
+      if (sum > 64 || p < 2) continue;
+      if (p == lastp && std::equal(wid, wid + p, last)) continue;
+      std::copy(wid, wid + p, last); lastp = p; ++tried;
+      // (and the same with what is left of the wave given to the narrow slices, next need up: slack for the sub-chunks' mix)
+      for (int variant = 0; variant < 2; ++variant) {
+        if (variant)
+          for (int j = p - 1; j >= 1; --j) {
+            int up = wid[j] + 1;
+            while (up <= wid[j - 1] && !hist[up]) ++up;
+            if (up <= wid[j - 1] && sum - wid[j] + up <= 64) { sum += up - wid[j]; wid[j] = up; }
+          }
+        const long long rows = rows_of(wid, p);
+        if (rows >= 0 && (best_rows < 0 || rows < best_rows)) { best_rows = rows; bestp = p; std::copy(wid, wid + p, best); }
+      }
+    }
+    if (best_rows < 0 || rows_eq < 0 || best_rows * 16 > rows_eq * 15) return;
+    // deal the tracks of every sub-chunk to their slots
+    slot_of.assign((size_t)ntrk, 0); sc_slots.assign((size_t)nsc, 0);
+    uint8_t fits_of[66];   // slices wide enough for a need (widths do not increase)
+    for (int v = 0, fits = bestp; v <= r.ntgt; ++v) { while (fits > 0 && best[fits - 1] < v) --fits; fits_of[v] = (uint8_t)fits; }
+    long long dealt_rows = 0;
+    for (int sc = 0; sc < nsc; ++sc) {
+      {   // the sub-chunk's tracks by need, descending, ties in plan order (one counting pass)
+        int at[66];
+        for (int v = 0; v <= r.ntgt; ++v) at[v] = sc_gt[(size_t)sc * NW + v];   // the tracks with need > v come first
+        by_need.assign((size_t)(sc_first[sc + 1] - sc_first[sc]), 0);
+        for (int i = sc_first[sc]; i < sc_first[sc + 1]; ++i) by_need[(size_t)at[run_trk[i].need]++] = i;
+      }
+      int fill[kFusedMaxSlices] = {0};
+      for (int i : by_need) {
+        const int fits = fits_of[run_trk[i].need];
+        int to = 0;
+        for (int j = 1; j < fits; ++j) if (fill[j] <= fill[to]) to = j;
+        const int slot = fill[to]++ * bestp + to;
+        if (slot >= kFusedTileTracks * tps) return;   // (rows_of said it fits: not reached; equal slices stay)
+        slot_of[i] = slot; sc_slots[sc] = std::max(sc_slots[sc], slot + 1);
+      }
+      dealt_rows += *std::max_element(fill, fill + bestp);
+    }
+    // rows_of() is the closed form of what this dealing reaches (most demanding first, emptiest fitting slice: optimal for nested
+    // slices); the shape was chosen on it, so a dealing that needs more rows does not stand
+    if (dealt_rows != best_rows) { shape_mismatches().fetch_add(1, std::memory_order_relaxed); return; }
+    for (int i = 0; i < ntrk; ++i)
+      for (int s = run_trk[i].s0; s < run_trk[i].s0 + run_trk[i].len; ++s) obs_tl[s] = (uint8_t)slot_of[i];
+    for (int sc = 0; sc < nsc; ++sc) fp.tile_trk_end[(size_t)run_tile0 + std::min(run_ntiles, (sc + 1) * tps) - 1] = sc_slots[sc];
+    r.gp = 1 | (bestp << 8) | kFusedUnequalSlices;
+    for (int j = 0, at = 0; j < bestp; ++j) { fp.tgts.push_back((unsigned short)(at | (best[j] << 8))); at += best[j]; }
+  };
   auto finalize_run = [&]() {
-    if (!run_ntiles) { run_cams.clear(); run_pairs.clear(); run_ccams.clear(); run_obs = 0; run_key0 = -1; ++serial; return; }
+    if (!run_ntiles) { run_cams.clear(); run_pairs.clear(); run_ccams.clear(); run_trk.clear(); run_kmin = 64; run_obs = 0; run_key0 = -1; ++serial; return; }
     std::sort(run_cams.begin(), run_cams.end());
     std::sort(run_pairs.begin(), run_pairs.end());
     FusedRun r;
@@ -626,6 +754,7 @@ void build_fused_segment(const theia_ba_handle_s* h, const std::vector<int64_t>&
     const int need = (int)std::max(lanes_tgt * r.ntgt, rows_cam * r.W);
     const int G = need <= 64 ? 1 : (need <= 128 ? 2 : 4);
     r.gp = G | ((G == 1 ? std::max(1, packing((size_t)r.ntgt, (size_t)r.W)) : 1) << 8);
+    if (bw == 0 && G == 1 && unequal_slices) shape_slices(r);
     r.part_off = (int)fp.part_doubles;
     fp.part_doubles += (size_t)r.ntgt * part_tgt + (size_t)r.W * part_cam;
     r.stage_off = (int)fp.stage.size();
@@ -639,7 +768,7 @@ void build_fused_segment(const theia_ba_handle_s* h, const std::vector<int64_t>&
       }
     fp.runs.push_back(r);
     run_tile0 += run_ntiles; run_ntiles = 0; run_obs = 0; run_key0 = -1;
-    run_cams.clear(); run_pairs.clear(); run_ccams.clear(); ++serial;
+    run_cams.clear(); run_pairs.clear(); run_ccams.clear(); run_trk.clear(); run_kmin = 64; ++serial;
   };
   auto push_long = [&](int q) {
     const int slot = (int)l_pt.size();
@@ -666,8 +795,12 @@ void build_fused_segment(const theia_ba_handle_s* h, const std::vector<int64_t>&
       push_long(q);
       continue;
     }
-    // the camera set of the previous track of this run again (tracks are ordered by first camera: common): nothing new
-    const bool same_set = serial == prev_serial && tc == prev_tc;
+    // a camera set that already joined this run (tracks are ordered by first camera: common): nothing new
+    unsigned set_hash = (unsigned)tc.size();
+    for (int c : tc) set_hash = set_hash * 0x9E3779B1u + (unsigned)c;
+    SeenSet& seen = seen_sets[(set_hash >> 16) & (kSeenSets - 1)];
+    const int prev_serial = serial;   // (the run open when the set was looked up)
+    const bool same_set = seen.stamp == serial && seen.n == (int)tc.size() && std::equal(tc.begin(), tc.end(), seen.cams);
     size_t ucams = run_cams.size(), upairs = run_pairs.size();
     if (!same_set) {
       tp.clear();
@@ -728,9 +861,12 @@ void build_fused_segment(const theia_ba_handle_s* h, const std::vector<int64_t>&
         const int sl = pair_slot(key);
         if (pair_stamp[sl] != serial) { pair_stamp[sl] = serial; pair_key[sl] = key; run_pairs.push_back(key); }
       }
-      prev_tc = tc; prev_serial = serial;
+      seen.stamp = serial; seen.n = (int)tc.size();
+      std::copy(tc.begin(), tc.end(), seen.cams);
     }
     for (int c : tcc) if (ccam_stamp[c] != serial) { ccam_stamp[c] = serial; ccam_local[c] = (uint8_t)run_ccams.size(); run_ccams.push_back(c); }
+    run_trk.push_back(RunTrack{(int)off[q], tc.empty() ? -1 : tc.back(), (int)tstart.size(), (uint8_t)L, 0});
+    run_kmin = std::min(run_kmin, (int)tc.size());
   }
   close_tile(q_end);
   finalize_run();
@@ -1502,7 +1638,16 @@ int ba_create_impl(const theia_ba_problem* p, const theia_ba_options* o, theia_b
       for (const FusedRun& r : fplan.runs) { auto& e = by[r.gp]; e.first++; e.second += (r.ntiles + 3) / 4; nsc += (r.ntiles + 3) / 4; }
       fprintf(stderr, "theia_hip fused plan: %zu runs, %lld sub-chunks (%.1f obs each), %zu partial doubles, %d sum items\n",
               fplan.runs.size(), nsc, nsc ? (double)h->nobs_main / nsc : 0.0, fplan.part_doubles, h->n_sum_items);
-      for (auto& kv : by) fprintf(stderr, "  G=%d slices/wave=%d: %d runs, %d sub-chunks\n", kv.first & 0xff, kv.first >> 8, kv.second.first, kv.second.second);
+      fprintf(stderr, "  slice shapes whose dealing missed the closed-form rows (process total): %lld\n", shape_mismatches().load());
+      for (auto& kv : by) fprintf(stderr, "  G=%d slices/wave=%d%s: %d runs, %d sub-chunks\n", kv.first & 0xff, (kv.first >> 8) & 0xff, (kv.first & kFusedUnequalSlices) ? " (unequal)" : "", kv.second.first, kv.second.second);
+    }
+    // THEIA_HIP_PLAN_STATS=<path>: the lane-occupancy model of phase S over this plan (ba_plan_stats.h), as JSON
+    if (const char* sp = getenv("THEIA_HIP_PLAN_STATS")) {
+      if (*sp && h->fused_bw == 0) {
+        const PlanStats ps = fused_plan_occupancy(fplan.runs.data(), (int)fplan.runs.size(), fplan.tgts.data(), tstart.data(), tcount.data(),
+                                                  fplan.tile_trk_end.data(), fplan.obs_lc.data(), fplan.obs_tl.data(), fused_tiles_per_subchunk(h->pd));
+        if (FILE* f = fopen(sp, "w")) { write_plan_stats_json(f, ps, kFusedRunCostSteps); fclose(f); }
+      }
     }
     if (fplan.runs.empty()) fplan.runs.push_back(FusedRun{0, 0, 0, 0, 0, 0, 0, 1 | (1 << 8), 0, 0});
     {   // the workgroups of k_lin_schur take runs from a queue, the most expensive first (cost ~ wave tiles, weighted by the
