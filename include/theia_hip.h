@@ -1375,6 +1375,48 @@ int theia_hip_build_tracks(int32_t num_views, const int64_t* feat_off, int32_t n
                            const theia_track_builder_options* options, int64_t* track_off, int32_t* obs_view,
                            int32_t* obs_feature, int32_t* obs_track, theia_track_builder_stats* stats);
 int theia_hip_track_builder_last_timings(theia_track_builder_timings* out);
+/* The image-pair selection in front of the matcher, as FeatureExtractorAndMatcher::
+ * SelectImagePairsWithGlobalDescriptorMatching (sfm/feature_extractor_and_matcher.cc:356-381; on by default with 100 neighbours,
+ * sfm/reconstruction_builder.h:113-118) runs it: one global descriptor per image, then GraphMatch.
+ *
+ * theia_hip_mean_pool_descriptors: FisherVectorExtractor::ExtractGlobalDescriptor (matching/fisher_vector_extractor.cc:56-69),
+ * the element-wise mean in this fork, for every image of the flat feat_off / descriptors [total][dim] form the matcher takes:
+ * pooled = +0; for the image's features in order: pooled += f (float); pooled /= float(n), correctly rounded.  Bit for bit the
+ * reference's (element-wise float adds in feature order are the same whatever Eigen vectorises).  THEIA_HIP_ERR_INVALID_ARGUMENT
+ * (nothing written): negative num_images, dim < 1, null arrays, feat_off that does not start at 0 or decreases, an image without
+ * features (the reference's CHECK_GT, :58), num_images * dim >= 2^31, and -- the one refusal that reads the data, on the device --
+ * a NaN among the descriptors (the reference's CHECK, :64).  num_images == 0 returns 0. */
+int theia_hip_mean_pool_descriptors(int32_t num_images, const int64_t* feat_off, int32_t dim, const float* descriptors,
+                                    float* global_descriptors /*[num_images][dim]*/);
+/* theia_hip_graph_match: GraphMatch (matching/graph_match.cc:48-130) on global_descriptors [num_images][dim].  With
+ * k = min(num_images - 1, num_nearest_neighbors) (:56-58), for i ascending: image i's k nearest images under (squared distance,
+ * image index) ascending (the partial_sort of pair<float, int>, :78-80); for each such neighbour s, every image currently in
+ * ranked[s] gets i into its expanded set (:88-92), then i and s enter each other's ranked sets (:96-97).  Selected: every ranked
+ * or expanded entry (a, m) with a < m (:108-122), once.  The rule depends on the order of i, and an expanded entry (a, i) with
+ * a > i is dropped, not turned around; both are kept.  The closed form the device evaluates, with kNN(x) the list above and
+ * inv(x) = { y : x in kNN(y) }: a < i is selected iff i in kNN(a) or a in kNN(i); or some s is in kNN(a) and in kNN(i); or some
+ * s < i has a in kNN(s) and s in kNN(i).
+ * The distance, every operation fixed: d = fmaf chain over the dimensions ascending from +0.0f of (a - b) * (a - b), the float
+ * subtraction first, one accumulator; symmetric bit for bit.  Stated deviation: Eigen's (a - b).squaredNorm() (:71) sums in
+ * packet order, so the two can order differently two images whose distances differ in the last bits.
+ * Outputs: *num_pairs is always the full count; pair_image1 < pair_image2, ascending by (image1, image2), written only when the
+ * count fits pair_capacity (ask with capacity 0, call again); knn_index / knn_distance (each may be NULL) [num_images][k], row i
+ * the k nearest of image i in ascending (distance, index); stats may be NULL.  The same bytes on every run.
+ * THEIA_HIP_ERR_INVALID_ARGUMENT (nothing written, no device touched): negative sizes, dim < 1, num_nearest_neighbors < 0, null
+ * arrays with non-zero sizes, num_images * dim >= 2^31, a NaN or infinite global descriptor (a NaN distance has no place in the
+ * order).  num_images <= 1 or num_nearest_neighbors == 0: 0 with zero pairs, nothing launched.  THEIA_HIP_ERR_OUT_OF_MEMORY: the
+ * num_images^2-bit matrix, the kNN workspace or a row of num_images bits (beyond 262 144 images) does not fit.
+ * THEIA_HIP_ERR_NO_DEVICE without a device: there is no CPU fallback. */
+typedef struct theia_graph_match_stats {
+  int64_t num_nearest_neighbors;   /* k after the clamp to N - 1 */
+  int64_t num_ranked_pairs;        /* unordered pairs with i in kNN(a) or a in kNN(i) */
+  int64_t num_expanded_pairs;      /* selected by the expansion only */
+  int64_t num_pairs;               /* the two together */
+} theia_graph_match_stats;
+int theia_hip_graph_match(int32_t num_images, int32_t dim, const float* global_descriptors, int32_t num_nearest_neighbors,
+                          int64_t pair_capacity, int32_t* pair_image1, int32_t* pair_image2, int64_t* num_pairs,
+                          int32_t* knn_index /* optional [num_images][k] */, float* knn_distance /* optional */,
+                          theia_graph_match_stats* stats /* optional */);
 /* n draws of RandomNumberGenerator(seed).RandInt(lo, hi) (util/random.cc:46-84): host code that follows the reference's
  * generator outside the RANSAC sampler (the random candidates of GuidedEpipolarMatcher::FindFeaturesNearEpipolarLines). */
 int theia_hip_randint_stream(uint32_t seed, int32_t n, int32_t lo, int32_t hi, int32_t* out);

@@ -168,3 +168,105 @@ class BruteForceFeatureMatcher:
             m.correspondences = [FeatureCorrespondence(fa.keypoints[a], fb.keypoints[b]) for a, b in idx]
             out.append(m)
         return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Image-pair selection by global descriptors (csrc/graph_match.hip): FisherVectorExtractor (matching/
+# fisher_vector_extractor.cc:56-69, the element-wise mean in the reference's fork), GraphMatch (matching/graph_match.cc:48-130)
+# and FeatureExtractorAndMatcher::SelectImagePairsWithGlobalDescriptorMatching (sfm/feature_extractor_and_matcher.cc:356-381).
+
+
+def mean_pool_descriptors(descriptors_list):
+    """theia_hip_mean_pool_descriptors on a list of per-image descriptor arrays [n_i][dim]: the global descriptors
+    [num_images][dim], float32."""
+    descs = [np.ascontiguousarray(d, dtype=np.float32) for d in descriptors_list]
+    descs = [d.reshape(len(d), -1) if d.ndim != 2 else d for d in descs]
+    dims = {d.shape[1] for d in descs if len(d)}
+    if len(dims) > 1:
+        raise capi.TheiaHipError(capi.THEIA_HIP_ERR_INVALID_ARGUMENT, "descriptor lengths differ")
+    dim = dims.pop() if dims else 1
+    feat_off = np.zeros(len(descs) + 1, dtype=np.int64)
+    feat_off[1:] = np.cumsum([len(d) for d in descs])
+    flat = np.ascontiguousarray(np.concatenate([d.reshape(-1, dim) for d in descs]) if descs else np.zeros((0, dim), np.float32))
+    out = np.zeros((len(descs), dim), np.float32)
+    capi.check(capi.lib().theia_hip_mean_pool_descriptors(len(descs), capi.ptr(feat_off, C.c_int64), dim, capi.ptr(flat, C.c_float),
+                                                           capi.ptr(out, C.c_float)))
+    return out
+
+
+def graph_match(global_descriptors, k, want_knn=False):
+    """theia_hip_graph_match on global descriptors [num_images][dim]: (pairs [num_pairs][2] int32 with image1 < image2, ascending,
+    stats dict), and with want_knn also (knn_index [num_images][k'], knn_distance [num_images][k']), k' = min(num_images - 1, k)."""
+    g = np.ascontiguousarray(global_descriptors, dtype=np.float32)
+    if g.ndim != 2:
+        raise capi.TheiaHipError(capi.THEIA_HIP_ERR_INVALID_ARGUMENT, "global descriptors must be [num_images][dim]")
+    n, dim = g.shape
+    k = int(k)
+    L = capi.lib()
+    count = C.c_int64(0)
+    stats = capi.GraphMatchStats()
+    kk = max(0, min(n - 1, k))
+    knn_index = np.zeros((n, kk), np.int32) if want_knn else None
+    knn_distance = np.zeros((n, kk), np.float32) if want_knn else None
+
+    def call(capacity, p1, p2):
+        capi.check(L.theia_hip_graph_match(n, dim, capi.ptr(g, C.c_float), k, capacity, capi.ptr(p1, C.c_int32),
+                                           capi.ptr(p2, C.c_int32), C.byref(count), capi.ptr(knn_index, C.c_int32),
+                                           capi.ptr(knn_distance, C.c_float), C.byref(stats)))
+
+    # a row holds about 2 k^2 + k pairs where the inverse lists are about as long as the lists (and there are never more than all
+    # pairs): one call where that guess is a modest array, else the count first; a count beyond the guess repeats the call
+    guess = min(n * (n - 1) // 2, n * (2 * kk * kk + kk))
+    capacity = guess if guess <= (1 << 24) else 0
+    p1 = np.zeros(capacity, np.int32); p2 = np.zeros(capacity, np.int32)
+    call(capacity, p1, p2)
+    if count.value > capacity:
+        capacity = count.value
+        p1 = np.zeros(capacity, np.int32); p2 = np.zeros(capacity, np.int32)
+        call(capacity, p1, p2)
+    pairs = np.stack([p1[:count.value], p2[:count.value]], axis=1)
+    if want_knn:
+        return pairs, stats.as_dict(), knn_index, knn_distance
+    return pairs, stats.as_dict()
+
+
+class FisherVectorExtractor:
+    """matching/fisher_vector_extractor.h in the reference's shape: the options and the training calls are kept and do nothing,
+    ExtractGlobalDescriptor is the element-wise mean of the features."""
+
+    class Options:
+        def __init__(self):
+            self.num_gmm_clusters = 16
+            self.max_num_features_for_training = 100000
+
+    def __init__(self, options=None):
+        self.options_ = options if options is not None else FisherVectorExtractor.Options()
+
+    def AddFeaturesForTraining(self, features):
+        pass
+
+    def Train(self):
+        return True
+
+    def ExtractGlobalDescriptor(self, features):
+        return mean_pool_descriptors([np.asarray(features, dtype=np.float32)])[0]
+
+
+def GraphMatch(image_names, global_descriptors, num_nearest_neighbors_for_global_descriptor_matching):
+    """[(name, name)]: every selected pair oriented by image index, the list sorted by the pair of names (graph_match.cc:125-128)."""
+    names = list(image_names)
+    g = np.asarray(global_descriptors, dtype=np.float32).reshape(len(names), -1) if len(names) else np.zeros((0, 1), np.float32)
+    pairs, _ = graph_match(g, num_nearest_neighbors_for_global_descriptor_matching)
+    return sorted((names[a], names[b]) for a, b in pairs.tolist())
+
+
+def SelectImagePairsWithGlobalDescriptorMatching(matcher, num_nearest_neighbors=100):
+    """Pools the features of matcher.image_names_ in AddImage order (stated deviation: the reference takes the order of its
+    database's ImageNamesOfFeatures), runs GraphMatch and hands the pairs to matcher.SetImagePairsToMatch; returns them."""
+    names = list(matcher.image_names_)
+    if not FisherVectorExtractor().Train():
+        raise RuntimeError("the global descriptor extractor did not train")
+    pooled = mean_pool_descriptors([matcher.features_[name].descriptors for name in names])
+    pairs = GraphMatch(names, pooled, num_nearest_neighbors)
+    matcher.SetImagePairsToMatch(pairs)
+    return pairs
