@@ -571,6 +571,94 @@ int theia_hip_linear_rotations(int32_t num_views, int32_t num_edges, const int32
                                const double* relative_rotations, const theia_linear_rotation_options* options /*NULL = defaults*/,
                                double* orientations_out, uint8_t* estimated_out, theia_linear_rotation_summary* summary);
 
+/* LagrangeDualRotationEstimator::EstimateRotations (global_pose_estimation/lagrange_dual_rotation_estimator.cc:51-197;
+ * pybind sfm.cc:1797-1801; the LAGRANGE_DUAL global rotation estimator of the global pipeline,
+ * global_reconstruction_estimator.cc:354-360, and the first half of HYBRID, hybrid_rotation_estimator.cc:69-109): global
+ * orientations from the pairs' relative rotations alone, without an initial guess, by the rank-restricted SDP relaxation
+ * of rotation averaging with its certificate of global optimality (csrc/lagrange_dual_rotations.hip).
+ * Per pair e = (i, j) with R_e = AngleAxisToRotationMatrix(relative_rotations[e]), R_j ~ R_e R_i, the symmetric 3n x 3n
+ * matrix R over the n views that have an edge, indexed in ascending view order, has R_e' at block (i, j) and R_e at block
+ * (j, i) (:167-197); Q = -R.  The unknown is Y [r][3n], r = min_rank at first, all zero unless y_init is given.
+ *   BCM (math/rank_restricted_sdp_solver.cc:58-129): per sweep, for every view in the sweep order, G_i = sum over its
+ *     neighbours j of Y_j Q_ji and Y_i = U V' of the thin SVD of -G_i ([I_3; 0] for a zero block, as Eigen's JacobiSVD
+ *     gives).  f = tr(Y Q Y').  Before each sweep err = |f_prev - f| / max(|f_prev|, 1) with f_prev = DBL_MAX at first
+ *     (math/bcm_sdp_solver.h:64-72); the BCM stops when err <= tolerance or after max_iterations sweeps;
+ *     total_iterations_num = sweeps + 1 (:127).
+ *   Staircase (math/riemannian_staircase.cc:57-111), for r = min_rank .. max_rank: the BCM; Lambda = SymBlockDiag(Q Y' Y);
+ *     lambda_min(Q - Lambda) > -min_eigenvalue_nonnegativity_tolerance: certified, stop.  Otherwise a zero row is added to
+ *     Y, Ydot = that row set to v', v a unit direction of negative curvature, and alpha is backtracked from
+ *     max(16e-6, 10 gradient_tolerance / |lambda_min|) by halving down to 1e-6 (:215-309): the first trial
+ *     Y+ = per-view polar factor of Y + alpha Ydot with f(Y+) < f(Y), Riemannian gradient norm > gradient_tolerance and
+ *     > preconditioned_gradient_tolerance (no preconditioner) is taken, else the trial of least f when that is below
+ *     f(Y), else the staircase stops (the added zero row stays, as in the reference).  After an uncertified level at
+ *     max_rank the escape still runs, so final_rank is at most max_rank + 1.
+ *   Solution (:311-319, :148-165): X_i = Y_0' Y_i, projected by ProjectToSOd (math/rotation.cc:105-120) when the rank left
+ *     behind is above min_rank; view i's orientation is X_i', negated when its determinant is negative, as angle-axis.
+ *     The gauge view, whose orientation is the identity, is the lowest view that has an edge (the reference: its view of
+ *     index 0, which may have no edge).
+ * Stated deviations.  (1) G_i is gathered from the neighbours at every update, where the reference keeps G incrementally:
+ * the same sums in another order.  (2) The sweep is scheduled in levels of views that share no edge; sweep_order INDEX is
+ * the reference's order, COLOURED the order by (greedy colour in index order, index), which is the reference's sweep on a
+ * relabelled graph (its SetViewIdToIndex allows it) and needs as many launches per sweep as there are colours.  (3) The
+ * certificate is a dense FP64 Cholesky of Q - Lambda + sigma I: no failed pivot at sigma = the tolerance is the
+ * reference's test.  (4) Where the reference's Lanczos starts from a random vector, v comes from a shift bracketed to 5 %
+ * between a failing and a succeeding factorisation and inverse iteration from a fixed start; it is admitted only when
+ * v'(Q - Lambda)v <= 0.9 lambda_min is proven by the bracket.  The staircase's path after an escape depends on v within
+ * the arithmetic of the BCM's tolerance.  No atomics: two runs on one input are bit-identical.
+ * The polar factor is defined where sigma_min(G_i) >= 1e-3 sigma_max(G_i) (|Y_i' Y_i - I| <= 1e-14); a non-zero block with
+ * a zero singular value makes f non-finite and the call returns THEIA_HIP_ERR_INTERNAL.
+ * solver_type THEIA_SDP_RANK_DEFICIENT_BCM runs one BCM at rank 3 (or rank_init) with no certificate, as the reference
+ * uses RankRestrictedSDPSolver; ComputeErrorBound (:86-145) is not part of EstimateRotations and is not built.
+ * edges [num_edges][2] = (i, j); y_init: NULL, or [rank_init][3n] with rank_init in 3 .. 10 (inside min_rank .. max_rank
+ * for the staircase) whose blocks have orthonormal columns; orientations_out [num_views][3] and estimated_out
+ * [num_views] as theia_hip_linear_rotations: a view without an edge gets 0 and its row is left untouched; y_out: NULL, or
+ * room for [max_rank + 1][3n], of which [final_rank][3n] is written; level_log_out: NULL, or [level_log_rows][8], one row
+ * per BCM: rank, sweeps, f after the level, certified, the lambda_min estimate (NaN where certified, which needs none),
+ * v'(Q - Lambda)v of the escape direction, the accepted alpha (0: none), 1 when the least-f fallback was used;
+ * summary->num_levels counts the rows there would be.
+ * Returns 0 whatever the staircase's end, as the reference returns true; summary->end_state says which it was.
+ * THEIA_HIP_ERR_UNSUPPORTED: solver_type THEIA_SDP_RBR_BCM (no caller's default; its dense 3n x 3n iterate is another
+ * design).  THEIA_HIP_ERR_INVALID_ARGUMENT (checked before the device is touched; outputs untouched, summary zeroed): no
+ * edge (the reference's CHECK_GT, :91); a view out of range; a pair naming one view twice; an unordered pair given twice
+ * (the reference's map cannot hold one, and its adjacency list would count it inconsistently); the views that have edges
+ * do not form one connected graph; min_rank or max_rank outside 3 .. 10 or min_rank > max_rank; rank_init out of range; a
+ * tolerance that is negative or not finite; max_iterations <= 0; an unknown solver_type or sweep_order.
+ * THEIA_HIP_ERR_OUT_OF_MEMORY: the dense (3n + 1)^2 array of doubles of the certificate does not fit on the device (only
+ * the staircase allocates it).  THEIA_HIP_ERR_INTERNAL: f not finite; no admissible v (outputs untouched). */
+enum { THEIA_SDP_RBR_BCM = 0, THEIA_SDP_RANK_DEFICIENT_BCM = 1, THEIA_SDP_RIEMANNIAN_STAIRCASE = 2 };   /* math/solver_options.h:43-49 */
+enum { THEIA_SWEEP_ORDER_INDEX = 0, THEIA_SWEEP_ORDER_COLOURED = 1 };
+enum {
+  THEIA_LAGRANGE_DUAL_END_BCM = 0,            /* RANK_DEFICIENT_BCM: no certificate asked for */
+  THEIA_LAGRANGE_DUAL_END_CERTIFIED = 1,
+  THEIA_LAGRANGE_DUAL_END_MAX_RANK = 2,       /* the level at max_rank was not certified */
+  THEIA_LAGRANGE_DUAL_END_ESCAPE_FAILED = 3   /* no trial step lowered f */
+};
+typedef struct theia_lagrange_dual_options {
+  int32_t solver_type;             /* THEIA_SDP_RIEMANNIAN_STAIRCASE */
+  int32_t max_iterations;          /* 500 sweeps per BCM */
+  int32_t min_rank, max_rank;      /* 3, 10 */
+  int32_t sweep_order;             /* THEIA_SWEEP_ORDER_INDEX */
+  int32_t reserved;
+  double tolerance;                /* 1e-8 */
+  double min_eigenvalue_nonnegativity_tolerance;   /* 1e-5 */
+  double gradient_tolerance, preconditioned_gradient_tolerance;   /* 1e-2, 1e-4 */
+} theia_lagrange_dual_options;
+typedef struct theia_lagrange_dual_summary {
+  int32_t total_iterations_num;    /* of the last BCM, as the reference's Summary: sweeps + 1 */
+  int32_t sweeps, total_sweeps;    /* of the last BCM; of all of them */
+  int32_t final_rank, end_state, num_levels, num_views_in_system, gauge_view;
+  int32_t schedule_levels, schedule_launches;   /* levels of the sweep order; launches per sweep */
+  int32_t factorisations, reserved;
+  double f;                        /* tr(Y Q Y') of the Y left behind */
+  double lambda_min;               /* the estimate of the last uncertified level; NaN when the last level was certified */
+  double setup_ms, sweep_ms, certificate_ms, escape_ms, total_ms;
+} theia_lagrange_dual_summary;
+int theia_hip_lagrange_dual_rotations(int32_t num_views, int32_t num_edges, const int32_t* edges,
+                                      const double* relative_rotations, const theia_lagrange_dual_options* options /*NULL = defaults*/,
+                                      int32_t rank_init, const double* y_init /* optional */, double* orientations_out,
+                                      uint8_t* estimated_out, double* y_out /* optional */, theia_lagrange_dual_summary* summary,
+                                      double* level_log_out /* optional */, int32_t level_log_rows);
+
 /* NonlinearRotationEstimator::EstimateRotations (global_pose_estimation/nonlinear_rotation_estimator.cc:49-98 with
  * pairwise_rotation_error.h:65-96; pybind sfm.cc:1782-1787; the NONLINEAR global rotation estimator of the global
  * pipeline): Ceres' Levenberg-Marquardt solve over one PairwiseRotationError block per pair, weight 1, under

@@ -179,6 +179,27 @@ class LinearRotationSummary(C.Structure):
                 ("factor_ms", C.c_double), ("iterate_ms", C.c_double)]
 
 
+class LagrangeDualOptions(C.Structure):
+    """theia_lagrange_dual_options."""
+    _fields_ = [("solver_type", C.c_int32), ("max_iterations", C.c_int32), ("min_rank", C.c_int32), ("max_rank", C.c_int32),
+                ("sweep_order", C.c_int32), ("reserved", C.c_int32), ("tolerance", C.c_double),
+                ("min_eigenvalue_nonnegativity_tolerance", C.c_double), ("gradient_tolerance", C.c_double),
+                ("preconditioned_gradient_tolerance", C.c_double)]
+
+
+class LagrangeDualSummary(C.Structure):
+    """theia_lagrange_dual_summary."""
+    _fields_ = [("total_iterations_num", C.c_int32), ("sweeps", C.c_int32), ("total_sweeps", C.c_int32),
+                ("final_rank", C.c_int32), ("end_state", C.c_int32), ("num_levels", C.c_int32),
+                ("num_views_in_system", C.c_int32), ("gauge_view", C.c_int32), ("schedule_levels", C.c_int32),
+                ("schedule_launches", C.c_int32), ("factorisations", C.c_int32), ("reserved", C.c_int32),
+                ("f", C.c_double), ("lambda_min", C.c_double), ("setup_ms", C.c_double), ("sweep_ms", C.c_double),
+                ("certificate_ms", C.c_double), ("escape_ms", C.c_double), ("total_ms", C.c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 class NonlinearRotationOptions(C.Structure):
     """theia_nonlinear_rotation_options."""
     _fields_ = [("max_num_iterations", C.c_int32), ("reserved", C.c_int32), ("robust_loss_width", C.c_double),
@@ -344,7 +365,7 @@ EXPORTED_SYMBOLS = [
     "theia_hip_ba_reset_parameters", "theia_hip_estimate_tracks", "theia_hip_ba_set_shard", "theia_hip_ba_snapshot_parameters", "theia_hip_ba_restore_parameters", "theia_hip_ba_set_options", "theia_hip_ba_run", "theia_hip_ba_download",
     "theia_hip_ba_destroy", "theia_hip_ba_covariance", "theia_hip_ba_evaluate", "theia_hip_ba_evaluate_ex", "theia_hip_ba_reduced_system",
     "theia_hip_ba_set_allreduce", "theia_hip_ba_set_inner_global", "theia_hip_ba_plan_info", "theia_hip_ba_kernel_instances", "theia_hip_rccl_unique_id", "theia_hip_rccl_comm_create",
-    "theia_hip_optimize_relative_position_batch", "theia_hip_rccl_comm_destroy", "theia_hip_rccl_comm_count", "theia_hip_ba_set_rccl", "theia_hip_dense_spd_solve", "theia_hip_dense_spd_solve_multi", "theia_hip_tile_sparse_spd_solve", "theia_hip_tile_sparse_spd_solve_sharded", "theia_hip_robust_rotation_averaging", "theia_hip_linear_rotations", "theia_hip_nonlinear_rotations", "theia_hip_nonlinear_positions", "theia_hip_lud_positions", "theia_hip_ligt_positions", "theia_hip_linear_triplet_positions", "theia_hip_filter_view_pairs_from_relative_translation", "theia_hip_translation_filter_last_stats", "theia_hip_filter_view_pairs_from_orientation", "theia_hip_filter_view_graph_cycles_by_rotation", "theia_hip_remove_disconnected_view_pairs", "theia_ransac_params_default",
+    "theia_hip_optimize_relative_position_batch", "theia_hip_rccl_comm_destroy", "theia_hip_rccl_comm_count", "theia_hip_ba_set_rccl", "theia_hip_dense_spd_solve", "theia_hip_dense_spd_solve_multi", "theia_hip_tile_sparse_spd_solve", "theia_hip_tile_sparse_spd_solve_sharded", "theia_hip_robust_rotation_averaging", "theia_hip_linear_rotations", "theia_hip_lagrange_dual_rotations", "theia_hip_nonlinear_rotations", "theia_hip_nonlinear_positions", "theia_hip_lud_positions", "theia_hip_ligt_positions", "theia_hip_linear_triplet_positions", "theia_hip_filter_view_pairs_from_relative_translation", "theia_hip_translation_filter_last_stats", "theia_hip_filter_view_pairs_from_orientation", "theia_hip_filter_view_graph_cycles_by_rotation", "theia_hip_remove_disconnected_view_pairs", "theia_ransac_params_default",
     "theia_hip_ransac_estimate_batch", "theia_hip_five_point_relative_pose",
     "theia_hip_pose_from_three_points", "theia_hip_sqpnp", "theia_hip_dls_pnp", "theia_hip_dls_macaulay_terms", "theia_hip_four_point_pose_and_focal_length", "theia_hip_four_point_focal_length_radial_distortion", "theia_hip_four_point_focal_length_radial_distortion_ex", "theia_hip_release_scratch", "theia_hip_guided_knn", "theia_hip_brute_force_options_default", "theia_hip_brute_force_knn2", "theia_hip_brute_force_match_pairs", "theia_hip_track_builder_options_default", "theia_hip_build_tracks", "theia_hip_track_builder_last_timings", "theia_hip_mean_pool_descriptors", "theia_hip_graph_match", "theia_hip_randint_stream", "theia_hip_selftest_wave_primitives",
     "theia_hip_selftest_eig_team", "theia_hip_selftest_svd9_team", "theia_hip_selftest_five_point_pre_team",
@@ -400,6 +421,9 @@ def lib():
                                                       C.POINTER(RotationOptions), C.POINTER(RotationSummary)]
     L.theia_hip_linear_rotations.argtypes = [C.c_int32, C.c_int32, c_int32_p, c_double_p, C.POINTER(LinearRotationOptions),
                                              c_double_p, c_uint8_p, C.POINTER(LinearRotationSummary)]
+    L.theia_hip_lagrange_dual_rotations.argtypes = [C.c_int32, C.c_int32, c_int32_p, c_double_p, C.POINTER(LagrangeDualOptions),
+                                                    C.c_int32, c_double_p, c_double_p, c_uint8_p, c_double_p,
+                                                    C.POINTER(LagrangeDualSummary), c_double_p, C.c_int32]
     L.theia_hip_nonlinear_rotations.argtypes = [C.c_int32, c_double_p, c_uint8_p, C.c_int32, c_int32_p, c_double_p,
                                                 C.POINTER(NonlinearRotationOptions), C.POINTER(NonlinearRotationSummary),
                                                 c_double_p, C.c_int32]

@@ -11,7 +11,11 @@ global_pose_estimation/linear_rotation_estimator.{h,cc}), runs through theia_hip
 (csrc/linear_rotations.hip); the Ceres refinement of given orientations, pytheia.sfm.NonlinearRotationEstimator
 (sfm.cc:1782-1787 -> global_pose_estimation/nonlinear_rotation_estimator.{h,cc}), through theia_hip_nonlinear_rotations
 (csrc/nonlinear_rotations.hip); both pipelines seed it with OrientationsFromMaximumSpanningTree
-(view_graph/orientations_from_maximum_spanning_tree.cc), host code here as there.  The positions run
+(view_graph/orientations_from_maximum_spanning_tree.cc), host code here as there.  The two estimators that certify their
+answer, pytheia.sfm.LagrangeDualRotationEstimator and HybridRotationEstimator (sfm.cc:1797-1807 ->
+global_pose_estimation/lagrange_dual_rotation_estimator.{h,cc}, hybrid_rotation_estimator.{h,cc}), run through
+theia_hip_lagrange_dual_rotations (csrc/lagrange_dual_rotations.hip), the second followed by the IRLS half of
+theia_hip_robust_rotation_averaging.  The positions run
 through theia_hip_lud_positions (csrc/lud_positions.hip), or, from the tracks' features and without the pairs' relative
 translations, through theia_hip_ligt_positions (pytheia.sfm.LiGTPositionEstimator, sfm.cc:1728-1747 ->
 global_pose_estimation/LiGT_position_estimator.{h,cc}; csrc/ligt_positions.hip), or, from the pairs' relative poses and
@@ -42,7 +46,8 @@ from .synth import angle_axis_to_matrix
 
 class GlobalRotationEstimatorType(enum.IntEnum):  # reconstruction_estimator_options.h:64-70
     # on the device: ROBUST_L1L2 (RobustRotationEstimator), NONLINEAR (NonlinearRotationEstimator), LINEAR
-    # (LinearRotationEstimator); LAGRANGE_DUAL and HYBRID need an SDP solver and have no counterpart here
+    # (LinearRotationEstimator), LAGRANGE_DUAL (LagrangeDualRotationEstimator: the rank-restricted SDP relaxation by block
+    # coordinate minimisation with the Riemannian staircase) and HYBRID (HybridRotationEstimator: that, then IRLS)
     ROBUST_L1L2 = 0
     NONLINEAR = 1
     LINEAR = 2
@@ -212,6 +217,211 @@ class LinearRotationEstimator:
         for v, k in ids.items():
             result.setdefault(v, out[k].copy())
         return result
+
+
+class SDPSolverType(enum.IntEnum):  # math/solver_options.h:43-49
+    RBR_BCM = 0
+    RANK_DEFICIENT_BCM = 1
+    RIEMANNIAN_STAIRCASE = 2
+    SE_SYNC = 3   # not implemented in the reference either
+    SHONAN = 4    # not implemented in the reference either
+
+
+class PreconditionerType(enum.IntEnum):  # math/solver_options.h:51-56; only None is implemented in the reference
+    NONE = 0
+    JACOBI = 1
+    INCOMPLETE_CHOLESKY = 2
+    REGULARIZED_CHOLESKY = 3
+
+
+class SweepOrder(enum.IntEnum):
+    """The order of a BCM sweep: INDEX is the reference's; COLOURED orders the views by (greedy colour, index), the
+    reference's sweep on a relabelled graph, in as many launches per sweep as there are colours."""
+    INDEX = 0
+    COLOURED = 1
+
+
+class RiemannianStaircaseOptions:  # math/solver_options.h:58-73
+    def __init__(self):
+        self.min_rank = 3
+        self.max_rank = 10
+        self.max_eigen_solver_iterations = 20   # of the reference's Lanczos; the certificate here is a factorisation
+        self.min_eigenvalue_nonnegativity_tolerance = 1e-5
+        self.num_Lanczos_vectors = 20           # likewise unused
+        self.local_solver_type = SDPSolverType.RANK_DEFICIENT_BCM
+        self.gradient_tolerance = 1e-2
+        self.preconditioned_gradient_tolerance = 1e-4
+
+
+class SDPSolverOptions:  # math/solver_options.h:75-97
+    def __init__(self, max_iter=500, tol=1e-8, log=True):
+        self.max_iterations = max_iter
+        self.tolerance = tol
+        self.verbose = log
+        self.num_threads = 8
+        self.solver_type = SDPSolverType.RIEMANNIAN_STAIRCASE
+        self.preconditioner_type = PreconditionerType.NONE
+        self.riemannian_staircase_options = RiemannianStaircaseOptions()
+        self.sweep_order = SweepOrder.INDEX     # no counterpart in the reference
+
+    def to_c(self):
+        r = self.riemannian_staircase_options
+        o = capi.LagrangeDualOptions()
+        o.solver_type = int(self.solver_type)
+        o.max_iterations = int(self.max_iterations)
+        o.min_rank = int(r.min_rank)
+        o.max_rank = int(r.max_rank)
+        o.sweep_order = int(self.sweep_order)
+        o.tolerance = float(self.tolerance)
+        o.min_eigenvalue_nonnegativity_tolerance = float(r.min_eigenvalue_nonnegativity_tolerance)
+        o.gradient_tolerance = float(r.gradient_tolerance)
+        o.preconditioned_gradient_tolerance = float(r.preconditioned_gradient_tolerance)
+        return o
+
+
+LAGRANGE_DUAL_END_STATES = ("bcm", "certified", "max_rank", "escape_failed")   # THEIA_LAGRANGE_DUAL_END_*
+
+
+def lagrange_dual_rotations(num_views, edges, relative_rotations, options=None, y_init=None, orientations_out=None,
+                            want_y=False, want_log=False):
+    """theia_hip_lagrange_dual_rotations on arrays: edges [E][2] view indices, relative_rotations [E][3] =
+    TwoViewInfo::rotation_2, y_init: None or [rank][3 m] over the m views that have an edge, in view order.  Returns
+    (return code, orientations [num_views][3], estimated [num_views] bool, LagrangeDualSummary) and then, with want_y,
+    Y [final_rank][3 m] and, with want_log, the per-level log [levels][8] = (rank, sweeps, f, certified, lambda_min
+    estimate, v' S v of the escape direction, accepted alpha, fallback used).  A view without an edge keeps its
+    orientations_out row (zeros without orientations_out); on a refusal nothing is written."""
+    o = (options or SDPSolverOptions()).to_c()
+    n = int(num_views)
+    e, r = _pair_arrays(edges, relative_rotations, "relative rotation")
+    out = np.zeros((max(n, 0), 3)) if orientations_out is None else orientations_out
+    if out.shape != (n, 3) or out.dtype != np.float64 or not out.flags["C_CONTIGUOUS"]:
+        raise ValueError("orientations_out must be a C-contiguous float64 [num_views][3] array")
+    est = np.zeros(max(n, 0), dtype=np.uint8)
+    y0, rank_init = None, 0
+    if y_init is not None:
+        y0 = np.ascontiguousarray(np.asarray(y_init, dtype=np.float64))
+        if y0.ndim != 2 or y0.shape[1] % 3:
+            raise ValueError("y_init must be [rank][3 m]")
+        in_range = e[(e >= 0).all(axis=1) & (e < n).all(axis=1)]
+        if y0.shape[1] != 3 * len(np.unique(in_range)):
+            raise ValueError("y_init must have three columns per view that has an edge")
+        rank_init = y0.shape[0]
+    cols = 3 * max(n, 1)
+    y = np.zeros((12, cols)) if want_y else None
+    log = np.full((16, 8), np.nan) if want_log else None
+    s = capi.LagrangeDualSummary()
+    rc = capi.lib().theia_hip_lagrange_dual_rotations(
+        n, e.shape[0], capi.ptr(e, C.c_int32), capi.ptr(r, C.c_double), C.byref(o), rank_init, capi.ptr(y0, C.c_double),
+        capi.ptr(out, C.c_double), capi.ptr(est, C.c_uint8), capi.ptr(y, C.c_double), C.byref(s), capi.ptr(log, C.c_double),
+        16 if want_log else 0)
+    ret = [rc, out, est.astype(bool), s]
+    if want_y:   # the call wrote [final_rank][3 m] densely at the front of the buffer
+        m3 = 3 * s.num_views_in_system
+        ret.append(y.reshape(-1)[:s.final_rank * m3].reshape(s.final_rank, m3).copy())
+    if want_log:
+        ret.append(log[:min(s.num_levels, 16)].copy())
+    return tuple(ret)
+
+
+class LagrangeDualRotationEstimator:
+    """LagrangeDualRotationEstimator(options=SDPSolverOptions()) with SetRAOption(options), GetRASummary() and
+    EstimateRotations(view_pairs, orientations) -> dict (sfm.cc:1797-1801 -> lagrange_dual_rotation_estimator.{h,cc}), in
+    NonlinearRotationEstimator's conventions: the input dict is not modified and the dict comes back whatever the
+    staircase's end, the reference's bool (always true) is in last_success.
+
+    `orientations` names the views (its values are not read: the estimator needs no initial guess); they are indexed in
+    ascending id (ViewIdToAscentIndex).  A pair that names a view without an entry is refused (the reference's
+    operator[] would give it index 0 silently).  A view without a pair keeps the value passed in.  The view whose
+    orientation comes out as the identity is the lowest id that has a pair.  ComputeErrorBound / GetErrorBound are not
+    part of EstimateRotations and are not built."""
+
+    def __init__(self, options=None):
+        self.options = options or SDPSolverOptions()
+        self.last_summary = None
+        self.last_success = None
+        self.gauge_view = None
+
+    def SetRAOption(self, options):
+        self.options = options
+
+    def GetRASummary(self):
+        return self.last_summary
+
+    def EstimateRotations(self, view_pairs, orientations):
+        result = {int(v): np.asarray(r, dtype=np.float64).reshape(3).copy() for v, r in orientations.items()}
+        ids = sorted(result)
+        if not view_pairs:   # CHECK_GT(view_pairs.size(), 0)
+            raise capi.TheiaHipError(capi.THEIA_HIP_ERR_INVALID_ARGUMENT, "no relative rotation constraints")
+        if not ids:          # CHECK_GT(N, 0)
+            raise capi.TheiaHipError(capi.THEIA_HIP_ERR_INVALID_ARGUMENT, "no orientations")
+        pos = {v: k for k, v in enumerate(ids)}
+        try:
+            edges = np.array([(pos[int(a)], pos[int(b)]) for (a, b) in view_pairs], dtype=np.int32)
+        except KeyError as ex:
+            raise capi.TheiaHipError(capi.THEIA_HIP_ERR_INVALID_ARGUMENT, f"view {ex.args[0]} has no orientation") from None
+        rel = np.array([np.asarray(info.rotation_2, dtype=np.float64).reshape(3) for info in view_pairs.values()])
+        out = np.array([result[v] for v in ids])
+        rc, out, est, s = lagrange_dual_rotations(len(ids), edges, rel, self.options, orientations_out=out)
+        capi.check(rc)
+        self.last_success = True
+        self.last_summary = s
+        self.gauge_view = ids[s.gauge_view]
+        self._edges, self._rel, self._ids = edges, rel, ids
+        return {v: out[k].copy() for k, v in enumerate(ids)}
+
+
+class IRLSRefinerOptions:  # irls_rotation_local_refiner.h:54-66
+    def __init__(self):
+        self.num_threads = 8
+        self.max_num_irls_iterations = 10
+        self.irls_step_convergence_threshold = 0.001
+        self.irls_loss_parameter_sigma = math.radians(5.0)
+
+
+class HybridRotationEstimatorOptions:  # hybrid_rotation_estimator.h:53-56
+    def __init__(self):
+        self.sdp_solver_options = SDPSolverOptions()
+        self.irls_options = IRLSRefinerOptions()
+
+
+class HybridRotationEstimator:
+    """HybridRotationEstimator(options=HybridRotationEstimatorOptions()) with EstimateRotations(view_pairs, orientations)
+    -> dict (sfm.cc:1803-1807 -> hybrid_rotation_estimator.cc:69-109): LagrangeDualRotationEstimator, then the IRLS of
+    irls_rotation_local_refiner.cc:77-160 alone -- theia_hip_robust_rotation_averaging with max_num_l1_iterations = 0 --
+    from its result, with the gauge view held (the reference holds its view of index 0, which is the same view when that
+    one has a pair).  last_success is the IRLS solve's outcome; last_summary the SDP stage's, last_irls_summary the
+    refinement's."""
+
+    def __init__(self, options=None):
+        self.options = options or HybridRotationEstimatorOptions()
+        self._ld = LagrangeDualRotationEstimator(self.options.sdp_solver_options)
+        self.last_summary = None
+        self.last_irls_summary = None
+        self.last_success = None
+
+    def EstimateRotations(self, view_pairs, orientations):
+        self._ld.SetRAOption(self.options.sdp_solver_options)
+        result = self._ld.EstimateRotations(view_pairs, orientations)
+        self.last_summary = self._ld.last_summary
+        ids, edges, rel = self._ld._ids, self._ld._edges, self._ld._rel
+        io = self.options.irls_options
+        ro = RobustRotationEstimatorOptions()
+        ro.max_num_l1_iterations = 0
+        ro.max_num_irls_iterations = io.max_num_irls_iterations
+        ro.irls_step_convergence_threshold = io.irls_step_convergence_threshold
+        ro.irls_loss_parameter_sigma = io.irls_loss_parameter_sigma
+        # the views without a pair are outside the IRLS system: they are held as well
+        live = np.zeros(len(ids), dtype=bool)
+        live[np.unique(edges)] = True
+        fixed = ~live
+        fixed[ids.index(self._ld.gauge_view)] = True
+        aa = np.array([result[v] for v in ids])
+        rc, out, s = robust_rotation_averaging(aa, edges, rel, fixed, ro)
+        if rc not in (0, capi.THEIA_HIP_ERR_INTERNAL):
+            capi.check(rc)
+        self.last_success = rc == 0
+        self.last_irls_summary = s
+        return {v: out[k].copy() for k, v in enumerate(ids)}
 
 
 class NonlinearRotationEstimatorOptions:

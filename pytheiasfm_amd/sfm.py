@@ -24,6 +24,9 @@ from .global_pose import (GlobalRotationEstimatorType, RobustRotationEstimator, 
                           RobustRotationEstimatorOptions, LinearRotationEstimator,
                           LinearRotationEstimatorOptions, NonlinearRotationEstimator,
                           NonlinearRotationEstimatorOptions, OrientationsFromMaximumSpanningTree,
+                          LagrangeDualRotationEstimator, HybridRotationEstimator, HybridRotationEstimatorOptions,
+                          IRLSRefinerOptions, SDPSolverOptions, RiemannianStaircaseOptions, SDPSolverType,
+                          PreconditionerType, SweepOrder,
                           GlobalPositionEstimatorType,
                           LeastUnsquaredDeviationPositionEstimator, LeastUnsquaredDeviationPositionEstimatorOptions,
                           LiGTPositionEstimator, LiGTPositionEstimatorOptions,
