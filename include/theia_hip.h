@@ -1505,6 +1505,44 @@ int theia_hip_graph_match(int32_t num_images, int32_t dim, const float* global_d
                           int64_t pair_capacity, int32_t* pair_image1, int32_t* pair_image2, int64_t* num_pairs,
                           int32_t* knn_index /* optional [num_images][k] */, float* knn_distance /* optional */,
                           theia_graph_match_stats* stats /* optional */);
+/* The counting stages of the incremental estimator's inner loop (csrc/next_view.hip).
+ *
+ * theia_hip_visibility_scores: the VisibilityPyramid score (sfm/visibility_pyramid.cc:47-103) of every view, filled as
+ * FindViewsToLocalize fills it (sfm/incremental_reconstruction_estimator.cc:437-447): view v's observations are the rows
+ * [obs_off[v], obs_off[v + 1]) of obs_uv (pixels) / obs_track, and only those whose track is estimated count.  With
+ * C = 1 << num_pyramid_levels the finest cell of a point is clamp((int)(C * x / width), 0, C - 1) (:71-78) and the same for y
+ * with the height, in double, the product first, then the division by the size converted to double.  The reference's cast is
+ * undefined for a quotient outside the int range; here the clamp is taken in double before the truncation toward zero, which is
+ * the reference's result wherever it has one.  Level i (0 = the coarsest, 2 x 2) has 2^(i+1) cells per side and is the finest
+ * level shifted right (:82-90); score = sum_i (occupied cells of level i) * 4^(i+1) (:97-103).  num_estimated_tracks[v] is
+ * written for every view; FindViewsToLocalize's cut at 30 (:451) is the caller's.  One workgroup per view, integers only, no
+ * global atomic: the same bytes on every run.
+ * THEIA_HIP_ERR_INVALID_ARGUMENT (outputs untouched): num_pyramid_levels outside 1..7 (at 8 the reference's int score overflows,
+ * 16^8 = 2^32); a negative count; with num_views > 0 a NULL array, a width or height <= 0 (the reference's CHECK_GT, :54-55), a
+ * track index outside [0, num_tracks), obs_off that starts below 0 or decreases; and -- the one refusal that reads the data on
+ * the device -- a NaN or infinite obs_uv among the observations passed (estimated track or not).  num_views == 0 returns 0 and
+ * launches nothing.  THEIA_HIP_ERR_NO_DEVICE without a device: there is no CPU fallback. */
+int theia_hip_visibility_scores(int32_t num_views, const int64_t* obs_off /*[num_views+1]*/,
+                                const double* obs_uv /*[total][2] pixels*/, const int32_t* obs_track /*[total]*/,
+                                int32_t num_tracks, const uint8_t* track_estimated /*[num_tracks]*/,
+                                const int32_t* image_size /*[num_views][2] width, height*/, int32_t num_pyramid_levels,
+                                int32_t* num_estimated_tracks /*[num_views]*/, int32_t* score /*[num_views]*/);
+/* theia_hip_set_underconstrained_unestimated: the estimators' SetUnderconstrainedAsUnestimated loop
+ * (incremental_reconstruction_estimator.cc:612-620, global_reconstruction_estimator.cc:100-110) as written: both counts start at
+ * -1; while BOTH are non-zero, SetUnderconstrainedViewsToUnestimated (reconstruction_estimator_utils.cc:321-350: every estimated
+ * view with fewer than 3 estimated tracks is cleared), then SetUnderconstrainedTracksToUnestimated (:291-319: every estimated
+ * track with fewer than 2 estimated views is cleared, reading the views the view pass just updated).  The condition is `&&`, not
+ * a fixed point: the loop ends as soon as either pass removed nothing, so a view can be left with two estimated tracks.  Inside a
+ * pass the flags that are read do not change, hence the parallel pass equals the sequential one.  view_estimated /
+ * track_estimated are updated in place; views_removed / tracks_removed are totals over the rounds, *rounds the number of loop
+ * iterations (each may be NULL).  The observations follow theia_ba_problem's convention, at most one per (view, track); this is
+ * not validated (a repeated row would be counted twice).
+ * THEIA_HIP_ERR_INVALID_ARGUMENT (nothing written): a negative count, a view or track index out of range, NULL index arrays with
+ * num_obs > 0, a NULL flag array with a non-zero count.  THEIA_HIP_ERR_NO_DEVICE without a device. */
+int theia_hip_set_underconstrained_unestimated(int32_t num_views, int32_t num_tracks, int64_t num_obs, const int32_t* obs_view,
+                                               const int32_t* obs_track, uint8_t* view_estimated /*in/out*/,
+                                               uint8_t* track_estimated /*in/out*/, int32_t* views_removed,
+                                               int32_t* tracks_removed, int32_t* rounds /*optional, each*/);
 /* n draws of RandomNumberGenerator(seed).RandInt(lo, hi) (util/random.cc:46-84): host code that follows the reference's
  * generator outside the RANSAC sampler (the random candidates of GuidedEpipolarMatcher::FindFeaturesNearEpipolarLines). */
 int theia_hip_randint_stream(uint32_t seed, int32_t n, int32_t lo, int32_t hi, int32_t* out);

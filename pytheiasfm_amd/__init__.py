@@ -1,3 +1,10 @@
 """pytheiasfm_amd -- MI355X-native bundle adjustment + RANSAC engine behind
 pyTheia's BundleAdjust* / Estimate* entry points."""
 __version__ = "0.1.0"
+
+from . import incremental  # noqa: E402,F401
+from .incremental import (FindViewsToLocalize, VisibilityPyramid, LocalizeViewToReconstruction,  # noqa: E402,F401
+                          LocalizeViewsToReconstruction, LocalizeViewToReconstructionOptions,
+                          SetUnderconstrainedAsUnestimated, SetUnderconstrainedTracksToUnestimated,
+                          SetUnderconstrainedViewsToUnestimated, NumEstimatedViews, NumEstimatedTracks,
+                          OrderViewPairsByInitializationCriterion)

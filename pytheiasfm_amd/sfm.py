@@ -188,6 +188,11 @@ class Reconstruction:
         # View::{Position,Gravity,Orientation}Prior (+ sqrt information), view.h; mask bits = capi.THEIA_PRIOR_*
         self.view_prior_mask = None
         self.view_priors = {}
+        # Camera::ImageWidth() / ImageHeight() per view, [nv][2]; None = not known (the stages of incremental.py that
+        # need a size raise THEIA_HIP_ERR_INVALID_ARGUMENT)
+        self.view_image_size = None
+        # View::CameraIntrinsicsPrior().focal_length.is_set per view, [nv] bool; None = all false
+        self.view_focal_prior_set = None
 
     @classmethod
     def from_flat(cls, p):
