@@ -430,6 +430,16 @@ int theia_hip_ba_plan_info(theia_ba_handle h, int32_t* n, int32_t* k3_levels, do
  * THEIA_HIP_ERR_INVALID_ARGUMENT when cap is too small. */
 int theia_hip_ba_kernel_instances(theia_ba_handle h, char* buf, int32_t cap);
 
+/* DIAGNOSTIC, for the tests only (like theia_hip_ba_kernel_instances; no caller needs it to solve anything).
+ * Which launches a run() of the handle takes between the large kernels of an LM iteration: *folded = 1 when
+ * its bodies after the first take the folded chain (k_schur_sum finishes the reduced system, k_cam_update and the control
+ * kernel clear it), 0 when every body keeps the separate launches.  The value is the one run() branches on,
+ * from the handle, its options and the environment (THEIA_HIP_LM_GLUE_KERNELS=1 keeps the separate launches).
+ * Note: a handle CREATED with use_inner_iterations != 0 carries the inner-iteration lists and keeps the separate launches
+ * even after theia_hip_ba_set_options switched the inner iterations off (its per-camera blocks are rebuilt every
+ * iteration); create the handle with use_inner_iterations = 0 to get the folded chain. */
+int theia_hip_ba_lm_chain(theia_ba_handle h, int32_t* folded);
+
 
 /* Covariance blocks at the handle's current state for the two block-diagonal problems behind the
  * *WithCov entry points (bundle_adjustment.cc:288-386,420-499; GetCovarianceFor{Track,Tracks,View,Views},

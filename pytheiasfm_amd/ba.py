@@ -87,6 +87,14 @@ class BaHandle:
         capi.check(L.theia_hip_ba_kernel_instances(self._h, buf, len(buf)))
         return buf.value.decode().splitlines()
 
+    def lm_chain_folded(self):
+        """theia_hip_ba_lm_chain: True when run() takes the folded chain of glue launches for its bodies after the first."""
+        L = capi.lib()
+        L.theia_hip_ba_lm_chain.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+        f = C.c_int32(0)
+        capi.check(L.theia_hip_ba_lm_chain(self._h, C.byref(f)))
+        return bool(f.value)
+
     def snapshot(self):
         """Keep a device-resident copy of the current parameters (theia_hip_ba_snapshot_parameters)."""
         L = capi.lib()

@@ -349,6 +349,7 @@ __global__ __launch_bounds__(64 * TPS, THIP_FUSED_WAVES) void k_lin_schur(DevPro
   static_assert(SUB * 18 <= SUB * RD, "slice-combination scratch does not fit the record buffer");
   static_assert(kFusedMaxSlices <= 16, "slice table too short");
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  if constexpr (!FIRST) { if (lm_flip(P)) { P.camrot = P.camrot_cand; pts = P.pts_alt; } }   // the state is in the second buffers
   const double radius = *radius_p;
   const double inv_radius = 1.0 / radius;
   __shared__ int s_next;
@@ -543,6 +544,7 @@ __global__ __launch_bounds__(64 * TPS, WPS) void k_backsub_runs(DevProblem P, co
   __shared__ __attribute__((aligned(16))) double s_slot[TPS][64 * 4];
   __shared__ int s_next;
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  if constexpr (!INTR) { if (lm_flip(P)) { double* t = P.camrot; P.camrot = P.camrot_cand; P.camrot_cand = t; const double* p0 = pts; pts = cand_pts; cand_pts = const_cast<double*>(p0); } }   // state and candidate the other way round
   int pending = 0;
   if (tid == 0) pending = atomicAdd(P.frun_next + 1, 1);
   for (;;) {
@@ -799,12 +801,35 @@ __global__ __launch_bounds__(64 * TPS, WPS) void k_backsub_runs(DevProblem P, co
 // One wave per S block (ri, rj): the partial blocks of the runs that touch it are added in run order and the block
 // is WRITTEN (never accumulated): S_ij = - sum What_a What_b^T; for a camera (ri == rj) also the per-observation
 // sums  F^T F - ..,  rhs = F^T r - What ghat,  gradient, column norms.
+// GLUE (the folded LM chain, ba_solver.hip: lm_glue_applies): the launch also finishes the system and starts the scalar
+// reduction -- what k_finalize_rcs, k_sp_symm and the linearisation's k_reduce_tiles_stage1 did in launches of their own:
+//  - the wave of a camera's own block holds the final sums of its six diagonal entries, column norms and gradient entries:
+//    it adds the LM diagonal (k_finalize_rcs's expression on the same operands) and folds |g_d / scale_d| into
+//    scal[SC_GMAX] by the same atomic maximum (non-negative values: the result does not depend on the order);
+//  - an entry whose 64-wide tile is a source of the K3 plan's symm list is written at its mirrored place too (decided per
+//    entry: a camera's six columns straddle the tile boundaries); with the plan's tiles clear, K3 finds the bytes
+//    k_sp_symm left;
+//  - the first G.nblocks_red workgroups are the first stage of the tile reduction (into G.red_out).
+struct SchurGlue {
+  const double* radius; const double* scale_red; double* scal; const int* symm_map; int nt;
+  int nblocks_red; int ntiles; const double* tile_part; const int* fmaxflag; double* red_out;
+};
+template <bool GLUE>
 __global__ __launch_bounds__(256) void k_schur_sum(int nitems, const int* __restrict__ items, const int* __restrict__ src,
                                                    const double* __restrict__ part, double* __restrict__ S, int n,
                                                    double* __restrict__ rhs, double* __restrict__ gc,
-                                                   double* __restrict__ colsq, int* __restrict__ qhead) {
-  const int it = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (blockIdx.x == 0 && threadIdx.x == 0 && qhead) *qhead = 0;   // k_lin_schur (the previous kernel on the stream) is done with its run queue: ready for the next launch
+                                                   double* __restrict__ colsq, int* __restrict__ qhead, SchurGlue G) {
+  int blk = blockIdx.x;
+  if constexpr (GLUE) {   // (the reducing workgroups come first: they are in flight while the item ones run)
+    if (blk < G.nblocks_red) {
+      __shared__ double sm[8][4];
+      reduce_tiles_stage1_body(G.ntiles, G.tile_part, 4, G.fmaxflag, G.red_out, blk, G.nblocks_red, sm);
+      return;
+    }
+    blk -= G.nblocks_red;
+  }
+  const int it = blk * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (blk == 0 && threadIdx.x == 0 && qhead) *qhead = 0;   // k_lin_schur (the previous kernel on the stream) is done with its run queue: ready for the next launch
   if (it >= nitems) return;
   const int* d = items + 6 * it;
   const int ri = d[0], rj = d[1], tbeg = d[2], tend = d[3], dbeg = d[4], dend = d[5];
@@ -826,10 +851,47 @@ __global__ __launch_bounds__(256) void k_schur_sum(int nitems, const int* __rest
     for (int u = 0; u < 8; ++u) if (q + u < qe) v += t[u];
     return v;
   };
+  // GLUE: is the entry (R, C) of the lower triangle in a tile k_sp_symm would have mirrored? (looked up before the sums)
+  auto mirrored = [&](int R, int C) {
+    if constexpr (GLUE) { const int tr = R >> 6, tc = C >> 6; return tr != tc && G.symm_map[tr * G.nt + tc] != 0; }
+    return false;
+  };
   if (ri != rj) {
     if (lane >= 36) return;
+    const int R = 6 * ri + lane / 6, C = 6 * rj + lane % 6;
+    const bool mir = mirrored(R, C);
     const double v = (tend > tbeg) ? sum_sources(tbeg, tend, lane) : 0.0;
-    S[(size_t)(6 * ri + lane / 6) * n + 6 * rj + lane % 6] = -v;
+    S[(size_t)R * n + C] = -v;
+    if (mir) S[(size_t)C * n + R] = -v;
+    return;
+  }
+  if constexpr (GLUE) {
+    const bool on = lane < 54;
+    const int a = on ? lane / 9 : 0, j = on ? lane % 9 : 0;
+    const int R = 6 * ri + a, C = 6 * ri + min(j, 5);
+    const bool mir = j < a && mirrored(R, C);
+    const double radius = *G.radius, sr = G.scale_red[R];   // (in flight under the sums)
+    double x = 0.0;   // this lane's sum: entry (a, j) of the block for j < 6, then rhs / gradient / column norm of row a
+    if (j < 6) { if (tend > tbeg) x = sum_sources(tbeg, tend, a * 6 + j); }
+    else if (dend > dbeg) x = sum_sources(dbeg, dend, a * 3 + (j - 6));
+    const double gv = __shfl(x, a * 9 + 7, 64), cv = __shfl(x, a * 9 + 8, 64);
+    double gmax = 0.0;
+    if (on) {
+      if (j < 6) {
+        if (j < a) { S[(size_t)R * n + C] = -x; if (mir) S[(size_t)C * n + R] = -x; }
+        else if (j == a) {
+          S[(size_t)R * n + R] = lm_diag_entry(-x, cv, radius);
+          gmax = lm_grad_entry(gv, sr);
+        }
+      } else if (j == 6) rhs[R] = x;
+      else if (j == 7) gc[R] = x;
+      else colsq[R] = x;
+    }
+    gmax = wave_max(gmax);
+    // (as k_finalize_rcs: fmax drops a NaN too.  A wave whose maximum does not exceed what the scalar already holds has nothing
+    // to add: the scalar only grows during the launch, so a stale read costs an atomic, never a result)
+    if (lane == 0 && gmax == gmax && gmax > __builtin_nontemporal_load(&G.scal[SC_GMAX]))
+      atomicMax(reinterpret_cast<unsigned long long*>(&G.scal[SC_GMAX]), (unsigned long long)__double_as_longlong(gmax));
     return;
   }
   if (lane >= 54) return;
@@ -901,7 +963,7 @@ void launch_cam_prep(const DevProblem& P, const double* cam, const double* intr,
 }
 
 void launch_linearize_fused(const DevProblem& P, const double* cam, const double* pts, const double* radius,
-                            const ReduceBuf& rb, double* Vinv, double* tile_part, hipStream_t st) {
+                            const ReduceBuf& rb, double* Vinv, double* tile_part, hipStream_t st, const LinGlue* glue) {
   if (P.n_fruns == 0) return;
   if (!P.camrot_current || P.n_sum_items == 0) launch_cam_prep(P, cam, P.intr, P.camrot, st);   // (otherwise k_schur_sum left the run queue's head at zero)
   static const int wgs = [] { const char* e = getenv("THEIA_HIP_FUSED_WGS"); return e ? std::max(1, atoi(e)) : 512; }();   // 2 per CU
@@ -926,7 +988,7 @@ void launch_linearize_fused(const DevProblem& P, const double* cam, const double
         for (int k = 0; k < 12; ++k) fprintf(stderr, "  %-20s %14llu  %5.1f%%  per wave sub-chunk %8.0f\n", nm[k], hst[k], 100.0 * (double)hst[k] / tot, (double)hst[k] / std::max(1.0, (double)hst[11]));
       }
       if (P.n_sum_items)
-        k_schur_sum<<<(P.n_sum_items + 3) / 4, 256, 0, st>>>(P.n_sum_items, P.sum_items, P.sum_src, P.fpart, rb.S, P.n, rb.rhs, rb.gc, rb.colsq, P.frun_next);
+        k_schur_sum<false><<<(P.n_sum_items + 3) / 4, 256, 0, st>>>(P.n_sum_items, P.sum_items, P.sum_src, P.fpart, rb.S, P.n, rb.rhs, rb.gc, rb.colsq, P.frun_next, SchurGlue{});
       return;
     }
 #define THIP_LS(PD_, M_) do { \
@@ -937,9 +999,15 @@ void launch_linearize_fused(const DevProblem& P, const double* cam, const double
     else { if (trig) THIP_LS(4, kModelsAll); else THIP_LS(4, kModelsNoTrig); }
 #undef THIP_LS
   }
-  if (P.n_sum_items)
-    k_schur_sum<<<(P.n_sum_items + 3) / 4, 256, 0, st>>>(P.n_sum_items, P.sum_items, P.sum_src, P.fpart, rb.S, P.n, rb.rhs,
-                                                         rb.gc, rb.colsq, P.frun_next);
+  const int nb_items = (P.n_sum_items + 3) / 4;
+  if (glue && P.n_sum_items) {
+    const int nb_red = glue->red_out ? kReduceBlocks : 0;
+    const SchurGlue G{radius, glue->scale_red, rb.scal, glue->symm_map, glue->nt, nb_red, P.ntiles, tile_part, glue->fmaxflag, glue->red_out};
+    k_schur_sum<true><<<nb_red + nb_items, 256, 0, st>>>(P.n_sum_items, P.sum_items, P.sum_src, P.fpart, rb.S, P.n,
+                                                                                     rb.rhs, rb.gc, rb.colsq, P.frun_next, G);
+  } else if (P.n_sum_items)
+    k_schur_sum<false><<<nb_items, 256, 0, st>>>(P.n_sum_items, P.sum_items, P.sum_src, P.fpart, rb.S, P.n, rb.rhs,
+                                                 rb.gc, rb.colsq, P.frun_next, SchurGlue{});
 }
 
 void launch_linearize_fused_first(const DevProblem& P, const double* ones_c, const double* ones_p, double* scale_c, double* scale_p,
@@ -961,7 +1029,7 @@ void launch_linearize_fused_first(const DevProblem& P, const double* ones_c, con
   if (fi.pd == 3) { if (trig) THIP_LS1(3, kModelsAll); else THIP_LS1(3, kModelsNoTrig); }
   else { if (trig) THIP_LS1(4, kModelsAll); else THIP_LS1(4, kModelsNoTrig); }
 #undef THIP_LS1
-  k_schur_sum<<<(P.n_sum_items + 3) / 4, 256, 0, st>>>(P.n_sum_items, P.sum_items, P.sum_src, P.fpart, rb.S, P.n, rb.rhs, rb.gc, rb.colsq, P.frun_next);
+  k_schur_sum<false><<<(P.n_sum_items + 3) / 4, 256, 0, st>>>(P.n_sum_items, P.sum_items, P.sum_src, P.fpart, rb.S, P.n, rb.rhs, rb.gc, rb.colsq, P.frun_next, SchurGlue{});
   k_scale_from_colsq<<<(6 * P.nc + 255) / 256, 256, 0, st>>>(P, rb.colsq, scale_c);
   DevProblem R = P;
   R.scale_c = scale_c;

@@ -69,6 +69,7 @@ struct PoolBuf {
   PoolBuf(const PoolBuf&) = delete;
   PoolBuf& operator=(const PoolBuf&) = delete;
   ~PoolBuf() { if (p) dev_pool().give(p, bytes); }
+  void swap(PoolBuf& o) { std::swap(p, o.p); std::swap(n, o.n); std::swap(bytes, o.bytes); }   // the two buffers change owners
   int alloc(size_t count) {
     if (p) { (void)hipDeviceSynchronize(); dev_pool().give(p, bytes); p = nullptr; bytes = 0; }
     n = count;
@@ -186,6 +187,7 @@ struct theia_ba_handle_s {
   PoolBuf<uint8_t> obs_lc, obs_tl;
   PoolBuf<double> fpart, camrot, camrot_cand, camdir;
   int n_fruns = 0, n_sum_items = 0;
+  bool sum_covers_n = false;   // every row of the reduced system belongs to a camera with a diagonal item of sum_items
   double* h_scal = nullptr;  // pinned: [scalA(16) | scalB(16) | stop flag out / in (2) | spare]
   char* h_state = nullptr;   // pinned: read-back of lm_state (kLmBlockBytes)
   int cur = 0;
@@ -268,6 +270,7 @@ struct LmState {
       fail_at_first, bodies;
   int inner_enabled;   // inner iterations still running (they switch themselves off: inner_iteration_tolerance)
   int use_inner;       // this body's candidate is the point the inner iterations ended at (k_lm_accept copies that one)
+  int cur;             // the folded LM chain: the parameter buffers that hold the state (0 or 1), flipped by k_reduce_control on an accepted step
 };
 // The five trace arrays (cost, gradient max norm, step norm, radius, accepted) are cut in two: entries [0, kTraceHead) sit
 // right behind the LmState, so that the read-back of the state every chunk of iterations ends with brings them along and a
@@ -300,8 +303,15 @@ int do_allreduce(theia_ba_handle_s* h, double* buf, size_t count, int op);
 int cost_of_tiles(theia_ba_handle_s* h, int tile0, int ntiles, const double* cam, const double* pts, double* cost, double* invalid);
 int compute_scale(theia_ba_handle_s* h);
 bool scale_fold_applies(const theia_ba_handle_s* h);
-int enqueue_linearize(theia_ba_handle_s* h, int slot = 0, bool first_fold = false);
-int enqueue_solve_and_backsub(theia_ba_handle_s* h, int slot = 0, bool defer_reduce = false);
+bool lm_glue_applies(const theia_ba_handle_s* h);
+bool lm_glue_run(const theia_ba_handle_s* h);   // ... and the handle's options and the environment let run() take it
+// What a body of run() launches between its large kernels: LM_SEPARATE the glue kernels in launches of their own and
+// k_lm_accept; LM_FOLD_FIRST the first body of a run where lm_glue_run(): the same launches, but it clears the reduced system
+// behind itself and an accepted step flips LmState::cur instead of the copy; LM_FOLDED the bodies after it: no clear on entry,
+// k_schur_sum finishes the system, no k_sp_symm, k_cam_update finishes the scalars and clears
+enum LmChain { LM_SEPARATE = 0, LM_FOLD_FIRST = 1, LM_FOLDED = 2 };
+int enqueue_linearize(theia_ba_handle_s* h, int slot = 0, bool first_fold = false, LmChain chain = LM_SEPARATE);
+int enqueue_solve_and_backsub(theia_ba_handle_s* h, int slot = 0, bool defer_reduce = false, LmChain chain = LM_SEPARATE);
 int sync_plan(theia_ba_handle_s* h);
 void debug_sticky(const char* where);
 

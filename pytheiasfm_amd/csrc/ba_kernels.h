@@ -114,6 +114,13 @@ struct DevProblem {
   double* camrot_cand;         // the same for the candidate cameras of the trial step (back-substitution)
   double* camdir;              // [nc][12] the trial step of each camera as {D (3 x 3), v (3)} (camera_step_direction; k_cam_update)
   int camrot_current;          // host-set per launch: camrot already holds the blocks of `cam` (launch_linearize_fused skips k_cam_prep)
+  // The folded LM chain (ba_solver.hip: lm_glue_applies): which of the two parameter buffers holds the state is a number on
+  // the device, LmState::cur, flipped by the control kernel on an accepted step instead of a copy.  lm_cur != null (host-set
+  // for the bodies of such a run): k_lin_schur, k_cam_update<1> and k_backsub_runs read it once per workgroup and, where it is
+  // 1, take camrot / camrot_cand and their state / candidate arguments the other way round (lm_flip); pts_alt: the point
+  // buffer k_lin_schur linearises at then.  Null everywhere else: the buffers are the ones passed.
+  const int* lm_cur;
+  const double* pts_alt;
   unsigned model_mask;         // bit m = some intrinsics group uses camera model m (picks the kernel instance)
   int fused_dbg;               // development switches (THEIA_HIP_FUSED_DBG): 1 = skip phase S, 2 = skip phase L arithmetic
   int n_sum_items;
@@ -225,8 +232,12 @@ void launch_linearize(const DevProblem& P, const double* cam, const double* pts,
                       const ReduceBuf& rb, double* Vinv, double* gp, double* tile_part,
                       hipStream_t st);
 // fused path: k_cam_prep + k_lin_schur + k_schur_sum (S blocks are WRITTEN, the buffer must be clear where nothing lands)
+// glue (the folded LM chain, ba_solver.hip: lm_glue_applies): k_schur_sum also adds the LM diagonal, folds the camera
+// gradient into rb.scal[SC_GMAX], writes the entries k_sp_symm would mirror (symm_map / nt: chol_plan_tile_lists) and, with
+// red_out, carries the first stage of the reduction of tile_part's four fields (fmaxflag) -- no k_finalize_rcs, no k_sp_symm
+struct LinGlue { const double* scale_red; const int* symm_map; int nt; const int* fmaxflag; double* red_out; };
 void launch_linearize_fused(const DevProblem& P, const double* cam, const double* pts, const double* radius /* device */,
-                            const ReduceBuf& rb, double* Vinv, double* tile_part, hipStream_t st);
+                            const ReduceBuf& rb, double* Vinv, double* tile_part, hipStream_t st, const LinGlue* glue = nullptr);
 // the first linearisation of a solve with the Jacobi scaling folded in (no separate column-norm pass): P is the solve's view,
 // the kernels run on unit scales and leave scale_p, scale_c and scale_red; the reduced system in rb is the UNIT-camera-scale
 // one until the caller has rescaled it (chol_plan_rescale with scale_red), and P.camrot holds unit-scale blocks
@@ -262,8 +273,17 @@ void launch_cam_priors(const DevProblem& P, int mode, const double* cam, const d
 void launch_finalize_rcs(const DevProblem& P, const double* radius /* device */, const ReduceBuf& rb, hipStream_t st,
                          int ntiles = 0, const double* tile_part = nullptr, const int* f2s = nullptr,
                          const int* fmaxflag = nullptr, const uint8_t* tile_cls = nullptr, int want_cls = 0);
+int cam_update_preps(const DevProblem& P);   // 1 / 2: launch_cam_update writes the candidate's per-camera blocks itself (1: no free intrinsics)
+// glue (the folded LM chain; fused path without intrinsics only): further workgroups of the launch zero the tiles zero_items
+// of the reduced system zero_S (chol_plan_tile_lists), which is dead once the solve has left y, and, with lin_part, one folds
+// the linearisation's scalars (lin_ntiles rows of 4 fields, k_schur_sum's stage-1 sums or the per-tile partials) into scal
+struct CamUpdateGlue {
+  double* zero_S; const int* zero_items; int nzero; int prep_blocks;
+  const double* lin_part; int lin_ntiles; const int* lin_f2s; const int* lin_fmaxflag; double* scal;
+};
 void launch_cam_update(const DevProblem& P, const double* cam, const double* y, double* cand_cam,
-                       double* cand_intr, double* out_stepsq, double* out_xnormsq, hipStream_t st, double* zero16 = nullptr);
+                       double* cand_intr, double* out_stepsq, double* out_xnormsq, hipStream_t st, double* zero16 = nullptr,
+                       const CamUpdateGlue* glue = nullptr);
 void launch_backsub(const DevProblem& P, const double* cam, const double* pts, const double* cand_cam,
                     double* cand_pts, const double* yc, const double* Vinv, double* tile_part,
                     double* scal, hipStream_t st);
@@ -300,11 +320,67 @@ void chol_plan_destroy(CholPlan* plan);
 bool chol_plan_clear(const CholPlan* plan, double* A, int lda, hipStream_t st, double* tail = nullptr, size_t tail_count = 0);
 // S <- D S D, rhs <- D rhs, gc <- D gc, colsq <- D^2 colsq over the tiles chol_plan_clear clears (D = diag(s), n entries)
 void chol_plan_rescale(const CholPlan* plan, double* A, int lda, int n, const double* s, double* rhs, double* colsq, double* gc, hipStream_t st);
+// For a caller that clears and mirrors inside launches of its own (sparse plan only; nzero = 0 otherwise):
+// zero_items: {r0, h, c0, w} (device) of the tiles k_sp_symm writes followed by the tiles chol_plan_clear zeroes -- every tile
+// of A a solve on the plan reads or writes; symm_map[tr * nt + tc] != 0 (device): the lower tile (tr, tc) is mirrored
+// into (tc, tr) before the factorisation (what k_sp_symm does; a caller that writes both entries itself on a buffer whose
+// zero_items are clear leaves the bytes k_sp_symm leaves).
+struct CholTileLists { const int* zero_items; int nzero; const int* symm_map; int nt; };
+CholTileLists chol_plan_tile_lists(const CholPlan* plan);
 int chol_plan_levels(const CholPlan* plan);
 double chol_plan_flops(const CholPlan* plan);   // FP64 flops of one solve on the plan (n^3 / 3 for the dense schedule)
 void chol_plan_solve(const CholPlan* plan, double* A, int lda, double* b, double* work, double* fail_flag, hipStream_t st);
 
 #ifdef __HIPCC__
+// The LM diagonal on a diagonal entry of the reduced system (sv: the assembled entry, cv: the squared column norm) and the
+// entry's share of the gradient max-norm (gv: gradient entry, sr: Jacobi scale): one definition for k_finalize_rcs and
+// for the k_schur_sum that does its work, so the two produce the same bits
+__device__ __forceinline__ double lm_diag_entry(double sv, double cv, double radius) { return sv + fmin(fmax(cv, 1e-6), 1e32) / radius; }
+__device__ __forceinline__ double lm_grad_entry(double gv, double sr) { return fabs(gv / sr); }
+// DevProblem::lm_cur: does this launch take its state / candidate buffers the other way round?  (a scalar load, uniform)
+__device__ __forceinline__ bool lm_flip(const DevProblem& P) { return P.lm_cur != nullptr && *P.lm_cur != 0; }
+// one {r0, h, c0, w} tile item of a CholPlan list zeroed by the calling workgroup
+__device__ __forceinline__ void clear_tile_item(double* __restrict__ A, int lda, const int* __restrict__ it) {
+  const int r0 = it[0], h = it[1], c0 = it[2], w = it[3];
+  for (int e = threadIdx.x; e < 64 * 64; e += blockDim.x) {
+    const int r = e >> 6, c = e & 63;
+    if (r < h && c < w) A[(size_t)(r0 + r) * lda + c0 + c] = 0.0;
+  }
+}
+// Workgroup b of nb (256 threads) folds its contiguous slice of the per-tile partials into out[b][nfields]: the first stage
+// of the two-stage reduction (k_reduce_tiles_stage1, and the launches that carry it as extra workgroups)
+__device__ __forceinline__ void reduce_tiles_stage1_body(int ntiles, const double* __restrict__ part, int nfields,
+                                                         const int* __restrict__ fmaxflag, double* __restrict__ out, int b, int nb,
+                                                         double (*sm)[4]) {
+  const int per = (ntiles + nb - 1) / nb;
+  const int t0 = b * per, t1 = min(ntiles, t0 + per);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  double acc[8];
+  bool ismax[8];
+#pragma unroll
+  for (int f = 0; f < 8; ++f) { acc[f] = 0.0; ismax[f] = f < nfields && fmaxflag[f] != 0; }
+  for (int t = t0 + (int)threadIdx.x; t < t1; t += 256) {
+    const double* row = part + (size_t)t * nfields;
+#pragma unroll
+    for (int f = 0; f < 8; ++f)
+      if (f < nfields) { const double v = row[f]; acc[f] = ismax[f] ? fmax(acc[f], v) : acc[f] + v; }
+  }
+#pragma unroll
+  for (int f = 0; f < 8; ++f) {
+    if (f >= nfields) break;
+    double v = acc[f];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { const double o = __shfl_xor(v, off, 64); v = ismax[f] ? fmax(v, o) : v + o; }
+    if (lane == 0) sm[f][wv] = v;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < nfields) {
+    const int f = threadIdx.x;
+    double v = sm[f][0];
+    for (int w = 1; w < 4; ++w) v = ismax[f] ? fmax(v, sm[f][w]) : v + sm[f][w];
+    out[(size_t)b * nfields + f] = v;
+  }
+}
 // Deterministic reduction of per-tile partials into a scalar block by ONE workgroup of 1024 threads:
 // field f of tile t at part[t * nfields + f]; result -> scal[f2s[f]] (sum, or max if fmaxflag[f]).
 // Every thread folds its tiles for all fields, a wave shuffle tree per field, the 16 wave results are combined

@@ -816,35 +816,7 @@ __global__ __launch_bounds__(1024) void k_reduce_tiles(int ntiles, const double*
 __global__ __launch_bounds__(256) void k_reduce_tiles_stage1(int ntiles, const double* __restrict__ part, int nfields,
                                                              const int* __restrict__ fmaxflag, double* __restrict__ out) {
   __shared__ double sm[8][4];
-  const int nb = gridDim.x, b = blockIdx.x;
-  const int per = (ntiles + nb - 1) / nb;
-  const int t0 = b * per, t1 = min(ntiles, t0 + per);
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  double acc[8];
-  bool ismax[8];
-#pragma unroll
-  for (int f = 0; f < 8; ++f) { acc[f] = 0.0; ismax[f] = f < nfields && fmaxflag[f] != 0; }
-  for (int t = t0 + (int)threadIdx.x; t < t1; t += 256) {
-    const double* row = part + (size_t)t * nfields;
-#pragma unroll
-    for (int f = 0; f < 8; ++f)
-      if (f < nfields) { const double v = row[f]; acc[f] = ismax[f] ? fmax(acc[f], v) : acc[f] + v; }
-  }
-#pragma unroll
-  for (int f = 0; f < 8; ++f) {
-    if (f >= nfields) break;
-    double v = acc[f];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { const double o = __shfl_xor(v, off, 64); v = ismax[f] ? fmax(v, o) : v + o; }
-    if (lane == 0) sm[f][wv] = v;
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < nfields) {
-    const int f = threadIdx.x;
-    double v = sm[f][0];
-    for (int w = 1; w < 4; ++w) v = ismax[f] ? fmax(v, sm[f][w]) : v + sm[f][w];
-    out[(size_t)b * nfields + f] = v;
-  }
+  reduce_tiles_stage1_body(ntiles, part, nfields, fmaxflag, out, blockIdx.x, gridDim.x, sm);
 }
 
 // Add the LM diagonal to the camera-side blocks (intrinsics + extrinsics) and
@@ -866,8 +838,8 @@ __global__ __launch_bounds__(1024) void k_finalize_rcs(DevProblem P, const doubl
   // tile_cls (sharded solve with a distributed K3): only the columns of the 64-wide tiles of class want_cls
   if (d < P.n && (!tile_cls || tile_cls[d >> 6] == want_cls)) {
     const double sv = S[(size_t)d * P.n + d], cv = colsq[d], gv = gc[d], sr = P.scale_red[d];
-    S[(size_t)d * P.n + d] = sv + fmin(fmax(cv, 1e-6), 1e32) / radius;
-    gmax = fabs(gv / sr);
+    S[(size_t)d * P.n + d] = lm_diag_entry(sv, cv, radius);
+    gmax = lm_grad_entry(gv, sr);
   }
   gmax = wave_max(gmax);
   if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = gmax;
@@ -931,9 +903,25 @@ template <int PREP>
 __global__ __launch_bounds__(1024) void k_cam_update(DevProblem P, const double* __restrict__ cam, const double* __restrict__ y,
                              double* __restrict__ cand, double* __restrict__ cand_intr,
                              double* __restrict__ out_stepsq, double* __restrict__ out_xnormsq,
-                             double* __restrict__ zero16) {
+                             double* __restrict__ zero16, CamUpdateGlue G) {
   const double* yc = y + P.ni;
+  if constexpr (PREP == 1) { if (lm_flip(P)) { double* t = P.camrot; P.camrot = P.camrot_cand; P.camrot_cand = t; const double* c0 = cam; cam = cand; cand = const_cast<double*>(c0); } }   // state and candidate the other way round
   if constexpr (PREP != 0) {
+    // the workgroups behind the preparing ones (the folded LM chain): first one that folds the linearisation's scalars into
+    // scal (what k_finalize_rcs's first workgroup did: the same body on the same rows; the sums land on zeros, the maximum
+    // meets k_schur_sum's by the same atomic).  scal[SC_NOTPD] is summed in the other order: the count of singular point
+    // blocks used to be in place before K3 added one per failed factorisation (unsafeAtomicAdd, cholesky_device.h; K3 never
+    // reads the scalar), here K3's count is there first and this one is added -- small integers, exact either way, the
+    // same value.  Then one per tile of the reduced
+    // system, which nobody reads any more -- the solve has left y in the row behind the matrix, outside every tile
+    if ((int)blockIdx.x > G.prep_blocks) {
+      const int b = (int)blockIdx.x - 1 - G.prep_blocks - (G.lin_part ? 1 : 0);
+      if (b < 0) {
+        __shared__ double smr[8][16];
+        reduce_tiles_body(G.lin_ntiles, G.lin_part, 4, G.lin_f2s, G.lin_fmaxflag, G.scal, smr, true);
+      } else clear_tile_item(G.zero_S, P.n, G.zero_items + 4 * b);
+      return;
+    }
     if (blockIdx.x > 0) {
       if (threadIdx.x >= 256) return;   // 256 cameras per workgroup, as k_cam_prep: the blocks spread over the CUs
       const int c = (blockIdx.x - 1) * 256 + threadIdx.x;
@@ -1617,18 +1605,23 @@ void launch_finalize_rcs(const DevProblem& P, const double* radius, const Reduce
 }
 
 // 1 / 2 when launch_cam_update writes the candidate's per-camera blocks itself (launch_backsub then skips its k_cam_prep)
-static int cam_update_preps(const DevProblem& P) {
+int cam_update_preps(const DevProblem& P) {
   if (P.n_fruns == 0 || !P.camrot || !P.camrot_cand || P.ntiles == 0 || getenv("THEIA_HIP_CAM_PREP_SEPARATE")) return 0;
   if (!P.ni) return P.camdir ? 1 : 0;
   return P.fused_bw > 0 ? 2 : 0;
 }
 
 void launch_cam_update(const DevProblem& P, const double* cam, const double* y, double* cand_cam,
-                       double* cand_intr, double* out_stepsq, double* out_xnormsq, hipStream_t st, double* zero16) {
+                       double* cand_intr, double* out_stepsq, double* out_xnormsq, hipStream_t st, double* zero16, const CamUpdateGlue* glue) {
   const int prep = cam_update_preps(P);
-  if (prep == 1) k_cam_update<1><<<1 + (P.nc + 255) / 256, 1024, 0, st>>>(P, cam, y, cand_cam, cand_intr, out_stepsq, out_xnormsq, zero16);
-  else if (prep == 2) k_cam_update<2><<<1 + (P.nc + 255) / 256, 1024, 0, st>>>(P, cam, y, cand_cam, cand_intr, out_stepsq, out_xnormsq, zero16);
-  else k_cam_update<0><<<1, 1024, 0, st>>>(P, cam, y, cand_cam, cand_intr, out_stepsq, out_xnormsq, zero16);
+  CamUpdateGlue G{};
+  G.prep_blocks = (P.nc + 255) / 256;
+  const int pb = G.prep_blocks;
+  if (prep == 1 && glue) { G = *glue; G.prep_blocks = pb; }
+  const int extra = (G.zero_S ? G.nzero : 0) + (G.lin_part ? 1 : 0);
+  if (prep == 1) k_cam_update<1><<<1 + pb + extra, 1024, 0, st>>>(P, cam, y, cand_cam, cand_intr, out_stepsq, out_xnormsq, zero16, G);
+  else if (prep == 2) k_cam_update<2><<<1 + pb, 1024, 0, st>>>(P, cam, y, cand_cam, cand_intr, out_stepsq, out_xnormsq, zero16, G);
+  else k_cam_update<0><<<1, 1024, 0, st>>>(P, cam, y, cand_cam, cand_intr, out_stepsq, out_xnormsq, zero16, G);
 }
 
 void launch_backsub(const DevProblem& P, const double* cam, const double* pts, const double* cand_cam,

@@ -1631,6 +1631,12 @@ int ba_create_impl(const theia_ba_problem* p, const theia_ba_options* o, theia_b
   if (h->ni == 0 && h->ntiles_main > 0 && (rc = build_gather_lists(h, ocam, opt, l_obs, !h->use_fused))) return rc;
   if (h->use_fused) {
     h->n_fruns = (int)fplan.runs.size(); h->n_sum_items = (int)fplan.sum_items.size() / 6 - h->n_sum_items2;
+    {   // does every row of the reduced system belong to a camera with a diagonal sum item? (lm_glue_applies: k_schur_sum
+        // then writes every entry of rhs / gc / colsq and visits every diagonal entry)
+      int ndiag = 0;
+      for (int k = 0; k < h->n_sum_items; ++k) ndiag += fplan.sum_items[6 * (size_t)k] == fplan.sum_items[6 * (size_t)k + 1];
+      h->sum_covers_n = h->ni == 0 && h->n_sum_items2 == 0 && 6 * ndiag == h->n;
+    }
     fplan.tile_trk_end.resize(std::max<size_t>(1, fplan.tile_trk_end.size()));
     if (ctiming) {   // THEIA_HIP_CREATE_TIMING: shape of the fused plan
       std::map<int, std::pair<int, int>> by;   // gp -> (runs, sub-chunks)

@@ -54,6 +54,12 @@ int theia_hip_ba_kernel_instances(theia_ba_handle h, char* buf, int32_t cap) {
   return 0;
 }
 
+int theia_hip_ba_lm_chain(theia_ba_handle h, int32_t* folded) {
+  if (!h || !folded) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "null argument");
+  *folded = (!h->idh && lm_glue_run(h)) ? 1 : 0;
+  return 0;
+}
+
 int theia_hip_ba_evaluate(theia_ba_handle h, double* cost, double* residuals, double* jac_cam, double* jac_pt, uint8_t* valid) {
   return theia_hip_ba_evaluate_ex(h, cost, residuals, jac_cam, jac_pt, nullptr, valid);
 }

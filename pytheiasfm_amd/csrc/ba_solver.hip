@@ -31,7 +31,8 @@ __device__ void lm_trace(LmState* st, const LmCtl& c, double cost, double g, dou
 // One pass of the TrustRegionMinimizer loop body (ceres trust_region_minimizer.cc; the
 // same rules the host loop of the first versions applied after each read-back):
 // sa = scalars of the linearisation at x, sb = scalars of the trial step.
-__device__ void lm_control_body(LmState* st, const double* __restrict__ sa, const double* __restrict__ sb,
+// (sa carries no __restrict__: on the folded chain k_reduce_control clears those scalars itself afterwards, through another pointer)
+__device__ void lm_control_body(LmState* st, const double* sa, const double* __restrict__ sb,
                                 const LmCtl* __restrict__ cp) {
   const LmCtl c = *cp;
   st->accepted = 0; st->use_inner = 0;
@@ -92,7 +93,7 @@ __device__ void lm_control_body(LmState* st, const double* __restrict__ sa, cons
   }
   const double rho = cost_change / mcc;
   if (inner_useful || rho > 1e-3) {   // IsStepSuccessful
-    st->accepted = 1;   // k_lm_accept copies the candidate buffers over the state
+    st->accepted = 1;   // k_lm_accept copies the candidate buffers over the state (or k_reduce_control makes the buffers change roles)
     st->x_norm = sqrt(xnormsq);
     st->radius = st->radius / fmax(1.0 / 3.0, 1.0 - pow(2.0 * rho - 1.0, 3));
     st->radius = fmin(c.max_radius, st->radius);
@@ -121,13 +122,24 @@ __global__ void k_lm_pending_gradient(LmState* st, const double* __restrict__ sa
   st->pending_grad = -1;
 }
 // The tile reduction of the trial step (launch_reduce_tiles cfg 1 -> scalB) and the step control in one launch.
+// clear16 (the folded LM chain, lm_glue_applies): an accepted step flips LmState::cur instead of the copy of k_lm_accept, and
+// the scalars of the linearisation are cleared once the control body has read them
+// -- the next k_schur_sum and K3 need SC_GMAX and SC_NOTPD at zero, the sums land on zeros; the vectors in front of them
+// (rhs | colsq | gc) need no clear there: k_schur_sum writes every entry (theia_ba_handle_s::sum_covers_n).
 __global__ __launch_bounds__(1024) void k_reduce_control(int ntiles, const double* __restrict__ part,
                                                          const int* __restrict__ f2s, const int* __restrict__ fmaxflag,
-                                                         LmState* st, const double* __restrict__ sa, double* __restrict__ sb,
-                                                         const LmCtl* __restrict__ cp) {
+                                                         LmState* st, const double* sa, double* __restrict__ sb,
+                                                         const LmCtl* __restrict__ cp, double* __restrict__ clear16, int flip) {
   __shared__ double sm[8][16];
   thip::reduce_tiles_body(ntiles, part, 5, f2s, fmaxflag, sb, sm);
-  if (threadIdx.x == 0) lm_control_body(st, sa, sb, cp);
+  if (threadIdx.x == 0) {
+    lm_control_body(st, sa, sb, cp);
+    if (flip && st->accepted) st->cur ^= 1;   // an accepted step: state and candidate buffers change roles (never after done)
+  }
+  if (clear16) {
+    __syncthreads();   // the control body has read the scalars
+    if (threadIdx.x < 16) clear16[threadIdx.x] = 0.0;
+  }
 }
 
 // |x| over the variable parameter blocks (TrustRegionMinimizer's x_norm at the start):
@@ -334,6 +346,7 @@ void fill_devproblem(theia_ba_handle_s* h) {
   P.obs_lc = h->obs_lc.p; P.obs_tl = h->obs_tl.p; P.tile_trk_end = h->tile_trk_end.p; P.fpart = h->fpart.p; P.camrot = h->camrot.p; P.camrot_cand = h->camrot_cand.p; P.camdir = h->camdir.p;
   { const char* dbg = getenv("THEIA_HIP_FUSED_DBG"); P.fused_dbg = dbg ? atoi(dbg) : 0; }
   P.model_mask = h->model_mask;
+  P.lm_cur = nullptr; P.pts_alt = nullptr;   // (set by run() around the bodies of the folded chain only)
   P.n_sum_items = h->n_sum_items; P.sum_items = h->sum_items.p; P.sum_src = h->sum_src.p;
   P.fused_bw = h->use_fused ? h->fused_bw : 0; P.n_sum_items2 = h->n_sum_items2; P.fused_kmask = h->fused_kmask;
   P.diag_items = h->diag_items.p; P.rec_slot = h->cam_obs.p; P.slot_obs = h->slot_obs.p; P.slot_pt = h->slot_pt.p; P.blk_items = h->blk_items.p; P.blk_pairs = h->blk_pairs.p;
@@ -459,25 +472,70 @@ bool scale_fold_applies(const theia_ba_handle_s* h) {
          h->long_ntracks == 0 && h->n_priors == 0 && !(genv && genv[0] == '1') && !(pass && pass[0] == '1');
 }
 
+// Where run() takes the folded LM chain for its bodies: per iteration
+//   k_lin_schur -> k_schur_sum<glue> -> K3 levels -> k_cam_update<1> (+ the linearisation's scalars, + clear of S) ->
+//   k_backsub_runs -> k_reduce_tiles_stage1 -> k_reduce_control (+ clear of the scalars) -> the next k_lin_schur
+// instead of the chain with k_sp_clear, the linearisation's k_reduce_tiles_stage1, k_finalize_rcs, k_sp_symm and k_lm_accept
+// in launches of their own.  An accepted step flips LmState::cur instead of copying the candidate over the
+// state: the three kernels that read parameters select their buffers by it (DevProblem::lm_cur), and run() swaps the
+// handle's own pointers after its last read-back if the state ended in the second buffers.  The first body of a run keeps
+// the glue launches but k_lm_accept (nothing assumes a clean S on entry, and with the scale fold k_sp_rescale stands
+// between the sums and the LM diagonal); it already clears behind itself.
+// It applies to: the fused plan without free intrinsics, on one rank, every track inside a wave tile, no camera priors,
+// direct launches, a sparse K3 plan, every row of the system owned by a camera that k_schur_sum visits, and the candidate's
+// blocks written by k_cam_update's extra workgroups, k_backsub_runs for the trial step, a handle without inner-iteration
+// lists.  run() adds: no phase timing.
+// THEIA_HIP_LM_GLUE_KERNELS=1 keeps the separate launches everywhere (A/B runs, the equality test).
+bool lm_glue_applies(const theia_ba_handle_s* h) {
+  const char* keep = getenv("THEIA_HIP_LM_GLUE_KERNELS");
+  const char* genv = getenv("THEIA_HIP_LM_GRAPH");
+  if ((keep && keep[0] == '1') || (genv && genv[0] == '1')) return false;
+  if (!(h->use_fused && h->ni == 0 && h->n_fruns > 0 && h->n_sum_items > 0 && h->n > 0 && h->ntiles_main > 0 && !h->allreduce &&
+        !h->dist_k3 && h->long_ntracks == 0 && h->n_priors == 0 && h->sum_covers_n))
+    return false;
+  // (the state's per-camera blocks stay current between bodies -- enqueue_linearize: keep_blocks -- so no k_cam_prep, which
+  // does not look at LmState::cur, runs after the first body)
+  if (h->inner || getenv("THEIA_HIP_CAM_PREP_ALWAYS")) return false;
+  return cam_update_preps(h->P) == 1 && backsub_runs_applies(h->P) && linearize_route(h->P) == LIN_FUSED &&
+         chol_plan_tile_lists(h->plan).nzero > 0;
+}
+
+// what run() branches on: the chain applies to the handle, and this run has no inner iterations, no phase timing
+bool lm_glue_run(const theia_ba_handle_s* h) {
+  const bool inner = h->inner && h->opt.use_inner_iterations != 0;
+  return lm_glue_applies(h) && !inner && getenv("THEIA_HIP_PHASE_TIMING") == nullptr;
+}
+
 // enqueue: clear, linearize + Schur, tile reduction, (all-reduce), LM diagonal.
 // The trust-region radius is read from the device-resident LM state.
 // slot < 0: no phase-timing events (graph capture, or timing not requested)
 // first_fold: the first linearisation of a run where scale_fold_applies(): it also makes the Jacobi scaling
-int enqueue_linearize(theia_ba_handle_s* h, int slot, bool first_fold) {
+// chain == LM_FOLDED: a later body of a run on the folded chain (lm_glue_applies): no clear, k_schur_sum finishes the system
+int enqueue_linearize(theia_ba_handle_s* h, int slot, bool first_fold, LmChain chain) {
+  const bool folded = chain == LM_FOLDED;
   const double* radius = &reinterpret_cast<const LmState*>(h->lm_state.p)->radius;
   h->P.intr = h->intr[h->cur].p; h->P.intr_cand = h->intr[1 - h->cur].p;
   // clear the reduced system: the tiles the K3 plan knows (assembly + fill) and the vector tail; everything else in
   // the n x n buffer is never written (it was zeroed once at create())
-  if (h->n > 0 && !(h->allreduce && h->n_pack_tiles == 0) &&
-      chol_plan_clear(h->plan, h->rb.S, h->n, h->stream, h->rb.rhs, h->reduce.n - (size_t)h->n * h->n)) {
-  } else
-    HIP_TRYR(hipMemsetAsync(h->reduce.p, 0, sizeof(double) * h->reduce.n, h->stream));
+  const bool plan_clears = !folded && h->n > 0 && !(h->allreduce && h->n_pack_tiles == 0) &&
+                           chol_plan_clear(h->plan, h->rb.S, h->n, h->stream, h->rb.rhs, h->reduce.n - (size_t)h->n * h->n);
+  if (!folded && !plan_clears) HIP_TRYR(hipMemsetAsync(h->reduce.p, 0, sizeof(double) * h->reduce.n, h->stream));
   if (slot >= 0) HIP_TRYR(hipEventRecord(h->ev[slot][4], h->stream));
   // the state's per-camera blocks (k_cam_prep) are still current after the first body: an accepted step copies the candidate's
   // blocks over them (k_lm_accept), a rejected one leaves the state where it was.  Not with inner iterations (the accepted
   // point may be the swept one, and the sweep reuses the candidate's blocks) and not with free intrinsics.
   const bool keep_blocks = h->use_fused && h->ni == 0 && !h->inner && !getenv("THEIA_HIP_CAM_PREP_ALWAYS");
   h->P.camrot_current = keep_blocks && h->camrot_valid;
+  if (folded) {
+    // the body before this one left the plan's tiles and the scalars clear; k_schur_sum finishes the system, the scalars of
+    // the linearisation wait in tile_part / red_part for k_cam_update's folding workgroup (the trial step reuses both later)
+    const CholTileLists tl = chol_plan_tile_lists(h->plan);
+    const bool two_stage = h->ntiles_main > 4 * kReduceBlocks;
+    const LinGlue lg{h->scale_red.p, tl.symm_map, tl.nt, h->fmaxflag.p, two_stage ? h->red_part.p : nullptr};
+    launch_linearize_fused(h->P, h->cam[h->cur].p, h->pts[h->cur].p, radius, h->rb, h->Vinv.p, h->tile_part.p, h->stream, &lg);
+    h->camrot_valid = keep_blocks;
+    return 0;
+  }
   if (first_fold) {
     // unit scales in, scale_p / scale_c / scale_red out; the camera scaling factors out of the Schur complement exactly
     // (S(D) = D S(I) D, rhs(D) = D rhs(I), the same for g_c and the column norms), so the assembled system is rescaled
@@ -531,9 +589,11 @@ int enqueue_linearize(theia_ba_handle_s* h, int slot, bool first_fold) {
 
 // enqueue: dense solve, candidate cameras, back-substitution + trial cost.
 // defer_reduce: the tile reduction of the trial step is left to k_reduce_control (no all-reduce in between).
-int enqueue_solve_and_backsub(theia_ba_handle_s* h, int slot, bool defer_reduce) {
+int enqueue_solve_and_backsub(theia_ba_handle_s* h, int slot, bool defer_reduce, LmChain chain) {
   double* yc = h->rb.rhs;  // the solution overwrites the rhs row
-  if (h->dist_k3) {
+  // (folded: k_schur_sum has written the mirrored tiles; phase 0 of an unsharded plan is nothing but k_sp_symm)
+  if (chain == LM_FOLDED) chol_plan_solve_phase(h->plan, 1, h->rb.S, h->n, h->rb.rhs, h->chol_work.p, h->rb.scal + SC_NOTPD, h->stream);
+  else if (h->dist_k3) {
     chol_plan_solve_phase(h->plan, 1, h->rb.S, h->n, h->rb.rhs, h->chol_work.p, h->rb.scal + SC_NOTPD, h->stream);
     k_y_own<<<(h->n + 255) / 256, 256, 0, h->stream>>>(h->n, yc, h->d_tile_cls.p, h->shard_rank);
     const int rcy = do_allreduce(h, yc, (size_t)h->n, THEIA_REDUCE_SUM);
@@ -542,8 +602,21 @@ int enqueue_solve_and_backsub(theia_ba_handle_s* h, int slot, bool defer_reduce)
   chol_plan_solve(h->plan, h->rb.S, h->n, h->rb.rhs, h->chol_work.p, h->rb.scal + SC_NOTPD, h->stream);
   if (slot >= 0) HIP_TRYR(hipEventRecord(h->ev[slot][2], h->stream));
   const int nxt = 1 - h->cur;
+  // LM_FOLD_FIRST, LM_FOLDED: S is dead once the solve has left y in the row behind it (h->rb.rhs = S + n * n, outside every tile of the plan):
+  // the tiles the next body's assembly and factorisation touch are cleared beside the candidate cameras; LM_FOLDED: the
+  // scalars of the linearisation (k_schur_sum's stage-1 sums, or the per-tile partials) are folded into rb.scal there too
+  CamUpdateGlue cg{};
+  if (chain != LM_SEPARATE) {
+    const CholTileLists tl = chol_plan_tile_lists(h->plan);
+    cg.zero_S = h->rb.S; cg.zero_items = tl.zero_items; cg.nzero = tl.nzero;
+  }
+  if (chain == LM_FOLDED) {
+    const bool two_stage = h->ntiles_main > 4 * kReduceBlocks;
+    cg.lin_part = two_stage ? h->red_part.p : h->tile_part.p; cg.lin_ntiles = two_stage ? kReduceBlocks : h->ntiles_main;
+    cg.lin_f2s = h->f2s.p; cg.lin_fmaxflag = h->fmaxflag.p; cg.scal = h->rb.scal;
+  }
   launch_cam_update(h->P, h->cam[h->cur].p, yc, h->cam[nxt].p, h->ni ? h->intr[nxt].p : nullptr,
-                    h->scalB.p + SB_STEPSQ_CAM, h->scalB.p + SB_XNORMSQ_CAM, h->stream, h->scalB.p);
+                    h->scalB.p + SB_STEPSQ_CAM, h->scalB.p + SB_XNORMSQ_CAM, h->stream, h->scalB.p, chain != LM_SEPARATE ? &cg : nullptr);
   launch_backsub(h->P, h->cam[h->cur].p, h->pts[h->cur].p, h->cam[nxt].p, h->pts[nxt].p, yc, h->Vinv.p, h->tile_part.p, h->scalB.p, h->stream);
   if (h->ntiles_main && !defer_reduce) launch_reduce_tiles(h->ntiles_main, h->tile_part.p, 5, h->f2s.p + 8, h->fmaxflag.p + 8, h->scalB.p, h->stream, h->red_part.p);
   launch_long_backsub(h->P, h->cam[h->cur].p, h->pts[h->cur].p, h->cam[nxt].p, h->pts[nxt].p, yc, h->Vinv.p, h->long_scratch.p, h->scalB.p, h->stream);
@@ -875,6 +948,22 @@ int theia_hip_ba_run(theia_ba_handle h, theia_ba_summary* S) {
   ctl.th = ctl.trace_capacity ? reinterpret_cast<double*>(h->lm_state.p + kLmStateBytes) : nullptr;
   ctl.tt = h->tr_tail.p; ctl.tt_cap = (int)h->tr_tail_cap;
   ctl.inner_scal = inner ? h->in_scal.p : nullptr;
+  // the folded chain of glue launches: state and candidate buffers change roles on the device (LmState::cur), and the handle
+  // puts its own pointers right again on EVERY way out of this function -- after the last read-back that succeeded
+  const bool glue_run = lm_glue_run(h);
+  struct Normalise {
+    theia_ba_handle_s* h; LmState* st; bool on;
+    void operator()() {
+      if (!on || st->cur != 1) return;
+      // the host's invariant "state = buffer 0" (download, snapshot, the queries, the next run): the buffers changed roles an
+      // odd number of times; a replay graph captured on the old pointers is dropped with them
+      h->cam[0].swap(h->cam[1]); h->pts[0].swap(h->pts[1]); h->camrot.swap(h->camrot_cand);
+      h->P.camrot = h->camrot.p; h->P.camrot_cand = h->camrot_cand.p;
+      h->drop_graph();
+      st->cur = 0;
+    }
+    ~Normalise() { (*this)(); }
+  } normalise{h, &st, glue_run};
   if (h->xnorm_part.n < 2 * (size_t)kXnormBlocks && (rc = h->xnorm_part.alloc(2 * kXnormBlocks))) return rc;
   // the initial state and the control block travel as kernel arguments: no host buffer whose lifetime would need a
   // synchronisation before the first iteration
@@ -891,13 +980,18 @@ int theia_hip_ba_run(theia_ba_handle h, theia_ba_summary* S) {
   const LmCtl* dctl = reinterpret_cast<const LmCtl*>(h->lm_ctl.p);
   const int nxt = 1;
   // one LM iteration ("body"): linearise + Schur, solve, trial step, step control, accept
-  auto enqueue_body = [&](int slot, bool first_fold = false) -> int {
+  auto enqueue_body = [&](int slot, bool first_fold = false, LmChain chain = LM_SEPARATE) -> int {
+    const bool flip = chain != LM_SEPARATE;   // no k_lm_accept: an accepted step flips LmState::cur
     int r;
     if (slot >= 0) HIP_TRYR(hipEventRecord(h->ev[slot][0], h->stream));
-    if ((r = enqueue_linearize(h, slot, first_fold))) return r;
+    // (flip: the kernels pick state and candidate by LmState::cur; the first body runs at cur = 0, so its launches that do
+    // not look -- the first-fold linearisation, k_cam_prep -- are right)
+    struct CurScope { DevProblem& P; ~CurScope() { P.lm_cur = nullptr; P.pts_alt = nullptr; } } cur_scope{h->P};
+    if (flip) { h->P.lm_cur = &dst->cur; h->P.pts_alt = h->pts[nxt].p; }
+    if ((r = enqueue_linearize(h, slot, first_fold, chain))) return r;
     if (slot >= 0) HIP_TRYR(hipEventRecord(h->ev[slot][1], h->stream));
     const bool fuse = !h->allreduce && !inner && slot < 0 && h->ntiles_main > 0;   // tile reduction inside the control kernel
-    if ((r = enqueue_solve_and_backsub(h, slot, fuse))) return r;
+    if ((r = enqueue_solve_and_backsub(h, slot, fuse, chain))) return r;
     if (inner) {
       // DoInnerIterationsIfNeeded: one sweep of block coordinate descent on a copy of the candidate, its cost and its
       // distance from x; every kernel returns at once when the gate is closed (step invalid, inner iterations off, done)
@@ -951,11 +1045,14 @@ int theia_hip_ba_run(theia_ba_handle h, theia_ba_summary* S) {
       }
     }
     if (slot >= 0) HIP_TRYR(hipEventRecord(h->ev[slot][3], h->stream));
-    if (fuse && h->ntiles_main > 4 * kReduceBlocks) {
+    const bool two_stage = h->ntiles_main > 4 * kReduceBlocks;
+    double* clear16 = flip ? h->rb.scal : nullptr;
+    if (fuse && two_stage) {
       launch_reduce_tiles_stage1(h->ntiles_main, h->tile_part.p, 5, h->fmaxflag.p + 8, h->red_part.p, h->stream);
-      k_reduce_control<<<1, 1024, 0, h->stream>>>(kReduceBlocks, h->red_part.p, h->f2s.p + 8, h->fmaxflag.p + 8, dst, h->rb.scal, h->scalB.p, dctl);
-    } else if (fuse) k_reduce_control<<<1, 1024, 0, h->stream>>>(h->ntiles_main, h->tile_part.p, h->f2s.p + 8, h->fmaxflag.p + 8, dst, h->rb.scal, h->scalB.p, dctl);
+      k_reduce_control<<<1, 1024, 0, h->stream>>>(kReduceBlocks, h->red_part.p, h->f2s.p + 8, h->fmaxflag.p + 8, dst, h->rb.scal, h->scalB.p, dctl, clear16, flip ? 1 : 0);
+    } else if (fuse) k_reduce_control<<<1, 1024, 0, h->stream>>>(h->ntiles_main, h->tile_part.p, h->f2s.p + 8, h->fmaxflag.p + 8, dst, h->rb.scal, h->scalB.p, dctl, clear16, flip ? 1 : 0);
     else k_lm_control<<<1, 1, 0, h->stream>>>(dst, h->rb.scal, h->scalB.p, dctl);
+    if (!flip)
     k_lm_accept<<<256, 256, 0, h->stream>>>(dst, h->cam[0].p, h->cam[nxt].p, (size_t)6 * h->nc, h->pts[0].p, h->pts[nxt].p,
                                             (size_t)4 * h->np, h->intr[0].p, h->intr[nxt].p, h->ni ? (size_t)THEIA_MAX_INTRINSICS * h->ng : 0,
                                             h->in_cam.p, h->in_pts.p, h->in_intr.p,
@@ -1014,7 +1111,10 @@ int theia_hip_ba_run(theia_ba_handle h, theia_ba_summary* S) {
     if (nb <= 0) break;
     for (int b = 0; b < nb; ++b) {
       if (use_graph) HIP_TRYR(hipGraphLaunch(h->graph_exec, h->stream));
-      else if ((rc = enqueue_body(timing ? b : -1, fold && bodies_enqueued == 0 && b == 0))) return rc;   // (a host-side fact: bodies are enqueued ahead of the device)
+      else {   // (first: a host-side fact -- bodies are enqueued ahead of the device)
+        const bool first = bodies_enqueued == 0 && b == 0;
+        if ((rc = enqueue_body(timing ? b : -1, fold && first, glue_run ? (first ? LM_FOLD_FIRST : LM_FOLDED) : LM_SEPARATE))) return rc;
+      }
     }
     bodies_enqueued += nb;
     HIP_TRYR(hipGetLastError());   // a rejected launch configuration would otherwise go unnoticed
@@ -1035,6 +1135,7 @@ int theia_hip_ba_run(theia_ba_handle h, theia_ba_summary* S) {
     }
     if (st.done) break;
   }
+  normalise();   // before anything else looks at the handle's buffers: the extra linearisation below, download, the queries
   if (ctl.trace_capacity && st.pending_grad >= 0 && st.term != THEIA_TERM_FAILURE) {
     // the last step was accepted at the iteration cap (or the time ran out after it): the gradient its trace entry reports
     // is the one at the accepted point (ceres evaluates it as part of the successful step), so linearise there once more

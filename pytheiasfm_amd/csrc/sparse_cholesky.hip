@@ -501,6 +501,7 @@ struct CholPlan {
   std::vector<Level> lev;
   int symm_off = 0, nsymm = 0;
   int clear_off = 0, nclear = 0;   // {r0, h, c0, w} of every structure tile (fill included) at its physical lower position
+  int symm_map_off = 0;            // [nt][nt]: 1 where the lower tile (row, column) is the source of a symm item
   double flops = 0.0;              // FP64 flops of one factorisation + solve on this schedule (useful ones: h x w x nb extents)
   // deferred border updates (k_sp_update_partial / k_sp_update_reduce), run before level def_level
   int def_level = -1, def_part_off = 0, n_def_part = 0, def_src_off = 0, def_red_off = 0, n_def_red = 0;
@@ -718,7 +719,7 @@ CholPlan* chol_plan_create_impl(int n, const uint8_t* adj_in, const uint8_t* til
       if (perm[I] < perm[K]) { prog.push_back(r0(I)); prog.push_back(hh(I)); prog.push_back(r0(K)); prog.push_back(hh(K)); pl->nsymm++; }
   // every tile the assembly or the factorisation touches, at its physical lower-triangle position: the per-iteration
   // clear of the reduced system visits these instead of the whole n x n buffer (288 MB at 1000 cameras)
-  pl->clear_off = (int)prog.size();
+  pl->clear_off = (int)prog.size();   // (directly behind the symm list: chol_plan_tile_lists hands the two out as one)
   {
     std::vector<char> seen((size_t)nt * nt, 0);
     auto add = [&](int I, int K) {
@@ -737,6 +738,13 @@ CholPlan* chol_plan_create_impl(int n, const uint8_t* adj_in, const uint8_t* til
         pl->shared_tiles.push_back(perm[K]); pl->shared_tiles.push_back(perm[K]);
         for (int I : best.below[K]) { pl->shared_tiles.push_back(perm[I]); pl->shared_tiles.push_back(perm[K]); }
       }
+  }
+  // the symm list once more as a map by source tile, for an assembly that writes the mirrored entries itself
+  pl->symm_map_off = (int)prog.size();
+  prog.resize(prog.size() + (size_t)nt * nt, 0);
+  for (int q = 0; q < pl->nsymm; ++q) {
+    const int* it = prog.data() + pl->symm_off + 4 * q;   // dst tile (it[0], it[2]) <- source tile (it[2], it[0])
+    prog[(size_t)pl->symm_map_off + (size_t)(it[2] / NB) * nt + it[0] / NB] = 1;
   }
   if (getenv("THEIA_HIP_CREATE_TIMING")) {   // shape of the schedule
     fprintf(stderr, "theia_hip K3 plan: n = %d, %d tiles, %d levels, %lld factor tiles, %.1f MFLOP\n", n, nt, pl->nlev, best.ntiles, pl->flops * 1e-6);
@@ -769,14 +777,17 @@ __global__ __launch_bounds__(256) void k_sp_clear(double* __restrict__ A, int ld
     for (size_t e = b0 + threadIdx.x; e < tail_count && e < b0 + 4096; e += 256) tail[e] = 0.0;
     return;
   }
-  const int* it = items + 4 * blockIdx.x;
-  const int r0 = it[0], h = it[1], c0 = it[2], w = it[3];
-  for (int e = threadIdx.x; e < NB * NB; e += 256) {
-    const int r = e >> 6, c = e & 63;
-    if (r < h && c < w) A[(size_t)(r0 + r) * lda + c0 + c] = 0.0;
-  }
+  clear_tile_item(A, lda, items + 4 * blockIdx.x);
 }
 }  // namespace
+
+CholTileLists chol_plan_tile_lists(const CholPlan* pl) {
+  CholTileLists L{};
+  if (!pl || pl->dense || pl->nclear == 0) return L;
+  L.zero_items = pl->prog + pl->symm_off; L.nzero = pl->nsymm + pl->nclear;
+  L.symm_map = pl->prog + pl->symm_map_off; L.nt = pl->nt;
+  return L;
+}
 
 bool chol_plan_clear(const CholPlan* pl, double* A, int lda, hipStream_t st, double* tail, size_t tail_count) {
   if (!pl || pl->dense || pl->nclear == 0) return false;
