@@ -1553,6 +1553,51 @@ int theia_hip_set_underconstrained_unestimated(int32_t num_views, int32_t num_tr
                                                const int32_t* obs_track, uint8_t* view_estimated /*in/out*/,
                                                uint8_t* track_estimated /*in/out*/, int32_t* views_removed,
                                                int32_t* tracks_removed, int32_t* rounds /*optional, each*/);
+/* Pixels to camera points, normalised features and world rays for all eight camera models (csrc/unproject.hip,
+ * csrc/unproject_device.h): Camera::PixelToNormalizedCoordinates and Camera::PixelToUnitDepthRay (sfm/camera/camera.cc:218-230)
+ * over CameraIntrinsicsModel::ImageToCameraCoordinates (camera_intrinsics_model.cc:150-167), one lane per observation.  Every
+ * model's PixelToCameraCoordinates is restated operation for operation, in the reference's order, without FMA contraction:
+ *   PINHOLE pinhole_camera_model.h:213-300; PINHOLE_RADIAL_TANGENTIAL pinhole_radial_tangential_camera_model.h:222-362;
+ *   FISHEYE fisheye_camera_model.h:191-341; FOV fov_camera_model.h:183-305; DIVISION_UNDISTORTION
+ *   division_undistortion_camera_model.h:232-321; DOUBLE_SPHERE double_sphere_camera_model.h:189-286 (XI slot 5, ALPHA slot 6);
+ *   EXTENDED_UNIFIED extended_unified_camera_model.h:189-285; ORTHOGRAPHIC orthographic_camera_model.h:188-274 (epsilon 1e-16).
+ * The arrays are theia_ba_problem's: observation k is the pixel obs_uv[k] of camera obs_cam[k] (NULL: camera 0), whose
+ * intrinsics are the row cam_group[camera] of `intrinsics` under the model group_model[group]; cam_ext is read only for the
+ * world rays (its angle-axis half, through the library's angle-axis -> matrix routine, ceres' small-angle branch included).
+ * Outputs, each optional (NULL: neither computed nor downloaded):
+ *   camera_point   [n][3] ImageToCameraCoordinates
+ *   normalized     [n][2] .hnormalized(): x / z, y / z -- the normalized_features row of the position, localisation and
+ *                  triangulation entries
+ *   world_ray      [n][3] PixelToUnitDepthRay = R' camera_point
+ *   world_ray_unit [n][3] world_ray / |world_ray| -- theia_hip_estimate_tracks' obs_ray_dir
+ *   status         [n] bit 0 = valid (the model's return value); bit 1 = converged: the fixed-point loop of models 0, 1, 2, 7
+ *                  left by its break (or by the fisheye's early return); always set for the closed forms 3, 4, 5, 6
+ *   iterations     [n] loop trips run (at most 100), 0 for the closed forms.  The reference silently returns the 100th iterate
+ *                  of a loop that has not settled; so does this call, with bit 1 clear.
+ * STATED DEVIATION: where a model returns false (DOUBLE_SPHERE / EXTENDED_UNIFIED beyond their domain, alpha > 0.5)
+ * ImageToCameraCoordinates ignores the bool and returns an uninitialised vector; here every output of such an observation is
+ * NaN and its valid bit is clear.  A NaN pixel is not refused: it propagates as in the reference.
+ * *summary (optional): the counts over the call, and the kernel's and the call's time.
+ * THEIA_HIP_ERR_INVALID_ARGUMENT, before the device is touched and with nothing written: a negative count; a NULL obs_uv with
+ * num_obs > 0, a NULL cam_group with num_cameras > 0, a NULL intrinsics or group_model with num_groups > 0; obs_cam[k] outside
+ * [0, num_cameras) (obs_cam NULL with num_obs > 0: no camera 0), cam_group[c] outside [0, num_groups), group_model[g] outside
+ * 0..7; world_ray or world_ray_unit asked for with num_obs > 0 and cam_ext NULL.  num_obs == 0 returns 0 and launches nothing.
+ * THEIA_HIP_ERR_NO_DEVICE without a device (there is no CPU fallback), THEIA_HIP_ERR_OUT_OF_MEMORY when a buffer cannot be had. */
+typedef struct theia_unproject_summary {
+  int64_t num_invalid;        /* observations with the valid bit clear                      */
+  int64_t num_not_converged;  /* observations with the converged bit clear                  */
+  int32_t max_iterations;     /* largest entry of `iterations`                              */
+  int32_t reserved;
+  double kernel_ms;           /* the kernel alone (device events)                           */
+  double call_ms;             /* the whole call: validation, upload, kernel, download       */
+} theia_unproject_summary;
+int theia_hip_unproject(int64_t num_obs, const double* obs_uv /*[n][2]*/, const int32_t* obs_cam /*[n], NULL = camera 0*/,
+                        int32_t num_cameras, const int32_t* cam_group /*[num_cameras]*/,
+                        const double* cam_ext /*[num_cameras][6] position, angle-axis; NULL allowed when no world ray is asked for*/,
+                        int32_t num_groups, const double* intrinsics /*[num_groups][THEIA_MAX_INTRINSICS]*/,
+                        const int32_t* group_model /*[num_groups]*/,
+                        double* camera_point, double* normalized, double* world_ray, double* world_ray_unit,
+                        uint8_t* status, uint8_t* iterations, theia_unproject_summary* summary /*or NULL*/);
 /* n draws of RandomNumberGenerator(seed).RandInt(lo, hi) (util/random.cc:46-84): host code that follows the reference's
  * generator outside the RANSAC sampler (the random candidates of GuidedEpipolarMatcher::FindFeaturesNearEpipolarLines). */
 int theia_hip_randint_stream(uint32_t seed, int32_t n, int32_t lo, int32_t hi, int32_t* out);

@@ -2,6 +2,7 @@
 pyTheia's BundleAdjust* / Estimate* entry points."""
 __version__ = "0.1.0"
 
+from . import camera  # noqa: E402,F401
 from . import incremental  # noqa: E402,F401
 from .incremental import (FindViewsToLocalize, VisibilityPyramid, LocalizeViewToReconstruction,  # noqa: E402,F401
                           LocalizeViewsToReconstruction, LocalizeViewToReconstructionOptions,
