@@ -28,7 +28,8 @@
 #include <hip/hip_runtime.h>
 
 #include "dls_tables.h"
-#include "ransac_device.h"
+#include "eig_general.h"
+#include "rotation_maps.h"
 
 namespace thip {
 namespace dlsdev {

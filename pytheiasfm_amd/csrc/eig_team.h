@@ -1,5 +1,5 @@
 // Real general eigen-decomposition by a TEAM of lanes with the matrices in LDS: the same algorithm, the same
-// arithmetic per matrix entry and the same summation order as the one-thread eig_general_t (ransac_device.h: EISPACK
+// arithmetic per matrix entry and the same summation order as the one-thread eig_general_t (eig_general.h: EISPACK
 // orthes + hqr2 as Eigen's EigenSolver runs them), so the results are bit-identical to it -- but the n x n work arrays
 // live on chip instead of in per-lane scratch, where the QR sweeps of 64 independent matrices per wave moved
 // ~200 KB of HBM traffic per 10 x 10 matrix (measured on k_fit: FETCH + WRITE = 3.2 TB/s).
@@ -18,7 +18,7 @@
 
 #include <hip/hip_runtime.h>
 
-#include "ransac_device.h"
+#include "eig_general.h"
 
 namespace thip {
 namespace rsc {

@@ -1,4 +1,4 @@
-// Steps 1-3 of the five-point solver (five_point_pre, ransac_device.h; five_point_relative_pose.cc:228-273) by a TEAM of
+// Steps 1-3 of the five-point solver (five_point_pre, five_point_device.h; five_point_relative_pose.cc:228-273) by a TEAM of
 // lanes with the work arrays in LDS: the same arithmetic per entry and the same order inside every sum as the one-thread
 // routine, so the null space and the action matrix come out bit-identical -- but the 5 x 9 system, the nine E E^T
 // polynomials, the 10 x 20 constraint matrix and its elimination (5 KB per hypothesis as per-lane scratch, which made the
@@ -11,6 +11,7 @@
 #define THEIA_HIP_FIT5_TEAM_H_
 
 #include "eig_team.h"
+#include "five_point_device.h"
 #include "wave_reduce.h"
 
 namespace thip {

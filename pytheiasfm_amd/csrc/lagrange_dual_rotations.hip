@@ -48,7 +48,8 @@
 //
 // Determinism: no atomics.  Every G_i is a sum in a fixed lane order and a fixed butterfly, f a fixed tree (block_sum),
 // every entry of S has one writer.  Two runs on one input are bit-identical.
-#include "ransac_device.h"
+#include "small_linalg.h"
+#include "rotation_maps.h"
 #include "dense_cholesky.h"
 #include "smallest_eigenvector.h"
 #include "view_graph_plan.h"

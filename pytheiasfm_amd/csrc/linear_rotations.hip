@@ -30,7 +30,8 @@
 //
 // Determinism: no floating-point atomics.  Every entry of M is a sum in edge order by one owner, every dot product and norm
 // a fixed tree (block_sum).  Two runs on one input are bit-identical.
-#include "ransac_device.h"
+#include "small_linalg.h"
+#include "rotation_maps.h"
 #include "dense_cholesky.h"
 #include "spectral_shift.h"
 #include "view_graph_device.h"

@@ -22,7 +22,7 @@
 // unordered free-view pair: its edges in edge order); a free view's sums over its edges are strided over a wavefront's
 // lanes and added by the butterfly; every norm is a per-block sum followed by one workgroup summing the blocks in order.
 // Two runs on one input are bit-identical.
-#include "ransac_device.h"
+#include "rotation_maps.h"
 #include "dense_cholesky.h"
 #include "view_graph_device.h"
 

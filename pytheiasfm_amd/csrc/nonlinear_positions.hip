@@ -21,7 +21,7 @@
 //
 // Determinism: no atomics of this file's own.  Every sum has one owner and a fixed order.  Two runs on one input are
 // bit-identical.
-#include "ransac_device.h"
+#include "rotation_maps.h"
 #include "graph_lm.h"
 
 #include <chrono>

@@ -33,6 +33,7 @@
 // Determinism: no atomics of this file's own (the factorisation's fail flag is the only one, and it is only compared with
 // zero).  Every sum has one owner and a fixed order.  Two runs on one input are bit-identical.
 #include "graph_lm.h"
+#include "small_linalg.h"
 
 #include <chrono>
 #include <vector>
@@ -175,13 +176,7 @@ __device__ __forceinline__ void log_rot_d(const double* E, const double* dE, con
   }
 }
 
-// C = A B, C = A' B', all row-major 3 x 3
-__device__ __forceinline__ void mul33(const double* A, const double* B, double* C) {
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) C[3 * r + c] = (A[3 * r] * B[c] + A[3 * r + 1] * B[3 + c]) + A[3 * r + 2] * B[6 + c];
-}
+// C = A' B', all row-major 3 x 3 (C = A B: rsc::matmul3)
 __device__ __forceinline__ void mul33_tt(const double* A, const double* B, double* C) {
 #pragma unroll
   for (int r = 0; r < 3; ++r)
@@ -202,7 +197,7 @@ __device__ __forceinline__ void edge_eval(const double* wi, const double* wj, co
   aa_rot(wj, v.cj, v.Rj);
   aa_rot(wr, v.cr, v.Rrel);
   mul33_tt(Ri, v.Rrel, v.M);
-  mul33(v.Rj, v.M, v.Em);
+  rsc::matmul3(v.Rj, v.M, v.Em);
   log_rot(v.Em, v.L, v.r);
   const double s = (v.r[0] * v.r[0] + v.r[1] * v.r[1]) + v.r[2] * v.r[2];
   const double sq = sqrt(1.0 + s / b);
@@ -216,7 +211,7 @@ __device__ __forceinline__ void jacobian_columns(const EdgeEval& v, bool free_i,
   double D[9], N[9], dE[9], dr[3];
   if (free_j) {
     aa_rot_d<K>(v.cj, D);
-    mul33(D, v.M, dE);
+    rsc::matmul3(D, v.M, dE);
     log_rot_d(v.Em, dE, v.L, dr);
 #pragma unroll
     for (int r = 0; r < 3; ++r) Jj[3 * r + K] = (dr[r] * v.sr) * sj[K];
@@ -224,7 +219,7 @@ __device__ __forceinline__ void jacobian_columns(const EdgeEval& v, bool free_i,
   if (free_i) {
     aa_rot_d<K>(v.ci, D);
     mul33_tt(D, v.Rrel, N);
-    mul33(v.Rj, N, dE);
+    rsc::matmul3(v.Rj, N, dE);
     log_rot_d(v.Em, dE, v.L, dr);
 #pragma unroll
     for (int r = 0; r < 3; ++r) Ji[3 * r + K] = (dr[r] * v.sr) * si[K];

@@ -16,7 +16,8 @@
 
 #include "p4pf_tables.h"
 #include "wave_reduce.h"
-#include "ransac_device.h"
+#include "small_linalg.h"
+#include "eig_team.h"
 
 namespace thip {
 namespace p4pfdev {

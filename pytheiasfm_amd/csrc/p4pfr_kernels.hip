@@ -29,7 +29,7 @@
 #include "eig_team.h"
 #include "wave_reduce.h"
 #include "p4pfr_layout.h"
-#include "ransac_device.h"
+#include "small_linalg.h"
 #include "theia_hip_internal.h"
 
 namespace thip {

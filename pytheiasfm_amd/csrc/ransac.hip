@@ -316,7 +316,7 @@ __global__ __launch_bounds__(score_threads(EST)) void k_score(int est_rt, int np
   int cnt = 0;
   double mle = 0.0;
   if (EST == THEIA_EST_RELATIVE_POSE || EST == THEIA_EST_ESSENTIAL_MATRIX) {
-    // Sampson error without its division wherever the comparison is decided by the margin (ransac_device.h quotient_below)
+    // Sampson error without its division wherever the comparison is decided by the margin (twoview_device.h quotient_below)
     for (int i = 0; i < n; ++i) {
       const double* d = pd + (size_t)i * ds;
       bool in = false;

@@ -5,7 +5,8 @@
 
 #include <optional>
 
-#include "dls_device.h"      // dlsdev::kMaxSolutions, dls::GlibcRand (and ransac_device.h: rsc::kRadHomDatum)
+#include "dls_device.h"      // dlsdev::kMaxSolutions, dls::GlibcRand
+#include "radial_homography_device.h"   // rsc::kRadHomDatum
 #include "theia_hip.h"
 #include "device_util.h"
 #include "pools.h"

@@ -16,9 +16,10 @@
 // Built with -ffp-contract=off like the other micro-solvers; the sums run in wave order (strided partials + butterfly) where
 // Eigen's product kernel runs blocked: bit-identical to the oracle run in wave order, ~1e-4 .. 1e-15 from the index-order run
 // depending on the pair's noise (the IRLS amplifies summation-order roundings: tests/test_relpos_gpu.py).
-#include "ransac_device.h"
+#include "small_linalg.h"
+#include "twoview_device.h"
 #include "wave_reduce.h"
-#include "eig_team.h"
+#include "eig_team.h"   // row16_bcast, oct_bcast
 #include "device_util.h"
 
 #include <algorithm>

@@ -15,10 +15,9 @@
 // block partials summed by one workgroup in block order.  Two runs on one input are bit-identical.
 //
 // The per-edge residual e_ij = MultiplyRotations(-r_j, MultiplyRotations(r_ij, r_i)) and the update
-// r_i <- MultiplyRotations(r_i, delta_i) go through ceres' conversions (ransac_device.h) with the intermediate angle-axis
+// r_i <- MultiplyRotations(r_i, delta_i) go through ceres' conversions (rotation_maps.h) with the intermediate angle-axis
 // round trip the reference takes (math/rotation.cc:56-66).
-#include "ransac_device.h"
-#include "rotation_compose.h"
+#include "rotation_maps.h"
 #include "dense_cholesky.h"
 #include "view_graph_device.h"
 

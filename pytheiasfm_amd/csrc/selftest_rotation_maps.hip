@@ -1,8 +1,8 @@
 // selftest_rotation_maps.hip -- test-only entry point for the rotation maps every global-pose stage starts and ends with
-// (ransac_device.h: angle_axis_to_rot, rot_to_angle_axis, eigen_rot_to_rotvec; rotation_compose.h: multiply_rotations) on
+// (rotation_maps.h: angle_axis_to_rot, rot_to_angle_axis, eigen_rot_to_rotvec, multiply_rotations) on
 // angle-axis vectors the caller chooses.  The kernel keeps the production launch shape of the stages that call them:
 // 256-thread workgroups, one lane per case.  Nothing here runs on the estimation path.
-#include "rotation_compose.h"
+#include "rotation_maps.h"
 #include "device_util.h"
 
 namespace thip {

@@ -1,6 +1,6 @@
 // selftest_team_solvers.hip -- test-only entry points for the team linear algebra of the minimal solvers: the eigen-solver
 // teams (eig_team.h), the 9 x 9 SVD teams (svd_team.h) and stage A of the five-point solver (fit5_team.h), each run next to
-// the one-thread routine it claims to be bit-identical to (ransac_device.h: eig_general_t, svd_sq<9>, five_point_pre) on
+// the one-thread routine it claims to be bit-identical to (eig_general.h: eig_general_t, small_linalg.h: svd_sq<9>, five_point_device.h: five_point_pre) on
 // matrices the caller chooses.  The team kernels keep the production launch shapes: 64-lane blocks, the callers' teams per
 // wave (idle lanes included) and their LDS layouts; a team whose matrix is masked off returns at once, as the production
 // teams of a hypothesis past active_iters do.  Nothing here runs on the estimation path.

@@ -9,7 +9,8 @@
 // votes are integers.
 #ifndef THEIA_HIP_SMALLEST_EIGENVECTOR_H_
 #define THEIA_HIP_SMALLEST_EIGENVECTOR_H_
-#include "ransac_device.h"
+#include "small_linalg.h"
+#include "rotation_maps.h"
 #include "dense_cholesky.h"
 #include "spectral_shift.h"
 #include "wave_reduce.h"
@@ -25,11 +26,7 @@ struct InverseIterationState {
   double diff, eigenvalue, shift, max_diag;
 };
 
-__device__ __forceinline__ void cross3(const double* a, const double* b, double* c) {
-  c[0] = a[1] * b[2] - a[2] * b[1];
-  c[1] = a[2] * b[0] - a[0] * b[2];
-  c[2] = a[0] * b[1] - a[1] * b[0];
-}
+using rsc::cross3;
 
 // out = X' Y (3 x 3, row-major)
 __device__ __forceinline__ void atb(const double* X, const double* Y, double* out) {

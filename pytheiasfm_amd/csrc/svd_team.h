@@ -1,5 +1,5 @@
 // Two-sided Jacobi SVD of a 9 x 9 matrix by a TEAM of 9 lanes with the work matrices in LDS: the algorithm, the rotation
-// order and the arithmetic per matrix entry of the one-thread svd_sq<9> (ransac_device.h: Eigen::JacobiSVD for square
+// order and the arithmetic per matrix entry of the one-thread svd_sq<9> (small_linalg.h: Eigen::JacobiSVD for square
 // real input, as sqpnp.cc:234 runs it), so U and S come out with the same bits -- but a rotation updates its 2 x 9 row
 // and column entries on nine lanes at once and the 81-double arrays live on chip instead of in per-lane scratch (the
 // SVD was 77 % of the SQPnP RANSAC fit kernel).  V is not accumulated: SQPnP never reads it and the iteration does not
@@ -13,6 +13,7 @@
 #define THEIA_HIP_SVD_TEAM_H_
 
 #include "eig_team.h"
+#include "small_linalg.h"
 
 namespace thip {
 namespace rsc {

@@ -18,7 +18,7 @@
 // estimate_uncalibrated_relative_pose.cc:142-176) the step is the exact solution (solve5).
 #include "ba_device.h"
 #include "wave_reduce.h"
-#include "ransac_device.h"
+#include "small_linalg.h"
 #include "device_util.h"
 
 #include <chrono>
@@ -81,6 +81,7 @@ __device__ void sphere3_plus_jacobian(const double x[3], double J[6]) {
 }
 
 // ceres AngleAxisToRotationMatrix (rotation.h), operation order kept; R row-major
+// (rsc::angle_axis_to_rot of rotation_maps.h, except that this one takes sine and cosine from one sincos call)
 __device__ void aa_to_rot(const double* aa, double* R) {
   const double theta2 = aa[0] * aa[0] + aa[1] * aa[1] + aa[2] * aa[2];
   if (theta2 > DBL_EPSILON) {
@@ -122,7 +123,7 @@ __device__ __forceinline__ void mat3_vec(const double* A, const double* v, doubl
 __device__ __forceinline__ void mat3t_vec(const double* A, const double* v, double* o) {
   for (int i = 0; i < 3; ++i) o[i] = (A[i] * v[0] + A[3 + i] * v[1]) + A[6 + i] * v[2];
 }
-__device__ __forceinline__ double dot3(const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+using rsc::dot3;
 
 // AngularEpipolarError::operator() (angular_epipolar_error.h:54-91); J = d r / d [rotation (3) | position tangent (2)]
 template <bool WANT_JAC>
@@ -459,6 +460,7 @@ struct HomographyBatch {
 };
 
 // Eigen's 3 x 3 inverse (InverseImpl.h compute_inverse<.., 3>): cofactors and the determinant along column 0
+// (rsc::inverse3 of small_linalg.h for a COLUMN-major matrix: on the same nine doubles that one expands along the other line)
 __device__ __forceinline__ double cof3(const double* m, int i, int j) {   // m column-major
   const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
   return m[i1 + 3 * j1] * m[i2 + 3 * j2] - m[i1 + 3 * j2] * m[i2 + 3 * j1];

@@ -23,6 +23,7 @@
 #include <mutex>
 
 #include "eig_team.h"
+#include "rotation_maps.h"
 #include "wave_reduce.h"
 #include "theia_hip_internal.h"
 #include "upnp_layout.h"

@@ -18,7 +18,7 @@
 // Owner-writes: a triangle is visited from each of its three pairs, so no result is ever added to from two places and
 // there is no atomic.  Minimum and integer sum do not depend on the order: two runs are byte-identical.
 // A NaN error validates nothing (`err < m` is false), so the minimum ignores it; the triangle is still counted.
-#include "ransac_device.h"
+#include "rotation_maps.h"
 #include "wave_reduce.h"
 #include "device_util.h"
 #include "view_graph_plan.h"
@@ -75,7 +75,7 @@ __device__ __forceinline__ double team_min_nonneg(double v) {
   return __hiloint2double((int)~hm, (int)~lm);
 }
 
-// |RotationMatrixToAngleAxis(R)|: rsc::rot_to_angle_axis (ransac_device.h), operation for operation, with its
+// |RotationMatrixToAngleAxis(R)|: rsc::rot_to_angle_axis (rotation_maps.h), operation for operation, with its
 // largest-diagonal branch written out per index.  That function picks the index at run time, which puts the matrix and
 // the quaternion into scratch (80 bytes per lane here); with the index a template argument everything stays in registers.
 struct Quat { double w, x, y, z; };

@@ -31,8 +31,7 @@
 // Rules where the reference leaves the choice to the iteration order of its hash maps: the lowest view
 // index among the sources; the lowest view index among equal scores; a view's initial weights are summed over its pairs in
 // pair order; the iterations add into a pair's weight in iteration order.  No atomics anywhere: two runs are bit-identical.
-#include "ransac_device.h"
-#include "rotation_compose.h"
+#include "rotation_maps.h"
 #include "wave_reduce.h"
 #include "device_util.h"
 

@@ -233,7 +233,7 @@ def write_header(rows, others, targets, B):
                 "// polynomial kRowPoly[r] times the monomial x^e0 y^e1 z^e2 w^e3 of kRowMul[r]; column c is the monomial kColMono[c].\n"
                 "// Columns: kOthers monomials to eliminate, kTargets = z * basis[5 + i], then the kBasis quotient-ring basis\n"
                 "// [1, z, y, x, w, z^2, yz, xz, wz, wy].  kRows < kOthers + kTargets: the rows reduce the targets onto the basis\n"
-                "// without determining every other monomial, so the solver works on the TRANSPOSED system (p4pf in ransac_device.h).\n"
+                "// without determining every other monomial, so the solver works on the TRANSPOSED system (p4pf_device.h).\n"
                 "#ifndef THEIA_HIP_P4PF_TABLES_H_\n#define THEIA_HIP_P4PF_TABLES_H_\n\n#include <cstdint>\n\nnamespace thip {\nnamespace p4pf {\n\n")
         f.write("constexpr int kRows = %d;\nconstexpr int kOthers = %d;\nconstexpr int kTargets = %d;\nconstexpr int kBasis = %d;\n"
                 "constexpr int kElim = kOthers + kTargets;\nconstexpr int kCols = kElim + kBasis;\n\n" % (len(rows), len(others), len(targets), len(B)))

@@ -5,7 +5,7 @@
 * Device five-point / P3P / SQPnP / 8-point / 4-point solvers against numpy (np.linalg.svd / eig / lstsq): solution
   sets, constraint residuals and recovery of the generating pose on thousands of random instances.  The numpy
   five-point solver below is derived here from the algebra (constraint polynomials fitted by interpolation, action
-  matrix of multiplication by x in the quotient ring), it shares no table with csrc/ransac_device.h or the oracle.
+  matrix of multiplication by x in the quotient ring), it shares no table with csrc/five_point_device.h or the oracle.
 * The reference's own test scenes through the GPU mirror with the reference's thresholds:
   estimate_relative_pose_test.cc:60-196, estimate_calibrated_absolute_pose_test.cc:60-215 (KNEIP and SQPnP),
   lmed_test.cc:108-140 (quality measure of the correct model: restated on the dominant-plane estimator, the line
