@@ -1638,6 +1638,19 @@ int theia_hip_selftest_five_point_pre_team(int32_t count, const double* corr, do
 int theia_hip_selftest_rotation_maps(int32_t count, const double* a, const double* b, double* out);
 int theia_hip_selftest_pairwise_rotation_error(int32_t count, const double* w_i, const double* w_j, const double* rel,
                                                double width, double* out);
+/* Self-check of the trust-region step rules of every Levenberg-Marquardt loop (csrc/lm_rules.h, played by
+ * csrc/selftest_lm_rules.hip): a script of 1 .. 16 records runs from a fresh state (radius 1e4, decrease factor 2) once in
+ * one device thread and once on the host; the tests compare both with a restatement of Ceres' rules.  No reference
+ * counterpart.  THEIA_HIP_ERR_INVALID_ARGUMENT for a count outside 1 .. 16 or a null pointer.
+ * records [count][4] = op | a | b | c with op 1: an invalid step; 2: an evaluated step, a = rho, b = max_radius (accepted
+ * iff rho > 1e-3, else rejected); 3: the rules before a step, a = gradient max norm, b = gradient_tolerance; 4: the
+ * parameter rule, step norm | x norm | tolerance; 5: the function rule, cost | candidate cost | tolerance; 6: the LM
+ * diagonal of a at radius b; 7: the Jacobi scale of the squared column norm a; 8, 9: the model cost change on 3 x 3, 6 x 6
+ * with packed H[k] = a + k, g[i] = b + i, y[i] = c - i.
+ * Output per record, 7 doubles: radius | decrease factor | invalid steps in a row | last step successful | the rule's
+ * decision (op 1: 0 = the fifth in a row, the solve fails) | the value (op 2: the radius had the cube been pow(t, 3)) |
+ * 1 when the radius floor 1e-32 is reached. */
+int theia_hip_selftest_lm_rules(int32_t count, const double* records, double* device_out, double* host_out);
 
 /* The batch entry points above keep their device workspace and the pinned host blocks of their per-round transfers in
  * process-wide caches between calls (up to 6 GiB of device memory and 2 GiB of pinned host memory); the buffers of a

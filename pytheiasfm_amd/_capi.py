@@ -378,7 +378,7 @@ EXPORTED_SYMBOLS = [
     "theia_hip_ransac_estimate_batch", "theia_hip_five_point_relative_pose",
     "theia_hip_pose_from_three_points", "theia_hip_sqpnp", "theia_hip_dls_pnp", "theia_hip_dls_macaulay_terms", "theia_hip_four_point_pose_and_focal_length", "theia_hip_four_point_focal_length_radial_distortion", "theia_hip_four_point_focal_length_radial_distortion_ex", "theia_hip_release_scratch", "theia_hip_guided_knn", "theia_hip_brute_force_options_default", "theia_hip_brute_force_knn2", "theia_hip_brute_force_match_pairs", "theia_hip_track_builder_options_default", "theia_hip_build_tracks", "theia_hip_track_builder_last_timings", "theia_hip_mean_pool_descriptors", "theia_hip_graph_match", "theia_hip_visibility_scores", "theia_hip_set_underconstrained_unestimated", "theia_hip_unproject", "theia_hip_randint_stream", "theia_hip_selftest_wave_primitives",
     "theia_hip_selftest_eig_team", "theia_hip_selftest_svd9_team", "theia_hip_selftest_five_point_pre_team",
-    "theia_hip_selftest_rotation_maps", "theia_hip_selftest_pairwise_rotation_error",
+    "theia_hip_selftest_rotation_maps", "theia_hip_selftest_pairwise_rotation_error", "theia_hip_selftest_lm_rules",
     "theia_hip_rng_seed", "theia_hip_rng_rand_int", "theia_hip_rng_rand_double", "theia_hip_rng_rand_gaussian", "theia_hip_rng_discard", "theia_hip_ransac_estimate_streams",
 ]
 
@@ -463,6 +463,7 @@ def lib():
     L.theia_hip_selftest_five_point_pre_team.argtypes = [C.c_int32, c_double_p, c_double_p, c_double_p]
     L.theia_hip_selftest_rotation_maps.argtypes = [C.c_int32, c_double_p, c_double_p, c_double_p]
     L.theia_hip_selftest_pairwise_rotation_error.argtypes = [C.c_int32, c_double_p, c_double_p, c_double_p, C.c_double, c_double_p]
+    L.theia_hip_selftest_lm_rules.argtypes = [C.c_int32, c_double_p, c_double_p, c_double_p]
     L.theia_hip_brute_force_options_default.argtypes = [C.POINTER(BruteForceOptions)]
     L.theia_hip_brute_force_options_default.restype = None
     L.theia_hip_brute_force_knn2.argtypes = [C.c_int32, C.c_int32, C.c_int32, c_float_p, c_float_p, c_float_p, c_int32_p, c_float_p, c_int32_p]

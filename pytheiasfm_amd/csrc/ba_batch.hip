@@ -14,6 +14,7 @@
 // (stride 64); the 6 x 6 normal equations are wave-reduced in a fixed order.
 #include "ba_device.h"
 #include "device_util.h"
+#include "lm_rules.h"
 
 #include <chrono>
 #include <cmath>
@@ -118,7 +119,7 @@ __device__ void view_linearize(const ViewBatch& B, int p, const double* ext, con
   *invalid = wsum(inv);
 }
 
-__device__ __forceinline__ int tri(int a, int b) { return a * (a + 1) / 2 + b; }
+using lm::tri;
 
 // (H + diag(d)) y = g by Cholesky; false if not positive definite
 __device__ bool solve6(const double* H, const double* d, const double* g, double* y) {
@@ -159,11 +160,11 @@ __global__ __launch_bounds__(256) void k_view_lm(ViewBatch B, BatchLmOut* __rest
   // Jacobi scaling from the column norms at the initial point (once per solve)
   view_linearize(B, p, x, scale, mask, lane, H, g, &x_cost, &invalid);
 #pragma unroll
-  for (int q = 0; q < 6; ++q) scale[q] = 1.0 / (1.0 + sqrt(H[tri(q, q)]));
+  for (int q = 0; q < 6; ++q) scale[q] = lm::jacobi_scale(H[tri(q, q)]);
   const bool all_const = (mask & 0x3fu) == 0x3fu;
-  double radius = 1e4, decrease_factor = 2.0;
-  bool step_successful = true, need_linearize = true;
-  int iter = 0, invalid_steps = 0, term = THEIA_TERM_NO_CONVERGENCE;
+  lm::TrustRegion tr;
+  bool need_linearize = true;
+  int iter = 0, term = THEIA_TERM_NO_CONVERGENCE;
   double x_norm = 0.0, minimum_cost = 0.0, gmax = 0.0;
 #pragma unroll
   for (int q = 0; q < 6; ++q) x_norm += x[q] * x[q];
@@ -185,22 +186,14 @@ __global__ __launch_bounds__(256) void k_view_lm(ViewBatch B, BatchLmOut* __rest
       if (all_const) { term = THEIA_TERM_CONVERGENCE; break; }
     }
     if (iter >= B.max_iterations) { term = THEIA_TERM_NO_CONVERGENCE; break; }
-    if (step_successful && gmax <= B.gradient_tolerance) { term = THEIA_TERM_CONVERGENCE; break; }
-    if (radius <= 1e-32) { term = THEIA_TERM_CONVERGENCE; break; }
+    if (lm::converged_before_step(tr, gmax, B.gradient_tolerance)) { term = THEIA_TERM_CONVERGENCE; break; }
     ++iter;
     double d[6], y[6];
 #pragma unroll
-    for (int q = 0; q < 6; ++q) d[q] = fmin(fmax(H[tri(q, q)], 1e-6), 1e32) / radius;
+    for (int q = 0; q < 6; ++q) d[q] = lm::lm_diagonal(H[tri(q, q)], tr.radius);
     const bool pd = solve6(H, d, g, y);
     // model cost change of the step -y:  y'g - y'Hy/2  (H without the LM diagonal)
-    double yg = 0.0, yHy = 0.0;
-    for (int a = 0; a < 6; ++a) {
-      yg += y[a] * g[a];
-      double row = 0.0;
-      for (int b = 0; b < 6; ++b) row += H[a >= b ? tri(a, b) : tri(b, a)] * y[b];
-      yHy += y[a] * row;
-    }
-    const double mcc = yg - 0.5 * yHy;
+    const double mcc = lm::model_cost_change<6>(H, g, y);
     double cand[6], stepsq = 0.0, xnormsq = 0.0;
 #pragma unroll
     for (int q = 0; q < 6; ++q) {
@@ -210,31 +203,28 @@ __global__ __launch_bounds__(256) void k_view_lm(ViewBatch B, BatchLmOut* __rest
     }
     const bool step_valid = pd && isfinite(mcc) && isfinite(stepsq) && mcc > 0.0;
     if (!step_valid) {
-      if (++invalid_steps >= 5) { term = THEIA_TERM_FAILURE; break; }
-      radius /= decrease_factor; decrease_factor *= 2.0; step_successful = false;
+      if (!lm::invalid_step(tr)) { term = THEIA_TERM_FAILURE; break; }
       continue;
     }
-    invalid_steps = 0;
+    lm::valid_step(tr);
     double cinv;
     double cand_cost = view_cost(B, p, cand, lane, &cinv);
     if (cinv > 0.0 || !isfinite(cand_cost)) cand_cost = DBL_MAX;
     const double step_norm = sqrt(stepsq);
-    if (step_norm <= B.parameter_tolerance * (x_norm + B.parameter_tolerance)) { term = THEIA_TERM_CONVERGENCE; break; }
+    if (lm::parameter_rule(step_norm, x_norm, B.parameter_tolerance)) { term = THEIA_TERM_CONVERGENCE; break; }
     const double cost_change = x_cost - cand_cost;
-    if (fabs(cost_change) <= B.function_tolerance * x_cost) { term = THEIA_TERM_CONVERGENCE; break; }
+    if (lm::function_rule(x_cost, cand_cost, B.function_tolerance)) { term = THEIA_TERM_CONVERGENCE; break; }
     const double rho = cost_change / mcc;
-    if (rho > 1e-3) {
+    if (lm::step_accepted(rho)) {
 #pragma unroll
       for (int q = 0; q < 6; ++q) x[q] = cand[q];
       x_norm = sqrt(xnormsq);
-      const double t = 2.0 * rho - 1.0;
-      radius = radius / fmax(1.0 / 3.0, 1.0 - t * t * t);
-      radius = fmin(B.max_radius, radius);
-      decrease_factor = 2.0; step_successful = true; need_linearize = true;
+      lm::accept(tr, rho, B.max_radius);
+      need_linearize = true;
       R.nsucc++;
       if (cand_cost < minimum_cost) minimum_cost = cand_cost;
     } else {
-      radius /= decrease_factor; decrease_factor *= 2.0; step_successful = false;
+      lm::shrink(tr);
     }
   }
   R.iters = iter; R.term = term; R.success = term != THEIA_TERM_FAILURE;
@@ -353,7 +343,9 @@ __global__ __launch_bounds__(64) void k_track_lm(TrackBatch B, BatchLmOut* __res
     out[p] = R;
     return;
   }
-  for (int q = 0; q < PD; ++q) scale[q] = 1.0 / (1.0 + sqrt(H[tri(q, q)]));
+  for (int q = 0; q < PD; ++q) scale[q] = lm::jacobi_scale(H[tri(q, q)]);
+  // The state and its updates stay written out here (lm_rules.h: shrink, invalid_step, accept, converged_before_step): with
+  // the state in a TrustRegion this kernel, which fills the register file, came out 12 / 20 registers larger
   double radius = 1e4, decrease_factor = 2.0;
   bool step_successful = true, need_linearize = true, first = true;
   int iter = 0, invalid_steps = 0, term = THEIA_TERM_NO_CONVERGENCE;
@@ -376,16 +368,9 @@ __global__ __launch_bounds__(64) void k_track_lm(TrackBatch B, BatchLmOut* __res
     if (radius <= 1e-32) { term = THEIA_TERM_CONVERGENCE; break; }
     ++iter;
     double d[PD], y[PD];
-    for (int q = 0; q < PD; ++q) d[q] = fmin(fmax(H[tri(q, q)], 1e-6), 1e32) / radius;
+    for (int q = 0; q < PD; ++q) d[q] = lm::lm_diagonal(H[tri(q, q)], radius);
     const bool pd = solve_small<PD>(H, d, g, y);
-    double yg = 0.0, yHy = 0.0;
-    for (int a = 0; a < PD; ++a) {
-      yg += y[a] * g[a];
-      double row = 0.0;
-      for (int b = 0; b < PD; ++b) row += H[a >= b ? tri(a, b) : tri(b, a)] * y[b];
-      yHy += y[a] * row;
-    }
-    const double mcc = yg - 0.5 * yHy;
+    const double mcc = lm::model_cost_change<PD>(H, g, y);
     double Xp[4] = {X[0], X[1], X[2], X[3]};
     if (PD == 3) {
       const double d3[3] = {-y[0] * scale[0], -y[1] * scale[1], -y[2] * scale[2]};
@@ -407,11 +392,11 @@ __global__ __launch_bounds__(64) void k_track_lm(TrackBatch B, BatchLmOut* __res
     track_linearize<PD>(B, p, Xp, scale, Hd, gd, &cand_cost, &cinv, false);
     if (cinv || !isfinite(cand_cost)) cand_cost = DBL_MAX;
     const double step_norm = sqrt(stepsq);
-    if (step_norm <= B.parameter_tolerance * (x_norm + B.parameter_tolerance)) { term = THEIA_TERM_CONVERGENCE; break; }
+    if (lm::parameter_rule(step_norm, x_norm, B.parameter_tolerance)) { term = THEIA_TERM_CONVERGENCE; break; }
     const double cost_change = x_cost - cand_cost;
-    if (fabs(cost_change) <= B.function_tolerance * x_cost) { term = THEIA_TERM_CONVERGENCE; break; }
+    if (lm::function_rule(x_cost, cand_cost, B.function_tolerance)) { term = THEIA_TERM_CONVERGENCE; break; }
     const double rho = cost_change / mcc;
-    if (rho > 1e-3) {
+    if (lm::step_accepted(rho)) {
       for (int q = 0; q < 4; ++q) X[q] = Xp[q];
       x_norm = sqrt(xnormsq);
       const double t = 2.0 * rho - 1.0;

@@ -27,6 +27,7 @@
 #include "ba_kernels.h"
 #include "ba_device.h"
 #include "ba_priors.h"
+#include "lm_rules.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -39,7 +40,7 @@ constexpr int kInnerMaxIterations = 50;              // Solver::Options defaults
 constexpr double kInnerFunctionTolerance = 1e-6, kInnerGradientTolerance = 1e-10, kInnerParameterTolerance = 1e-8;
 constexpr double kInnerMaxRadius = 1e16;
 
-__device__ __forceinline__ int itri(int a, int b) { return a * (a + 1) / 2 + b; }
+using lm::tri;
 
 // ------------------------------------------------------------------ team solves (cameras, shared intrinsics)
 // Round 5.  A block whose residuals are summed by a TEAM of threads (a workgroup per camera; up to 32 workgroups per intrinsics
@@ -64,7 +65,7 @@ __device__ __forceinline__ void team_lm_init(TeamLm<N>& S, const double* x0, uns
   S.base_normsq = base_normsq;
   for (int q = 0; q < N; ++q) { S.x[q] = x0[q]; S.xc[q] = x0[q]; S.scale[q] = 1.0; xn += x0[q] * x0[q]; }
   S.x_norm = sqrt(xn);
-  S.radius = 1e4; S.decrease_factor = 2.0; S.iter = 0; S.invalid_steps = 0; S.step_successful = 1; S.first = 1;
+  lm::start(S); S.iter = 0; S.first = 1;
   S.phase = TL_LIN; S.frozen = (int)frozen; S.x_cost = 0.0; S.gmax = 0.0;
 }
 // (H + D) y = g on the LDS arrays; false if not positive definite
@@ -72,20 +73,20 @@ template <int N>
 __device__ __forceinline__ bool team_lm_solve(TeamLm<N>& S) {
   for (int i = 0; i < N; ++i)
     for (int j = 0; j <= i; ++j) {
-      double s = S.H[itri(i, j)] + (i == j ? fmin(fmax(S.H[itri(i, i)], 1e-6), 1e32) / S.radius : 0.0);
-      for (int k = 0; k < j; ++k) s -= S.L[itri(i, k)] * S.L[itri(j, k)];
-      if (i == j) { if (!(s > 0.0)) return false; S.L[itri(i, i)] = sqrt(s); }
-      else S.L[itri(i, j)] = s / S.L[itri(j, j)];
+      double s = S.H[tri(i, j)] + (i == j ? lm::lm_diagonal(S.H[tri(i, i)], S.radius) : 0.0);
+      for (int k = 0; k < j; ++k) s -= S.L[tri(i, k)] * S.L[tri(j, k)];
+      if (i == j) { if (!(s > 0.0)) return false; S.L[tri(i, i)] = sqrt(s); }
+      else S.L[tri(i, j)] = s / S.L[tri(j, j)];
     }
   for (int i = 0; i < N; ++i) {
     double s = S.g[i];
-    for (int k = 0; k < i; ++k) s -= S.L[itri(i, k)] * S.z[k];
-    S.z[i] = s / S.L[itri(i, i)];
+    for (int k = 0; k < i; ++k) s -= S.L[tri(i, k)] * S.z[k];
+    S.z[i] = s / S.L[tri(i, i)];
   }
   for (int i = N - 1; i >= 0; --i) {
     double s = S.z[i];
-    for (int k = i + 1; k < N; ++k) s -= S.L[itri(k, i)] * S.y[k];
-    S.y[i] = s / S.L[itri(i, i)];
+    for (int k = i + 1; k < N; ++k) s -= S.L[tri(k, i)] * S.y[k];
+    S.y[i] = s / S.L[tri(i, i)];
   }
   return true;
 }
@@ -97,45 +98,45 @@ __device__ __forceinline__ void team_lm_advance(TeamLm<N>& S, const double* tot)
     if (S.first) {
       S.first = 0;
       if (tot[NT + N + 1] > 0.0 || !isfinite(tot[NT + N])) { S.phase = TL_DONE; return; }   // failure: the parameters stay as they are
-      for (int q = 0; q < N; ++q) S.scale[q] = 1.0 / (1.0 + sqrt(tot[itri(q, q)]));
+      for (int q = 0; q < N; ++q) S.scale[q] = lm::jacobi_scale(tot[tri(q, q)]);
     }
     for (int a = 0; a < N; ++a) {
-      for (int b = 0; b <= a; ++b) S.H[itri(a, b)] = tot[itri(a, b)] * S.scale[a] * S.scale[b];
+      for (int b = 0; b <= a; ++b) S.H[tri(a, b)] = tot[tri(a, b)] * S.scale[a] * S.scale[b];
       S.g[a] = tot[NT + a] * S.scale[a];
     }
     S.x_cost = tot[NT + N];
     S.gmax = 0.0;
     for (int q = 0; q < N; ++q) S.gmax = fmax(S.gmax, fabs(S.g[q] / S.scale[q]));
   } else {   // the candidate's cost
-    S.invalid_steps = 0;
+    lm::valid_step(S);
     double cand_cost = tot[NT + N];
     if (tot[NT + N + 1] > 0.0 || !isfinite(cand_cost)) cand_cost = DBL_MAX;
-    if (sqrt(S.stepsq) <= kInnerParameterTolerance * (S.x_norm + kInnerParameterTolerance)) { S.phase = TL_DONE; return; }
+    if (lm::parameter_rule(sqrt(S.stepsq), S.x_norm, kInnerParameterTolerance)) { S.phase = TL_DONE; return; }
     const double cost_change = S.x_cost - cand_cost;
-    if (fabs(cost_change) <= kInnerFunctionTolerance * S.x_cost) { S.phase = TL_DONE; return; }
+    if (lm::function_rule(S.x_cost, cand_cost, kInnerFunctionTolerance)) { S.phase = TL_DONE; return; }
     const double rho = cost_change / S.mcc;
-    if (rho > 1e-3) {
+    if (lm::step_accepted(rho)) {
       for (int q = 0; q < N; ++q) S.x[q] = S.xc[q];
       S.x_norm = sqrt(S.xnormsq);
-      const double t = 2.0 * rho - 1.0;
-      S.radius = fmin(kInnerMaxRadius, S.radius / fmax(1.0 / 3.0, 1.0 - t * t * t));
-      S.decrease_factor = 2.0; S.step_successful = 1;
+      lm::accept(S, rho, kInnerMaxRadius);
       S.phase = TL_LIN;   // re-linearise at the new point, then try a step from there
       return;
     }
-    S.radius /= S.decrease_factor; S.decrease_factor *= 2.0; S.step_successful = 0;
+    lm::shrink(S);
   }
   // try steps until one needs its cost (or the solve ends)
   while (true) {
-    if (S.iter >= kInnerMaxIterations || (S.step_successful && S.gmax <= kInnerGradientTolerance) || S.radius <= 1e-32) { S.phase = TL_DONE; return; }
+    if (S.iter >= kInnerMaxIterations || lm::converged_before_step(S, S.gmax, kInnerGradientTolerance)) { S.phase = TL_DONE; return; }
     ++S.iter;
     const bool pd = team_lm_solve<N>(S);
+    // (lm::model_cost_change, written out: it is skipped when the factorisation failed and y was not written, and through
+    // the call k_inner_groups<.., 10> came out 4 registers larger)
     double yg = 0.0, yHy = 0.0;
     if (pd)
       for (int a = 0; a < N; ++a) {
         yg += S.y[a] * S.g[a];
         double row = 0.0;
-        for (int b = 0; b < N; ++b) row += S.H[a >= b ? itri(a, b) : itri(b, a)] * S.y[b];
+        for (int b = 0; b < N; ++b) row += S.H[a >= b ? tri(a, b) : tri(b, a)] * S.y[b];
         yHy += S.y[a] * row;
       }
     S.mcc = yg - 0.5 * yHy;
@@ -148,8 +149,7 @@ __device__ __forceinline__ void team_lm_advance(TeamLm<N>& S, const double* tot)
     }
     S.stepsq = stepsq; S.xnormsq = xnormsq;
     if (pd && isfinite(S.mcc) && isfinite(stepsq) && S.mcc > 0.0) { S.phase = TL_COST; return; }
-    if (++S.invalid_steps >= 5) { S.phase = TL_DONE; return; }
-    S.radius /= S.decrease_factor; S.decrease_factor *= 2.0; S.step_successful = 0;
+    if (!lm::invalid_step(S)) { S.phase = TL_DONE; return; }
   }
 }
 
@@ -601,6 +601,8 @@ __device__ __forceinline__ void pt_block_lm(double (&x)[4], bool live, SumJ&& su
 #pragma unroll
   for (int q = 0; q < PD; ++q) scale[q] = 1.0;
   double x_cost = 0.0, gmax = 0.0;
+  // The state and its updates stay written out here (lm_rules.h: shrink, invalid_step, accept, converged_before_step): with
+  // the state in a TrustRegion the k_inner_tracks instances came out up to 22 registers larger
   double radius = 1e4, decrease_factor = 2.0, x_norm = sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2] + x[3] * x[3]);
   bool step_successful = true;
   int iter = 0, invalid_steps = 0;
@@ -610,7 +612,7 @@ __device__ __forceinline__ void pt_block_lm(double (&x)[4], bool live, SumJ&& su
       if (first) {
         if (tot[NT + PD + 1] > 0.0 || !isfinite(tot[NT + PD])) done = true;   // failure: the parameters stay as they are
 #pragma unroll
-        for (int q = 0; q < PD; ++q) scale[q] = 1.0 / (1.0 + sqrt(tot[q * (q + 1) / 2 + q]));
+        for (int q = 0; q < PD; ++q) scale[q] = lm::jacobi_scale(tot[tri(q, q)]);
         first = false;
       }
       if (relin) {
@@ -632,18 +634,9 @@ __device__ __forceinline__ void pt_block_lm(double (&x)[4], bool live, SumJ&& su
     ++iter;
     double d[PD], y[PD];
 #pragma unroll
-    for (int q = 0; q < PD; ++q) d[q] = fmin(fmax(H[q * (q + 1) / 2 + q], 1e-6), 1e32) / radius;
+    for (int q = 0; q < PD; ++q) d[q] = lm::lm_diagonal(H[tri(q, q)], radius);
     const bool pd = pt_chol_solve<PD>(H, d, g, y);
-    double yg = 0.0, yHy = 0.0;
-#pragma unroll
-    for (int a = 0; a < PD; ++a) {
-      yg += y[a] * g[a];
-      double row = 0.0;
-#pragma unroll
-      for (int b = 0; b < PD; ++b) row += H[a >= b ? a * (a + 1) / 2 + b : b * (b + 1) / 2 + a] * y[b];
-      yHy += y[a] * row;
-    }
-    const double mcc = yg - 0.5 * yHy;
+    const double mcc = lm::model_cost_change<PD>(H, g, y);
     double xc[4], stepsq = 0.0, xnormsq = 0.0;
     {
       double step[PD];
@@ -674,11 +667,11 @@ __device__ __forceinline__ void pt_block_lm(double (&x)[4], bool live, SumJ&& su
       double cand_cost = ct[0];
       if (ct[1] > 0.0 || !isfinite(cand_cost)) cand_cost = DBL_MAX;
       const double cost_change = x_cost - cand_cost;
-      if (sqrt(stepsq) <= kInnerParameterTolerance * (x_norm + kInnerParameterTolerance)) done = true;
-      else if (fabs(cost_change) <= kInnerFunctionTolerance * x_cost) done = true;
+      if (lm::parameter_rule(sqrt(stepsq), x_norm, kInnerParameterTolerance)) done = true;
+      else if (lm::function_rule(x_cost, cand_cost, kInnerFunctionTolerance)) done = true;
       else {
         const double rho = cost_change / mcc;
-        if (rho > 1e-3) {
+        if (lm::step_accepted(rho)) {
 #pragma unroll
           for (int q = 0; q < 4; ++q) x[q] = xc[q];
           x_norm = sqrt(xnormsq);

@@ -33,6 +33,7 @@
 #include "ba_host_rules.h"
 #include "theia_hip.h"
 #include "device_util.h"
+#include "lm_rules.h"
 
 namespace thip {
 namespace {
@@ -270,7 +271,7 @@ __global__ __launch_bounds__(64) void k_id_track(IdProblem P, const double* __re
   const bool pconst = P.pt_const[p] != 0;
   double vi = 0.0;        // a constant track keeps the direct terms only
   if (!pconst) {
-    const double d = fmin(fmax(v, 1e-6), 1e32) / *radius_p;
+    const double d = lm::lm_diagonal(v, *radius_p);
     vi = 1.0 / (v + d);
     if (ln == 0) { vinv[p] = vi; grho[p] = g; atomic_max_nonneg(&scal[ID_GMAX], fabs(g / P.scale_r[p])); }
   }
@@ -369,7 +370,7 @@ __global__ void k_id_finalize(int n, const double* __restrict__ radius_p, double
                               const double* __restrict__ gc, const double* __restrict__ scale_red, double* __restrict__ scal) {
   double gmax = 0.0;
   for (int d = threadIdx.x; d < n; d += blockDim.x) {
-    S[(size_t)d * n + d] += fmin(fmax(colsq[d], 1e-6), 1e32) / *radius_p;
+    S[(size_t)d * n + d] += lm::lm_diagonal(colsq[d], *radius_p);
     gmax = fmax(gmax, fabs(gc[d] / scale_red[d]));
   }
   atomic_max_nonneg(&scal[ID_GMAX], gmax);
@@ -469,7 +470,7 @@ __global__ __launch_bounds__(64) void k_id_back(IdProblem P, const double* __res
 
 __global__ void k_id_make_scale(int count, const double* __restrict__ colsq, double* __restrict__ scale) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < count) scale[i] = 1.0 / (1.0 + sqrt(colsq[i]));
+  if (i < count) scale[i] = lm::jacobi_scale(colsq[i]);
 }
 __global__ void k_id_scale_red(IdProblem P, double* __restrict__ scale_red) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -742,9 +743,10 @@ int IdHandle::run(const theia_ba_options* o, theia_ba_summary* S) {
     *out = std::sqrt(hs[0]);
     return 0;
   };
-  double radius = 1e4, decrease_factor = 2.0, x_cost = 0.0, gmax = 0.0, x_norm = 0.0, fixed_cost = 0.0;
-  auto linearize = [&]() -> int {   // records, reduced system with the damping of `radius`, gradient max
-    HIP_TRYR(hipMemcpyAsync(d_radius.p, &radius, sizeof(double), hipMemcpyHostToDevice, st));
+  lm::TrustRegion tr;
+  double x_cost = 0.0, gmax = 0.0, x_norm = 0.0, fixed_cost = 0.0;
+  auto linearize = [&]() -> int {   // records, reduced system with the damping of `tr.radius`, gradient max
+    HIP_TRYR(hipMemcpyAsync(d_radius.p, &tr.radius, sizeof(double), hipMemcpyHostToDevice, st));
     // only the tiles the plan's assembly and factorisation touch are cleared (the whole n x n buffer with the dense plan)
     if (!(n > 0 && chol_plan_clear(plan, dS, n, st, drhs, 3 * (size_t)n)))
       HIP_TRYR(hipMemsetAsync(d_red.p, 0, sizeof(double) * std::max<size_t>(1, red_count), st));
@@ -764,16 +766,14 @@ int IdHandle::run(const theia_ba_options* o, theia_ba_summary* S) {
   S->initial_cost = x_cost + fixed_cost;
   if (hs[ID_INVALID] > 0.0 || !std::isfinite(x_cost)) { S->termination_type = THEIA_TERM_FAILURE; S->final_cost = x_cost + fixed_cost; return 0; }
   double minimum_cost = x_cost;
-  bool step_successful = true;
-  int iter = 0, invalid_steps = 0, term = THEIA_TERM_NO_CONVERGENCE;
-  trace_push(S, x_cost + fixed_cost, gmax, 0.0, radius, 1);
+  int iter = 0, term = THEIA_TERM_NO_CONVERGENCE;
+  trace_push(S, x_cost + fixed_cost, gmax, 0.0, tr.radius, 1);
   bool fresh = true;   // the reduced system in d_red belongs to the current radius
   while (true) {
     const double elapsed = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
     if (elapsed >= o->max_solver_time_in_seconds && iter > 0) { term = THEIA_TERM_NO_CONVERGENCE; break; }
     if (iter >= o->max_num_iterations) { term = THEIA_TERM_NO_CONVERGENCE; break; }
-    if (step_successful && gmax <= o->gradient_tolerance) { term = THEIA_TERM_CONVERGENCE; break; }
-    if (radius <= 1e-32) { term = THEIA_TERM_CONVERGENCE; break; }
+    if (lm::converged_before_step(tr, gmax, o->gradient_tolerance)) { term = THEIA_TERM_CONVERGENCE; break; }
     ++iter;
     if (!fresh && (rc = linearize())) return rc;   // same point, new radius: the damping sits inside the Schur complement
     fresh = false;
@@ -788,33 +788,31 @@ int IdHandle::run(const theia_ba_options* o, theia_ba_summary* S) {
     const double mcc = hs[ID_MCC], stepsq = hs[ID_STEPSQ], xnormsq = hs[ID_XNORMSQ];
     const bool solved = hs[ID_NOTPD] == 0.0 && std::isfinite(mcc) && std::isfinite(stepsq);
     if (!(solved && mcc > 0.0)) {
-      if (++invalid_steps >= 5) { term = THEIA_TERM_FAILURE; break; }
-      radius /= decrease_factor; decrease_factor *= 2.0; step_successful = false;
-      trace_push(S, x_cost + fixed_cost, gmax, 0.0, radius, 0);
+      if (!lm::invalid_step(tr)) { term = THEIA_TERM_FAILURE; break; }
+      trace_push(S, x_cost + fixed_cost, gmax, 0.0, tr.radius, 0);
       continue;
     }
-    invalid_steps = 0;
+    lm::valid_step(tr);
     double cand_cost; bool cok;
     if ((rc = cost_at(d_cam[nxt].p, d_rho[nxt].p, d_intr[nxt].p, &cand_cost, &cok))) return rc;
     if (!cok) cand_cost = std::numeric_limits<double>::max();
     const double step_norm = std::sqrt(stepsq);
-    if (step_norm <= o->parameter_tolerance * (x_norm + o->parameter_tolerance)) { trace_push(S, cand_cost + fixed_cost, gmax, step_norm, radius, 0); term = THEIA_TERM_CONVERGENCE; break; }
+    if (lm::parameter_rule(step_norm, x_norm, o->parameter_tolerance)) { trace_push(S, cand_cost + fixed_cost, gmax, step_norm, tr.radius, 0); term = THEIA_TERM_CONVERGENCE; break; }
     const double cost_change = x_cost - cand_cost;
-    if (std::fabs(cost_change) <= o->function_tolerance * x_cost) { trace_push(S, cand_cost + fixed_cost, gmax, step_norm, radius, 0); term = THEIA_TERM_CONVERGENCE; break; }
+    if (lm::function_rule(x_cost, cand_cost, o->function_tolerance)) { trace_push(S, cand_cost + fixed_cost, gmax, step_norm, tr.radius, 0); term = THEIA_TERM_CONVERGENCE; break; }
     const double rho_q = cost_change / mcc;
-    if (rho_q > 1e-3) {
+    if (lm::step_accepted(rho_q)) {
       cur = nxt;
       x_norm = std::sqrt(xnormsq);
-      radius = std::min(o->max_trust_region_radius, radius / std::max(1.0 / 3.0, 1.0 - std::pow(2.0 * rho_q - 1.0, 3)));
-      decrease_factor = 2.0; step_successful = true;
+      lm::accept<true>(tr, rho_q, o->max_trust_region_radius);   // pow, as the oracle
       S->num_successful_steps++;
       if ((rc = linearize())) return rc;
       fresh = true;
       if (x_cost < minimum_cost) minimum_cost = x_cost;
-      trace_push(S, x_cost + fixed_cost, gmax, step_norm, radius, 1);
+      trace_push(S, x_cost + fixed_cost, gmax, step_norm, tr.radius, 1);
     } else {
-      radius /= decrease_factor; decrease_factor *= 2.0; step_successful = false;
-      trace_push(S, cand_cost + fixed_cost, gmax, step_norm, radius, 0);
+      lm::shrink(tr);
+      trace_push(S, cand_cost + fixed_cost, gmax, step_norm, tr.radius, 0);
     }
   }
   S->num_iterations = iter; S->termination_type = term; S->success = term != THEIA_TERM_FAILURE;

@@ -17,6 +17,9 @@
 
 #include "ba_handle.h"
 #include "ba_host_rules.h"
+#include "lm_rules.h"
+
+namespace lm = thip::lm;
 
 namespace {
 
@@ -51,19 +54,17 @@ __device__ void lm_control_body(LmState* st, const double* sa, const double* __r
     lm_trace(st, c, x_cost + c.fixed_cost, gmax, 0.0, st->radius, 1);
   }
   if (st->iter >= c.max_iterations) { st->term = THEIA_TERM_NO_CONVERGENCE; st->done = 1; return; }
-  if (st->step_successful && gmax <= c.gradient_tolerance) { st->term = THEIA_TERM_CONVERGENCE; st->done = 1; return; }
-  if (st->radius <= 1e-32) { st->term = THEIA_TERM_CONVERGENCE; st->done = 1; return; }
+  if (lm::converged_before_step(*st, gmax, c.gradient_tolerance)) { st->term = THEIA_TERM_CONVERGENCE; st->done = 1; return; }
   st->iter++;
   double mcc = sb[SB_MCC];
   double stepsq = sb[SB_STEPSQ] + sb[SB_STEPSQ_CAM];
   const bool solved = sa[SC_NOTPD] == 0.0 && isfinite(mcc) && isfinite(stepsq);
   if (!(solved && mcc > 0.0)) {
-    if (++st->invalid_steps >= 5) { st->term = THEIA_TERM_FAILURE; st->done = 1; return; }
-    st->radius /= st->decrease_factor; st->decrease_factor *= 2.0; st->step_successful = 0;
+    if (!lm::invalid_step(*st)) { st->term = THEIA_TERM_FAILURE; st->done = 1; return; }
     lm_trace(st, c, x_cost + c.fixed_cost, gmax, 0.0, st->radius, 0);
     return;
   }
-  st->invalid_steps = 0;
+  lm::valid_step(*st);
   double cand_cost = sb[SB_COST];
   if (sb[SB_INVALID] > 0.0 || !isfinite(cand_cost)) cand_cost = DBL_MAX;
   // TrustRegionMinimizer::DoInnerIterationsIfNeeded: the sweep ran on a copy of the candidate (k_inner_gate said so
@@ -82,28 +83,26 @@ __device__ void lm_control_body(LmState* st, const double* sa, const double* __r
     }
   }
   const double step_norm = sqrt(stepsq);
-  if (step_norm <= c.parameter_tolerance * (st->x_norm + c.parameter_tolerance)) {
+  if (lm::parameter_rule(step_norm, st->x_norm, c.parameter_tolerance)) {
     lm_trace(st, c, cand_cost + c.fixed_cost, gmax, step_norm, st->radius, 0);
     st->term = THEIA_TERM_CONVERGENCE; st->done = 1; return;
   }
   const double cost_change = x_cost - cand_cost;
-  if (fabs(cost_change) <= c.function_tolerance * x_cost) {
+  if (lm::function_rule(x_cost, cand_cost, c.function_tolerance)) {
     lm_trace(st, c, cand_cost + c.fixed_cost, gmax, step_norm, st->radius, 0);
     st->term = THEIA_TERM_CONVERGENCE; st->done = 1; return;
   }
   const double rho = cost_change / mcc;
-  if (inner_useful || rho > 1e-3) {   // IsStepSuccessful
+  if (inner_useful || lm::step_accepted(rho)) {   // IsStepSuccessful
     st->accepted = 1;   // k_lm_accept copies the candidate buffers over the state (or k_reduce_control makes the buffers change roles)
     st->x_norm = sqrt(xnormsq);
-    st->radius = st->radius / fmax(1.0 / 3.0, 1.0 - pow(2.0 * rho - 1.0, 3));
-    st->radius = fmin(c.max_radius, st->radius);
-    st->decrease_factor = 2.0; st->step_successful = 1;
+    lm::accept<true>(*st, rho, c.max_radius);   // pow, as the oracle
     st->num_successful++;
     if (cand_cost < st->minimum_cost) st->minimum_cost = cand_cost;
     if (c.th && st->trace_size < c.trace_capacity) st->pending_grad = st->trace_size;
     lm_trace(st, c, cand_cost + c.fixed_cost, -1.0, step_norm, st->radius, 1);
   } else {
-    st->radius /= st->decrease_factor; st->decrease_factor *= 2.0; st->step_successful = 0;
+    lm::shrink(*st);
     lm_trace(st, c, cand_cost + c.fixed_cost, gmax, step_norm, st->radius, 0);
   }
   // the iteration cap is known now: no further pass is needed to detect it
@@ -925,7 +924,7 @@ int theia_hip_ba_run(theia_ba_handle h, theia_ba_summary* S) {
   // device-resident LM state, control block and trace
   LmState st;
   std::memset(&st, 0, sizeof(st));
-  st.radius = 1e4; st.decrease_factor = 2.0; st.step_successful = 1; st.first = 1;
+  lm::start(st); st.first = 1;
   st.term = THEIA_TERM_NO_CONVERGENCE; st.pending_grad = -1;
   // inner iterations need every residual block of a camera on this rank: a sharded solve that asks for them (the
   // reference's default, bundle_adjustment.h:144) is refused instead of silently walking another trajectory

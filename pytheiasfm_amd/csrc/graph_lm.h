@@ -14,6 +14,7 @@
 // fixed order.
 #pragma once
 #include "dense_cholesky.h"
+#include "lm_rules.h"
 #include "view_graph_device.h"
 
 #include <algorithm>
@@ -32,11 +33,11 @@ constexpr int kMaxChunk = 64;
 
 struct NlState {
   int done, term, iterations, successful, unsuccessful, invalid;
-  int invalid_run;       // consecutive invalid steps
+  int invalid_steps;     // consecutive invalid steps
   int step_successful;   // the last step was accepted (the gradient rule applies after successful steps only)
   int fresh;             // the iterate changed: k_linearise / k_gradient run, k_post takes the new gradient
   int trace_rows, pad0, pad1;
-  double cost, initial_cost, gmax, x_norm, radius, decrease;
+  double cost, initial_cost, gmax, x_norm, radius, decrease_factor;   // (with the two ints above: the state of lm_rules.h)
 };
 
 // The first linearisation ran with scale = 1; one wavefront per free view sums the squares of its three columns over its
@@ -54,7 +55,7 @@ __global__ __launch_bounds__(kThreads) void k_column_norms(ViewGraphLists vg, co
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     const double t = wave_sum_butterfly(s[c]);
-    if (lane == 0) scale[3 * (size_t)v + c] = 1.0 / (1.0 + sqrt(t));
+    if (lane == 0) scale[3 * (size_t)v + c] = lm::jacobi_scale(t);
   }
 }
 
@@ -151,12 +152,12 @@ __global__ __launch_bounds__(kThreads) void k_post(int init, int m, const int* _
     }
     st->fresh = 0;
   }
-  const bool grad = st->step_successful && st->gmax <= gradient_tolerance;
+  const bool grad = st->step_successful && st->gmax <= gradient_tolerance;   // lm::gradient_rule, written out (2 registers)
   const bool cap = st->iterations >= max_iterations;
   if (init && grad) { st->done = 1; st->term = term_gradient; }
   else if (cap) { st->done = 1; st->term = term_cap; }
   else if (grad) { st->done = 1; st->term = term_gradient; }
-  else if (st->radius <= 1e-32) { st->done = 1; st->term = term_radius; }
+  else if (lm::radius_floor(*st)) { st->done = 1; st->term = term_radius; }
 }
 
 // The lower triangle of Js'Js + D into the cleared array (row-major, leading dimension lda), D = clamp(diag(Js'Js), 1e-6,
@@ -183,7 +184,7 @@ __global__ __launch_bounds__(kThreads) void k_assemble(ViewGraphLists vg, int ld
 #pragma unroll
       for (int c = 0; c < r; ++c) A[(size_t)(3 * t + r) * lda + 3 * t + c] = acc[3 * r + c];
       const double d = acc[4 * r];
-      A[(size_t)(3 * t + r) * lda + 3 * t + r] = d + fmin(fmax(d, 1e-6), 1e32) / radius;
+      A[(size_t)(3 * t + r) * lda + 3 * t + r] = d + lm::lm_diagonal(d, radius);
       A[(size_t)(3 * m) * lda + 3 * t + r] = g[3 * (size_t)t + r];
     }
   } else if (t < m + vg.P) {
@@ -260,37 +261,34 @@ __global__ __launch_bounds__(kThreads) void k_decide(DecideArgs a, const double*
     const bool ok = failed == 0.0 && isfinite(step_sq) && isfinite(model) && model > 0.0;
     if (!ok) {
       st->invalid += 1;
-      st->invalid_run += 1;
-      if (st->invalid_run >= 5) {
+      if (!lm::invalid_step(*st)) {
         st->done = 1; st->term = a.term_failure;
       } else {
-        st->radius /= st->decrease; st->decrease *= 2.0; st->step_successful = 0;
         trace_row(trace, a.capacity_rows, st, st->cost, st->gmax, 0.0, st->radius, 0);
       }
     } else {
-      st->invalid_run = 0;
+      lm::valid_step(*st);
       double cand = 0.5 * sum[0];
       if (!isfinite(cand)) cand = DBL_MAX;
       const double step_norm = sqrt(step_sq);
       const double change = st->cost - cand;
-      if (step_norm <= a.parameter_tolerance * (st->x_norm + a.parameter_tolerance)) {
+      if (lm::parameter_rule(step_norm, st->x_norm, a.parameter_tolerance)) {
         trace_row(trace, a.capacity_rows, st, cand, st->gmax, step_norm, st->radius, 0);
         st->done = 1; st->term = a.term_parameter;
-      } else if (fabs(change) <= a.function_tolerance * st->cost) {
+      } else if (lm::function_rule(st->cost, cand, a.function_tolerance)) {
         trace_row(trace, a.capacity_rows, st, cand, st->gmax, step_norm, st->radius, 0);
         st->done = 1; st->term = a.term_function;
       } else {
         const double rho = change / model;
-        if (rho > 1e-3) {
-          const double w = 2.0 * rho - 1.0;
+        if (lm::step_accepted(rho)) {
           st->cost = cand;
           st->x_norm = sqrt(sum[3]);
-          st->radius = fmin(a.max_radius, st->radius / fmax(1.0 / 3.0, 1.0 - w * w * w));
-          st->decrease = 2.0; st->step_successful = 1; st->successful += 1; st->fresh = 1;
+          lm::accept(*st, rho, a.max_radius);
+          st->successful += 1; st->fresh = 1;
           trace_row(trace, a.capacity_rows, st, cand, st->gmax, step_norm, st->radius, 1);   // k_post: the new gradient
           flags[1] = 1;
         } else {
-          st->radius /= st->decrease; st->decrease *= 2.0; st->step_successful = 0; st->unsuccessful += 1;
+          lm::shrink(*st); st->unsuccessful += 1;
           trace_row(trace, a.capacity_rows, st, cand, st->gmax, step_norm, st->radius, 0);
         }
       }

@@ -304,7 +304,7 @@ extern "C" int theia_hip_nonlinear_positions(int32_t num_views, const double* or
   const ViewGraphLists& vg = dg.lists;
 
   NlState hs{};
-  hs.radius = 1e4; hs.decrease = 2.0; hs.fresh = 1; hs.step_successful = 1;
+  lm::start(hs); hs.fresh = 1;
   HIP_TRY(hipMemcpy(d_st.p, &hs, sizeof(NlState), hipMemcpyHostToDevice));
   HIP_TRY(hipMemsetAsync(A.flag(), 0, sizeof(double), st));
   HIP_TRY(hipMemsetAsync(d_rec.p, 0, sizeof(double) * kRec * (size_t)E, st));

@@ -16,6 +16,7 @@
 #include "ba_device.h"
 #include "wave_reduce.h"
 #include "device_util.h"
+#include "lm_rules.h"
 
 #include <chrono>
 #include <cmath>
@@ -55,7 +56,7 @@ __device__ __forceinline__ int intrinsics_count(int model) {   // kIntrinsicsSiz
   const int K[8] = {7, 10, 9, 5, 5, 7, 7, 7};
   return (model >= 0 && model < 8) ? K[model] : 0;
 }
-__device__ __forceinline__ int tri(int a, int b) { return a * (a + 1) / 2 + b; }   // a >= b
+using lm::tri;   // a >= b
 
 // Everything one point contributes at a linearisation point.
 struct PointLin {
@@ -229,15 +230,15 @@ __global__ __launch_bounds__(64) void k_two_view_ba(TvBatch B, TvOut* __restrict
         for (int q = 0; q < 4; ++q) pn[q] += L.E[k][q] * L.E[k][q];
         for (int q = 0; q < NC; ++q) cn[q] += L.F[k][q] * L.F[k][q];
       }
-      B.sp[o0 + i] = make_double4(1.0 / (1.0 + sqrt(pn[0])), 1.0 / (1.0 + sqrt(pn[1])), 1.0 / (1.0 + sqrt(pn[2])), 1.0 / (1.0 + sqrt(pn[3])));
+      B.sp[o0 + i] = make_double4(lm::jacobi_scale(pn[0]), lm::jacobi_scale(pn[1]), lm::jacobi_scale(pn[2]), lm::jacobi_scale(pn[3]));
     }
-    for (int q = 0; q < NC; ++q) { cn[q] = wsum(cn[q]); sc[q] = ((frozen >> q) & 1u) ? 0.0 : 1.0 / (1.0 + sqrt(cn[q])); }
+    for (int q = 0; q < NC; ++q) { cn[q] = wsum(cn[q]); sc[q] = ((frozen >> q) & 1u) ? 0.0 : lm::jacobi_scale(cn[q]); }
   }
 
   double H[36], g[NC], x_cost = 0.0, gmax = 0.0;
-  double radius = 1e4, decrease_factor = 2.0;
-  bool step_successful = true, need_linearize = true, first = true;
-  int iter = 0, invalid_steps = 0, term = THEIA_TERM_NO_CONVERGENCE;
+  lm::TrustRegion tr;
+  bool need_linearize = true, first = true;
+  int iter = 0, term = THEIA_TERM_NO_CONVERGENCE;
   double minimum_cost = 0.0, invalid = 0.0;
 
   // |x| over the variable blocks: camera 2, the intrinsics blocks with a free focal length (whole block), the points
@@ -288,8 +289,7 @@ __global__ __launch_bounds__(64) void k_two_view_ba(TvBatch B, TvOut* __restrict
       if (invalid > 0.0 || !isfinite(x_cost)) { term = THEIA_TERM_FAILURE; R.final_cost = x_cost; break; }
     }
     if (iter >= B.max_iterations) { term = THEIA_TERM_NO_CONVERGENCE; break; }
-    if (step_successful && gmax <= B.gradient_tolerance) { term = THEIA_TERM_CONVERGENCE; break; }
-    if (radius <= 1e-32) { term = THEIA_TERM_CONVERGENCE; break; }
+    if (lm::converged_before_step(tr, gmax, B.gradient_tolerance)) { term = THEIA_TERM_CONVERGENCE; break; }
     ++iter;
     // ---- reduced camera system at this radius
     double hl[36], rl[NC], cd[NC], npd = 0.0;
@@ -304,7 +304,7 @@ __global__ __launch_bounds__(64) void k_two_view_ba(TvBatch B, TvOut* __restrict
       point_ne(L, N);
       double Vd[10], Vi[10];
       for (int k = 0; k < 10; ++k) Vd[k] = N.V[k];
-      for (int a = 0; a < 4; ++a) Vd[tri(a, a)] += fmin(fmax(N.V[tri(a, a)], 1e-6), 1e32) / radius;
+      for (int a = 0; a < 4; ++a) Vd[tri(a, a)] += lm::lm_diagonal(N.V[tri(a, a)], tr.radius);
       if (!inv4(Vd, Vi)) { npd += 1.0; for (int k = 0; k < 10; ++k) Vi[k] = 0.0; }
       double T[4][NC];   // Vinv W
       for (int a = 0; a < 4; ++a)
@@ -329,7 +329,7 @@ __global__ __launch_bounds__(64) void k_two_view_ba(TvBatch B, TvOut* __restrict
     }
     double rhs[NC], d[NC];
     for (int k = 0; k < 36; ++k) H[k] = wsum(hl[k]);
-    for (int q = 0; q < NC; ++q) { rhs[q] = wsum(rl[q]); d[q] = fmin(fmax(wsum(cd[q]), 1e-6), 1e32) / radius; }
+    for (int q = 0; q < NC; ++q) { rhs[q] = wsum(rl[q]); d[q] = lm::lm_diagonal(wsum(cd[q]), tr.radius); }
     npd = wsum(npd);
     double y[NC];
     const bool pd = solve8(H, d, rhs, frozen, y) && npd == 0.0;
@@ -349,7 +349,7 @@ __global__ __launch_bounds__(64) void k_two_view_ba(TvBatch B, TvOut* __restrict
       point_ne(L, N);
       double Vd[10], Vi[10];
       for (int k = 0; k < 10; ++k) Vd[k] = N.V[k];
-      for (int a = 0; a < 4; ++a) Vd[tri(a, a)] += fmin(fmax(N.V[tri(a, a)], 1e-6), 1e32) / radius;
+      for (int a = 0; a < 4; ++a) Vd[tri(a, a)] += lm::lm_diagonal(N.V[tri(a, a)], tr.radius);
       if (!inv4(Vd, Vi)) for (int k = 0; k < 10; ++k) Vi[k] = 0.0;
       double t[4], yp[4];
       for (int a = 0; a < 4; ++a) { double s = N.gp[a]; for (int q = 0; q < NC; ++q) s -= N.W[a][q] * y[q]; t[a] = s; }
@@ -367,11 +367,10 @@ __global__ __launch_bounds__(64) void k_two_view_ba(TvBatch B, TvOut* __restrict
     mcc = wsum(mcc); stepsq += wsum(pstep);
     const bool step_valid = pd && isfinite(mcc) && isfinite(stepsq) && mcc > 0.0;
     if (!step_valid) {
-      if (++invalid_steps >= 5) { term = THEIA_TERM_FAILURE; break; }
-      radius /= decrease_factor; decrease_factor *= 2.0; step_successful = false;
+      if (!lm::invalid_step(tr)) { term = THEIA_TERM_FAILURE; break; }
       continue;
     }
-    invalid_steps = 0;
+    lm::valid_step(tr);
     // ---- cost at the candidate
     double cc = 0.0, ci = 0.0;
     for (int i = lane; i < n; i += 64) {
@@ -385,22 +384,20 @@ __global__ __launch_bounds__(64) void k_two_view_ba(TvBatch B, TvOut* __restrict
     double cand_cost = wsum(cc);
     if (wsum(ci) > 0.0 || !isfinite(cand_cost)) cand_cost = DBL_MAX;
     const double step_norm = sqrt(stepsq);
-    if (step_norm <= B.parameter_tolerance * (x_norm + B.parameter_tolerance)) { term = THEIA_TERM_CONVERGENCE; break; }
+    if (lm::parameter_rule(step_norm, x_norm, B.parameter_tolerance)) { term = THEIA_TERM_CONVERGENCE; break; }
     const double cost_change = x_cost - cand_cost;
-    if (fabs(cost_change) <= B.function_tolerance * x_cost) { term = THEIA_TERM_CONVERGENCE; break; }
+    if (lm::function_rule(x_cost, cand_cost, B.function_tolerance)) { term = THEIA_TERM_CONVERGENCE; break; }
     const double rho = cost_change / mcc;
-    if (rho > 1e-3) {
+    if (lm::step_accepted(rho)) {
       S = C;
       for (int i = lane; i < n; i += 64) B.X[o0 + i] = B.Xc[o0 + i];
       x_norm = sqrt(x_norm_sq(S, B.X));
-      const double tt = 2.0 * rho - 1.0;
-      radius = radius / fmax(1.0 / 3.0, 1.0 - tt * tt * tt);
-      radius = fmin(B.max_radius, radius);
-      decrease_factor = 2.0; step_successful = true; need_linearize = true;
+      lm::accept(tr, rho, B.max_radius);
+      need_linearize = true;
       R.nsucc++;
       if (cand_cost < minimum_cost) minimum_cost = cand_cost;
     } else {
-      radius /= decrease_factor; decrease_factor *= 2.0; step_successful = false;
+      lm::shrink(tr);
     }
   }
   R.iters = iter; R.term = term; R.success = term != THEIA_TERM_FAILURE;

@@ -20,6 +20,7 @@
 #include "wave_reduce.h"
 #include "small_linalg.h"
 #include "device_util.h"
+#include "lm_rules.h"
 
 #include <chrono>
 #include <cmath>
@@ -32,7 +33,7 @@ double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock:
 
 // the XOR butterfly over the 64 lanes, on permlane swaps + DPP (wave_reduce.h: the bits of the __shfl_xor loop)
 __device__ __forceinline__ double wsum(double v) { return wave_sum_butterfly(v); }
-__device__ __forceinline__ int tri(int a, int b) { return a * (a + 1) / 2 + b; }
+using lm::tri;
 
 struct TwoViewBatch {
   int num;
@@ -349,10 +350,10 @@ __global__ __launch_bounds__(256) void k_twoview_lm(TwoViewBatch B, BatchLmOut* 
   // Jacobi scaling from the column norms at the initial point (once per solve)
   twoview_linearize(B, p, x, scale, lane, H, g, &x_cost);
 #pragma unroll
-  for (int q = 0; q < 5; ++q) scale[q] = 1.0 / (1.0 + sqrt(H[tri(q, q)]));
-  double radius = 1e4, decrease_factor = 2.0;
-  bool step_successful = true, need_linearize = true, first = true;
-  int iter = 0, invalid_steps = 0, term = THEIA_TERM_NO_CONVERGENCE;
+  for (int q = 0; q < 5; ++q) scale[q] = lm::jacobi_scale(H[tri(q, q)]);
+  lm::TrustRegion tr;
+  bool need_linearize = true, first = true;
+  int iter = 0, term = THEIA_TERM_NO_CONVERGENCE;
   double x_norm = 0.0, minimum_cost = 0.0, gmax = 0.0;
 #pragma unroll
   for (int q = 0; q < 6; ++q) x_norm += x[q] * x[q];
@@ -377,22 +378,14 @@ __global__ __launch_bounds__(256) void k_twoview_lm(TwoViewBatch B, BatchLmOut* 
       if (!isfinite(x_cost)) { term = THEIA_TERM_FAILURE; R.c1 = x_cost; break; }
     }
     if (iter >= B.max_iterations) { term = THEIA_TERM_NO_CONVERGENCE; break; }
-    if (step_successful && gmax <= B.gradient_tolerance) { term = THEIA_TERM_CONVERGENCE; break; }
-    if (radius <= 1e-32) { term = THEIA_TERM_CONVERGENCE; break; }
+    if (lm::converged_before_step(tr, gmax, B.gradient_tolerance)) { term = THEIA_TERM_CONVERGENCE; break; }
     ++iter;
     double d[5], y[5];
 #pragma unroll
-    for (int q = 0; q < 5; ++q) d[q] = fmin(fmax(H[tri(q, q)], 1e-6), 1e32) / radius;
+    for (int q = 0; q < 5; ++q) d[q] = lm::lm_diagonal(H[tri(q, q)], tr.radius);
     const bool solved = B.cgnr ? cgnr5(H, d, g, y) : solve5(H, d, g, y);
     // model cost change of the step -y:  y'g - y'Hy/2  (H without the LM diagonal)
-    double yg = 0.0, yHy = 0.0;
-    for (int a = 0; a < 5; ++a) {
-      yg += y[a] * g[a];
-      double row = 0.0;
-      for (int b = 0; b < 5; ++b) row += H[a >= b ? tri(a, b) : tri(b, a)] * y[b];
-      yHy += y[a] * row;
-    }
-    const double mcc = yg - 0.5 * yHy;
+    const double mcc = lm::model_cost_change<5>(H, g, y);
     double cand[6], dl[5], stepsq = 0.0, xnormsq = 0.0;
 #pragma unroll
     for (int q = 0; q < 5; ++q) dl[q] = -y[q] * scale[q];
@@ -406,30 +399,27 @@ __global__ __launch_bounds__(256) void k_twoview_lm(TwoViewBatch B, BatchLmOut* 
     }
     const bool step_valid = solved && isfinite(mcc) && isfinite(stepsq) && mcc > 0.0;
     if (!step_valid) {
-      if (++invalid_steps >= 5) { term = THEIA_TERM_FAILURE; break; }
-      radius /= decrease_factor; decrease_factor *= 2.0; step_successful = false;
+      if (!lm::invalid_step(tr)) { term = THEIA_TERM_FAILURE; break; }
       continue;
     }
-    invalid_steps = 0;
+    lm::valid_step(tr);
     double cand_cost = twoview_cost(B, p, cand, lane);
     if (!isfinite(cand_cost)) cand_cost = DBL_MAX;
     const double step_norm = sqrt(stepsq);
-    if (step_norm <= B.parameter_tolerance * (x_norm + B.parameter_tolerance)) { term = THEIA_TERM_CONVERGENCE; break; }
+    if (lm::parameter_rule(step_norm, x_norm, B.parameter_tolerance)) { term = THEIA_TERM_CONVERGENCE; break; }
     const double cost_change = x_cost - cand_cost;
-    if (fabs(cost_change) <= B.function_tolerance * x_cost) { term = THEIA_TERM_CONVERGENCE; break; }
+    if (lm::function_rule(x_cost, cand_cost, B.function_tolerance)) { term = THEIA_TERM_CONVERGENCE; break; }
     const double rho = cost_change / mcc;
-    if (rho > 1e-3) {
+    if (lm::step_accepted(rho)) {
 #pragma unroll
       for (int q = 0; q < 6; ++q) x[q] = cand[q];
       x_norm = sqrt(xnormsq);
-      const double t = 2.0 * rho - 1.0;
-      radius = radius / fmax(1.0 / 3.0, 1.0 - t * t * t);
-      radius = fmin(B.max_radius, radius);
-      decrease_factor = 2.0; step_successful = true; need_linearize = true;
+      lm::accept(tr, rho, B.max_radius);
+      need_linearize = true;
       R.nsucc++;
       if (cand_cost < minimum_cost) minimum_cost = cand_cost;
     } else {
-      radius /= decrease_factor; decrease_factor *= 2.0; step_successful = false;
+      lm::shrink(tr);
     }
   }
   R.iters = iter; R.term = term; R.success = term != THEIA_TERM_FAILURE;
@@ -582,10 +572,10 @@ __global__ __launch_bounds__(256) void k_homography_lm(HomographyBatch B, BatchL
   for (int q = 0; q < 9; ++q) scale[q] = 1.0;
   double A[45], g[9], x_cost;
   homography_linearize(B, p, x, scale, lane, A, g, &x_cost);
-  for (int q = 0; q < 9; ++q) scale[q] = 1.0 / (1.0 + sqrt(A[tri(q, q)]));
-  double radius = 1e4, decrease_factor = 2.0;
-  bool step_successful = true, need_linearize = true, first = true;
-  int iter = 0, invalid_steps = 0, term = THEIA_TERM_NO_CONVERGENCE;
+  for (int q = 0; q < 9; ++q) scale[q] = lm::jacobi_scale(A[tri(q, q)]);
+  lm::TrustRegion tr;
+  bool need_linearize = true, first = true;
+  int iter = 0, term = THEIA_TERM_NO_CONVERGENCE;
   double x_norm = 0.0, minimum_cost = 0.0, gmax = 0.0;
   for (int q = 0; q < 9; ++q) x_norm += x[q] * x[q];
   x_norm = sqrt(x_norm);
@@ -603,20 +593,12 @@ __global__ __launch_bounds__(256) void k_homography_lm(HomographyBatch B, BatchL
       if (!isfinite(x_cost)) { term = THEIA_TERM_FAILURE; break; }
     }
     if (iter >= B.max_iterations) { term = THEIA_TERM_NO_CONVERGENCE; break; }
-    if (step_successful && gmax <= B.gradient_tolerance) { term = THEIA_TERM_CONVERGENCE; break; }
-    if (radius <= 1e-32) { term = THEIA_TERM_CONVERGENCE; break; }
+    if (lm::converged_before_step(tr, gmax, B.gradient_tolerance)) { term = THEIA_TERM_CONVERGENCE; break; }
     ++iter;
     double d[9], y[9];
-    for (int q = 0; q < 9; ++q) d[q] = fmin(fmax(A[tri(q, q)], 1e-6), 1e32) / radius;
+    for (int q = 0; q < 9; ++q) d[q] = lm::lm_diagonal(A[tri(q, q)], tr.radius);
     const bool solved = solve9(A, d, g, y);
-    double yg = 0.0, yAy = 0.0;
-    for (int a = 0; a < 9; ++a) {
-      yg += y[a] * g[a];
-      double row = 0.0;
-      for (int b = 0; b < 9; ++b) row += A[a >= b ? tri(a, b) : tri(b, a)] * y[b];
-      yAy += y[a] * row;
-    }
-    const double mcc = yg - 0.5 * yAy;
+    const double mcc = lm::model_cost_change<9>(A, g, y);
     double cand[9], stepsq = 0.0, xnormsq = 0.0;
     for (int q = 0; q < 9; ++q) {
       cand[q] = x[q] - y[q] * scale[q];
@@ -625,29 +607,26 @@ __global__ __launch_bounds__(256) void k_homography_lm(HomographyBatch B, BatchL
     }
     const bool step_valid = solved && isfinite(mcc) && isfinite(stepsq) && mcc > 0.0;
     if (!step_valid) {
-      if (++invalid_steps >= 5) { term = THEIA_TERM_FAILURE; break; }
-      radius /= decrease_factor; decrease_factor *= 2.0; step_successful = false;
+      if (!lm::invalid_step(tr)) { term = THEIA_TERM_FAILURE; break; }
       continue;
     }
-    invalid_steps = 0;
+    lm::valid_step(tr);
     double cand_cost = homography_cost(B, p, cand, lane);
     if (!isfinite(cand_cost)) cand_cost = DBL_MAX;
     const double step_norm = sqrt(stepsq);
-    if (step_norm <= B.parameter_tolerance * (x_norm + B.parameter_tolerance)) { term = THEIA_TERM_CONVERGENCE; break; }
+    if (lm::parameter_rule(step_norm, x_norm, B.parameter_tolerance)) { term = THEIA_TERM_CONVERGENCE; break; }
     const double cost_change = x_cost - cand_cost;
-    if (fabs(cost_change) <= B.function_tolerance * x_cost) { term = THEIA_TERM_CONVERGENCE; break; }
+    if (lm::function_rule(x_cost, cand_cost, B.function_tolerance)) { term = THEIA_TERM_CONVERGENCE; break; }
     const double rho = cost_change / mcc;
-    if (rho > 1e-3) {
+    if (lm::step_accepted(rho)) {
       for (int q = 0; q < 9; ++q) x[q] = cand[q];
       x_norm = sqrt(xnormsq);
-      const double t = 2.0 * rho - 1.0;
-      radius = radius / fmax(1.0 / 3.0, 1.0 - t * t * t);
-      radius = fmin(B.max_radius, radius);
-      decrease_factor = 2.0; step_successful = true; need_linearize = true;
+      lm::accept(tr, rho, B.max_radius);
+      need_linearize = true;
       R.nsucc++;
       if (cand_cost < minimum_cost) minimum_cost = cand_cost;
     } else {
-      radius /= decrease_factor; decrease_factor *= 2.0; step_successful = false;
+      lm::shrink(tr);
     }
   }
   R.iters = iter; R.term = term; R.success = term != THEIA_TERM_FAILURE;
@@ -810,7 +789,9 @@ __global__ __launch_bounds__(256) void k_fundamental_lm(FundBatch B, BatchLmOut*
   for (int q = 0; q < 7; ++q) scale[q] = 1.0;
   double A[28], g[7], x_cost;
   fund_linearize(B, p, x, scale, lane, A, g, &x_cost);
-  for (int q = 0; q < 7; ++q) scale[q] = 1.0 / (1.0 + sqrt(A[tri(q, q)]));
+  for (int q = 0; q < 7; ++q) scale[q] = lm::jacobi_scale(A[tri(q, q)]);
+  // The state and its updates stay written out here (lm_rules.h: shrink, invalid_step, accept, converged_before_step): with
+  // the state in a TrustRegion, as in the two kernels above, this one came out 3 registers larger
   double radius = 1e4, decrease_factor = 2.0;
   bool step_successful = true, need_linearize = true, first = true;
   int iter = 0, invalid_steps = 0, term = THEIA_TERM_NO_CONVERGENCE;
@@ -839,16 +820,9 @@ __global__ __launch_bounds__(256) void k_fundamental_lm(FundBatch B, BatchLmOut*
     if (radius <= 1e-32) { term = THEIA_TERM_CONVERGENCE; break; }
     ++iter;
     double d[7], y[7];
-    for (int q = 0; q < 7; ++q) d[q] = fmin(fmax(A[tri(q, q)], 1e-6), 1e32) / radius;
+    for (int q = 0; q < 7; ++q) d[q] = lm::lm_diagonal(A[tri(q, q)], radius);
     const bool solved = solve7(A, d, g, y);
-    double yg = 0.0, yAy = 0.0;
-    for (int a = 0; a < 7; ++a) {
-      yg += y[a] * g[a];
-      double row = 0.0;
-      for (int b = 0; b < 7; ++b) row += A[a >= b ? tri(a, b) : tri(b, a)] * y[b];
-      yAy += y[a] * row;
-    }
-    const double mcc = yg - 0.5 * yAy;
+    const double mcc = lm::model_cost_change<7>(A, g, y);
     double cand[9], dl[7], stepsq = 0.0, xnormsq = 0.0;
     for (int q = 0; q < 7; ++q) dl[q] = -y[q] * scale[q];
     fund_plus(x, dl, cand);
@@ -866,11 +840,11 @@ __global__ __launch_bounds__(256) void k_fundamental_lm(FundBatch B, BatchLmOut*
     double cand_cost = fund_cost(B, p, cand, lane);
     if (!isfinite(cand_cost)) cand_cost = DBL_MAX;
     const double step_norm = sqrt(stepsq);
-    if (step_norm <= B.parameter_tolerance * (x_norm + B.parameter_tolerance)) { term = THEIA_TERM_CONVERGENCE; break; }
+    if (lm::parameter_rule(step_norm, x_norm, B.parameter_tolerance)) { term = THEIA_TERM_CONVERGENCE; break; }
     const double cost_change = x_cost - cand_cost;
-    if (fabs(cost_change) <= B.function_tolerance * x_cost) { term = THEIA_TERM_CONVERGENCE; break; }
+    if (lm::function_rule(x_cost, cand_cost, B.function_tolerance)) { term = THEIA_TERM_CONVERGENCE; break; }
     const double rho = cost_change / mcc;
-    if (rho > 1e-3) {
+    if (lm::step_accepted(rho)) {
       for (int q = 0; q < 9; ++q) x[q] = cand[q];
       x_norm = sqrt(xnormsq);
       const double t = 2.0 * rho - 1.0;
