@@ -1219,7 +1219,15 @@ enum {
    * come out of the SAMPLER's stream, three after every sample -- reproduced here; with the fifth entry set, the stream is re-seeded
    * with 42 after the first sample, as the solver's function-static RandomNumberGenerator(42) does the first time it runs in a
    * process.  model = rotation (9, row-major), translation (3), focal_length, radial_distortion. */
-  THEIA_EST_RADIAL_DIST_UNCALIBRATED_ABSOLUTE_POSE = 16
+  THEIA_EST_RADIAL_DIST_UNCALIBRATED_ABSOLUTE_POSE = 16,
+  /* CameraAlignmentEstimator of AlignReconstructionsRobust (sfm/transformation/align_reconstructions.cc:54-93): datum =
+   * CameraCorrespondence [camera1 (3) | camera2 (3)], two camera positions; sample = 4; EstimateModel =
+   * AlignPointCloudsUmeyama(positions2 -> positions1) on the four data (align_point_clouds.cc:56-150, in the reference's
+   * sequential order), always one model: a degenerate sample (collinear, coplanar, or small -- the rule is on absolute
+   * singular values) yields the identity transformation, which is scored like any other; Error = |camera1 - (s R camera2 + t)|^2.
+   * RefineModel is the default "return true".  model = SimilarityTransformation: rotation (9, row-major), translation (3),
+   * scale -- the layout of THEIA_EST_SIMILARITY_2D3D.  (csrc/alignment_device.h) */
+  THEIA_EST_CAMERA_ALIGNMENT = 17
 };
 
 /* A batch of independent estimation problems ("pairs").  Datum layout:
@@ -1233,7 +1241,8 @@ enum {
  *   radial-distortion homography: RadialDistortionFeatureCorrespondence, 12 doubles (THEIA_EST_RADIAL_HOMOGRAPHY)
  *   similarity 2D-3D, rigid transformation 2D-3D: CameraAndFeatureCorrespondence2D3D, 26 doubles (THEIA_EST_SIMILARITY_2D3D)
  *   uncalibrated absolute pose (with or without radial distortion): FeatureCorrespondence2D3D = [u v X Y Z], pixels with the
- *     principal point removed */
+ *     principal point removed
+ *   camera alignment: CameraCorrespondence = [camera1 (3) | camera2 (3)] (THEIA_EST_CAMERA_ALIGNMENT) */
 typedef struct theia_ransac_batch {
   int32_t estimator;           /* THEIA_EST_*                              */
   int32_t num_problems;
@@ -1255,7 +1264,8 @@ typedef struct theia_ransac_batch {
  *   UNCALIBRATED_RELATIVE_POSE: F(9) R(9) position(3) focal_length1 focal_length2 = 23
  *   UNCALIBRATED_ABSOLUTE_POSE: projection matrix 3 x 4, row-major    = 12
  *   RIGID_TRANSFORMATION_2D3D: R(9, row-major) translation(3)        = 12
- *   RADIAL_DIST_UNCALIBRATED_ABSOLUTE_POSE: R(9) translation(3) focal_length radial_distortion = 14 */
+ *   RADIAL_DIST_UNCALIBRATED_ABSOLUTE_POSE: R(9) translation(3) focal_length radial_distortion = 14
+ *   SIMILARITY_2D3D / CAMERA_ALIGNMENT: R(9, row-major) translation(3) scale = 13 */
 #define THEIA_RANSAC_MODEL_STRIDE 24
 typedef struct theia_ransac_result {
   int32_t* success;            /* [num_problems] Estimate() return value; 0 (with no inliers and a zero
@@ -1598,6 +1608,78 @@ int theia_hip_unproject(int64_t num_obs, const double* obs_uv /*[n][2]*/, const 
                         const int32_t* group_model /*[num_groups]*/,
                         double* camera_point, double* normalized, double* world_ray, double* world_ray_unit,
                         uint8_t* status, uint8_t* iterations, theia_unproject_summary* summary /*or NULL*/);
+/* ---- reconstruction alignment (sfm/transformation/; csrc/alignment.hip, csrc/alignment_device.h) ----
+ * AlignPointCloudsUmeyamaWithWeights (align_point_clouds.cc:56-150; weights == NULL: AlignPointCloudsUmeyama, :45-54) for a
+ * batch of point-cloud pairs: problem p owns the points offsets[p] .. offsets[p + 1] of left, right [.][3] and weights [.].
+ * Per problem the similarity that maps left onto right, right ~ s R left + t: rotation [p][9] row-major, translation [p][3],
+ * scale [p] and status [p] (THEIA_ALIGN_OK / THEIA_ALIGN_DEGENERATE).  The arithmetic is the reference's: weighted
+ * centroids, sigma of the left cloud, the centred cross-correlation over the weight sum, the Jacobi SVD of its transpose
+ * (Eigen::JacobiSVD restated, csrc/small_linalg.h svd3), s(2,2) = -1 when det(U) det(V^T) <= 0, scale = (s0 + s1 + s(2,2) s2) /
+ * sigma, R = U S V^T, t = right centroid - scale * (R * left centroid).
+ * THEIA_ALIGN_DEGENERATE: max_sv / (min_sv + 1e-12) > 1e6 or min_sv < 1e-8 -- the reference's test, on ABSOLUTE singular
+ * values (a cloud of small extent is "degenerate" whatever its shape); the result is then identity / zero / 1, as the
+ * reference returns it with a warning.
+ * STATED DEVIATION: the reference adds point after point; here every sum is a fixed tree (a lane's strided partial sums, then
+ * the XOR butterfly over the wave, then the waves of a workgroup in order), so a call returns the same bytes on every run, but
+ * not the sequential sum's last bits.  Problems of up to THEIA_ALIGN_WAVE_MAX_POINTS points take one wavefront each (four per
+ * workgroup), larger ones one workgroup of 256 lanes.
+ * THEIA_HIP_ERR_INVALID_ARGUMENT, before the device is touched and with nothing written: num_problems < 0; a NULL offsets,
+ * left, right or output array with num_problems > 0; offsets[0] != 0 or decreasing offsets; a problem without points (the
+ * reference reads left[0]); a negative weight (CHECK_GE); a problem whose weights do not sum to more than zero (CHECK_GT); a
+ * non-finite coordinate or weight.  num_problems == 0 returns 0 and launches nothing.
+ * timings_ms (optional, [2]): the kernels alone (device events) | the whole call. */
+enum { THEIA_ALIGN_OK = 0, THEIA_ALIGN_DEGENERATE = 1 };
+#define THEIA_ALIGN_WAVE_MAX_POINTS 256
+int theia_hip_align_point_clouds(int32_t num_problems, const int64_t* offsets /*[num_problems+1]*/,
+                                 const double* left /*[.][3]*/, const double* right /*[.][3]*/,
+                                 const double* weights /*[.] or NULL = all ones*/, double* rotation /*[p][9]*/,
+                                 double* translation /*[p][3]*/, double* scale /*[p]*/, int32_t* status /*[p]*/,
+                                 double* timings_ms /*[2] or NULL*/);
+/* TransformReconstruction (transform_reconstruction.cc:48-94) on flat arrays, in place: one lane per camera or point.
+ * cameras [n][6] = position | angle-axis (theia_ba_problem's cam_ext) with camera_estimated [n] (NULL: all estimated);
+ * points [m][4] homogeneous with point_estimated [m] (NULL: all).  Entries whose mask byte is 0 keep their bytes.
+ *   camera position    c' = s * (R c) + t          (TransformPoint; the order is this library's STATED order: every row of
+ *                      R times the vector, products added left to right, then the scale, then the translation -- Eigen's
+ *                      own evaluation order of `scale * rotation * point` is not claimed)
+ *   camera orientation R_cam' = R_cam R^T through ceres' AngleAxisToRotationMatrix / RotationMatrixToAngleAxis
+ *                      (Camera::Get/SetOrientation..., csrc/rotation_maps.h)
+ *   point              p = (x / w, y / w, z / w) (hnormalized), p' = s * (R p) + t, w' = 1 (homogeneous); w == 0 divides as
+ *                      the reference does and propagates
+ * As in the reference, tracks' inverse depths and reference bearing vectors are not touched.
+ * THEIA_HIP_ERR_INVALID_ARGUMENT before the device is touched: a negative count; a NULL cameras / points with a non-zero
+ * count; a NULL or non-finite rotation, translation or scale.  Both counts zero: returns 0, launches nothing. */
+int theia_hip_transform_reconstruction(int32_t num_cameras, double* cameras /*[n][6]*/, const uint8_t* camera_estimated,
+                                       int64_t num_points, double* points /*[m][4]*/, const uint8_t* point_estimated,
+                                       const double* rotation /*[9] row-major*/, const double* translation /*[3]*/,
+                                       double scale, double* timings_ms /*[2] or NULL*/);
+/* AlignRotations (sfm/transformation/align_rotations.cc:127-156; pybind sfm.cc AlignRotations): the rotation R(w) that takes
+ * `rotation` onto `gt_rotation`, rotation_i R(w) ~ gt_rotation_i, by the reference's ceres::Solve restated on the device
+ * (csrc/alignment.hip k_align_rotations; the twelfth Levenberg-Marquardt loop on the rules of csrc/lm_rules.h), then
+ * ApplyRotationTransformation (:100-123): rotation_i becomes AngleAxis(R(rotation_i) R(w)).  All vectors are angle-axis.
+ * One 3-parameter block w starting at zero, one residual block per rotation, no loss; the residual is the reference's as
+ * written, gt_i - AngleAxis(R(rotation_i) R(w)) -- a DIFFERENCE OF ANGLE-AXIS VECTORS, which wraps near pi (two nearly equal
+ * rotations on either side of a half turn have a residual of about 2 pi): kept.  Jacobians in closed form, with Ceres'
+ * small-angle branches (csrc/rotation_derivatives.h).  Options as the reference leaves them: function_tolerance 0 (the rule
+ * then fires only on a cost that does not change at all), and Ceres 2.2's defaults -- 50 iterations, gradient tolerance
+ * 1e-10, parameter tolerance 1e-8, initial radius 1e4, maximum radius 1e16, Jacobi scaling.
+ * STATED DEVIATION: DENSE_QR on the 3-column Jacobian is solved as the 3 x 3 normal equations (Cholesky in registers), and
+ * the sums over the rotations are fixed trees, not sequential: rounding level.  Two calls on one input return the same bytes.
+ * alignment [3] (out) = w; after THEIA_ROTATION_TERM_FAILURE w = 0, as Ceres leaves a block of a failed solve as passed in,
+ * and the rotations still go through ApplyRotationTransformation, as the reference applies whatever the solve left.
+ * trace_out (optional) [trace_capacity][5]: (cost, gradient max norm, step norm, radius, accepted) per row, row 0 the start,
+ * in theia_hip_nonlinear_rotations' convention; summary->trace_size rows are written.  Returns 0 whatever the termination.
+ * THEIA_HIP_ERR_INVALID_ARGUMENT before the device is touched, with nothing but the zeroed summary written: num_rotations < 1;
+ * a NULL gt_rotation, rotation or alignment; trace_capacity < 0, or > 0 with a NULL trace_out; a non-finite entry. */
+typedef struct theia_align_rotations_summary {
+  int32_t iterations;              /* passes of the loop, as theia_nonlinear_rotation_summary counts them */
+  int32_t num_successful_steps, num_unsuccessful_steps, num_invalid_steps;
+  int32_t termination;             /* THEIA_ROTATION_TERM_* */
+  int32_t trace_size;
+  double initial_cost, final_cost, final_radius, final_gradient_max_norm, seconds;
+} theia_align_rotations_summary;
+int theia_hip_align_rotations(int32_t num_rotations, const double* gt_rotation /*[n][3]*/, double* rotation /*[n][3], in/out*/,
+                              double* alignment /*[3], out*/, theia_align_rotations_summary* summary /*or NULL*/,
+                              double* trace_out /*optional*/, int32_t trace_capacity);
 /* n draws of RandomNumberGenerator(seed).RandInt(lo, hi) (util/random.cc:46-84): host code that follows the reference's
  * generator outside the RANSAC sampler (the random candidates of GuidedEpipolarMatcher::FindFeaturesNearEpipolarLines). */
 int theia_hip_randint_stream(uint32_t seed, int32_t n, int32_t lo, int32_t hi, int32_t* out);

@@ -9,3 +9,8 @@ from .incremental import (FindViewsToLocalize, VisibilityPyramid, LocalizeViewTo
                           SetUnderconstrainedAsUnestimated, SetUnderconstrainedTracksToUnestimated,
                           SetUnderconstrainedViewsToUnestimated, NumEstimatedViews, NumEstimatedTracks,
                           OrderViewPairsByInitializationCriterion)
+from . import alignment  # noqa: E402,F401
+from .alignment import (AlignPointCloudsUmeyama, AlignPointCloudsUmeyamaWithWeights,  # noqa: E402,F401
+                        AlignPointCloudsUmeyamaBatch, AlignPointCloudsUmeyamaWithWeightsBatch, AlignReconstructions,
+                        AlignReconstructionsRobust, TransformReconstruction, TransformReconstruction4,
+                        FindCommonViewsByName, AlignRotations, AlignOrientations)

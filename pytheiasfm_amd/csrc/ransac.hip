@@ -34,6 +34,7 @@
 #include "fit5_team.h"
 #include "svd_team.h"
 #include "p4pf_device.h"
+#include "alignment_device.h"   // CameraAlignmentEstimator
 #include "theia_hip.h"
 #include <atomic>
 #include <mutex>
@@ -129,6 +130,7 @@ __device__ int estimate_models(int est, const double* subset, double* models, Es
     else if (est == THEIA_EST_HOMOGRAPHY) ok = rsc::four_point_homography(subset, models);
     else if (est == THEIA_EST_DOMINANT_PLANE) ok = rsc::plane_from_three_points(subset, models);
     else if (est == THEIA_EST_RELATIVE_POSE_KNOWN_ORIENTATION) ok = rsc::two_point_relative_position(subset, models);
+    else if (est == THEIA_EST_CAMERA_ALIGNMENT) { rsc::camera_alignment_fit(subset, models); ok = true; }   // align_reconstructions.cc:66-84: always true
     return ok ? 1 : 0;
   }
   return 0;
@@ -228,6 +230,7 @@ __device__ inline double model_error(int est, const double* m, const double* d) 
   if (est == THEIA_EST_RELATIVE_POSE_KNOWN_ORIENTATION) return rsc::known_orientation_error(m, d);
   if (est == THEIA_EST_UNCALIBRATED_RELATIVE_POSE) return rsc::uncalibrated_relative_pose_error(m, d);
   if (est == THEIA_EST_ABSOLUTE_POSE_KNOWN_ORIENTATION) return rsc::known_orientation_abs_error(m, d);
+  if (est == THEIA_EST_CAMERA_ALIGNMENT) return rsc::camera_alignment_error(m, d);
   const double dx = d[2] - m[9], dy = d[3] - m[10], dz = d[4] - m[11];
   const double px = (m[0] * dx + m[1] * dy) + m[2] * dz;
   const double py = (m[3] * dx + m[4] * dy) + m[5] * dz;
@@ -1387,13 +1390,13 @@ int RansacCall::check() {
   }
   gdls_est = est == THEIA_EST_SIMILARITY_2D3D;
   dls_est = est == THEIA_EST_ABSOLUTE_POSE_DLS || gdls_est;   // the Macaulay pipeline: stage A -> eigen stage
-  if (est < 0 || est > THEIA_EST_RADIAL_DIST_UNCALIBRATED_ABSOLUTE_POSE) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "unknown estimator id");
+  if (est < 0 || est > THEIA_EST_CAMERA_ALIGNMENT) return set_error(THEIA_HIP_ERR_INVALID_ARGUMENT, "unknown estimator id");
   // estimators that keep Estimator::RefineModel's default "return true" (solvers/estimator.h:86-88): LO only counts
   trivial_refine = est == THEIA_EST_ESSENTIAL_MATRIX || est == THEIA_EST_DOMINANT_PLANE ||
                    est == THEIA_EST_RELATIVE_POSE_KNOWN_ORIENTATION || est == THEIA_EST_ABSOLUTE_POSE_KNOWN_ORIENTATION ||
                    est == THEIA_EST_TRIANGULATION || est == THEIA_EST_RADIAL_HOMOGRAPHY || est == THEIA_EST_SIMILARITY_2D3D ||
                    est == THEIA_EST_UNCALIBRATED_ABSOLUTE_POSE || est == THEIA_EST_RIGID_TRANSFORMATION_2D3D ||
-                   est == THEIA_EST_RADIAL_DIST_UNCALIBRATED_ABSOLUTE_POSE;
+                   est == THEIA_EST_RADIAL_DIST_UNCALIBRATED_ABSOLUTE_POSE || est == THEIA_EST_CAMERA_ALIGNMENT;
   rel_pose = est == THEIA_EST_RELATIVE_POSE; uncal_pose = est == THEIA_EST_UNCALIBRATED_RELATIVE_POSE;
   homog = est == THEIA_EST_HOMOGRAPHY; fund = est == THEIA_EST_FUNDAMENTAL_MATRIX;
   // every estimator's RefineModel is built: BundleAdjustView (absolute pose), BundleAdjustTwoViewsAngular ((un)calibrated
@@ -1705,6 +1708,7 @@ int RansacCall::launch_fit(const Round& r) {
       case THEIA_EST_UNCALIBRATED_RELATIVE_POSE: THIP_FIT(THEIA_EST_UNCALIBRATED_RELATIVE_POSE); break;
       case THEIA_EST_TRIANGULATION: THIP_FIT(THEIA_EST_TRIANGULATION); break;
       case THEIA_EST_RADIAL_HOMOGRAPHY: THIP_FIT(THEIA_EST_RADIAL_HOMOGRAPHY); break;
+      case THEIA_EST_CAMERA_ALIGNMENT: THIP_FIT(THEIA_EST_CAMERA_ALIGNMENT); break;
       default: THIP_FIT(THEIA_EST_ABSOLUTE_POSE_KNOWN_ORIENTATION); break;
     }
 #undef THIP_FIT

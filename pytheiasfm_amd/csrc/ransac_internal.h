@@ -22,6 +22,7 @@ __host__ __device__ inline int max_models(int est) {
   if (est == THEIA_EST_UNCALIBRATED_ABSOLUTE_POSE) return 10;
   if (est == THEIA_EST_RIGID_TRANSFORMATION_2D3D) return 8;
   if (est == THEIA_EST_RADIAL_DIST_UNCALIBRATED_ABSOLUTE_POSE) return 13;
+  if (est == THEIA_EST_CAMERA_ALIGNMENT) return 1;   // EstimateModel always returns its one (possibly identity) model
   if (est >= THEIA_EST_FUNDAMENTAL_MATRIX) return 1;
   if (est == THEIA_EST_ABSOLUTE_POSE_DLS) return dlsdev::kMaxSolutions;
   return est == THEIA_EST_ABSOLUTE_POSE_SQPNP ? 18 : (est == THEIA_EST_ABSOLUTE_POSE_KNEIP ? 4 : 10);
@@ -33,7 +34,8 @@ __host__ __device__ inline int sample_size(int est) {
     case THEIA_EST_RELATIVE_POSE: case THEIA_EST_ESSENTIAL_MATRIX: return 5;
     case THEIA_EST_FUNDAMENTAL_MATRIX: case THEIA_EST_UNCALIBRATED_RELATIVE_POSE: return 8;
     case THEIA_EST_HOMOGRAPHY: case THEIA_EST_SIMILARITY_2D3D: case THEIA_EST_UNCALIBRATED_ABSOLUTE_POSE:
-    case THEIA_EST_RIGID_TRANSFORMATION_2D3D: case THEIA_EST_RADIAL_DIST_UNCALIBRATED_ABSOLUTE_POSE: return 4;
+    case THEIA_EST_RIGID_TRANSFORMATION_2D3D: case THEIA_EST_RADIAL_DIST_UNCALIBRATED_ABSOLUTE_POSE:
+    case THEIA_EST_CAMERA_ALIGNMENT: return 4;
     case THEIA_EST_RADIAL_HOMOGRAPHY: return 6;
     case THEIA_EST_RELATIVE_POSE_KNOWN_ORIENTATION: case THEIA_EST_ABSOLUTE_POSE_KNOWN_ORIENTATION:
     case THEIA_EST_TRIANGULATION: return 2;
@@ -53,11 +55,12 @@ inline int model_doubles(int est) {
     case THEIA_EST_RELATIVE_POSE_KNOWN_ORIENTATION: case THEIA_EST_ABSOLUTE_POSE_KNOWN_ORIENTATION: return 3;
     case THEIA_EST_TRIANGULATION: return 4;
     case THEIA_EST_RADIAL_HOMOGRAPHY: return 20;   // H | l1 | l2 | H^-1
-    case THEIA_EST_SIMILARITY_2D3D: return 13;     // rotation | translation | scale
+    case THEIA_EST_SIMILARITY_2D3D: case THEIA_EST_CAMERA_ALIGNMENT: return 13;     // rotation | translation | scale
     default: return 9;   // essential / fundamental matrix, homography
   }
 }
 constexpr int kTriDatum = 33;   // PointObservation row of THEIA_EST_TRIANGULATION (theia_hip.h)
+constexpr int kAlignDatum = 6;  // CameraCorrespondence row of THEIA_EST_CAMERA_ALIGNMENT: camera1 (3) | camera2 (3)
 constexpr int kSimDatum = 26;   // CameraAndFeatureCorrespondence2D3D row of THEIA_EST_SIMILARITY_2D3D: dir (3) | point (4) | pixel (2) | extrinsics (6) | model | intrinsics (10)
 __host__ __device__ inline int datum_size(int est) {
   switch (est) {
@@ -65,6 +68,7 @@ __host__ __device__ inline int datum_size(int est) {
     case THEIA_EST_ABSOLUTE_POSE_KNOWN_ORIENTATION: case THEIA_EST_UNCALIBRATED_ABSOLUTE_POSE:
     case THEIA_EST_RADIAL_DIST_UNCALIBRATED_ABSOLUTE_POSE: return 5;
     case THEIA_EST_DOMINANT_PLANE: return 3;
+    case THEIA_EST_CAMERA_ALIGNMENT: return kAlignDatum;
     case THEIA_EST_TRIANGULATION: return kTriDatum;
     case THEIA_EST_RADIAL_HOMOGRAPHY: return rsc::kRadHomDatum;
     case THEIA_EST_SIMILARITY_2D3D: case THEIA_EST_RIGID_TRANSFORMATION_2D3D: return kSimDatum;

@@ -49,7 +49,7 @@ int theia_hip_ransac_estimate_streams(const theia_ransac_batch* batch, const the
   theia_ransac_batch sub = *batch;
   if (p4pfr_est && batch->estimator_params) sub.estimator_params = p4pfr_params;
   if (nprob == 0) { sub.num_problems = 0; return ransac_run(&sub, params, result, nullptr); }   // (the parameter checks)
-  const int ds = (est >= 0 && est <= THEIA_EST_RADIAL_DIST_UNCALIBRATED_ABSOLUTE_POSE) ? datum_size(est) : 1;
+  const int ds = (est >= 0 && est <= THEIA_EST_CAMERA_ALIGNMENT) ? datum_size(est) : 1;
 
   // the streams, worked on in copies: the caller's states change only when every wave succeeded
   std::vector<Mt19937> gen(ns);

@@ -40,6 +40,7 @@ EST_SIMILARITY_2D3D = 13
 EST_UNCALIBRATED_ABSOLUTE_POSE = 14
 EST_RIGID_TRANSFORMATION_2D3D = 15
 EST_RADIAL_DIST_UNCALIBRATED_ABSOLUTE_POSE = 16
+EST_CAMERA_ALIGNMENT = 17
 
 
 _MT_DEFAULT_SEED = 5489   # std::mt19937::default_seed: a thread's generator before anything seeds it
@@ -258,7 +259,7 @@ def estimate_batch(estimator, data, offsets, params, estimator_params=None, seed
             "time_fit_seconds": r.time_fit_seconds, "time_score_seconds": r.time_score_seconds}
 
 
-_SAMPLE_SIZE = {0: 5, 1: 5, 2: 3, 3: 3, 4: 3, 5: 8, 6: 4, 7: 3, 8: 2, 9: 8, 10: 2, 11: 2, 12: 6, 13: 4, 14: 4, 15: 4, 16: 4}   # Estimator::SampleSize() by THEIA_EST_*
+_SAMPLE_SIZE = {0: 5, 1: 5, 2: 3, 3: 3, 4: 3, 5: 8, 6: 4, 7: 3, 8: 2, 9: 8, 10: 2, 11: 2, 12: 6, 13: 4, 14: 4, 15: 4, 16: 4, 17: 4}   # Estimator::SampleSize() by THEIA_EST_*
 
 
 def _single(estimator, ransac_params, ransac_type, data, estimator_params=None):

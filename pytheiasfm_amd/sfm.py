@@ -193,6 +193,9 @@ class Reconstruction:
         self.view_image_size = None
         # View::CameraIntrinsicsPrior().focal_length.is_set per view, [nv] bool; None = all false
         self.view_focal_prior_set = None
+        # View::Name() per view, a sequence of nv strings; None = not known (the functions of alignment.py that match views
+        # by name raise THEIA_HIP_ERR_INVALID_ARGUMENT)
+        self.view_names = None
 
     @classmethod
     def from_flat(cls, p):

@@ -105,6 +105,7 @@ int datum_doubles(int estimator) {
     case THEIA_EST_ABSOLUTE_POSE_KNOWN_ORIENTATION: case THEIA_EST_UNCALIBRATED_ABSOLUTE_POSE:
     case THEIA_EST_RADIAL_DIST_UNCALIBRATED_ABSOLUTE_POSE: return 5;
     case THEIA_EST_DOMINANT_PLANE: return 3;
+    case THEIA_EST_CAMERA_ALIGNMENT: return 6;
     case THEIA_EST_TRIANGULATION: return 33;
     case THEIA_EST_RADIAL_HOMOGRAPHY: return 12;
     case THEIA_EST_SIMILARITY_2D3D: case THEIA_EST_RIGID_TRANSFORMATION_2D3D: return 26;

@@ -174,5 +174,10 @@ inline bool EstimateRigidTransformation2D3DBatch(const RansacParameters& p, int 
 // rotation (9) | translation (3) | focal_length | radial_distortion
 inline bool EstimateRadialDistUncalibratedAbsolutePoseBatch(const RansacParameters& p, int t, const double meta[5], const std::vector<std::vector<double>>& c, EstimatorBatchResult* r, std::string* e) { return EstimateBatch(THEIA_EST_RADIAL_DIST_UNCALIBRATED_ABSOLUTE_POSE, t, p, c, meta, r, e); }
 
+// CameraAlignmentEstimator of AlignReconstructionsRobust (align_reconstructions.cc:54-93): rows [camera1 (3) | camera2 (3)];
+// model = rotation (9) | translation (3) | scale, camera1 ~ scale * rotation * camera2 + translation.  The reference's own
+// call uses max_iterations 1000, use_mle, error_thresh = threshold^2, failure_probability 1e-4 (:156-160).
+inline bool EstimateCameraAlignmentBatch(const RansacParameters& p, int t, const std::vector<std::vector<double>>& c6, EstimatorBatchResult* r, std::string* e) { return EstimateBatch(THEIA_EST_CAMERA_ALIGNMENT, t, p, c6, nullptr, r, e); }
+
 }  // namespace theia_hip_shim
 #endif
