@@ -84,57 +84,75 @@ THIP_DEV unsigned segment_or(const Segment& s, int lane, unsigned v) {
 #endif
 template <int PD> constexpr int rec_doubles() { return PD == 3 ? 22 : 26; }   // 12 + 2 PD + 2 + 2 used
 
+// A word of the plan at a wave-uniform address, through the scalar cache (the plan is constant during a launch).  A plain load
+// behind the kernel's own global stores is not provably unclobbered and compiles to a vector load.
+THIP_DEV int uniform_load(const int* p) {
+  typedef const int __attribute__((address_space(4))) cint;
+  return *reinterpret_cast<cint*>(reinterpret_cast<uintptr_t>(p));
+}
+
 // Phase S of one sub-chunk: lane = target block (la, lb) of the track slice it serves; per-observation terms by the
 // lanes (local camera, row).  acc[] / dacc[] only ever see constant indices (they are registers of the caller).
-template <int PD, int RD>
+// A step's record reads hang on the slot bytes, which hang on the mask test: three dependent LDS round trips.  The mask word
+// and the slot bytes of a step are therefore read ONE STEP AHEAD -- unconditionally, at a track index clamped into the tables
+// (SUBT rows), the mask forced to zero where the step has no track for the lane, exactly the value the guarded read gave; a
+// slot byte of a track without the camera is garbage inside the table and only used behind the mask test -- so that a step
+// starts on registers and waits for its record reads only.  They are issued behind the step's products, where the 36 record
+// doubles are dead (the kernel has no register to spare while those are live), and arrive under the per-observation terms.
+template <int PD, int RD, int SUBT>
 THIP_DEV void fused_phase_s(const double* __restrict__ s_rec, const uint8_t* __restrict__ s_tslot, const unsigned* __restrict__ s_tmask,
                             int ntr, int tstride, int t0, bool slice_ok, unsigned tbits, int la, int lb, double diag_core,
                             int dP, int dbase, unsigned dbit, int dlc, int da, double (&acc)[36], double (&dacc)[3]) {
+  auto look_ahead = [&](int base, unsigned& mask, unsigned& ca, unsigned& cb) {
+    const int t = base + t0, tc = min(t, SUBT - 1);
+    const unsigned m = s_tmask[tc];
+    ca = s_tslot[tc * kRowBytes + la]; cb = s_tslot[tc * kRowBytes + lb];
+    mask = (slice_ok && t < ntr) ? m : 0u;
+  };
+  unsigned mask, ca, cb;
+  look_ahead(0, mask, ca, cb);
 #pragma unroll 1
   for (int base = 0; base < ntr; base += tstride) {   // wave-uniform trip count
-    {
-      const int t = base + t0;
-      const unsigned mask = (slice_ok && t < ntr) ? s_tmask[t] : 0u;
-      if ((mask & tbits) == tbits) {
-        const unsigned ca = s_tslot[t * kRowBytes + la], cb = s_tslot[t * kRowBytes + lb];
-        double Fa[12], Ea[2 * PD], Fb[12], Eb[2 * PD];
-        const double2* pa = reinterpret_cast<const double2*>(s_rec + ca * RD);
-        const double2* pb = reinterpret_cast<const double2*>(s_rec + cb * RD);
+    if ((mask & tbits) == tbits) {
+      double Fa[12], Ea[2 * PD], Fb[12], Eb[2 * PD];
+      const double2* pa = reinterpret_cast<const double2*>(s_rec + ca * RD);
+      const double2* pb = reinterpret_cast<const double2*>(s_rec + cb * RD);
+      // (the Ehat pieces first: the 2 x 2 core starts while F arrives)
 #pragma unroll
-        for (int q = 0; q < 6; ++q) { const double2 u = pa[q]; Fa[2 * q] = u.x; Fa[2 * q + 1] = u.y; }
+      for (int q = 0; q < PD; ++q) { const double2 u = pa[6 + q]; Ea[2 * q] = u.x; Ea[2 * q + 1] = u.y; }
 #pragma unroll
-        for (int q = 0; q < PD; ++q) { const double2 u = pa[6 + q]; Ea[2 * q] = u.x; Ea[2 * q + 1] = u.y; }
+      for (int q = 0; q < PD; ++q) { const double2 u = pb[6 + q]; Eb[2 * q] = u.x; Eb[2 * q + 1] = u.y; }
 #pragma unroll
-        for (int q = 0; q < 6; ++q) { const double2 u = pb[q]; Fb[2 * q] = u.x; Fb[2 * q + 1] = u.y; }
+      for (int q = 0; q < 6; ++q) { const double2 u = pa[q]; Fa[2 * q] = u.x; Fa[2 * q + 1] = u.y; }
 #pragma unroll
-        for (int q = 0; q < PD; ++q) { const double2 u = pb[6 + q]; Eb[2 * q] = u.x; Eb[2 * q + 1] = u.y; }
-        double M[2][2];   // Ehat_a Ehat_b^T
+      for (int q = 0; q < 6; ++q) { const double2 u = pb[q]; Fb[2 * q] = u.x; Fb[2 * q + 1] = u.y; }
+      double M[2][2];   // Ehat_a Ehat_b^T
 #pragma unroll
-        for (int i = 0; i < 2; ++i)
+      for (int i = 0; i < 2; ++i)
 #pragma unroll
-          for (int j = 0; j < 2; ++j) {
-            double sm = 0.0;
+        for (int j = 0; j < 2; ++j) {
+          double sm = 0.0;
 #pragma unroll
-            for (int q = 0; q < PD; ++q) sm += Ea[i * PD + q] * Eb[j * PD + q];
-            M[i][j] = sm;
-          }
-        M[0][0] -= diag_core; M[1][1] -= diag_core;
-#pragma unroll
-        for (int a = 0; a < 6; ++a) {
-          const double t0v = Fa[a] * M[0][0] + Fa[6 + a] * M[1][0];   // (F_a^T M)[a][0..1]
-          const double t1v = Fa[a] * M[0][1] + Fa[6 + a] * M[1][1];
-#pragma unroll
-          for (int b2 = 0; b2 < 6; ++b2)   // two chained FMAs: `acc += x y + z w` compiles to mul + fma + add (no reassociation)
-            acc[a * 6 + b2] = __builtin_fma(t1v, Fb[6 + b2], __builtin_fma(t0v, Fb[b2], acc[a * 6 + b2]));
+          for (int q = 0; q < PD; ++q) sm += Ea[i * PD + q] * Eb[j * PD + q];
+          M[i][j] = sm;
         }
+      M[0][0] -= diag_core; M[1][1] -= diag_core;
+#pragma unroll
+      for (int a = 0; a < 6; ++a) {
+        const double t0v = Fa[a] * M[0][0] + Fa[6 + a] * M[1][0];   // (F_a^T M)[a][0..1]
+        const double t1v = Fa[a] * M[0][1] + Fa[6 + a] * M[1][1];
+#pragma unroll
+        for (int b2 = 0; b2 < 6; ++b2)   // two chained FMAs: `acc += x y + z w` compiles to mul + fma + add (no reassociation)
+          acc[a * 6 + b2] = __builtin_fma(t1v, Fb[6 + b2], __builtin_fma(t0v, Fb[b2], acc[a * 6 + b2]));
       }
     }
+    look_ahead(base + tstride, mask, ca, cb);   // (issued here, where the 36 record doubles are dead; in flight under the terms below)
     // per-observation terms: lane = (local camera, row), over the dP tracks this wave serves in the step
 #pragma unroll 1
     for (int g2 = 0; g2 < dP; ++g2) {
       const int t = base + dbase + g2;
-      const unsigned mask = (t < ntr) ? s_tmask[t] : 0u;
-      if (mask & dbit) {
+      const unsigned dmask = (t < ntr) ? s_tmask[t] : 0u;
+      if (dmask & dbit) {
         const unsigned sd = s_tslot[t * kRowBytes + dlc];
         const double2* px = reinterpret_cast<const double2*>(s_rec + sd * RD);
         const double2 rr = px[6 + PD], rv = px[6 + PD + 1];   // r,  r - Ehat ghat
@@ -203,18 +221,34 @@ THIP_DEV void fused_phase_l5(const DevProblem& P, const LanePre<PD>& c, const do
     reinterpret_cast<unsigned*>(mine + NS)[0] = (active && is_tgt) ? (1u << c.lc) : 0u;
 #pragma unroll
     for (int k = 0; k < NS; ++k) tot[k] = 0.0;
-    for (int j = 0; j < sg.maxlen; ++j) {             // wave-uniform trip count
-      const bool take = j < sg.len;
-      const double* oth = s_rec + (wv * 64 + min(sg.start + j, 63)) * RD;
-      double v[NS];
+    // TB track positions per trip: the reads of all are issued before the first sum (one exposed round trip per trip, not
+    // per position), the sums follow in ascending position under the same predicate.  The slot offset moves by an increment
+    // clamped to the wave's last slot (a position behind maxlen, or behind lane 63, reads a valid slot and is not taken).
+    // PD = 4 keeps one position per trip and the offset made from the position: neither the 15 words more per position nor
+    // the running offset fit its registers (instances gained scratch).
+    constexpr int TB = PD == 3 ? 2 : 1;
+    const int olast = (wv * 64 + 63) * RD;
+    int o = (wv * 64 + sg.start) * RD;
+    for (int j = 0; j < sg.maxlen; j += TB) {         // wave-uniform trip count
+      double v[TB][NS];
+      unsigned ob[TB];
+      if constexpr (TB == 1) o = (wv * 64 + min(sg.start + j, 63)) * RD;
 #pragma unroll
-      for (int k = 0; k + 1 < NS; k += 2) { const double2 u = *reinterpret_cast<const double2*>(oth + k); v[k] = u.x; v[k + 1] = u.y; }
-      if constexpr (NS & 1) v[NS - 1] = oth[NS - 1];
-      const unsigned ob = reinterpret_cast<const unsigned*>(oth + NS)[0];
-      if (take) {
+      for (int h = 0; h < TB; ++h) {
+        const double* oth = s_rec + o;
 #pragma unroll
-        for (int k = 0; k < NS; ++k) tot[k] += v[k];
-        tmask |= ob;
+        for (int k = 0; k + 1 < NS; k += 2) { const double2 u = *reinterpret_cast<const double2*>(oth + k); v[h][k] = u.x; v[h][k + 1] = u.y; }
+        if constexpr (NS & 1) v[h][NS - 1] = oth[NS - 1];
+        ob[h] = reinterpret_cast<const unsigned*>(oth + NS)[0];
+        if constexpr (TB > 1) o = min(o + RD, olast);
+      }
+#pragma unroll
+      for (int h = 0; h < TB; ++h) {
+        if (j + h < sg.len) {
+#pragma unroll
+          for (int k = 0; k < NS; ++k) tot[k] += v[h][k];
+          tmask |= ob[h];
+        }
       }
     }
   }
@@ -373,7 +407,9 @@ __global__ __launch_bounds__(64 * TPS, THIP_FUSED_WAVES) void k_lin_schur(DevPro
   const FusedRun run = P.fruns[P.frun_order[rix]];
   const int nsc = (run.ntiles + TPS - 1) / TPS;
   // ---- the run's per-camera blocks (k_cam_prep) -> LDS, 16 B per thread and step
-  for (int j = tid; j < run.nstage * (kCamRot / 2); j += SUB) {
+  int rtid = tid;   // (behind an empty asm, as ctid of the slice combination below: what is made from it is made per run, not kept)
+  asm volatile("" : "+v"(rtid));
+  for (int j = rtid; j < run.nstage * (kCamRot / 2); j += SUB) {
     const int k = j / (kCamRot / 2), piece = j - k * (kCamRot / 2);
     const int cidx = P.frun_stage[run.stage_off + k];
     reinterpret_cast<double2*>(s_cam + k * kCamLds)[piece] = reinterpret_cast<const double2*>(P.camrot + (size_t)kCamRot * cidx)[piece];
@@ -427,6 +463,9 @@ __global__ __launch_bounds__(64 * TPS, THIP_FUSED_WAVES) void k_lin_schur(DevPro
     int ntile = 0; bool ntile_ok = false;
     const int scn = min(sc + 1, nsc - 1);   // (the last sub-chunk reloads itself: unconditional loads, nothing is used)
     pre_level1<PD, TPS>(P, run, scn, wv, lane, ntile, ntile_ok, nxt);
+    // the sub-chunk's track count, for phase S: a scalar load issued here, a whole phase L ahead of its use -- read behind the
+    // barrier it was a vector load whose wait also drained the pre_level2 gathers issued just before the barrier
+    const int ntr = uniform_load(P.tile_trk_end + min(run.tile0 + TPS * sc + TPS - 1, run.tile0 + run.ntiles - 1));
     if (P.fused_dbg & 16) __builtin_amdgcn_s_setprio(1);   // development: issue priority to the latency-bound phase
     unsigned* const tmask = s_tmask + (sc & 1) * SUBT;
     fused_phase_l5<PD, MODELS, LOSSK, STAMPS, FIRST>(P, cur, s_cam, run.W, tile, tile_ok, wv, lane, inv_radius, Vinv, tile_part, s_rec, s_tslot, tmask, stamps, scale_out);
@@ -440,9 +479,7 @@ __global__ __launch_bounds__(64 * TPS, THIP_FUSED_WAVES) void k_lin_schur(DevPro
     sk.lap(stamps, 7);
     // ------------------------------------------------------------------ phase S: lane = target block
     if (!(P.fused_dbg & 1)) {
-      const int last_tile = min(run.tile0 + TPS * sc + TPS - 1, run.tile0 + run.ntiles - 1);
-      const int ntr = P.tile_trk_end[last_tile];
-      fused_phase_s<PD, RD>(s_rec, s_tslot, tmask, ntr, tstride, t0, slice_ok, tbits, la, lb, diag_core, dP, dbase, dbit, dlc, da, acc, dacc);
+      fused_phase_s<PD, RD, SUBT>(s_rec, s_tslot, tmask, ntr, tstride, t0, slice_ok, tbits, la, lb, diag_core, dP, dbase, dbit, dlc, da, acc, dacc);
     }
     sk.lap(stamps, 8);
     if (!(P.fused_dbg & 32)) __builtin_amdgcn_s_setprio(0);
@@ -456,16 +493,20 @@ __global__ __launch_bounds__(64 * TPS, THIP_FUSED_WAVES) void k_lin_schur(DevPro
   double* scratch = s_rec;   // SUB x 18 doubles
   double* out = P.fpart + run.part_off;
   const int nrep = (G == 1) ? NWV * PS : NWV / G;
+  // (the thread index behind an empty asm: the addresses made from it below are then made here, once per run, instead of being
+  // hoisted out of the run loop into registers that stay live across phases L and S -- where the kernel has none to spare)
+  int ctid = tid;
+  asm volatile("" : "+v"(ctid));
 #pragma unroll
   for (int h = 0; h < 2; ++h) {   // fully unrolled: acc[] must only ever see constant indices (else it lives in scratch)
     if (h) __syncthreads();
 #pragma unroll
-    for (int q = 0; q < 18; ++q) scratch[tid * 18 + q] = acc[18 * h + q];
+    for (int q = 0; q < 18; ++q) scratch[ctid * 18 + q] = acc[18 * h + q];
     __syncthreads();
     // every ENTRY (target, q) of the half blocks is summed over the target's replicas, in slice order (the order, and so the
     // bits, of the one-lane-per-target loop this replaces: that left ntgt of the 256 lanes adding nrep - 1 rows of 18 each),
     // and leaves for the partial-sum buffer at once: consecutive threads on consecutive doubles of a 144-B half block
-    for (int e = tid; e < run.ntgt * 18; e += SUB) {
+    for (int e = ctid; e < run.ntgt * 18; e += SUB) {
       const int k = e / 18, q = e - 18 * k;
       double v = scratch[k * 18 + q];   // (replica 0 of target k is thread k)
       if (unequal) {   // the slices that own target k, slice by slice over the waves
@@ -488,13 +529,13 @@ __global__ __launch_bounds__(64 * TPS, THIP_FUSED_WAVES) void k_lin_schur(DevPro
   }
   __syncthreads();
 #pragma unroll
-  for (int q = 0; q < 3; ++q) scratch[tid * 3 + q] = dacc[q];
+  for (int q = 0; q < 3; ++q) scratch[ctid * 3 + q] = dacc[q];
   __syncthreads();
-  if (has_d && tid == dix) {
+  if (has_d && ctid == dix) {
     const int nrd = (G == 1) ? NWV : NWV / G;
     double v[3];
 #pragma unroll
-    for (int q = 0; q < 3; ++q) v[q] = scratch[tid * 3 + q];
+    for (int q = 0; q < 3; ++q) v[q] = scratch[ctid * 3 + q];
 #pragma unroll 1
     for (int r = 1; r < nrd; ++r) {
       const int oth = (G == 1) ? (r * 64 + dix) : (dix + r * G * 64);
@@ -708,13 +749,21 @@ __global__ __launch_bounds__(64 * TPS, WPS) void k_backsub_runs(DevProblem P, co
       *reinterpret_cast<double2*>(mine + 2) = make_double2(in[2], in[3]);
 #pragma unroll
       for (int k = 0; k < PD; ++k) tsum[k] = 0.0;
-      for (int j = 0; j < sg.maxlen; ++j) {
-        const double* oth = s_slot[wv] + min(sg.start + j, 63) * 4;
-        const double2 a = *reinterpret_cast<const double2*>(oth), b = *reinterpret_cast<const double2*>(oth + 2);
-        const double v4[4] = {a.x, a.y, b.x, b.y};
-        if (j < sg.len) {
+      // (two track positions per trip, read before the first sum and added in ascending position: as the track sums of k_lin_schur)
+      for (int j = 0; j < sg.maxlen; j += 2) {
+        double v4[2][4];
 #pragma unroll
-          for (int k = 0; k < PD; ++k) tsum[k] += v4[k];
+        for (int h = 0; h < 2; ++h) {   // (a position behind maxlen, or behind lane 63: a valid slot, not taken)
+          const double* oth = s_slot[wv] + min(sg.start + j + h, 63) * 4;
+          const double2 a = *reinterpret_cast<const double2*>(oth), b = *reinterpret_cast<const double2*>(oth + 2);
+          v4[h][0] = a.x; v4[h][1] = a.y; v4[h][2] = b.x; v4[h][3] = b.y;
+        }
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          if (j + h < sg.len) {
+#pragma unroll
+            for (int k = 0; k < PD; ++k) tsum[k] += v4[h][k];
+          }
         }
       }
     }
