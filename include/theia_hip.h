@@ -452,6 +452,40 @@ int theia_hip_ba_lm_chain(theia_ba_handle h, int32_t* folded);
  * by the empirical variance factor 2 * final_cost / redundancy (the caller's bookkeeping). */
 int theia_hip_ba_covariance(theia_ba_handle h, double* point_cov, double* cam_cov);
 
+/* Covariance blocks of a problem in which cameras and points are BOTH free: what BundleAdjuster::GetCovarianceForTrack(s)
+ * and GetCovarianceForView(s) (bundle_adjuster.cc:660-773) return when ceres::Covariance is handed the coupled problem of
+ * BundleAdjustReconstruction / BundleAdjustPartialReconstruction.  The result is the camera (6 x 6) and point (d x d)
+ * diagonal blocks of (J'J)^-1 at the handle's current state, with EVERY variable block in J -- camera extrinsics, the free
+ * intrinsics of variable groups, points -- J being the loss-corrected, unscaled Jacobian in tangent space with the
+ * camera-prior and depth-prior rows included.  With H = J'J = [U W; W' V] and S = U - W V^-1 W':
+ *   cam_cov[c]   = [S^-1]_cc,
+ *   point_cov[p] = V_p^-1 + V_p^-1 (sum over the observations a, b of p: W_ap' [S^-1]_ab W_bp) V_p^-1.
+ * view_sel / track_sel: camera / point indices whose blocks are wanted, NULL = all of them; only the columns of S^-1 these
+ * need are solved for, at most max_rhs_columns unit vectors at a time (0 = chosen by the library).
+ * cam_cov [num_cameras][6][6], point_cov [num_points][d][d], either may be NULL.  Blocks that are not selected, constant
+ * or unobserved are zero.  NOT multiplied by the empirical variance factor.
+ * Deviations from the reference, and limits:
+ *  - a partially constant camera (cam_const 1 or 2) comes back as the ambient 6 x 6 with zero rows and columns at its
+ *    frozen parameters; Ceres returns the (6 - k)-sized tangent block, which the reference writes into a Matrix6d unpadded;
+ *  - a pivot that is not positive, in a point block or in S, returns THEIA_HIP_ERR_INTERNAL ("rank deficient
+ *    (ceres::Covariance::Compute fails)").  A point block's pivot below 1e-13 of its diagonal entry counts as not positive
+ *    (a track with one observation, an un-parametrised homogeneous point: the exact value is zero).  No other rank test is
+ *    made: on a gauge-free problem the pivots of S are rounding noise of either sign and the result is the caller's
+ *    business, as with Ceres;
+ *  - the covariance of the intrinsics blocks themselves and cross-covariances between blocks are not returned;
+ *  - inverse-depth handles and sharded handles: THEIA_HIP_ERR_UNSUPPORTED; a workspace that does not fit (the factored
+ *    copy of S, X [needed columns][n], the per-observation Jacobians): THEIA_HIP_ERR_OUT_OF_MEMORY.
+ * The handle stays usable: the next run() starts from the same state. */
+int theia_hip_ba_covariance_full(theia_ba_handle h, int32_t num_view_sel, const int32_t* view_sel, int32_t num_track_sel,
+                                 const int32_t* track_sel, int32_t max_rhs_columns, double* cam_cov, double* point_cov);
+/* Device time of the phases of the last theia_hip_ba_covariance_full call of this process, in milliseconds:
+ * {linearisation + Jacobians + copy, factorisation, column solves, block kernels}. */
+int theia_hip_ba_covariance_full_timing(double* phase_ms);
+/* Tangent dimensions of the handle's variable blocks: 6 minus the frozen parameters per variable camera, the free
+ * intrinsics of every variable group, d per variable point -- the "free parameters" of the variance factor
+ * 2 * final_cost / (number of residuals - free parameters) of a coupled problem. */
+int theia_hip_ba_free_parameter_count(theia_ba_handle h, int64_t* count);
+
 
 /* Introspection used by parity tests (device results copied to host):
  *  - per-observation residual r[2] and Jacobian blocks J_cam[2][6],

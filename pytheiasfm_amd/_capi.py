@@ -389,7 +389,7 @@ EXPORTED_SYMBOLS = [
     "theia_hip_init", "theia_hip_shutdown", "theia_hip_device_count", "theia_hip_last_error",
     "theia_hip_version", "theia_ba_options_default", "theia_hip_ba_solve", "theia_hip_ba_views_batch", "theia_hip_ba_two_views_angular_batch", "theia_hip_ba_two_views_batch", "theia_hip_optimize_homography_batch", "theia_hip_optimize_fundamental_matrix_batch", "theia_hip_ba_tracks_batch", "theia_hip_track_statistics", "theia_hip_ba_create",
     "theia_hip_ba_reset_parameters", "theia_hip_estimate_tracks", "theia_hip_ba_set_shard", "theia_hip_ba_snapshot_parameters", "theia_hip_ba_restore_parameters", "theia_hip_ba_set_options", "theia_hip_ba_run", "theia_hip_ba_download",
-    "theia_hip_ba_destroy", "theia_hip_ba_covariance", "theia_hip_ba_evaluate", "theia_hip_ba_evaluate_ex", "theia_hip_ba_reduced_system",
+    "theia_hip_ba_destroy", "theia_hip_ba_covariance", "theia_hip_ba_covariance_full", "theia_hip_ba_covariance_full_timing", "theia_hip_ba_free_parameter_count", "theia_hip_ba_evaluate", "theia_hip_ba_evaluate_ex", "theia_hip_ba_reduced_system",
     "theia_hip_ba_set_allreduce", "theia_hip_ba_set_inner_global", "theia_hip_ba_plan_info", "theia_hip_ba_kernel_instances", "theia_hip_ba_lm_chain", "theia_hip_rccl_unique_id", "theia_hip_rccl_comm_create",
     "theia_hip_optimize_relative_position_batch", "theia_hip_rccl_comm_destroy", "theia_hip_rccl_comm_count", "theia_hip_ba_set_rccl", "theia_hip_dense_spd_solve", "theia_hip_dense_spd_solve_multi", "theia_hip_tile_sparse_spd_solve", "theia_hip_tile_sparse_spd_solve_sharded", "theia_hip_robust_rotation_averaging", "theia_hip_linear_rotations", "theia_hip_lagrange_dual_rotations", "theia_hip_nonlinear_rotations", "theia_hip_nonlinear_positions", "theia_hip_lud_positions", "theia_hip_ligt_positions", "theia_hip_linear_triplet_positions", "theia_hip_filter_view_pairs_from_relative_translation", "theia_hip_translation_filter_last_stats", "theia_hip_filter_view_pairs_from_orientation", "theia_hip_filter_view_graph_cycles_by_rotation", "theia_hip_remove_disconnected_view_pairs", "theia_ransac_params_default",
     "theia_hip_ransac_estimate_batch", "theia_hip_five_point_relative_pose",

@@ -127,6 +127,46 @@ class BaHandle:
                                              capi.ptr(cc, C.c_double) if cameras else None))
         return pc, cc
 
+    def covariance_full(self, cameras=False, points=False, view_sel=None, track_sel=None, max_rhs_columns=0):
+        """theia_hip_ba_covariance_full at the current state, cameras and points both free: the blocks of (J'J)^-1 of the
+        coupled problem, (cam_cov [nc][6][6] or None, point_cov [np][d][d] or None).  view_sel / track_sel: the camera /
+        point indices wanted (None = all); the other blocks, constant and unobserved ones are zero."""
+        L = capi.lib()
+        L.theia_hip_ba_covariance_full.argtypes = [C.c_void_p, C.c_int32, capi.c_int32_p, C.c_int32, capi.c_int32_p, C.c_int32,
+                                                   capi.c_double_p, capi.c_double_p]
+        vs = None if view_sel is None else np.ascontiguousarray(view_sel, dtype=np.int32).reshape(-1)
+        ts = None if track_sel is None else np.ascontiguousarray(track_sel, dtype=np.int32).reshape(-1)
+        # (an empty list selects nothing; NULL selects everything: keep one element behind an empty selection's pointer)
+        vbuf = None if vs is None else (vs if len(vs) else np.zeros(1, np.int32))
+        tbuf = None if ts is None else (ts if len(ts) else np.zeros(1, np.int32))
+        cc = np.zeros((self.problem.cam_ext.shape[0], 6, 6)) if cameras else None
+        pc = np.zeros((self.problem.points.shape[0], self.pd, self.pd)) if points else None
+        want_c = cameras and not (vs is not None and len(vs) == 0)
+        want_p = points and not (ts is not None and len(ts) == 0)
+        capi.check(L.theia_hip_ba_covariance_full(
+            self._h, 0 if vs is None else len(vs), capi.ptr(vbuf, C.c_int32) if vbuf is not None else None,
+            0 if ts is None else len(ts), capi.ptr(tbuf, C.c_int32) if tbuf is not None else None, int(max_rhs_columns),
+            capi.ptr(cc, C.c_double) if want_c else None, capi.ptr(pc, C.c_double) if want_p else None))
+        return cc, pc
+
+    def covariance_full_timing(self):
+        """Device milliseconds of the last covariance_full(): linearisation + Jacobians + copy, factorisation, column
+        solves, block kernels."""
+        L = capi.lib()
+        L.theia_hip_ba_covariance_full_timing.argtypes = [capi.c_double_p]
+        ms = np.zeros(4)
+        capi.check(L.theia_hip_ba_covariance_full_timing(capi.ptr(ms, C.c_double)))
+        return {"linearise": ms[0], "factor": ms[1], "solve": ms[2], "blocks": ms[3]}
+
+    def free_parameter_count(self):
+        """theia_hip_ba_free_parameter_count: tangent dimensions of the variable blocks (camera extrinsics that are not
+        frozen, free intrinsics of variable groups, variable points)."""
+        L = capi.lib()
+        L.theia_hip_ba_free_parameter_count.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        n = C.c_int64(0)
+        capi.check(L.theia_hip_ba_free_parameter_count(self._h, C.byref(n)))
+        return n.value
+
     def evaluate(self):
         n = self.problem.obs_uv.shape[0]
         cost = C.c_double(0)

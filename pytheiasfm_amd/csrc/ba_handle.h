@@ -1,5 +1,5 @@
 // ba_handle.h -- what the translation units of the BA handle API share (ba_plan.hip: create; ba_solver.hip: the LM side;
-// ba_query.hip: evaluate, covariance, reduced system): the pinned staging arena and the pooled device buffer, the handle
+// ba_query.hip: evaluate, covariance, reduced system; ba_covariance.hip: the covariance of the coupled problem): the pinned staging arena and the pooled device buffer, the handle
 // itself, the host threading of its passes, the device-resident LM state, and the handle-level functions of ba_solver.hip.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -99,7 +99,7 @@ struct PoolBuf {
 
 }  // namespace thip
 
-using namespace thip;   // (an internal header: its three includers speak of the library's own names unqualified)
+using namespace thip;   // (an internal header: its includers speak of the library's own names unqualified)
 struct theia_ba_handle_s {
   theia_ba_options opt;
   void* idh = nullptr;   // inverse-depth problems (THEIA_BA_FLAG_INVERSE_DEPTH) live in their own object (ba_invdepth.hip): create / reset / run / download only

@@ -670,6 +670,61 @@ def BundleAdjustViewWithCov(reconstruction, options, view_id):
     return summary, covs.get(int(view_id), np.eye(6)), factor
 
 
+def _coupled_with_cov(options, reconstruction, flat, track_ids, cov_view_ids, cov_track_ids):
+    """The solve of a problem with free cameras AND free points on one handle, then theia_hip_ba_covariance_full for the
+    listed views / tracks (None: the problem's free ones) times 2 * final_cost / (2 * #observations - #free parameters)."""
+    options = _no_inner(options)
+    c_opts = options.to_c()
+    free_views = np.flatnonzero(np.asarray(flat.cam_const) == 0)
+    free_tracks = np.flatnonzero(np.asarray(flat.point_const) == 0)
+    views = [int(v) for v in (free_views if cov_view_ids is None else cov_view_ids)]
+    tracks = [int(t) for t in (free_tracks if cov_track_ids is None else cov_track_ids)]
+    with _ba.BaHandle(flat, c_opts) as h:
+        s, _ = h.run()
+        h.download(flat)
+        summary = BundleAdjustmentSummary(s)
+        if not summary.success:
+            return summary, {}, {}, 1.0
+        try:
+            cc, pc = h.covariance_full(cameras=True, points=True, view_sel=views, track_sel=tracks)
+            free = h.free_parameter_count()
+        except capi.TheiaHipError:
+            summary.success = False      # GetCovarianceFor* returned false
+            return summary, {}, {}, 1.0
+    reconstruction.cam_ext[:] = flat.cam_ext
+    reconstruction.points[:] = flat.points
+    reconstruction.group_intrinsics[:] = flat.intrinsics
+    _update_inverse_depth(reconstruction, track_ids)
+    factor = (2.0 * summary.final_cost) / (2.0 * flat.obs_uv.shape[0] - free)
+    d = cc.shape[-1] if pc is None else pc.shape[-1]
+    return (summary, {v: (cc[v] * factor if cc is not None else np.zeros((6, 6))) for v in views},
+            {t: (pc[t] * factor if pc is not None else np.zeros((d, d))) for t in tracks}, factor)
+
+
+def BundleAdjustPartialReconstructionWithCov(options, view_ids, track_ids, reconstruction, cov_view_ids=None, cov_track_ids=None):
+    """BundleAdjustPartialReconstruction (bundle_adjustment.cc:111-143) followed by BundleAdjuster::GetCovarianceForViews /
+    GetCovarianceForTracks (bundle_adjuster.cc:660-773) on the same, coupled problem.  There is NO pyTheia function of this
+    name: the reference exposes the two getters on the adjuster only, and its *WithCov free functions cover the block-diagonal
+    problems.  Inner iterations are off, as in the other *WithCov functions.  cov_view_ids / cov_track_ids: the views / tracks
+    whose covariance is wanted (None: every free one).  Returns (summary, {view: 6 x 6}, {track: d x d}, variance_factor);
+    the blocks are those of (J'J)^-1 with cameras, free intrinsics and points in J, times the variance factor
+    2 * final_cost / (2 * #observations - #free parameters).  If the covariance cannot be computed (rank deficient J'J)
+    summary.success is False and the dictionaries are empty."""
+    if options.use_inverse_depth_parametrization:
+        raise capi.TheiaHipError(capi.THEIA_HIP_ERR_UNSUPPORTED, "covariance of the coupled problem: not built for the inverse-depth parametrisation")
+    flat = _flatten(reconstruction, view_ids, track_ids, options=options)
+    return _coupled_with_cov(options, reconstruction, flat, list(track_ids), cov_view_ids, cov_track_ids)
+
+
+def BundleAdjustReconstructionWithCov(options, reconstruction, cov_view_ids=None, cov_track_ids=None):
+    """BundleAdjustReconstruction (bundle_adjustment.cc:188-217) followed by BundleAdjuster::GetCovarianceForViews / Tracks
+    on the full problem; see BundleAdjustPartialReconstructionWithCov (no pyTheia function of this name either).  With every
+    view free the gauge is free too: J'J is rank deficient unless priors or constant views fix it, and the call then
+    reports success = False or noise, as ceres::Covariance would."""
+    return BundleAdjustPartialReconstructionWithCov(options, reconstruction.ViewIds(), reconstruction.TrackIds(), reconstruction,
+                                                    cov_view_ids, cov_track_ids)
+
+
 def SetOutlierTracksToUnestimated(track_ids, max_inlier_reprojection_error, min_triangulation_angle_degrees, reconstruction):
     """set_outlier_tracks_to_unestimated.cc:64-139 (the sweep that brackets every full BA in the estimators):
     un-estimates tracks that reproject behind a camera, whose mean squared reprojection error exceeds the

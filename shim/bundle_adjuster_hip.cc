@@ -114,9 +114,11 @@ int datum_doubles(int estimator) {
 }
 }  // namespace
 
-// ceres::Covariance of the block-diagonal problems behind the *WithCov entry points: the state the registered pointers hold
-// now (i.e. after Optimize()), through a device handle (theia_hip_ba_create + theia_hip_ba_covariance)
-bool BundleAdjuster::covariances(std::vector<double>* point_cov, std::vector<double>* cam_cov) {
+// ceres::Covariance at the state the registered pointers hold now (i.e. after Optimize()), through a device handle: the
+// block-diagonal problems behind the *WithCov entry points by theia_hip_ba_covariance, a problem with variable cameras AND
+// variable tracks by theia_hip_ba_covariance_full (the blocks of the coupled (J'J)^-1; view_sel / track_sel: the blocks wanted)
+bool BundleAdjuster::covariances(std::vector<double>* point_cov, std::vector<double>* cam_cov, const std::vector<int32_t>& view_sel,
+                                 const std::vector<int32_t>& track_sel) {
   const int nc = (int)cam_ptr_.size(), np = (int)pt_ptr_.size(), ng = (int)group_ptr_.size();
   std::vector<double> cam(6 * (size_t)nc), pts(4 * (size_t)np), intr((size_t)THEIA_MAX_INTRINSICS * ng, 0.0);
   std::vector<int32_t> cam_group(nc);
@@ -141,7 +143,16 @@ bool BundleAdjuster::covariances(std::vector<double>* point_cov, std::vector<dou
   const int d = options_.use_homogeneous_point_parametrization ? 3 : 4;
   if (point_cov) point_cov->assign((size_t)np * d * d, 0.0);
   if (cam_cov) cam_cov->assign((size_t)nc * 36, 0.0);
-  const int rc = theia_hip_ba_covariance(h, point_cov ? point_cov->data() : nullptr, cam_cov ? cam_cov->data() : nullptr);
+  bool var_cam = false, var_pt = false;
+  for (uint8_t c : cam_const_) var_cam |= (c & THEIA_CAM_CONST_ALL) != THEIA_CAM_CONST_ALL;
+  for (uint8_t c : point_const_) var_pt |= c == 0;
+  var_cam = var_cam && !(options_.constant_camera_orientation && options_.constant_camera_position);
+  int rc;
+  if (var_cam && var_pt)
+    rc = theia_hip_ba_covariance_full(h, (int32_t)view_sel.size(), view_sel.data(), (int32_t)track_sel.size(), track_sel.data(), 0,
+                                      cam_cov ? cam_cov->data() : nullptr, point_cov ? point_cov->data() : nullptr);
+  else
+    rc = theia_hip_ba_covariance(h, point_cov ? point_cov->data() : nullptr, cam_cov ? cam_cov->data() : nullptr);
   if (rc != THEIA_HIP_OK) error_ = theia_hip_last_error();
   theia_hip_ba_destroy(h);
   return rc == THEIA_HIP_OK;
@@ -149,12 +160,17 @@ bool BundleAdjuster::covariances(std::vector<double>* point_cov, std::vector<dou
 
 bool BundleAdjuster::GetCovarianceForTracks(const std::vector<TrackId>& tracks, std::vector<std::vector<double>>* covariances_out) {
   std::vector<double> pc;
-  if (!covariances(&pc, nullptr)) return false;
+  std::vector<int32_t> sel;
+  for (TrackId t : tracks) {
+    const auto it = track_index_.find(t);
+    if (it == track_index_.end()) { error_ = "unknown track"; return false; }
+    sel.push_back(it->second);
+  }
+  if (!covariances(&pc, nullptr, {}, sel)) return false;
   const int d = options_.use_homogeneous_point_parametrization ? 3 : 4;
   covariances_out->clear();
   for (TrackId t : tracks) {
     const auto it = track_index_.find(t);
-    if (it == track_index_.end()) { error_ = "unknown track"; return false; }
     covariances_out->emplace_back(pc.begin() + (size_t)it->second * d * d, pc.begin() + (size_t)(it->second + 1) * d * d);
   }
   return true;
@@ -162,11 +178,16 @@ bool BundleAdjuster::GetCovarianceForTracks(const std::vector<TrackId>& tracks, 
 
 bool BundleAdjuster::GetCovarianceForViews(const std::vector<ViewId>& views, std::vector<std::vector<double>>* covariances_out) {
   std::vector<double> cc;
-  if (!covariances(nullptr, &cc)) return false;
-  covariances_out->clear();
+  std::vector<int32_t> sel;
   for (ViewId v : views) {
     const auto it = view_index_.find(v);
     if (it == view_index_.end()) { error_ = "unknown view"; return false; }
+    sel.push_back(it->second);
+  }
+  if (!covariances(nullptr, &cc, sel, {})) return false;
+  covariances_out->clear();
+  for (ViewId v : views) {
+    const auto it = view_index_.find(v);
     covariances_out->emplace_back(cc.begin() + (size_t)it->second * 36, cc.begin() + (size_t)(it->second + 1) * 36);
   }
   return true;

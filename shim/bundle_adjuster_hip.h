@@ -67,11 +67,13 @@ class BundleAdjuster {
   void SetTrackVariable(TrackId track);            // :529-536
 
   BundleAdjustmentSummary Optimize();              // :315-355
-  // GetCovarianceForTracks (:705-741) after Optimize() with every camera constant: covariance[i] is the 3 x 3 tangent-space
-  // block of tracks[i] (row-major; SphereManifold<4>), as ceres::Covariance returns it.  NOT multiplied by the empirical
-  // variance factor (bundle_adjustment.cc:312-320 does that bookkeeping).  False + error() on failure.
+  // GetCovarianceForTracks (:705-741) after Optimize(): covariance[i] is the 3 x 3 tangent-space block of tracks[i]
+  // (row-major; SphereManifold<4>), as ceres::Covariance returns it -- the inverse of the track's own block when every camera
+  // is constant, the block of the coupled (J'J)^-1 when cameras and tracks are both variable (theia_hip_ba_covariance_full).
+  // NOT multiplied by the empirical variance factor (bundle_adjustment.cc:312-320 does that bookkeeping).  False + error() on failure.
   bool GetCovarianceForTracks(const std::vector<TrackId>& tracks, std::vector<std::vector<double>>* covariances);
-  // GetCovarianceForViews (:743-773) with every track constant: the 6 x 6 block of each view's extrinsics.
+  // GetCovarianceForViews (:743-773): the 6 x 6 block of each view's extrinsics, with every track constant or in the coupled
+  // problem; a partially constant camera comes back as the ambient 6 x 6 with zero rows and columns at its frozen parameters.
   bool GetCovarianceForViews(const std::vector<ViewId>& views, std::vector<std::vector<double>>* covariances);
   const std::string& error() const { return error_; }
 
@@ -85,7 +87,8 @@ class BundleAdjuster {
   std::vector<uint8_t> cam_const_, point_const_;
   std::vector<double> obs_uv_, obs_sqrt_info_;
   std::string error_;
-  bool covariances(std::vector<double>* point_cov, std::vector<double>* cam_cov);
+  bool covariances(std::vector<double>* point_cov, std::vector<double>* cam_cov, const std::vector<int32_t>& view_sel,
+                   const std::vector<int32_t>& track_sel);
 };
 
 // bundle_adjustment.cc:220-260 / :262-285: N x BundleAdjustView (one camera against constant points) and BundleAdjustTrack for
