@@ -1714,6 +1714,88 @@ typedef struct theia_align_rotations_summary {
 int theia_hip_align_rotations(int32_t num_rotations, const double* gt_rotation /*[n][3]*/, double* rotation /*[n][3], in/out*/,
                               double* alignment /*[3], out*/, theia_align_rotations_summary* summary /*or NULL*/,
                               double* trace_out /*optional*/, int32_t trace_capacity);
+/* ---- Sim(3) point-cloud alignment (csrc/sim3_alignment.hip, csrc/sim3_device.h) ----
+ * The tangent of Sim(3) is Sophus': a [7] = upsilon (3) | omega (3) | sigma, with Sim3::exp(a) = (exp(sigma) R(omega),
+ * W(omega, sigma) upsilon).  (The reference's comments name another order; its code uses this one.)
+ *
+ * theia_hip_sim3_maps: `count` conversions, one lane each.
+ *   THEIA_SIM3_MAP_EXP         in a [7]                     out sR [9] row-major | t [3]      Sophus::Sim3d::exp (sim3.hpp:557-572)
+ *   THEIA_SIM3_MAP_LOG         in scale | R [9] | t [3]     out a [7]                         Sim3d(RxSO3d(scale, R), t).log() (:144-164)
+ *   THEIA_SIM3_MAP_FROM_RTS    in R [9] | t [3] | scale     out a [7]                         Sim3FromRotationTranslationScale
+ *                                                                                            (align_point_clouds.cc:288-298)
+ *   THEIA_SIM3_MAP_TO_RTS      in a [7]                     out R [9] | t [3] | scale         Sim3ToRotationTranslationScale (:300-317)
+ *   THEIA_SIM3_MAP_TO_MATRIX4  in a [7]                     out [4][4] row-major              Sim3ToHomogeneousMatrix
+ *                                                                                            (transformation_wrapper.cc:125-132)
+ * LOG / FROM_RTS write NaN where Sophus would abort (a scale outside [1e-10, 1e10)).  THEIA_HIP_ERR_INVALID_ARGUMENT: an
+ * unknown op, count < 0, a NULL array with count > 0.  count == 0 returns 0. */
+enum { THEIA_SIM3_MAP_EXP = 0, THEIA_SIM3_MAP_LOG = 1, THEIA_SIM3_MAP_FROM_RTS = 2, THEIA_SIM3_MAP_TO_RTS = 3,
+       THEIA_SIM3_MAP_TO_MATRIX4 = 4 };
+int theia_hip_sim3_maps(int32_t op, int64_t count, const double* in, double* out);
+/* OptimizeAlignmentSim3's ceres::Solve (align_point_clouds.cc:200-282, alignment_error.h:60-161) for a batch of problems,
+ * restated on the device: the thirteenth Levenberg-Marquardt loop on the rules of csrc/lm_rules.h.  Problem p owns the
+ * points offsets[p] .. offsets[p + 1] of source, target [.][3], weights [.] and normals [.][3]; one 7-parameter block that
+ * starts at start[p]; one residual block per point:
+ *   THEIA_SIM3_POINT_TO_POINT          w_i (y_i - exp(a) x_i)                       (3 rows)
+ *   THEIA_SIM3_ROBUST_POINT_TO_POINT   the same under ceres::HuberLoss(huber_threshold)
+ *   THEIA_SIM3_POINT_TO_PLANE          w_i n_i . (y_i - exp(a) x_i), n_i normalised (1 row); with normals == NULL
+ *                                      point-to-point, as the reference falls back (:228-238)
+ * w_i = weights[i], or options[p].point_weight when weights == NULL; the weight multiplies the residual (it is not
+ * squared, and may be negative or zero).  Jacobians in closed form, equal to what Ceres' Jets give in every branch of
+ * Sophus' maps.  Options as :258-266 leave them with Ceres 2.2: max_num_iterations = max_iterations, function tolerance
+ * 1e-6, gradient tolerance 1e-10, parameter tolerance 1e-8, initial radius 1e4, maximum radius 1e16, Jacobi scaling.
+ * The entry starts where `start` says and has no policy of its own (the reference as written always starts at
+ * (0,0,0,0,0,0,1); pytheiasfm_amd/alignment.py keeps that).
+ * STATED DEVIATIONS: SPARSE_SCHUR over the single 7-block is solved as the 7 x 7 normal equations (Cholesky) -- the same
+ * system in exact arithmetic; the sums over the points are fixed trees, not sequential: rounding level.  A problem's output
+ * bytes do not depend on the other problems of the batch nor on the run.
+ * Problems of up to THEIA_SIM3_GROUP_MAX_POINTS points run whole in one workgroup and one launch (all of them together);
+ * a larger one runs two kernels per pass over a grid that depends on its point count only (summary.route = 1).
+ * A failed factorisation, a non-finite step or a model cost change that is not positive is an invalid step; after
+ * THEIA_SIM3_TERM_FAILURE (five in a row) params_out = start.  A problem without points is no error: THEIA_SIM3_TERM_NO_POINTS,
+ * success 0, params_out = start (:172-175).
+ * params_out [P][7]; summary_out [P]; trace_out (optional) [P][trace_capacity][5] = (cost, gradient max norm, step norm,
+ * radius, accepted) per row as theia_hip_align_rotations writes them, summary.trace_size rows per problem; timings_ms
+ * (optional) [2] = the kernels (device events) | the whole call.  Returns 0 whatever the terminations.
+ * THEIA_HIP_ERR_INVALID_ARGUMENT before the device is touched and with no output written: num_problems < 0; a NULL offsets,
+ * start, options, params_out or summary_out, or a NULL source / target with points; offsets[0] != 0 or descending offsets; a
+ * non-finite coordinate, weight, normal (when normals are read) or start; a zero normal; max_iterations < 0;
+ * huber_threshold <= 0 for the robust type; an unknown type; trace_capacity < 0, or > 0 with a NULL trace_out.
+ * num_problems == 0 returns 0. */
+enum { THEIA_SIM3_POINT_TO_POINT = 0, THEIA_SIM3_ROBUST_POINT_TO_POINT = 1, THEIA_SIM3_POINT_TO_PLANE = 2 };
+enum {
+  THEIA_SIM3_TERM_NO_POINTS = 0,
+  THEIA_SIM3_TERM_GRADIENT_TOLERANCE = 1,    /* 1, 2, 3, 6: ceres::CONVERGENCE */
+  THEIA_SIM3_TERM_FUNCTION_TOLERANCE = 2,
+  THEIA_SIM3_TERM_PARAMETER_TOLERANCE = 3,
+  THEIA_SIM3_TERM_MAX_ITERATIONS = 4,        /* ceres::NO_CONVERGENCE */
+  THEIA_SIM3_TERM_FAILURE = 5,               /* ceres::FAILURE */
+  THEIA_SIM3_TERM_MIN_RADIUS = 6
+};
+/* The largest problem of the group route.  Measured on the MI355X. */
+#define THEIA_SIM3_GROUP_MAX_POINTS 4096
+typedef struct theia_sim3_alignment_options {
+  int32_t alignment_type;          /* THEIA_SIM3_* */
+  int32_t max_iterations;
+  double point_weight;
+  double huber_threshold;
+} theia_sim3_alignment_options;
+typedef struct theia_sim3_alignment_summary {
+  int32_t termination;             /* THEIA_SIM3_TERM_* */
+  int32_t success;                 /* 1 iff ceres::CONVERGENCE (:269) */
+  int32_t num_iterations;          /* Ceres' summary.iterations.size() (:271): iteration 0 and every iteration that ended
+                                      in an accepted, rejected or (non-final) invalid step */
+  int32_t num_successful_steps, num_unsuccessful_steps, num_invalid_steps;
+  int32_t trace_size;
+  int32_t route;                   /* 0: one workgroup; 1: the grid */
+  double initial_cost, final_cost;
+  double alignment_error;          /* mean |y_i - exp(a) x_i|, unweighted, at params_out (:275-281) */
+} theia_sim3_alignment_summary;
+int theia_hip_optimize_alignment_sim3(int32_t num_problems, const int64_t* offsets /*[P+1]*/, const double* source /*[.][3]*/,
+                                      const double* target /*[.][3]*/, const double* weights /*[.] or NULL*/,
+                                      const double* normals /*[.][3] or NULL*/, const double* start /*[P][7]*/,
+                                      const theia_sim3_alignment_options* options /*[P]*/, double* params_out /*[P][7]*/,
+                                      theia_sim3_alignment_summary* summary_out /*[P]*/, double* trace_out /*optional*/,
+                                      int32_t trace_capacity, double* timings_ms /*[2] or NULL*/);
 /* n draws of RandomNumberGenerator(seed).RandInt(lo, hi) (util/random.cc:46-84): host code that follows the reference's
  * generator outside the RANSAC sampler (the random candidates of GuidedEpipolarMatcher::FindFeaturesNearEpipolarLines). */
 int theia_hip_randint_stream(uint32_t seed, int32_t n, int32_t lo, int32_t hi, int32_t* out);

@@ -13,4 +13,7 @@ from . import alignment  # noqa: E402,F401
 from .alignment import (AlignPointCloudsUmeyama, AlignPointCloudsUmeyamaWithWeights,  # noqa: E402,F401
                         AlignPointCloudsUmeyamaBatch, AlignPointCloudsUmeyamaWithWeightsBatch, AlignReconstructions,
                         AlignReconstructionsRobust, TransformReconstruction, TransformReconstruction4,
-                        FindCommonViewsByName, AlignRotations, AlignOrientations)
+                        FindCommonViewsByName, AlignRotations, AlignOrientations,
+                        Sim3AlignmentType, Sim3AlignmentOptions, Sim3AlignmentSummary, OptimizeAlignmentSim3,
+                        OptimizeAlignmentSim3Batch, Sim3FromRotationTranslationScale, Sim3ToRotationTranslationScale,
+                        Sim3ToHomogeneousMatrix)

@@ -382,6 +382,34 @@ class AlignRotationsSummary(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+# theia_hip.h THEIA_SIM3_*: the maps of theia_hip_sim3_maps, the residual kinds and terminations of
+# theia_hip_optimize_alignment_sim3, and the largest problem of its one-workgroup route
+THEIA_SIM3_MAP_EXP, THEIA_SIM3_MAP_LOG, THEIA_SIM3_MAP_FROM_RTS, THEIA_SIM3_MAP_TO_RTS, THEIA_SIM3_MAP_TO_MATRIX4 = range(5)
+THEIA_SIM3_MAP_WIDTHS = {0: (7, 12), 1: (13, 7), 2: (13, 7), 3: (7, 13), 4: (7, 16)}   # doubles in, out per item
+THEIA_SIM3_POINT_TO_POINT, THEIA_SIM3_ROBUST_POINT_TO_POINT, THEIA_SIM3_POINT_TO_PLANE = 0, 1, 2
+(THEIA_SIM3_TERM_NO_POINTS, THEIA_SIM3_TERM_GRADIENT_TOLERANCE, THEIA_SIM3_TERM_FUNCTION_TOLERANCE,
+ THEIA_SIM3_TERM_PARAMETER_TOLERANCE, THEIA_SIM3_TERM_MAX_ITERATIONS, THEIA_SIM3_TERM_FAILURE,
+ THEIA_SIM3_TERM_MIN_RADIUS) = range(7)
+THEIA_SIM3_GROUP_MAX_POINTS = 4096
+
+
+class Sim3AlignmentOptionsC(C.Structure):
+    """theia_sim3_alignment_options."""
+    _fields_ = [("alignment_type", C.c_int32), ("max_iterations", C.c_int32), ("point_weight", C.c_double),
+                ("huber_threshold", C.c_double)]
+
+
+class Sim3AlignmentSummaryC(C.Structure):
+    """theia_sim3_alignment_summary."""
+    _fields_ = [("termination", C.c_int32), ("success", C.c_int32), ("num_iterations", C.c_int32),
+                ("num_successful_steps", C.c_int32), ("num_unsuccessful_steps", C.c_int32), ("num_invalid_steps", C.c_int32),
+                ("trace_size", C.c_int32), ("route", C.c_int32), ("initial_cost", C.c_double), ("final_cost", C.c_double),
+                ("alignment_error", C.c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p)
 
 # every symbol include/theia_hip.h declares (checked by tests/test_capi_symbols.py)
@@ -393,7 +421,7 @@ EXPORTED_SYMBOLS = [
     "theia_hip_ba_set_allreduce", "theia_hip_ba_set_inner_global", "theia_hip_ba_plan_info", "theia_hip_ba_kernel_instances", "theia_hip_ba_lm_chain", "theia_hip_rccl_unique_id", "theia_hip_rccl_comm_create",
     "theia_hip_optimize_relative_position_batch", "theia_hip_rccl_comm_destroy", "theia_hip_rccl_comm_count", "theia_hip_ba_set_rccl", "theia_hip_dense_spd_solve", "theia_hip_dense_spd_solve_multi", "theia_hip_tile_sparse_spd_solve", "theia_hip_tile_sparse_spd_solve_sharded", "theia_hip_robust_rotation_averaging", "theia_hip_linear_rotations", "theia_hip_lagrange_dual_rotations", "theia_hip_nonlinear_rotations", "theia_hip_nonlinear_positions", "theia_hip_lud_positions", "theia_hip_ligt_positions", "theia_hip_linear_triplet_positions", "theia_hip_filter_view_pairs_from_relative_translation", "theia_hip_translation_filter_last_stats", "theia_hip_filter_view_pairs_from_orientation", "theia_hip_filter_view_graph_cycles_by_rotation", "theia_hip_remove_disconnected_view_pairs", "theia_ransac_params_default",
     "theia_hip_ransac_estimate_batch", "theia_hip_five_point_relative_pose",
-    "theia_hip_pose_from_three_points", "theia_hip_sqpnp", "theia_hip_dls_pnp", "theia_hip_dls_macaulay_terms", "theia_hip_four_point_pose_and_focal_length", "theia_hip_four_point_focal_length_radial_distortion", "theia_hip_four_point_focal_length_radial_distortion_ex", "theia_hip_release_scratch", "theia_hip_guided_knn", "theia_hip_brute_force_options_default", "theia_hip_brute_force_knn2", "theia_hip_brute_force_match_pairs", "theia_hip_track_builder_options_default", "theia_hip_build_tracks", "theia_hip_track_builder_last_timings", "theia_hip_mean_pool_descriptors", "theia_hip_graph_match", "theia_hip_visibility_scores", "theia_hip_set_underconstrained_unestimated", "theia_hip_unproject", "theia_hip_align_point_clouds", "theia_hip_transform_reconstruction", "theia_hip_align_rotations", "theia_hip_randint_stream", "theia_hip_selftest_wave_primitives",
+    "theia_hip_pose_from_three_points", "theia_hip_sqpnp", "theia_hip_dls_pnp", "theia_hip_dls_macaulay_terms", "theia_hip_four_point_pose_and_focal_length", "theia_hip_four_point_focal_length_radial_distortion", "theia_hip_four_point_focal_length_radial_distortion_ex", "theia_hip_release_scratch", "theia_hip_guided_knn", "theia_hip_brute_force_options_default", "theia_hip_brute_force_knn2", "theia_hip_brute_force_match_pairs", "theia_hip_track_builder_options_default", "theia_hip_build_tracks", "theia_hip_track_builder_last_timings", "theia_hip_mean_pool_descriptors", "theia_hip_graph_match", "theia_hip_visibility_scores", "theia_hip_set_underconstrained_unestimated", "theia_hip_unproject", "theia_hip_align_point_clouds", "theia_hip_transform_reconstruction", "theia_hip_align_rotations", "theia_hip_sim3_maps", "theia_hip_optimize_alignment_sim3", "theia_hip_randint_stream", "theia_hip_selftest_wave_primitives",
     "theia_hip_selftest_eig_team", "theia_hip_selftest_svd9_team", "theia_hip_selftest_five_point_pre_team",
     "theia_hip_selftest_rotation_maps", "theia_hip_selftest_pairwise_rotation_error", "theia_hip_selftest_lm_rules",
     "theia_hip_rng_seed", "theia_hip_rng_rand_int", "theia_hip_rng_rand_double", "theia_hip_rng_rand_gaussian", "theia_hip_rng_discard", "theia_hip_ransac_estimate_streams",
@@ -508,6 +536,10 @@ def lib():
                                                      c_double_p, c_double_p, C.c_double, c_double_p]
     L.theia_hip_align_rotations.argtypes = [C.c_int32, c_double_p, c_double_p, c_double_p, C.POINTER(AlignRotationsSummary),
                                             c_double_p, C.c_int32]
+    L.theia_hip_sim3_maps.argtypes = [C.c_int32, C.c_int64, c_double_p, c_double_p]
+    L.theia_hip_optimize_alignment_sim3.argtypes = [C.c_int32, c_int64_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                                    c_double_p, C.POINTER(Sim3AlignmentOptionsC), c_double_p,
+                                                    C.POINTER(Sim3AlignmentSummaryC), c_double_p, C.c_int32, c_double_p]
     _lib = L
     return L
 

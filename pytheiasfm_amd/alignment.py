@@ -1,11 +1,13 @@
 """Host-side mirror of pyTheia's reconstruction alignment (src/theia/sfm/transformation/, exported in
 src/pytheia/sfm/sfm.cc:620-628,938) over theia_hip_align_point_clouds, theia_hip_transform_reconstruction and the RANSAC
-estimator THEIA_EST_CAMERA_ALIGNMENT (include/theia_hip.h).
+estimator THEIA_EST_CAMERA_ALIGNMENT (include/theia_hip.h), and of the Sim(3) optimisation (sfm.cc:631-670) over
+theia_hip_optimize_alignment_sim3 and theia_hip_sim3_maps.
 
 Same names as the pybind wrappers; the Align* functions return (rotation [3][3], translation [3], scale).  Reconstructions are
 the array-backed pytheiasfm_amd.sfm.Reconstruction; the functions that match views by name need its `view_names`.
-Not built: OptimizeAlignmentSim3 and the Sim3 conversions, align_reconstructions_pose_graph_optim."""
+Not built: align_reconstructions_pose_graph_optim and the pose-graph Sim(3) terms."""
 import ctypes as C
+import enum
 
 import numpy as np
 
@@ -214,3 +216,247 @@ def AlignOrientations(gt_orientations, orientations):
     for k, a in zip(ids, aligned):
         out[k] = a.copy()
     return out
+
+
+# ---- Sim(3) point-cloud alignment (align_point_clouds.h:60-160, align_point_clouds.cc:161-317; sfm.cc:631-670)
+class Sim3AlignmentType(enum.IntEnum):
+    POINT_TO_POINT = capi.THEIA_SIM3_POINT_TO_POINT
+    ROBUST_POINT_TO_POINT = capi.THEIA_SIM3_ROBUST_POINT_TO_POINT
+    POINT_TO_PLANE = capi.THEIA_SIM3_POINT_TO_PLANE
+
+
+POINT_TO_POINT = Sim3AlignmentType.POINT_TO_POINT                  # export_values()
+ROBUST_POINT_TO_POINT = Sim3AlignmentType.ROBUST_POINT_TO_POINT
+POINT_TO_PLANE = Sim3AlignmentType.POINT_TO_PLANE
+
+
+class Sim3AlignmentOptions:
+    """align_point_clouds.h:76-140 with its defaults.  outlier_threshold, linear_solver_type and verbose are kept and not read
+    (the reference reads outlier_threshold nowhere; a single 7-block leaves the linear solver no choice); minimizer_type
+    "LINE_SEARCH" is refused.  start_from_initial_alignment is not in the reference: see OptimizeAlignmentSim3."""
+
+    def __init__(self):
+        self.alignment_type = Sim3AlignmentType.POINT_TO_POINT
+        self.point_weight = 1.0
+        self.huber_threshold = 0.1
+        self.outlier_threshold = 1.0
+        self.linear_solver_type = "SPARSE_SCHUR"
+        self.minimizer_type = "TRUST_REGION"
+        self.max_iterations = 100
+        self.verbose = False
+        self.perform_optimization = True
+        self.start_from_initial_alignment = False
+        self.initial_sim3_params = None
+        self.target_normals = None
+        self.point_weights = None
+
+    def set_initial_sim3_params(self, params):
+        self.initial_sim3_params = np.array(params, dtype=np.float64).reshape(7)
+
+    def set_target_normals(self, normals):
+        self.target_normals = np.array(normals, dtype=np.float64).reshape(-1, 3)
+
+    def set_point_weights(self, weights):
+        self.point_weights = np.array(weights, dtype=np.float64).reshape(-1)
+
+    def clear_initial_sim3_params(self):
+        self.initial_sim3_params = None
+
+    def clear_target_normals(self):
+        self.target_normals = None
+
+    def clear_point_weights(self):
+        self.point_weights = None
+
+
+class Sim3AlignmentSummary:
+    """align_point_clouds.h:143-160, and what the device loop adds: termination (capi.THEIA_SIM3_TERM_*), initial_cost, the
+    step counts and the trace rows (cost, gradient max norm, step norm, radius, accepted)."""
+
+    def __init__(self):
+        self.success = False
+        self.final_cost = 0.0
+        self.num_iterations = 0
+        self.alignment_error = 0.0
+        self.sim3_params = np.zeros(7)
+        self.termination = capi.THEIA_SIM3_TERM_NO_POINTS
+        self.initial_cost = 0.0
+        self.num_successful_steps = self.num_unsuccessful_steps = self.num_invalid_steps = 0
+        self.route = 0
+        self.trace = None
+
+
+def sim3_maps(op, values):
+    """theia_hip_sim3_maps on an [n][in width] array -> [n][out width]."""
+    wi, wo = capi.THEIA_SIM3_MAP_WIDTHS[op]
+    v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1, wi)
+    out = np.zeros((v.shape[0], wo))
+    capi.check(capi.lib().theia_hip_sim3_maps(op, v.shape[0], capi.ptr(v, C.c_double), capi.ptr(out, C.c_double)))
+    return out
+
+
+def Sim3FromRotationTranslationScale(rotation, translation, scale):
+    """align_point_clouds.cc:288-298 -> the 7 parameters [upsilon, omega, sigma] of Sim3d(RxSO3d(scale, R), t).log()."""
+    R, t, s = _transform(rotation, translation, scale)
+    if not (1e-10 <= s < 1e10):
+        raise _invalid("Scale factor must be greater-equal epsilon.")     # Sophus' SOPHUS_ENSURE
+    return sim3_maps(capi.THEIA_SIM3_MAP_FROM_RTS, np.concatenate([R.reshape(-1), t, [s]]))[0]
+
+
+def Sim3ToRotationTranslationScale(sim3_params):
+    """align_point_clouds.cc:300-317 -> (rotation [3][3], translation [3], scale)."""
+    o = sim3_maps(capi.THEIA_SIM3_MAP_TO_RTS, np.asarray(sim3_params, dtype=np.float64).reshape(1, 7))[0]
+    return o[:9].reshape(3, 3).copy(), o[9:12].copy(), float(o[12])
+
+
+def Sim3ToHomogeneousMatrix(sim3_params):
+    """transformation_wrapper.cc:125-132 -> Sim3d::exp(params).matrix() [4][4]."""
+    return sim3_maps(capi.THEIA_SIM3_MAP_TO_MATRIX4, np.asarray(sim3_params, dtype=np.float64).reshape(1, 7))[0].reshape(4, 4)
+
+
+def optimize_alignment_sim3(sources, targets, starts, options, weights=None, normals=None, want_trace=False, timings=None):
+    """theia_hip_optimize_alignment_sim3 on lists of clouds: problem p is sources[p] -> targets[p] from starts[p] under
+    options[p] (Sim3AlignmentOptions: alignment_type, point_weight, huber_threshold, max_iterations are read).  weights /
+    normals: None, or one array per problem (all problems or none: the C entry takes one array for the batch).
+    Returns (params [P][7], [capi.Sim3AlignmentSummaryC], [trace [rows][5]] or None)."""
+    P = len(sources)
+    src = [_cloud(a, "source") for a in sources]
+    tgt = [_cloud(a, "target") for a in targets]
+    if len(tgt) != P or len(options) != P or len(starts) != P:
+        raise _invalid("sources, targets, starts and options must hold one entry per problem")
+    for p in range(P):
+        if src[p].shape[0] != tgt[p].shape[0]:
+            raise _invalid(f"problem {p}: source and target differ in length")
+    offsets = np.concatenate([[0], np.cumsum([a.shape[0] for a in src])]).astype(np.int64)
+    cat = lambda arrs, w: np.ascontiguousarray(np.concatenate([np.asarray(a, dtype=np.float64).reshape(-1, w) for a in arrs]) if arrs
+                                               else np.zeros((0, w)))
+    S, T = cat(src, 3), cat(tgt, 3)
+    W = N = None
+    if weights is not None:
+        W = cat(weights, 1).reshape(-1)
+        if W.shape[0] != S.shape[0]:
+            raise _invalid("weights must hold one entry per point")
+    if normals is not None:
+        N = cat(normals, 3)
+        if N.shape[0] != S.shape[0]:
+            raise _invalid("normals must hold one entry per point")
+    st = np.ascontiguousarray(np.asarray(starts, dtype=np.float64).reshape(P, 7))
+    opts = (capi.Sim3AlignmentOptionsC * max(P, 1))()
+    for p, o in enumerate(options):
+        opts[p].alignment_type = int(o.alignment_type)
+        opts[p].max_iterations = int(o.max_iterations)
+        opts[p].point_weight = float(o.point_weight)
+        opts[p].huber_threshold = float(o.huber_threshold)
+    summ = (capi.Sim3AlignmentSummaryC * max(P, 1))()
+    params = np.zeros((max(P, 1), 7))
+    rows = (max((int(o.max_iterations) for o in options), default=0) + 2) if want_trace else 0
+    trace = np.zeros((max(P, 1), rows, 5)) if want_trace else None
+    tm = None if timings is None else np.zeros(2)
+    capi.check(capi.lib().theia_hip_optimize_alignment_sim3(
+        P, capi.ptr(offsets, C.c_int64), capi.ptr(S, C.c_double), capi.ptr(T, C.c_double), capi.ptr(W, C.c_double),
+        capi.ptr(N, C.c_double), capi.ptr(st, C.c_double), opts, capi.ptr(params, C.c_double), summ,
+        capi.ptr(trace, C.c_double), rows, capi.ptr(tm, C.c_double)))
+    if timings is not None:
+        timings[:] = tm.tolist()
+    traces = [trace[p, :summ[p].trace_size].copy() for p in range(P)] if want_trace else None
+    return params[:P], [summ[p] for p in range(P)], traces
+
+
+_SIM3_AS_WRITTEN_START = np.array([0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0])   # align_point_clouds.cc:178-179
+
+
+def OptimizeAlignmentSim3Batch(sources, targets, options=None, want_trace=False):
+    """OptimizeAlignmentSim3 for a list of cloud pairs: one launch for the problems that are optimised, one Umeyama call
+    for those that need an initial alignment.  options: None, one Sim3AlignmentOptions for all, or one per pair.  A list of
+    Sim3AlignmentSummary."""
+    P = len(sources)
+    if len(targets) != P:
+        raise _invalid("sources and targets must hold one entry per problem")
+    if options is None:
+        options = Sim3AlignmentOptions()
+    opts = list(options) if isinstance(options, (list, tuple)) else [options] * P
+    if len(opts) != P:
+        raise _invalid("one Sim3AlignmentOptions per problem is needed")
+    out = [Sim3AlignmentSummary() for _ in range(P)]
+    src = [np.asarray(a, dtype=np.float64).reshape(-1, 3) for a in sources]
+    tgt = [np.asarray(a, dtype=np.float64).reshape(-1, 3) for a in targets]
+    live = []
+    for p, o in enumerate(opts):
+        if str(getattr(o.minimizer_type, "name", o.minimizer_type)).upper() == "LINE_SEARCH":
+            raise _invalid("minimizer_type LINE_SEARCH is not built")
+        if src[p].shape[0] != tgt[p].shape[0] or src[p].shape[0] == 0:
+            continue   # "must have the same size" / "cannot be empty" (:168-175): the summary as constructed
+        live.append(p)
+    # the initial alignment (:181-198): the guess, or weighted Umeyama (all ones) -> Sim3FromRotationTranslationScale
+    need = [p for p in live if opts[p].initial_sim3_params is None]
+    if need:
+        R, t, s, _ = align_point_clouds_batch([src[p] for p in need], [tgt[p] for p in need],
+                                              [np.ones(src[p].shape[0]) for p in need])
+        rts = np.concatenate([R.reshape(len(need), 9), t, s[:, None]], axis=1)
+        inside = (rts[:, 12] >= 1e-10) & (rts[:, 12] < 1e10)
+        if not inside.all():
+            raise _invalid("Scale factor must be greater-equal epsilon.")
+        init = sim3_maps(capi.THEIA_SIM3_MAP_FROM_RTS, rts)
+        for k, p in enumerate(need):
+            out[p].sim3_params = init[k].copy()
+    for p in live:
+        if opts[p].initial_sim3_params is not None:
+            out[p].sim3_params = np.array(opts[p].initial_sim3_params, dtype=np.float64).reshape(7)
+        out[p].success = True
+    run = [p for p in live if opts[p].perform_optimization]
+    if not run:
+        return out
+    starts, W, N = [], [], []
+    any_w = any(opts[p].point_weights is not None for p in run)
+    any_n = any(opts[p].alignment_type == Sim3AlignmentType.POINT_TO_PLANE and opts[p].target_normals is not None for p in run)
+    run_opts = []
+    for p in run:
+        o = opts[p]
+        n = src[p].shape[0]
+        starts.append(out[p].sim3_params if o.start_from_initial_alignment else _SIM3_AS_WRITTEN_START)
+        w = np.full(n, float(o.point_weight))
+        if o.point_weights is not None:   # `i < point_weights->size()` (:210-215): the points past its end take point_weight
+            pw = np.asarray(o.point_weights, dtype=np.float64).reshape(-1)[:n]
+            w[:pw.shape[0]] = pw
+        W.append(w)
+        ro = Sim3AlignmentOptions()
+        ro.alignment_type, ro.point_weight = o.alignment_type, o.point_weight
+        ro.huber_threshold, ro.max_iterations = o.huber_threshold, o.max_iterations
+        nn = np.tile([0.0, 0.0, 1.0], (n, 1))
+        if o.alignment_type == Sim3AlignmentType.POINT_TO_PLANE:
+            tn = None if o.target_normals is None else np.asarray(o.target_normals, dtype=np.float64).reshape(-1, 3)
+            if tn is None or tn.shape[0] < n:
+                # no normals: point-to-point (:228-238).  (Normals for only some of the points -- the reference then mixes
+                # both residual kinds in one problem -- are not built.)
+                if tn is not None:
+                    raise _invalid(f"problem {p}: target_normals must hold one normal per point")
+                ro.alignment_type = Sim3AlignmentType.POINT_TO_POINT
+            else:
+                nn = tn[:n]
+        N.append(nn)
+        run_opts.append(ro)
+    params, summ, traces = optimize_alignment_sim3([src[p] for p in run], [tgt[p] for p in run], starts, run_opts,
+                                                   weights=W if any_w else None, normals=N if any_n else None,
+                                                   want_trace=want_trace)
+    for k, p in enumerate(run):
+        c = summ[k]
+        r = out[p]
+        r.success = bool(c.success)                       # :269
+        r.final_cost, r.initial_cost = c.final_cost, c.initial_cost
+        r.num_iterations = c.num_iterations               # :271
+        r.sim3_params = params[k].copy()                  # :272
+        r.alignment_error = c.alignment_error             # :275-281
+        r.termination, r.route = c.termination, c.route
+        r.num_successful_steps, r.num_unsuccessful_steps = c.num_successful_steps, c.num_unsuccessful_steps
+        r.num_invalid_steps = c.num_invalid_steps
+        r.trace = traces[k] if want_trace else None
+    return out
+
+
+def OptimizeAlignmentSim3(source_points, target_points, options=None):
+    """align_point_clouds.cc:161-284.  AS WRITTEN, the reference stores the initial alignment (the guess, or Umeyama) in the
+    summary, then optimises a separate block that starts at (0,0,0,0,0,0,1) -- identity rotation, scale e -- and overwrites
+    the summary with it (:178-198, :253, :272); so does this by default.  options.start_from_initial_alignment = True (a
+    field the reference does not have) starts the solve at the initial alignment, as the reference's comments intend.
+    A size mismatch or an empty cloud returns the summary as constructed (success False)."""
+    return OptimizeAlignmentSim3Batch([source_points], [target_points], options)[0]
