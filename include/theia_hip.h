@@ -1796,6 +1796,98 @@ int theia_hip_optimize_alignment_sim3(int32_t num_problems, const int64_t* offse
                                       const theia_sim3_alignment_options* options /*[P]*/, double* params_out /*[P][7]*/,
                                       theia_sim3_alignment_summary* summary_out /*[P]*/, double* trace_out /*optional*/,
                                       int32_t trace_capacity, double* timings_ms /*[2] or NULL*/);
+/* ---- co-visibility: from a reconstruction back to a view graph, and on to dense stereo (csrc/covisibility.hip; DESIGN.md
+ * 3.6w) ----
+ * The four entries read a reconstruction as flat arrays: observation k is (obs_view[k], obs_track[k]), rows in any order, at
+ * most one per (view, track) as in theia_ba_problem (not validated: a repeated row is counted twice); view_estimated
+ * [num_views] and track_estimated [num_tracks] (each NULL: all estimated); cam_ext [num_views][6] = position | angle-axis;
+ * points [num_tracks][4] homogeneous.  Every call builds two CSR forms on the host, by three counting passes: the
+ * observations by view with every view's tracks ascending, and by track with every track's views ascending; all kernels
+ * read these.  Device memory: 8 bytes per observation, 21 per view and 9 per track for the plan, the flags and the row
+ * counters (69 and 42 where the poses and points are read); 12 per emitted pair, 48 more with the edge data, 12 more
+ * with the scores.  Host memory: 12 bytes per observation.
+ * Common refusals, THEIA_HIP_ERR_INVALID_ARGUMENT before the device is touched and with every output untouched: a
+ * negative count; a view or track index out of range; a NULL required array with a non-zero count.  THEIA_HIP_ERR_NO_DEVICE
+ * without a device (there is no CPU fallback); THEIA_HIP_ERR_OUT_OF_MEMORY when one of the buffers above cannot be had.
+ * Everything that decides an output's position is integer arithmetic without a global atomic, every floating-point sum has
+ * a fixed order, and no floating-point atomic is used: the same input gives the same bytes.
+ *
+ * theia_hip_covisibility_graph: ViewGraphFromReconstruction (sfm/view_graph/view_graph_from_reconstruction.cc:41-105).
+ * For every pair i < j of estimated views, shared = the number of estimated tracks both observe (:63-71, :94-97); the pair
+ * is emitted when shared > min_shared_tracks (:99, strict).  pairs [.][2] ascending in (i, j); num_shared [.] =
+ * num_verified_matches (:58); optional rotation_2 [.][3] = RotationMatrixToAngleAxis(R_j * R_i') (:47-53, Eigen's product
+ * order, ceres' maps as csrc/rotation_maps.h restates them) and position_2 [.][3] = R_i * (c_j - c_i).normalized() (:55-57),
+ * the difference divided by sqrt((x x + y y) + z z) without a guard: coincident centres give NaN, which is passed
+ * through, not refused (Eigen from 3.3 on returns the zero vector there instead).
+ * *num_pairs is always the full count; the arrays are written only when it fits pair_capacity (ask with capacity 0, call
+ * again), as theia_hip_graph_match does it.
+ * One workgroup per row i counts in int32 counters in its LDS, one per column of a window of column_window views
+ * (0 = THEIA_COVISIBILITY_DEFAULT_WINDOW, the 32 KiB the kernel declares; larger values are clamped to it); a row with
+ * more columns j > i than one window takes further passes.  The result does not depend on the window.
+ * STATED DEVIATIONS: the reference walks ViewIds() in hash-map order and tests only the outer view for IsEstimated(), so
+ * which view is "1" of the TwoViewInfo, and whether a pair with one unestimated view appears, depend on that order.  Here
+ * view 1 is the smaller index and BOTH views must be estimated (the only consumer, ViewSelectionMVSNet :82, skips an
+ * unestimated neighbour anyway).
+ * Further refusals: min_shared_tracks < 0, column_window < 0, pair_capacity < 0, a NULL num_pairs, a NULL pairs or
+ * num_shared with pair_capacity > 0, rotation_2 or position_2 asked for with cam_ext NULL.  num_views == 0 or
+ * num_obs == 0: *num_pairs = 0, returns 0, launches nothing. */
+#define THEIA_COVISIBILITY_DEFAULT_WINDOW 8192
+int theia_hip_covisibility_graph(int32_t num_views, int32_t num_tracks, int64_t num_obs, const int32_t* obs_view,
+                                 const int32_t* obs_track, const uint8_t* view_estimated, const uint8_t* track_estimated,
+                                 const double* cam_ext /*[num_views][6]; NULL allowed without edge data*/,
+                                 int32_t min_shared_tracks, int32_t column_window, int64_t pair_capacity,
+                                 int32_t* pairs /*[.][2]*/, int32_t* num_shared /*[.]*/, double* rotation_2 /*optional [.][3]*/,
+                                 double* position_2 /*optional [.][3]*/, int64_t* num_pairs);
+/* theia_hip_mvsnet_pair_scores: the score of ViewSelectionMVSNet (mvs/view_selection_mvsnet.cc:39-52, :89-104) for a list
+ * of view pairs (the list above, or any; a pair may be listed more than once and in either order):
+ *   score[e] = sum over the tracks t both views observe, ascending in t, of ScoreFun(theta_t),
+ * with p = xyz / w (hnormalized), ray = (c - p) / sqrt((x x + y y) + z z) for both centres, theta = 180 / pi * acos((r1 r2)_x
+ * + ..., products added left to right), sigma = theta <= theta0 ? sigma1 : sigma2, and exp(-(d * d) / (2 * sigma * sigma)),
+ * d = theta - theta0 (the reference's pow(., 2) as a product).  As at :89-104 EVERY common track counts, estimated or not;
+ * track_mask [num_tracks] (optional) restricts the sum to the tracks whose byte is not 0.  The cosine is not clamped, as in
+ * the reference: a NaN term makes the score NaN.  num_common [e] = the number of terms.
+ * One team of 16 lanes per pair strides over the shorter of the two sorted track lists and bisects in the longer; a lane
+ * adds its hits in ascending order, then one fixed reduction over the team: the order of the sum is a function of the
+ * input alone.  A pair is evaluated as (smaller view, larger view), so (i, j) and (j, i) get the same bits.
+ * STATED DEVIATION: the reference calls std::set_intersection on View::TrackIds(), the keys of an unordered_map in hash
+ * order, which is undefined; the intersection of the sorted lists is what it means.  The sum's association differs from the
+ * reference's sequential one at rounding level.
+ * Further refusals: a pair naming one view twice; a NaN theta0, sigma1 or sigma2; a sigma of 0; a NULL cam_ext, points,
+ * pairs, score or num_common with num_pairs > 0.  num_pairs == 0 returns 0; num_obs == 0 writes zeros; neither launches. */
+int theia_hip_mvsnet_pair_scores(int32_t num_views, int32_t num_tracks, int64_t num_obs, const int32_t* obs_view,
+                                 const int32_t* obs_track, const double* cam_ext /*[num_views][6]*/,
+                                 const double* points /*[num_tracks][4]*/, const uint8_t* track_mask /*optional*/,
+                                 int64_t num_pairs, const int32_t* pairs /*[num_pairs][2]*/, double theta0, double sigma1,
+                                 double sigma2, double* score /*[num_pairs]*/, int32_t* num_common /*[num_pairs]*/);
+/* theia_hip_view_selection_mvsnet: ViewSelectionMVSNet (mvs/view_selection_mvsnet.cc:54-125) in one call: the graph above
+ * with min_shared_tracks (the reference's literal 10, :66), the scores above on its pairs without a mask, and for every
+ * estimated view its num_neighbors best neighbours.  neighbor [num_views][num_neighbors] (-1 padded), score likewise
+ * (0 padded), best first: score descending, NaN after every number, equal scores (and NaNs) by ascending view index.  An
+ * unestimated view gets an empty row.  The graph and the scores run on the device and stay there in between; the selection,
+ * at most a view's degree items, runs on the host.
+ * STATED DEVIATION: the reference keys a std::map by the score (:78, :105), so two neighbours with one score collapse into
+ * one, and which of them survives depends on hash order.  Here both stay.
+ * Further refusals: num_neighbors < 0, min_shared_tracks < 0, column_window < 0, NaN theta0 / sigma1 / sigma2, a sigma of 0, a
+ * NULL cam_ext or points with num_views > 0, a NULL output with num_views * num_neighbors > 0.  num_views == 0 returns 0;
+ * num_obs == 0 writes empty rows; neither launches. */
+int theia_hip_view_selection_mvsnet(int32_t num_views, int32_t num_tracks, int64_t num_obs, const int32_t* obs_view,
+                                    const int32_t* obs_track, const uint8_t* view_estimated, const uint8_t* track_estimated,
+                                    const double* cam_ext, const double* points, int32_t min_shared_tracks /*reference: 10*/,
+                                    int32_t num_neighbors, double theta0, double sigma1, double sigma2, int32_t column_window,
+                                    int32_t* neighbor /*[num_views][num_neighbors]*/, double* score /*likewise*/);
+/* theia_hip_find_common_tracks: FindCommonTracksInViews (sfm/find_common_tracks_in_views.cc:58-88) for a batch of queries:
+ * query q is the views views[offsets[q] .. offsets[q + 1]), and its answer the ascending list of the tracks every one of
+ * them observes, estimated or not, as the reference does (a view may be named twice).  One team of 16 lanes per query:
+ * the candidates are the shortest of the views' lists (the first such view of the query), each bisected in the others;
+ * count, scan, write.  track_off [num_queries + 1] and *num_found are always written; tracks only when *num_found fits
+ * track_capacity (ask with capacity 0, call again).
+ * Further refusals: a NULL offsets, views, track_off or num_found with num_queries > 0; offsets[0] != 0 or a query with
+ * fewer than 2 views (the reference's CHECK_GT, :60); track_capacity < 0, or > 0 with a NULL tracks.  num_queries == 0
+ * returns 0; num_obs == 0 gives empty answers; neither launches. */
+int theia_hip_find_common_tracks(int32_t num_views, int32_t num_tracks, int64_t num_obs, const int32_t* obs_view,
+                                 const int32_t* obs_track, int32_t num_queries, const int64_t* offsets /*[num_queries+1]*/,
+                                 const int32_t* views, int64_t track_capacity, int64_t* track_off /*[num_queries+1]*/,
+                                 int32_t* tracks, int64_t* num_found);
 /* n draws of RandomNumberGenerator(seed).RandInt(lo, hi) (util/random.cc:46-84): host code that follows the reference's
  * generator outside the RANSAC sampler (the random candidates of GuidedEpipolarMatcher::FindFeaturesNearEpipolarLines). */
 int theia_hip_randint_stream(uint32_t seed, int32_t n, int32_t lo, int32_t hi, int32_t* out);

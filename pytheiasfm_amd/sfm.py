@@ -37,6 +37,7 @@ from .global_pose import (GlobalRotationEstimatorType, RobustRotationEstimator, 
                           FilterViewGraphCyclesByRotation, RemoveDisconnectedViewPairs)
 from .tracks import (TrackBuilder, AddFeatureCorrespondencesToTrackBuilder,  # noqa: F401  (pyTheia's names)
                      AddFullFeatureCorrespondencesToTrackBuilder)
+from .covisibility import ViewGraphFromReconstruction, FindCommonTracksInViews  # noqa: F401  (pyTheia's names)
 
 kInvalidViewId = 0xFFFFFFFF
 
