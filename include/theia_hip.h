@@ -338,7 +338,11 @@ int theia_hip_optimize_relative_position_batch(int32_t num_problems, const int64
  * 7-dof manifold of fundamental_matrix_parameterization.h:15-75 (Plus through the SVD of the current F:
  * every accepted step re-normalises F to singular values (1, sigma, 0)) against one squared-Sampson
  * residual per correspondence (sampson_error.h:21-33); no loss function (options->loss_function_type
- * must be TRIVIAL), direct solver.  fundamental_matrices [num_problems][9] row-major in/out. */
+ * must be TRIVIAL), direct solver.  fundamental_matrices [num_problems][9] row-major in/out.
+ * A problem with no correspondences has a parameter block and no residual block: like Ceres (which drops the
+ * unused block: "no non-constant parameter blocks"; Ceres 2.2's rule as recalled, its source is not part of this
+ * tree) it ends at once with CONVERGENCE, success = 1, 0 iterations,
+ * both costs 0 and F untouched (not renormalised), as the angular and homography entries do. */
 int theia_hip_optimize_fundamental_matrix_batch(int32_t num_problems, const int64_t* offsets,
                                                 const double* correspondences, double* fundamental_matrices,
                                                 const theia_ba_options* options,

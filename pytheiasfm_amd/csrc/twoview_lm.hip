@@ -35,6 +35,15 @@ double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock:
 __device__ __forceinline__ double wsum(double v) { return wave_sum_butterfly(v); }
 using lm::tri;
 
+// loss_eval, except that a NaN squared norm stays NaN under every loss.  theia's TruncatedLoss (loss_functions.cc:40-44) is
+// std::min(s, e), which returns a NaN s, where loss_eval's fmin returns e: a homography whose inverse does not exist (NaN
+// residuals) then had the finite initial cost n e / 2 under the TRUNCATED loss and converged at iteration 0 instead of
+// failing there, as it does without a loss and as Ceres does for any residual that is not finite.
+__device__ __forceinline__ double loss_eval_nan(int type, double a, double s, double* rho1) {
+  const double rho = loss_eval(type, a, s, rho1);
+  return s != s ? s : rho;
+}
+
 struct TwoViewBatch {
   int num;
   const int64_t* offsets;
@@ -180,7 +189,7 @@ __device__ double twoview_cost(const TwoViewBatch& B, int p, const double x[6], 
   for (int64_t o = beg + lane; o < end; o += 64) {
     const double r = angular_error<false>(x, T, B.corr[o], nullptr);
     double rho1;
-    cost += 0.5 * loss_eval(B.loss_type, B.loss_width, r * r, &rho1);
+    cost += 0.5 * loss_eval_nan(B.loss_type, B.loss_width, r * r, &rho1);
   }
   return wsum(cost);
 }
@@ -198,7 +207,7 @@ __device__ void twoview_linearize(const TwoViewBatch& B, int p, const double x[6
     double J[5];
     const double r = angular_error<true>(x, T, B.corr[o], J);
     double rho1;
-    const double rho = loss_eval(B.loss_type, B.loss_width, r * r, &rho1);
+    const double rho = loss_eval_nan(B.loss_type, B.loss_width, r * r, &rho1);
     const double sr = sqrt(rho1);
     const double rr = sr * r;
 #pragma unroll
@@ -496,7 +505,7 @@ __device__ double homography_cost(const HomographyBatch& B, int p, const double*
     double r[4];
     homography_residuals<false>(H, G, B.corr[o], r, nullptr);
     double rho1;
-    cost += 0.5 * loss_eval(B.loss_type, B.loss_width, (r[0] * r[0] + r[1] * r[1]) + (r[2] * r[2] + r[3] * r[3]), &rho1);
+    cost += 0.5 * loss_eval_nan(B.loss_type, B.loss_width, (r[0] * r[0] + r[1] * r[1]) + (r[2] * r[2] + r[3] * r[3]), &rho1);
   }
   return wsum(cost);
 }
@@ -513,7 +522,7 @@ __device__ void homography_linearize(const HomographyBatch& B, int p, const doub
     double r[4], J[36];
     homography_residuals<true>(H, G, B.corr[o], r, J);
     double rho1;
-    const double rho = loss_eval(B.loss_type, B.loss_width, (r[0] * r[0] + r[1] * r[1]) + (r[2] * r[2] + r[3] * r[3]), &rho1);
+    const double rho = loss_eval_nan(B.loss_type, B.loss_width, (r[0] * r[0] + r[1] * r[1]) + (r[2] * r[2] + r[3] * r[3]), &rho1);
     const double sr = sqrt(rho1);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -785,6 +794,20 @@ __global__ __launch_bounds__(256) void k_fundamental_lm(FundBatch B, BatchLmOut*
   for (int q = 0; q < 9; ++q) x[q] = B.F[(size_t)p * 9 + q];
   BatchLmOut R;
   R.success = 0; R.term = THEIA_TERM_NO_CONVERGENCE; R.iters = 0; R.nsucc = 0; R.c0 = 0.0; R.c1 = 0.0;
+  // No correspondences: OptimizeFundamentalMatrix (bundle_adjust_two_views.cc:248-296) adds the parameter block and no
+  // residual block.  Ceres' preprocessor then removes the unused block and the solve ends at once with CONVERGENCE ("no
+  // non-constant parameter blocks"), 0 iterations, both costs 0 and F untouched -- not even renormalised by Plus.  (That rule
+  // is stated from Ceres 2.2 as recalled; its source is not part of this tree.)  Without this the gradient norm
+  // |F - Plus(F, 0)| is the renormalisation, every step has model cost change 0 and the fifth invalid step is FAILURE.
+  // Wave-uniform: offsets and counts are per problem.
+  {
+    const int64_t beg = B.offsets[p], end = B.counts ? beg + B.counts[p] : B.offsets[p + 1];
+    if (beg == end) {
+      R.success = 1; R.term = THEIA_TERM_CONVERGENCE;
+      if (lane == 0) out[p] = R;
+      return;
+    }
+  }
   double scale[7];
   for (int q = 0; q < 7; ++q) scale[q] = 1.0;
   double A[28], g[7], x_cost;

@@ -252,6 +252,44 @@ class Problem:
         return np.sqrt(acc)
 
 
+# ---- the trust-region step rules of the docstring, one statement each: solve() below and tests/twoview_lm_ref.py use them
+INITIAL_RADIUS = 1e4
+
+
+def jacobi_scale(J):
+    """1 / (1 + |column|), fixed at the initial point"""
+    return 1.0 / (1.0 + np.sqrt((J * J).sum(0)))
+
+
+def trial_step(Js, r, radius):
+    """(valid, y, model cost change) of the step -y: (Js'Js + D^2) y = Js'r exactly, D^2 = clamp(diag(Js'Js), 1e-6, 1e32) /
+    radius; model cost change -m . (r + m / 2) with m = Js (-y); valid iff the solve succeeds and the change is positive."""
+    D2 = np.clip((Js * Js).sum(0), 1e-6, 1e32) / radius
+    A = Js.T @ Js + np.diag(D2)
+    y = np.zeros(Js.shape[1])
+    try:
+        Lc = np.linalg.cholesky(A)
+        y = np.linalg.solve(Lc.T, np.linalg.solve(Lc, Js.T @ r))
+        ok = bool(np.all(np.isfinite(y)))
+    except np.linalg.LinAlgError:
+        ok = False
+    mcc = 0.0
+    if ok:
+        m = Js @ (-y)
+        mcc = -float(m @ (r + m / 2.0))
+        ok = mcc > 0.0
+    return ok, y, mcc
+
+
+def tolerance_stop(step_norm, x_norm, change, x_cost, parameter_tolerance, function_tolerance):
+    """parameter tolerance, then function tolerance: both before the acceptance test, the iterate stays"""
+    return bool(step_norm <= parameter_tolerance * (x_norm + parameter_tolerance) or abs(change) <= function_tolerance * x_cost)
+
+
+def step_accepted(rho):
+    return rho > 1e-3
+
+
 def solve(flat, max_num_iterations=50, function_tolerance=1e-6, gradient_tolerance=1e-10, parameter_tolerance=1e-8,
           max_trust_region_radius=1e12, manifold=False, loss_kind="trivial", loss_width=1.0, free_intr=None, prior_mask=0):
     """Returns the trace -- (cost, gradient max norm, step norm, radius, accepted) per entry, as the oracle and the library record
@@ -259,30 +297,18 @@ def solve(flat, max_num_iterations=50, function_tolerance=1e-6, gradient_toleran
     P = Problem(flat, manifold, loss_kind, loss_width, free_intr, prior_mask)
     cam, pts, intr = P.cam, P.pts, P.intr
     x_cost, r, J = P.evaluate(cam, pts, intr, True)
-    scale = 1.0 / (1.0 + np.sqrt((J * J).sum(0)))
+    scale = jacobi_scale(J)
     Js = J * scale
     gmax = float(np.abs(J.T @ r).max())
     x_norm = P.norms(cam, pts, intr)
-    radius, decrease = 1e4, 2.0
+    radius, decrease = INITIAL_RADIUS, 2.0
     trace = [(x_cost, gmax, 0.0, radius, 1)]
     it, invalid, successful = 0, 0, True
     while True:
         if it >= max_num_iterations or (successful and gmax <= gradient_tolerance) or radius <= 1e-32:
             break
         it += 1
-        D2 = np.clip((Js * Js).sum(0), 1e-6, 1e32) / radius
-        A = Js.T @ Js + np.diag(D2)
-        try:
-            Lc = np.linalg.cholesky(A)
-            y = np.linalg.solve(Lc.T, np.linalg.solve(Lc, Js.T @ r))
-            ok = bool(np.all(np.isfinite(y)))
-        except np.linalg.LinAlgError:
-            ok = False
-        mcc = 0.0
-        if ok:
-            m = Js @ (-y)
-            mcc = -float(m @ (r + m / 2.0))
-            ok = mcc > 0.0
+        ok, y, mcc = trial_step(Js, r, radius)
         if not ok:
             invalid += 1
             if invalid >= 5:
@@ -296,13 +322,11 @@ def solve(flat, max_num_iterations=50, function_tolerance=1e-6, gradient_toleran
         if not np.all(np.isfinite(rc)):
             cand = np.finfo(np.float64).max                     # Ceres: a candidate that fails to evaluate costs DBL_MAX
         step_norm = P.norms(cam, pts, intr, ccam, cpts, cintr)
-        if step_norm <= parameter_tolerance * (x_norm + parameter_tolerance):
-            trace.append((cand, gmax, step_norm, radius, 0)); break
         change = x_cost - cand
-        if abs(change) <= function_tolerance * x_cost:
+        if tolerance_stop(step_norm, x_norm, change, x_cost, parameter_tolerance, function_tolerance):
             trace.append((cand, gmax, step_norm, radius, 0)); break
         rho = change / mcc
-        if rho > 1e-3:
+        if step_accepted(rho):
             cam, pts, intr = ccam, cpts, cintr
             x_norm = P.norms(cam, pts, intr)
             x_cost, r, J = P.evaluate(cam, pts, intr, True)
