@@ -1800,6 +1800,68 @@ int theia_hip_optimize_alignment_sim3(int32_t num_problems, const int64_t* offse
                                       const theia_sim3_alignment_options* options /*[P]*/, double* params_out /*[P][7]*/,
                                       theia_sim3_alignment_summary* summary_out /*[P]*/, double* trace_out /*optional*/,
                                       int32_t trace_capacity, double* timings_ms /*[2] or NULL*/);
+/* ---- Sim(3) pose-graph optimisation of camera poses (csrc/pose_graph_sim3.hip, csrc/pose_graph_sim3_device.h; DESIGN.md
+ * 3.6x) ----
+ * The problem AlignOverlapReconstructionsWithPointsAndPosesRobust declares (sfm/transformation/align_reconstructions.h:61-68)
+ * and the reference never defines, built from the pieces it ships: one Sim3ReconAlignErrorTerm
+ * (pose_graph_sim3_error.h:46-103) per edge, every node a 7-vector on Sim3Manifold
+ * (align_reconstructions_pose_graph_optim.cc:39-81), nodes optionally held (SetParameterBlockConstant), solved by Ceres 2.2's
+ * TrustRegionMinimizer + LevenbergMarquardtStrategy at ceres::Solver::Options' defaults, restated on the device in FP64: the
+ * fourteenth Levenberg-Marquardt loop on the rules of csrc/lm_rules.h.
+ * nodes [num_nodes][7], in/out, tangents in Sophus' order upsilon | omega | sigma (a camera: log(Sim3(RxSO3(1, R_c_w),
+ * -R_c_w C)), align_reconstructions_pose_graph_optim_test.cc:71-79).  edges [num_edges][2] = (i, j) with measurements
+ * [num_edges][7] = log(Sji) and sqrt_information [num_edges][7][7] row-major, or NULL: identity.  Per edge
+ *   r = log(Sji exp(x_i) exp(x_j)^-1),  residual = sqrt_information r  (7 rows),
+ *   J_i = sqrt_information (I + Jr0 / 2 + Jr0^2 / 12) Adj(exp(x_j)),  J_j = -J_i,
+ * Jr0 from the unweighted r with blocks (0,0) = hat(omega_r) + sigma_r I, (0,3) = hat(upsilon_r), (0,6) = -upsilon_r,
+ * (3,3) = hat(omega_r); Adj is Sophus' (sim3.hpp).  These are the reference's hand-written Jacobians: the derivative along
+ * the manifold's Plus as a truncated series, not the derivative in the ambient vector; they are restated as written.
+ * Plus(x, d) = log(exp(x) exp(d')), d'[6] = max(d[6], -20); PlusJacobian is the identity.  The measurement that makes an
+ * edge's residual zero is log(exp(x_j) exp(x_i)^-1).
+ * fixed [num_nodes] non-zero = held constant (no columns, not in |x|, bits unchanged), or NULL: no node is held -- the
+ * gauge (a common similarity on the right) is then free and only the LM diagonal makes the system definite.  A "cross edge"
+ * to another reconstruction is an edge to a held node with an identity measurement.  A node without an edge is not in the
+ * problem and is left untouched; an edge between two held nodes is not in the problem either; repeated and reversed pairs
+ * add up.
+ * The system is the dense normal equations of order 7m, m = the free nodes that have an edge (STATED DEVIATION: Ceres would
+ * pick a sparse Cholesky -- the same system in exact arithmetic; the sums are trees and the group products are formed on
+ * (scale, R, t), not on Sophus' quaternions: rounding level; the gradient max norm is that of the tangent-space gradient, as
+ * in every loop of the library).  A pivot that is not positive, a non-finite step, a Plus whose logarithm leaves Sophus' scale
+ * range [1e-10, 1e10) and a model cost change that is not positive are invalid steps, not errors; after
+ * THEIA_SIM3_TERM_FAILURE (five in a row) the nodes are as passed in, after the cap they hold the last accepted iterate.
+ * summary->termination takes the THEIA_SIM3_TERM_* codes (NO_POINTS: nothing to solve, every node of every edge is held).
+ * trace_out (optional) [trace_capacity][5]: (cost, gradient max norm, step norm, radius, accepted) per row, row 0 the start,
+ * then one row per iteration, in theia_hip_nonlinear_rotations' convention; summary->trace_size rows are written.  Two calls
+ * on one input give the same bytes.  Returns 0 whatever the termination.
+ * THEIA_HIP_ERR_INVALID_ARGUMENT (checked before the device is touched; nothing written): a NULL summary, nodes, edges or
+ * measurements; no node; no edge; an edge naming a node out of range; an edge from a node to itself; a non-finite node,
+ * measurement or sqrt_information entry; max_num_iterations < 0; a tolerance that is negative or not finite (zero switches
+ * a rule off, as in Ceres); a radius that is not positive and finite; trace_capacity < 0, or > 0 with a NULL trace_out.
+ * THEIA_HIP_ERR_OUT_OF_MEMORY: the dense (7m + 1)^2 array of doubles does not fit on the device. */
+typedef struct theia_pose_graph_sim3_options {
+  int32_t max_num_iterations;          /* 50 */
+  int32_t reserved;
+  double function_tolerance;           /* 1e-6 */
+  double gradient_tolerance;           /* 1e-10 */
+  double parameter_tolerance;          /* 1e-8 */
+  double initial_trust_region_radius;  /* 1e4 */
+  double max_trust_region_radius;      /* 1e16 */
+} theia_pose_graph_sim3_options;
+typedef struct theia_pose_graph_sim3_summary {
+  int32_t iterations;              /* as theia_nonlinear_rotation_summary */
+  int32_t num_successful_steps, num_unsuccessful_steps, num_invalid_steps;
+  int32_t termination;             /* THEIA_SIM3_TERM_* */
+  int32_t num_nodes_in_problem;    /* m */
+  int32_t trace_size, reserved;
+  double initial_cost, final_cost, final_radius, final_gradient_max_norm, seconds;
+  double kernel_ms;                /* device events around the call's kernels */
+} theia_pose_graph_sim3_summary;
+int theia_hip_pose_graph_sim3(int32_t num_nodes, double* nodes /* [n][7], in/out */, const uint8_t* fixed /* [n] or NULL */,
+                              int32_t num_edges, const int32_t* edges /* [E][2] */, const double* measurements /* [E][7] */,
+                              const double* sqrt_information /* [E][7][7] or NULL */,
+                              const theia_pose_graph_sim3_options* options /*NULL = defaults*/,
+                              theia_pose_graph_sim3_summary* summary, double* trace_out /* optional */,
+                              int32_t trace_capacity);
 /* ---- co-visibility: from a reconstruction back to a view graph, and on to dense stereo (csrc/covisibility.hip; DESIGN.md
  * 3.6w) ----
  * The four entries read a reconstruction as flat arrays: observation k is (obs_view[k], obs_track[k]), rows in any order, at
@@ -1932,6 +1994,13 @@ int theia_hip_selftest_five_point_pre_team(int32_t count, const double* corr, do
 int theia_hip_selftest_rotation_maps(int32_t count, const double* a, const double* b, double* out);
 int theia_hip_selftest_pairwise_rotation_error(int32_t count, const double* w_i, const double* w_j, const double* rel,
                                                double width, double* out);
+/* Self-check of the Sim(3) pose graph's edge term (csrc/pose_graph_sim3.hip): the linearisation's code alone, one lane per
+ * edge, on x_i, x_j, measurements [num_edges][7] and sqrt_information [num_edges][7][7] (or NULL: identity);
+ * residual_out [num_edges][7] = sqrt_information log(Sji exp(x_i) exp(x_j)^-1), jacobian_i_out [num_edges][7][7] row-major =
+ * J_i (J_j is its negative); both NaN where the logarithm is not defined.  The tests compare with tests/pose_graph_sim3_ref.py.
+ * THEIA_HIP_ERR_INVALID_ARGUMENT for num_edges outside 1 .. 2^20 or a null pointer other than sqrt_information. */
+int theia_hip_selftest_sim3_pose_graph_term(int32_t num_edges, const double* x_i, const double* x_j, const double* measurements,
+                                            const double* sqrt_information, double* residual_out, double* jacobian_i_out);
 /* Self-check of the trust-region step rules of every Levenberg-Marquardt loop (csrc/lm_rules.h, played by
  * csrc/selftest_lm_rules.hip): a script of 1 .. 16 records runs from a fresh state (radius 1e4, decrease factor 2) once in
  * one device thread and once on the host; the tests compare both with a restatement of Ceres' rules.  No reference

@@ -16,4 +16,5 @@ from .alignment import (AlignPointCloudsUmeyama, AlignPointCloudsUmeyamaWithWeig
                         FindCommonViewsByName, AlignRotations, AlignOrientations,
                         Sim3AlignmentType, Sim3AlignmentOptions, Sim3AlignmentSummary, OptimizeAlignmentSim3,
                         OptimizeAlignmentSim3Batch, Sim3FromRotationTranslationScale, Sim3ToRotationTranslationScale,
-                        Sim3ToHomogeneousMatrix)
+                        Sim3ToHomogeneousMatrix, Sim3PoseGraphOptions, Sim3PoseGraphSummary, OptimizePoseGraphSim3,
+                        Sim3sFromReconstruction, RelativeSim3s, SetPosesFromSim3s, AlignOverlapReconstructionsPoseGraph)

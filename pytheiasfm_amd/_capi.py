@@ -410,6 +410,25 @@ class Sim3AlignmentSummaryC(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class PoseGraphSim3OptionsC(C.Structure):
+    """theia_pose_graph_sim3_options."""
+    _fields_ = [("max_num_iterations", C.c_int32), ("reserved", C.c_int32), ("function_tolerance", C.c_double),
+                ("gradient_tolerance", C.c_double), ("parameter_tolerance", C.c_double),
+                ("initial_trust_region_radius", C.c_double), ("max_trust_region_radius", C.c_double)]
+
+
+class PoseGraphSim3SummaryC(C.Structure):
+    """theia_pose_graph_sim3_summary (termination: THEIA_SIM3_TERM_*)."""
+    _fields_ = [("iterations", C.c_int32), ("num_successful_steps", C.c_int32), ("num_unsuccessful_steps", C.c_int32),
+                ("num_invalid_steps", C.c_int32), ("termination", C.c_int32), ("num_nodes_in_problem", C.c_int32),
+                ("trace_size", C.c_int32), ("reserved", C.c_int32), ("initial_cost", C.c_double),
+                ("final_cost", C.c_double), ("final_radius", C.c_double), ("final_gradient_max_norm", C.c_double),
+                ("seconds", C.c_double), ("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p)
 
 # every symbol include/theia_hip.h declares (checked by tests/test_capi_symbols.py)
@@ -421,9 +440,9 @@ EXPORTED_SYMBOLS = [
     "theia_hip_ba_set_allreduce", "theia_hip_ba_set_inner_global", "theia_hip_ba_plan_info", "theia_hip_ba_kernel_instances", "theia_hip_ba_lm_chain", "theia_hip_rccl_unique_id", "theia_hip_rccl_comm_create",
     "theia_hip_optimize_relative_position_batch", "theia_hip_rccl_comm_destroy", "theia_hip_rccl_comm_count", "theia_hip_ba_set_rccl", "theia_hip_dense_spd_solve", "theia_hip_dense_spd_solve_multi", "theia_hip_tile_sparse_spd_solve", "theia_hip_tile_sparse_spd_solve_sharded", "theia_hip_robust_rotation_averaging", "theia_hip_linear_rotations", "theia_hip_lagrange_dual_rotations", "theia_hip_nonlinear_rotations", "theia_hip_nonlinear_positions", "theia_hip_lud_positions", "theia_hip_ligt_positions", "theia_hip_linear_triplet_positions", "theia_hip_filter_view_pairs_from_relative_translation", "theia_hip_translation_filter_last_stats", "theia_hip_filter_view_pairs_from_orientation", "theia_hip_filter_view_graph_cycles_by_rotation", "theia_hip_remove_disconnected_view_pairs", "theia_ransac_params_default",
     "theia_hip_ransac_estimate_batch", "theia_hip_five_point_relative_pose",
-    "theia_hip_pose_from_three_points", "theia_hip_sqpnp", "theia_hip_dls_pnp", "theia_hip_dls_macaulay_terms", "theia_hip_four_point_pose_and_focal_length", "theia_hip_four_point_focal_length_radial_distortion", "theia_hip_four_point_focal_length_radial_distortion_ex", "theia_hip_release_scratch", "theia_hip_guided_knn", "theia_hip_brute_force_options_default", "theia_hip_brute_force_knn2", "theia_hip_brute_force_match_pairs", "theia_hip_track_builder_options_default", "theia_hip_build_tracks", "theia_hip_track_builder_last_timings", "theia_hip_mean_pool_descriptors", "theia_hip_graph_match", "theia_hip_visibility_scores", "theia_hip_set_underconstrained_unestimated", "theia_hip_unproject", "theia_hip_align_point_clouds", "theia_hip_transform_reconstruction", "theia_hip_align_rotations", "theia_hip_sim3_maps", "theia_hip_optimize_alignment_sim3", "theia_hip_covisibility_graph", "theia_hip_mvsnet_pair_scores", "theia_hip_view_selection_mvsnet", "theia_hip_find_common_tracks", "theia_hip_randint_stream", "theia_hip_selftest_wave_primitives",
+    "theia_hip_pose_from_three_points", "theia_hip_sqpnp", "theia_hip_dls_pnp", "theia_hip_dls_macaulay_terms", "theia_hip_four_point_pose_and_focal_length", "theia_hip_four_point_focal_length_radial_distortion", "theia_hip_four_point_focal_length_radial_distortion_ex", "theia_hip_release_scratch", "theia_hip_guided_knn", "theia_hip_brute_force_options_default", "theia_hip_brute_force_knn2", "theia_hip_brute_force_match_pairs", "theia_hip_track_builder_options_default", "theia_hip_build_tracks", "theia_hip_track_builder_last_timings", "theia_hip_mean_pool_descriptors", "theia_hip_graph_match", "theia_hip_visibility_scores", "theia_hip_set_underconstrained_unestimated", "theia_hip_unproject", "theia_hip_align_point_clouds", "theia_hip_transform_reconstruction", "theia_hip_align_rotations", "theia_hip_sim3_maps", "theia_hip_optimize_alignment_sim3", "theia_hip_pose_graph_sim3", "theia_hip_covisibility_graph", "theia_hip_mvsnet_pair_scores", "theia_hip_view_selection_mvsnet", "theia_hip_find_common_tracks", "theia_hip_randint_stream", "theia_hip_selftest_wave_primitives",
     "theia_hip_selftest_eig_team", "theia_hip_selftest_svd9_team", "theia_hip_selftest_five_point_pre_team",
-    "theia_hip_selftest_rotation_maps", "theia_hip_selftest_pairwise_rotation_error", "theia_hip_selftest_lm_rules",
+    "theia_hip_selftest_rotation_maps", "theia_hip_selftest_pairwise_rotation_error", "theia_hip_selftest_sim3_pose_graph_term", "theia_hip_selftest_lm_rules",
     "theia_hip_rng_seed", "theia_hip_rng_rand_int", "theia_hip_rng_rand_double", "theia_hip_rng_rand_gaussian", "theia_hip_rng_discard", "theia_hip_ransac_estimate_streams",
 ]
 
@@ -540,6 +559,11 @@ def lib():
     L.theia_hip_optimize_alignment_sim3.argtypes = [C.c_int32, c_int64_p, c_double_p, c_double_p, c_double_p, c_double_p,
                                                     c_double_p, C.POINTER(Sim3AlignmentOptionsC), c_double_p,
                                                     C.POINTER(Sim3AlignmentSummaryC), c_double_p, C.c_int32, c_double_p]
+    L.theia_hip_pose_graph_sim3.argtypes = [C.c_int32, c_double_p, c_uint8_p, C.c_int32, c_int32_p, c_double_p, c_double_p,
+                                            C.POINTER(PoseGraphSim3OptionsC), C.POINTER(PoseGraphSim3SummaryC), c_double_p,
+                                            C.c_int32]
+    L.theia_hip_selftest_sim3_pose_graph_term.argtypes = [C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                                          c_double_p]
     L.theia_hip_covisibility_graph.argtypes = [C.c_int32, C.c_int32, C.c_int64, c_int32_p, c_int32_p, c_uint8_p, c_uint8_p,
                                                c_double_p, C.c_int32, C.c_int32, C.c_int64, c_int32_p, c_int32_p, c_double_p,
                                                c_double_p, c_int64_p]

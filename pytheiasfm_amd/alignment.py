@@ -1,11 +1,12 @@
 """Host-side mirror of pyTheia's reconstruction alignment (src/theia/sfm/transformation/, exported in
 src/pytheia/sfm/sfm.cc:620-628,938) over theia_hip_align_point_clouds, theia_hip_transform_reconstruction and the RANSAC
 estimator THEIA_EST_CAMERA_ALIGNMENT (include/theia_hip.h), and of the Sim(3) optimisation (sfm.cc:631-670) over
-theia_hip_optimize_alignment_sim3 and theia_hip_sim3_maps.
+theia_hip_optimize_alignment_sim3 and theia_hip_sim3_maps, and the Sim(3) pose graph of camera poses
+(pose_graph_sim3_error.h, Sim3Manifold of align_reconstructions_pose_graph_optim.{h,cc}) over theia_hip_pose_graph_sim3
+(the reference has no driver for it, so the names from OptimizePoseGraphSim3 on are this library's).
 
 Same names as the pybind wrappers; the Align* functions return (rotation [3][3], translation [3], scale).  Reconstructions are
-the array-backed pytheiasfm_amd.sfm.Reconstruction; the functions that match views by name need its `view_names`.
-Not built: align_reconstructions_pose_graph_optim and the pose-graph Sim(3) terms."""
+the array-backed pytheiasfm_amd.sfm.Reconstruction; the functions that match views by name need its `view_names`."""
 import ctypes as C
 import enum
 
@@ -460,3 +461,165 @@ def OptimizeAlignmentSim3(source_points, target_points, options=None):
     field the reference does not have) starts the solve at the initial alignment, as the reference's comments intend.
     A size mismatch or an empty cloud returns the summary as constructed (success False)."""
     return OptimizeAlignmentSim3Batch([source_points], [target_points], options)[0]
+
+
+# ---- Sim(3) pose-graph optimisation of camera poses (theia_hip_pose_graph_sim3, DESIGN.md 3.6x)
+class Sim3PoseGraphOptions:
+    """ceres::Solver::Options' defaults, the six numbers theia_pose_graph_sim3_options carries."""
+
+    def __init__(self):
+        self.max_num_iterations = 50
+        self.function_tolerance = 1e-6
+        self.gradient_tolerance = 1e-10
+        self.parameter_tolerance = 1e-8
+        self.initial_trust_region_radius = 1e4
+        self.max_trust_region_radius = 1e16
+
+    def to_c(self):
+        o = capi.PoseGraphSim3OptionsC()
+        o.max_num_iterations = int(self.max_num_iterations)
+        o.function_tolerance, o.gradient_tolerance = float(self.function_tolerance), float(self.gradient_tolerance)
+        o.parameter_tolerance = float(self.parameter_tolerance)
+        o.initial_trust_region_radius = float(self.initial_trust_region_radius)
+        o.max_trust_region_radius = float(self.max_trust_region_radius)
+        return o
+
+
+class Sim3PoseGraphSummary:
+    """theia_pose_graph_sim3_summary; success as ceres::Solver::Summary::IsSolutionUsable (CONVERGENCE or NO_CONVERGENCE);
+    trace [rows][5] = (cost, gradient max norm, step norm, radius, accepted) when asked for."""
+
+    def __init__(self, c=None, trace=None):
+        c = capi.PoseGraphSim3SummaryC() if c is None else c
+        for name, _ in c._fields_:
+            if name != "reserved":
+                setattr(self, name, getattr(c, name))
+        self.success = self.termination not in (capi.THEIA_SIM3_TERM_NO_POINTS, capi.THEIA_SIM3_TERM_FAILURE)
+        self.trace = trace
+
+
+def OptimizePoseGraphSim3(nodes, edges, measurements, sqrt_information=None, fixed=None, options=None, want_trace=False):
+    """theia_hip_pose_graph_sim3: Levenberg-Marquardt over one Sim3ReconAlignErrorTerm (pose_graph_sim3_error.h:46-103) per
+    edge (i, j), residual sqrt_information log(Sji exp(x_i) exp(x_j)^-1) with measurements = log(Sji), every node on
+    Sim3Manifold, the nodes flagged in `fixed` held constant.  nodes [n][7] in Sophus' order upsilon | omega | sigma; edges
+    [E][2]; measurements [E][7]; sqrt_information [E][7][7] or None (identity).  Returns (nodes [n][7], Sim3PoseGraphSummary);
+    the input is not changed.  Not in the reference's scope here: SelfEdgesErrorTerm / CrossEdgesErrorTerm (a cross edge is
+    an edge to a held node with an identity measurement), a robust loss."""
+    x = np.array(nodes, dtype=np.float64, order="C")
+    if x.ndim != 2 or x.shape[1] != 7:
+        raise _invalid("nodes: an [n][7] array is needed")
+    n = x.shape[0]
+    e = np.ascontiguousarray(edges, dtype=np.int32).reshape(-1, 2)
+    E = e.shape[0]
+    z = np.ascontiguousarray(measurements, dtype=np.float64)
+    if z.size != 7 * E:
+        raise _invalid("measurements: one 7-vector per edge is needed")
+    W = None
+    if sqrt_information is not None:
+        W = np.ascontiguousarray(sqrt_information, dtype=np.float64)
+        if W.size != 49 * E:
+            raise _invalid("sqrt_information: one 7 x 7 matrix per edge is needed")
+    f = None
+    if fixed is not None:
+        f = np.ascontiguousarray(np.asarray(fixed).astype(bool), dtype=np.uint8).reshape(-1)
+        if f.shape[0] != n:
+            raise _invalid("fixed: one flag per node is needed")
+    o = (options or Sim3PoseGraphOptions()).to_c()
+    rows = max(int(o.max_num_iterations), 0) + 1 if want_trace else 0
+    trace = np.zeros((rows, 5)) if want_trace else None
+    summ = capi.PoseGraphSim3SummaryC()
+    capi.check(capi.lib().theia_hip_pose_graph_sim3(n, capi.ptr(x, C.c_double), capi.ptr(f, C.c_uint8), E, capi.ptr(e, C.c_int32),
+                                                    capi.ptr(z, C.c_double), capi.ptr(W, C.c_double), C.byref(o), C.byref(summ),
+                                                    capi.ptr(trace, C.c_double), rows))
+    return x, Sim3PoseGraphSummary(summ, trace[:summ.trace_size].copy() if want_trace else None)
+
+
+def _rotations(cam_ext):
+    from .synth import angle_axis_to_matrix
+    return angle_axis_to_matrix(np.asarray(cam_ext, dtype=np.float64).reshape(-1, 6)[:, 3:6])
+
+
+def Sim3sFromReconstruction(reconstruction):
+    """GetSim3s (align_reconstructions_pose_graph_optim_test.cc:71-79) for every view, in view order:
+    log(Sim3(RxSO3(1, R_c_w), -R_c_w C)) -> [num_views][7], through theia_hip_sim3_maps."""
+    cams = np.asarray(reconstruction.cam_ext, dtype=np.float64).reshape(-1, 6)
+    R = _rotations(cams)
+    t = -np.einsum("nij,nj->ni", R, cams[:, :3])
+    return sim3_maps(capi.THEIA_SIM3_MAP_LOG, np.concatenate([np.ones((len(cams), 1)), R.reshape(-1, 9), t], axis=1))
+
+
+def _groups(nodes):
+    o = sim3_maps(capi.THEIA_SIM3_MAP_TO_RTS, np.asarray(nodes, dtype=np.float64).reshape(-1, 7))
+    return o[:, :9].reshape(-1, 3, 3), o[:, 9:12], o[:, 12]
+
+
+def RelativeSim3s(nodes, edges):
+    """log(exp(x_j) exp(x_i)^-1) per edge (i, j): the measurement that makes the edge's residual zero at `nodes` -> [E][7]."""
+    e = np.asarray(edges, dtype=np.int64).reshape(-1, 2)
+    R, t, s = _groups(nodes)
+    Ri, ti, si = R[e[:, 0]], t[e[:, 0]], s[e[:, 0]]
+    Rj, tj, sj = R[e[:, 1]], t[e[:, 1]], s[e[:, 1]]
+    Rr = np.einsum("nij,nkj->nik", Rj, Ri)                       # R_j R_i'
+    sr = sj / si
+    tr = tj - sr[:, None] * np.einsum("nij,nj->ni", Rr, ti)      # t_j - (s_j / s_i) R_j R_i' t_i
+    return sim3_maps(capi.THEIA_SIM3_MAP_LOG, np.concatenate([sr[:, None], Rr.reshape(-1, 9), tr], axis=1))
+
+
+def SetPosesFromSim3s(reconstruction, view_ids, nodes):
+    """Writes nodes (tangents of camera-from-world similarities) back as poses: orientation from R, position -R' t / s."""
+    from .synth import matrix_to_angle_axis
+    ids = np.asarray(list(view_ids), dtype=np.int64)
+    R, t, s = _groups(nodes)
+    if len(ids) != len(s):
+        raise _invalid("one node per view id is needed")
+    cams = np.array(reconstruction.cam_ext, dtype=np.float64).reshape(-1, 6)
+    cams[ids, :3] = -np.einsum("nji,nj->ni", R, t) / s[:, None]
+    cams[ids, 3:6] = matrix_to_angle_axis(R)
+    reconstruction.cam_ext = cams
+
+
+def overlap_pose_graph(reconstruction1, reconstruction2, common_views=None, min_shared_tracks=1):
+    """The graph AlignOverlapReconstructionsPoseGraph solves -> (nodes [n][7], fixed [n], edges [E][2], measurements [E][7],
+    view_ids): nodes 0 .. len(view_ids) - 1 are reconstruction2's estimated views view_ids (free), the rest reconstruction1's
+    common views (held); first the self edges of reconstruction2 (ViewGraphFromReconstruction, measured at its current poses),
+    then one identity edge per common view that reconstruction2 has estimated."""
+    from .covisibility import ViewGraphFromReconstruction
+    r1, r2 = reconstruction1, reconstruction2
+    common = FindCommonViewsByName(r1, r2) if common_views is None else list(common_views)
+    id1 = {n: i for i, n in enumerate(_names(r1))}
+    id2 = {n: i for i, n in enumerate(_names(r2))}
+    view_ids = [v for v in range(r2.NumViews()) if r2.view_estimated[v]]
+    local = {v: k for k, v in enumerate(view_ids)}
+    x2, x1 = Sim3sFromReconstruction(r2), Sim3sFromReconstruction(r1)
+    held = [n for n in common if id2[n] in local]
+    nodes = np.concatenate([x2[view_ids], x1[[id1[n] for n in held]].reshape(-1, 7)])
+    fixed = np.zeros(len(nodes), dtype=np.uint8)
+    fixed[len(view_ids):] = 1
+    self_edges = np.array([(local[a], local[b]) for (a, b) in ViewGraphFromReconstruction(r2, min_shared_tracks)
+                           if a in local and b in local], dtype=np.int32).reshape(-1, 2)
+    cross = np.array([(local[id2[n]], len(view_ids) + k) for k, n in enumerate(held)], dtype=np.int32).reshape(-1, 2)
+    meas = np.concatenate([RelativeSim3s(nodes, self_edges) if len(self_edges) else np.zeros((0, 7)), np.zeros((len(cross), 7))])
+    return nodes, fixed, np.concatenate([self_edges, cross]), meas, view_ids
+
+
+def AlignOverlapReconstructionsPoseGraph(reconstruction1, reconstruction2, common_views=None, min_shared_tracks=1,
+                                         cross_weight=1.0, options=None, want_trace=False):
+    """The use align_reconstructions.h:61-68 declares and the reference never defines, from the pieces of
+    pose_graph_sim3_error.h and align_reconstructions_pose_graph_optim.{h,cc}: reconstruction2's estimated views are free
+    Sim(3) nodes, reconstruction1's common views (FindCommonViewsByName when not given) are held, an identity edge (weight
+    cross_weight) ties each common pair, and reconstruction2's co-visibility graph (at least min_shared_tracks shared tracks)
+    contributes self edges measured at its current poses, so that the correction the common views ask for is spread over the
+    chunk instead of applied rigidly.  reconstruction2's poses are written back (positions -R' t / s); its TRACKS ARE LEFT
+    ALONE: re-estimate them (EstimateAllTracks) or bundle-adjust afterwards.  Returns a Sim3PoseGraphSummary that also
+    carries `nodes` (the graph's nodes after the solve, overlap_pose_graph's order) and `view_ids`."""
+    nodes, fixed, edges, meas, view_ids = overlap_pose_graph(reconstruction1, reconstruction2, common_views, min_shared_tracks)
+    if int(fixed.sum()) == 0:
+        raise _invalid("the reconstructions have no estimated view in common")
+    W = None
+    if float(cross_weight) != 1.0:
+        W = np.tile(np.eye(7), (len(edges), 1, 1))
+        W[len(edges) - int(fixed.sum()):] *= float(cross_weight)
+    out, summary = OptimizePoseGraphSim3(nodes, edges, meas, W, fixed, options, want_trace)
+    SetPosesFromSim3s(reconstruction2, view_ids, out[:len(view_ids)])
+    summary.nodes, summary.view_ids = out, view_ids   # the graph's nodes after the solve (the held ones last)
+    return summary

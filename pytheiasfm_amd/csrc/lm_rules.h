@@ -2,7 +2,7 @@
 // (trust_region_minimizer.cc, levenberg_marquardt_strategy.cc), once, for every Levenberg-Marquardt loop of the library:
 // ba_solver.hip (lm_control_body), ba_invdepth.hip (host loop), ba_batch.hip (k_view_lm, k_track_lm), twoview_lm.hip
 // (three kernels), twoview_ba.hip, ba_inner.hip (TeamLm, pt_block_lm), graph_lm.h (k_post, k_decide), alignment.hip
-// (k_align_rotations) and sim3_alignment.hip (sim3_advance).
+// (k_align_rotations), sim3_alignment.hip (sim3_advance) and pose_graph_sim3.hip (k_pg_post, k_pg_decide).
 // Rules only: no loop, no linearisation, no manifold, no reduction -- each loop keeps its own body and control flow, its
 // trace, counters and masks.  DESIGN.md 3.3 has the rules in words.
 //
