@@ -521,11 +521,14 @@ __device__ inline void smallest_eigenvector4(double* A, double* x) {
 // eliminating the N scale unknowns from its normal equations leaves, for the eigenvalue mu,
 //     [ sum C^T C - mu (I + sum b_i b_i^T / (d_i (d_i - mu))) ] X = 0,   b_i = P_i^T x_i, d_i = x_i^T x_i, lambda_i = b_i.X / (d_i - mu)
 // -- the L2 matrix at mu = 0 -- solved by fixed-point steps on mu (the Rayleigh quotient of the full vector) until mu stops
-// moving (relative 1e-13, at most 24 steps; well-conditioned tracks take 2 - 3).  A track on which the iteration does not
-// settle (two nearly equal smallest eigenvalues) keeps the L2 solution of the first step.
+// moving (relative 1e-13, at most 24 steps; well-conditioned tracks take 3 - 8).  mu itself is only good to a few 1e-13: it is a
+// quotient of residuals of about a pixel between numbers of about 1e3, and on some tracks the converged iteration alternates
+// for ever between two neighbouring values up to 3.2e-13 mu apart.  So it has also settled once the steps are below 1e-10 mu and
+// have stopped shrinking.  A track on which the iteration does not settle (two nearly equal smallest eigenvalues) keeps the L2
+// solution of the first step.
 // The result carries the reference's normalisation (unit norm over all 4 + N entries).  The sign is arbitrary, as Eigen's is.
 __device__ inline void triangulate_nview(const TrackBatch& B, int64_t beg, int64_t end, bool svd, double* X) {
-  double mu = 0.0;
+  double mu = 0.0, dmu_prev = DBL_MAX;
   double x[4] = {0.0, 0.0, 0.0, 1.0}, x_l2[4] = {0.0, 0.0, 0.0, 1.0};
   const int rounds = svd ? 24 : 1;
   bool settled = !svd;
@@ -568,8 +571,9 @@ __device__ inline void triangulate_nview(const TrackBatch& B, int64_t beg, int64
       den += lam * lam;
     }
     const double mu_new = num / den;
-    settled = fabs(mu_new - mu) <= 1e-13 * mu_new || mu_new == mu;
-    mu = mu_new;
+    const double dmu = fabs(mu_new - mu);
+    settled = dmu <= 1e-13 * mu_new || mu_new == mu || (dmu <= 1e-10 * mu_new && dmu >= dmu_prev);
+    mu = mu_new; dmu_prev = dmu;
     if (settled || round == rounds - 1) { const double sc = 1.0 / sqrt(den); for (int k = 0; k < 4; ++k) x[k] *= sc; break; }
   }
   for (int k = 0; k < 4; ++k) X[k] = settled ? x[k] : x_l2[k];
